@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- img/s of the R50-FPN GeneralizedRCNN inference forward on synthetic 800x1333 batches.
 
-  python bench.py --gpus N --steps K --warmup W [--workload infer|train|knn]
+  python bench.py --gpus N --steps K --warmup W [--workload infer|train|knn] [--full] [--dump-outputs DIR]
 
 N > 1 without a launcher re-executes itself under `python -m torch.distributed.run --nproc-per-node N` (one rank per
 GPU over RCCL); launched BY torch.distributed.run (RANK / WORLD_SIZE in the environment) it runs as that rank.
@@ -11,7 +11,10 @@ batched_inputs) -> list[{"instances": Instances}]` (reference rcnn.py:100-125), 
 including the step's one device->host read; inputs are resident in HBM before the timed region; weights are the conditioned
 random-init R50-FPN (lvc_amd/utils/synthetic.py).  Images shard data-parallel across ranks with no data-path collective
 (reference InferenceSampler semantics), so scaling is "weak" and value = all images of all ranks / max-over-ranks time.
-Rank 0 prints ONE JSON line carrying
+Rank 0 prints ONE JSON line.  A plain run of the default workload sets up, warms up, times the K steps and prints the headline
+(`metric`, `value`, `unit`, `ms_per_step`, `higher_is_better`, `dtype`, config, per-rank times); `--dump-outputs DIR` also writes
+what the last timed step returned as DIR/<name>.npy (inputs and weights are seeded: equal arguments give equal inputs).
+With `--full` the line also carries
   roofline            the dominant conv kernel, HIP events around its launches inside the timed region; plus `backbone_mfma_busy`
                       (matrix-pipe occupancy of the whole backbone, duration-weighted) and `step_traffic` (fabric bytes of the whole
                       step) from live rocprofv3 --pmc passes, against `step_algorithmic_bytes`
@@ -736,6 +739,44 @@ def bandwidth_kernels(c, model, batch):
 
 
 # ----------------------------------------------------------------------------------------------- inference (cfg 2)
+def _headline(c, args, value, dt_max, dt_all, n_det):
+    """The fields every run of the default workload prints (the plain run prints only these)."""
+    return {
+        "metric": "img/s COCO 800x1333 R50-FPN inference (GeneralizedRCNN.forward(batched_inputs) -> Instances, 1000 proposals, 100 detections)",
+        "value": round(value, 2), "unit": "img/s", "n_gpus": c.world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(1e3 * dt_max / args.steps, 3), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32 (conv/GEMM inner products on the fp16 / bf16 matrix cores through fp32-accurate operand splits: two-way fp16 with main + cross fp32 accumulators for the 3x3 and wide 1x1 / FC layers, three-way bf16 for the rest; final boxes/scores closer to the fp64 evaluation than the reference's fp32 CPU path, tests/test_gpu_chain.py)", "data": "synthetic",
+        "config": {"workload": "COCO-detection R50-FPN inference, bs=8 synthetic 3x800x1333 per GPU, 1000 pre/post-NMS "
+                               "proposals per level/image, 80 classes, conditioned random-init weights",
+                   "batch_per_gpu": BATCH_PER_GPU, "global_batch": BATCH_PER_GPU * c.world, "parallelism": "dp%d" % c.world,
+                   "detections_per_image": n_det},
+        "rccl": c.rccl, "per_rank": {"img_per_s": [round(BATCH_PER_GPU * args.steps / t, 2) for t in dt_all],
+                                     "seconds": [round(t, 4) for t in dt_all], "max_over_ranks_s": round(dt_max, 4)},
+    }
+
+
+def _dump_outputs(c, out_dir, res):
+    """--dump-outputs DIR: what the last timed step returned to its caller (list[{"instances": Instances}]), as .npy files:
+    pred_boxes [D, 4] float32, scores [D] float32, pred_classes [D] float64 (exact for class ids), num_instances [images] float64
+    (row offsets of each image in the concatenated lists) and image_size [images, 2] float64.  Under N > 1 ranks every rank
+    writes its own shard with a `rank<r>_` prefix."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    prefix = "rank%d_" % c.rank if c.world > 1 else ""
+    insts = [r["instances"] for r in res]
+    arrays = {
+        "pred_boxes": torch.cat([i.pred_boxes.tensor.detach().float().cpu().view(-1, 4) for i in insts]).numpy().astype(np.float32),
+        "scores": torch.cat([i.scores.detach().float().cpu().view(-1) for i in insts]).numpy().astype(np.float32),
+        "pred_classes": torch.cat([i.pred_classes.detach().cpu().view(-1) for i in insts]).numpy().astype(np.float64),
+        "num_instances": np.array([len(i) for i in insts], dtype=np.float64),
+        "image_size": np.array([list(i.image_size) for i in insts], dtype=np.float64),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), a)
+
+
 def infer_main(c, args):
     import torch
     import torch.distributed as dist
@@ -775,7 +816,7 @@ def infer_main(c, args):
              "f16s1_chain": "conv_pw_chain_kernel (conv3 + shortcut add + ReLU -> the next block's conv1 in one launch: res2 / res3)",
              "f16s1_bneck": "conv_bneck_kernel (a whole res2 bottleneck block -- conv1, 3x3, conv3 + shortcut + ReLU -- in one launch)",
              "bf16x3": "conv_bf16x3_kernel (+ bf16 pointwise shapes)", "f32": "conv_igemm_f32_kernel"}
-    if not args.no_launch_timer:
+    if args.full and not args.no_launch_timer:
         probe = K.LaunchTimer()
         K.CONV_TIMER = probe
         step()
@@ -797,6 +838,17 @@ def infer_main(c, args):
     dt = time.perf_counter() - t0
     K.CONV_TIMER = None
     dt_max, dt_all = _max_and_all(c, dt)
+    host_cpu_all = [round(h, 1) for h in _gather_obj(c, 1e6 * host_cpu / args.steps)]
+    if args.dump_outputs:
+        _dump_outputs(c, args.dump_outputs, res)
+    if not args.full:
+        K.check_conv_error_word(c.dev)   # stream-K timeout / fp16x2 operand-range word of the conv kernels
+        if c.rank == 0:
+            line = _headline(c, args, BATCH_PER_GPU * c.world * args.steps / dt_max, dt_max, dt_all, [len(r["instances"]) for r in res])
+            line["per_rank"]["host_thread_cpu_us_per_step"] = host_cpu_all
+            line["full"] = False
+            print(json.dumps(line))
+        return
     # what the host must supply per step and rank: the time to ENQUEUE a step (inference_batched returns without a device->host read)
     enq = []
     for _ in range(3):
@@ -806,7 +858,6 @@ def infer_main(c, args):
         enq.append(time.perf_counter() - t1)
     torch.cuda.synchronize()
     host_us_all = [round(h, 1) for h in _gather_obj(c, 1e6 * min(enq))]
-    host_cpu_all = [round(h, 1) for h in _gather_obj(c, 1e6 * host_cpu / args.steps)]
     if timer is not None:
         full = K.LaunchTimer()
         K.CONV_TIMER = full
@@ -1002,25 +1053,17 @@ def infer_main(c, args):
         cpu_baseline, parity = _cpu_baseline(model, imgs, gpu_dets, _gpu_proposals(model, batch))
 
     if c.rank == 0:
-        line = {
-            "metric": "img/s COCO 800x1333 R50-FPN inference (GeneralizedRCNN.forward(batched_inputs) -> Instances, 1000 proposals, 100 detections)",
-            "value": round(value, 2), "unit": "img/s", "n_gpus": c.world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(1e3 * dt_max / args.steps, 3), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32 (conv/GEMM inner products on the fp16 / bf16 matrix cores through fp32-accurate operand splits: two-way fp16 with main + cross fp32 accumulators for the 3x3 and wide 1x1 / FC layers, three-way bf16 for the rest; final boxes/scores closer to the fp64 evaluation than the reference's fp32 CPU path, tests/test_gpu_chain.py)", "data": "synthetic",
-            "config": {"workload": "COCO-detection R50-FPN inference, bs=8 synthetic 3x800x1333 per GPU, 1000 pre/post-NMS "
-                                   "proposals per level/image, 80 classes, conditioned random-init weights",
-                       "batch_per_gpu": BATCH_PER_GPU, "global_batch": BATCH_PER_GPU * c.world, "parallelism": "dp%d" % c.world,
-                       "detections_per_image": n_det},
-            "rccl": c.rccl, "per_rank": {"img_per_s": [round(BATCH_PER_GPU * args.steps / t, 2) for t in dt_all],
-                                         "seconds": [round(t, 4) for t in dt_all], "max_over_ranks_s": round(dt_max, 4),
-                                         "host_enqueue_us_per_step": host_us_all, "host_thread_cpu_us_per_step": host_cpu_all,
-                                         "host_note": "enqueue = wall time of one inference_batched() call on an idle GPU (all launches of a step queued, no "
-                                                      "device->host read): a rank is host-bound when this approaches ms_per_step; thread_cpu = CPU time of the "
-                                                      "launching thread over the timed steps (includes the spin of the step's one blocking read)"},
+        line = _headline(c, args, value, dt_max, dt_all, n_det)
+        line["per_rank"].update({"host_enqueue_us_per_step": host_us_all, "host_thread_cpu_us_per_step": host_cpu_all,
+                                 "host_note": "enqueue = wall time of one inference_batched() call on an idle GPU (all launches of a step queued, no "
+                                              "device->host read): a rank is host-bound when this approaches ms_per_step; thread_cpu = CPU time of the "
+                                              "launching thread over the timed steps (includes the spin of the step's one blocking read)"})
+        line["full"] = True
+        line.update({
             "roofline": roofline, "value_inference_batched": through_forward, "pipelined": pipelined, "graphed": graphed,
             "eval_loop_host_inputs": eval_loop, "value_inputs": "device-resident (the 8 fp32 images are in HBM before the timed region, as the bench contract asks; `eval_loop_host_inputs` is the PCIe-inclusive loop)",
             "cpu_baseline": cpu_baseline, "timed_batch_parity": parity,
-        }
+        })
         line.update(extras)
         print(json.dumps(line))
         if parity is not None and not (parity["detection_counts_equal"] and parity["gate_ok"]):
@@ -1404,7 +1447,14 @@ def main():
     ap.add_argument("--no-launch-timer", action="store_true", help="skip the per-launch HIP events (A/B their cost)")
     ap.add_argument("--pipeline-depth", type=int, default=2,
                     help="streams of the extra pipelined pass reported as `pipelined` (1 = skip it); the timed region is always one stream")
+    ap.add_argument("--full", action="store_true",
+                    help="default workload: after the headline, every other measurement and check (roofline, pipelined / graphed passes, "
+                         "kNN, training and R101 legs, CPU baseline and the timed batch's parity gate); without it a run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="default workload: write what the last timed step returned (boxes, scores, classes per image) to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload != "infer":
+        ap.error("--dump-outputs applies to the default workload (infer)")
     global KNN_INPUTS
     KNN_INPUTS = args.knn_inputs
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:

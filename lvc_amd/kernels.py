@@ -836,7 +836,10 @@ def set_wino_streamk(mode):
     global WINO_STREAMK
     WINO_STREAMK = int(mode)
     _lib.lib().lvc_set_wino_streamk(c_int(int(mode)))
-WINO_RPN = True        # the RPN head's large levels too (kernels.conv3x3_levels_pred); False: the two-accumulator direct kernel for all levels
+# The RPN head's large levels on the Winograd kernel too (kernels.conv3x3_levels_pred).  Off: its single-accumulator form puts p2 proposal
+# boxes of the bench batch up to 3.5e-3 px from the exact (fp64) box, past the post-trunk chain test's bar (2 x the oracle's own fp32
+# error, ~1.3e-3 px); the two-accumulator direct kernel stays within it for all levels, at +0.3 ms per 8-image step.
+WINO_RPN = False
 _WINO_MIN_TILES = 512
 
 
@@ -1015,7 +1018,7 @@ def conv3x3_levels_pred(xs, pc, pred, relu=True, _outs=None):
         # The levels that fill the chip with one-workgroup tiles on the Winograd kernel, each alone, with the same epilogue; the small
         # ones stay one grouped launch of the two-accumulator direct kernel.  (The head is packed `two_acc`: its logits decide top-k and
         # NMS.  The Winograd form's measured error lies between the two direct forms' -- rms 4.8e-8 of the output scale against 6.7e-8
-        # one accumulator / ~4e-8 two -- and the post-trunk chain test holds it to the same logit bar: tests/test_gpu_chain.py.)
+        # one accumulator / ~4e-8 two -- but its largest box errors miss the post-trunk chain test's bar: off by default, see WINO_RPN.)
         big = [i for i, x in enumerate(xs) if wino_tiles(x.shape[0], x.shape[1], x.shape[2], pc.K) >= _WINO_MIN_TILES]
         if big:
             u, scale = pack_wino(pc)

@@ -5,7 +5,7 @@ for i in $(seq 1 $rounds); do
     timeout 300 python - $mod $name $v <<'PY' 2>/dev/null | tail -1 > $out/${v}_$i.json
 import importlib, runpy, sys
 m = importlib.import_module(sys.argv[1]); setattr(m, sys.argv[2], sys.argv[3] == "True")
-sys.argv = ["bench.py", "--steps", "40", "--warmup", "8", "--no-extras", "--no-cpu-baseline", "--no-live-pmc"]
+sys.argv = ["bench.py", "--steps", "40", "--warmup", "8", "--full", "--no-extras", "--no-cpu-baseline", "--no-live-pmc"]
 runpy.run_path("bench.py", run_name="__main__")
 PY
     python -c "

@@ -12,11 +12,11 @@ for lib in "" build/variants/dropcross.so build/variants/dropcross_pw.so; do
   echo "=== LVC_AMD_LIB=${lib:-<the shipped library>}"
   export LVC_AMD_LIB=$lib
   python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 | cut -c1-300; echo "smoke rc=${PIPESTATUS[0]}"
-  python bench.py --steps 5 --warmup 2 --no-extras --no-live-pmc > /tmp/b.json 2> /tmp/b.err; echo "bench rc=$?"; tail -2 /tmp/b.err | cut -c1-300
+  python bench.py --steps 5 --warmup 2 --full --no-extras --no-live-pmc > /tmp/b.json 2> /tmp/b.err; echo "bench rc=$?"; tail -2 /tmp/b.err | cut -c1-300
   python -m pytest tests/test_gpu_e2e.py -q -x 2>&1 | tail -2
 done
 echo "=== perturbation post_topk950 (the shipped library; scripts/perturb_run.py)"
 unset LVC_AMD_LIB
 python scripts/perturb_run.py post_topk950 smoke 2>&1 | tail -1 | cut -c1-300; echo "smoke rc=${PIPESTATUS[0]}"
-python scripts/perturb_run.py post_topk950 bench.py --steps 5 --warmup 2 --no-extras --no-live-pmc > /tmp/b.json 2> /tmp/b.err; echo "bench rc=$?"; tail -2 /tmp/b.err | cut -c1-300
+python scripts/perturb_run.py post_topk950 bench.py --steps 5 --warmup 2 --full --no-extras --no-live-pmc > /tmp/b.json 2> /tmp/b.err; echo "bench rc=$?"; tail -2 /tmp/b.err | cut -c1-300
 python scripts/perturb_run.py post_topk950 pytest tests/test_gpu_e2e.py -q -x 2>&1 | tail -2

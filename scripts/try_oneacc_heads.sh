@@ -1,6 +1,6 @@
 # A/B on one box: the RPN head's 3x3 conv (and the box head's FC layers) on the single-accumulator form.  Edits the box's scratch copy only.
 out=gpurun_out/oneacc; mkdir -p $out
-run() { timeout 300 python bench.py --steps 40 --warmup 8 --no-extras --no-cpu-baseline --no-live-pmc 2>/dev/null | tail -1 > $out/$1.json
+run() { timeout 300 python bench.py --steps 40 --warmup 8 --full --no-extras --no-cpu-baseline --no-live-pmc 2>/dev/null | tail -1 > $out/$1.json
   python - $out/$1.json $1 <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); p = d["timed_batch_parity"]

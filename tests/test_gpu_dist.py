@@ -62,7 +62,7 @@ def test_bench_gpus_2_end_to_end_on_this_box():
     env.pop("OMP_NUM_THREADS", None)
     if torch.cuda.device_count() < 2:
         env["LVC_BENCH_ALLOW_SHARED_GPU"] = "1"
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
                         "--no-live-pmc", "--pipeline-depth", "1"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=1500)
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -92,7 +92,7 @@ def test_bench_gpus_8_rehearsal_on_this_box():
     env.pop("OMP_NUM_THREADS", None)
     if torch.cuda.device_count() < 8:
         env["LVC_BENCH_ALLOW_SHARED_GPU"] = "1"
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
                         "--no-live-pmc", "--pipeline-depth", "1"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=1700)
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -115,6 +115,32 @@ def test_bench_gpus_8_rehearsal_on_this_box():
     assert len(legs["train_cfg3"]["per_rank_img_per_s"]) == 8
 
 
+def test_bench_plain_run_prints_the_headline_and_dumps_the_last_step(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W` without --full: the headline alone, and --dump-outputs DIR writes what the
+    last timed step returned (equal arguments -> equal inputs, so two runs of one build dump equal detections)."""
+    import numpy as np
+
+    dumps = []
+    for k in range(2):
+        d = tmp_path / ("run%d" % k)
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(d)], env=_env(), cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, lines
+        line = json.loads(lines[0])
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["full"] is False and line["unit"] == "img/s"
+        assert line["value"] > 0 and abs(line["value"] - 8 * 1e3 / line["ms_per_step"]) <= 0.01 * line["value"]
+        assert "roofline" not in line and "cpu_baseline" not in line and "timed_batch_parity" not in line
+        arrs = {n: np.load(str(d / (n + ".npy"))) for n in ("pred_boxes", "scores", "pred_classes", "num_instances", "image_size")}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        assert arrs["num_instances"].tolist() == line["config"]["detections_per_image"]
+        assert arrs["pred_boxes"].shape == (int(arrs["num_instances"].sum()), 4) and arrs["image_size"].tolist() == [[800, 1333]] * 8
+        dumps.append(arrs)
+    for n in dumps[0]:
+        assert np.array_equal(dumps[0][n], dumps[1][n]), n
+
+
 def _worker(mode):
     out = _torchrun(2, os.path.join(ROOT, "tests", "_dp_worker.py"), mode)
     line = [l for l in out.splitlines() if l.startswith("DP_WORKER_RESULT ")][-1]
@@ -130,7 +156,7 @@ def test_two_rank_gradient_average_equals_the_concatenated_batch():
     assert r["buckets_all_reduce"] <= 2e-4 and r["buckets_rs_ag"] <= 2e-4, r
 
 
-def test_gradient_buckets_reduce_scatter_all_gather_over_rccl_world_1():
+def test_gradient_buckets_reduce_scatter_all_gather_over_rccl_world_1(tmp_path):
     """RCCL's reduce_scatter_tensor / all_gather_into_tensor path of GradientBuckets (mode "rs_ag"), at the world size this
     box has (1): the collectives run through RCCL and leave the gradients unchanged."""
     code = (
@@ -143,8 +169,7 @@ def test_gradient_buckets_reduce_scatter_all_gather_over_rccl_world_1():
         "loss = sum((p * p).sum() for p in ps); loss.backward(); n = b.finish()\n"
         "ok = all(torch.equal(p.grad, 2 * p.detach()) for p in ps)\n"
         "print('RSAG', ok, n, len(b.buckets), dist.get_backend()); dist.destroy_process_group()\n" % ROOT)
-    path = os.path.join(ROOT, "gpurun_out", "_rsag_worker.py")
-    os.makedirs(os.path.dirname(path), exist_ok=True)
+    path = str(tmp_path / "_rsag_worker.py")
     open(path, "w").write(code)
     out = _torchrun(1, path)
     line = [l for l in out.splitlines() if l.startswith("RSAG")][-1].split()
