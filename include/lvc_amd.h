@@ -262,6 +262,21 @@ int lvc_preprocess_batch_nhwc4(const void* const* images, int dtype, const int* 
 int lvc_resize_bilinear_u8(const unsigned char* image, int H, int W, int new_h, int new_w, const int* xb, const int* xk,
                            int kxs, const int* yb, const int* yk, int kys, unsigned char* tmp, unsigned char* out_u8,
                            float* out_nhwc4, int Hp, int Wp, const float* mean3, const float* std3, void* stream);
+/* Test-time augmentation (lvc_amd/csrc/tta.hip; reference detectron2/modeling/test_time_augmentation.py).
+ * lvc_tta_resize_u8: every ResizeShortestEdge size (+ its horizontal mirror) of one uint8 image, Pillow-exact as
+ *   lvc_resize_bilinear_u8, in two launches for up to 16 sizes: image element (y,x,c) at image[y*sy + x*sx + c*sc];
+ *   hjobs host int64 [n_h][5] = (xb, xk, kxs, new_w, tmp) per distinct output width != W; vjobs host int64 [n_v][14] =
+ *   (source hjob or -1, yb, yk or 0, kys, new_h, new_w, u8, u8 mirrored, slot, Hp, Wp, mirrored slot, Hpm, Wpm), each output
+ *   optional (u8 [new_h,new_w,3]; slots [Hp,Wp,4] fp32 = (v - mean) / std, zero padded, as preprocess_image).
+ * lvc_tta_merge: union of B images' augmentation detections (boxes [A,topk_in,4], scores, classes int32, counts [A]) through
+ *   the inverse transforms (params [A][16] fp32 device), finite filter, clip, score > score_thresh, per-class NMS, first topk_out;
+ *   tab [B][4] int32 device = (first augmentation, end, height, width).  Outputs [B,topk_out] + count [B]; no host sync. */
+int lvc_tta_resize_u8(const unsigned char* image, int H, int W, long long sy, long long sx, long long sc, const long long* hjobs,
+                      int n_h, const long long* vjobs, int n_v, const float* mean3, const float* std3, void* stream);
+long long lvc_tta_merge_workspace_bytes(int B, int Nmax);
+int lvc_tta_merge(const float* boxes, const float* scores, const int* classes, const int* counts, int topk_in, const float* params,
+                  const int* tab, int B, int Nmax, float score_thresh, double nms_thresh, int topk_out, float* ob, float* osc, int* ocl,
+                  int* ocount, void* workspace, long long workspace_bytes, void* stream);
 /* F.max_pool2d on NHWC (BasicStem resnet.py:591: k3 s2 p1; LastLevelMaxPool fpn.py:176: k1 s2 p0). */
 int lvc_maxpool2d_nhwc(const float* x, float* y, int N, int H, int W, int C, int k, int stride, int pad,
                        void* stream);

@@ -1,4 +1,4 @@
 """Test-time input transform of the detector (the part of detectron2/data that sits on the device here)."""
-from .transforms import ResizeShortestEdge, ResizeTransform, resample_coeffs
+from .transforms import HFlipTransform, NoOpTransform, ResizeShortestEdge, ResizeTransform, TransformList, resample_coeffs
 
-__all__ = ["ResizeShortestEdge", "ResizeTransform", "resample_coeffs"]
+__all__ = ["HFlipTransform", "NoOpTransform", "ResizeShortestEdge", "ResizeTransform", "TransformList", "resample_coeffs"]

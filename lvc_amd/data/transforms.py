@@ -10,6 +10,7 @@ Only the host part of Pillow's algorithm lives here: the per-output coefficient 
 + normalize_coeffs_8bpc for the bilinear filter over the whole image), computed in float64 with the same operation
 order as the C code and cached per (input size, output size).
 """
+import collections
 import functools
 import math
 
@@ -50,11 +51,13 @@ def _coeffs_np(in_size, out_size):
     return bounds, kk, ksize
 
 
-_DEV_COEFFS = {}
+_DEV_COEFFS = collections.OrderedDict()
+_DEV_COEFFS_MAX = 512       # (in, out, device) tables kept on the device: a dataset of many image sizes (x 9 under the default
+                            # TEST.AUG) would otherwise grow this without bound; least recently used first out
 
 
 def resample_coeffs(in_size, out_size, device=None):
-    """(bounds [out,2] int32, coefficients [out,ksize] int32, ksize); on `device` when given (cached)."""
+    """(bounds [out,2] int32, coefficients [out,ksize] int32, ksize); on `device` when given (cached, bounded)."""
     b, k, ks = _coeffs_np(int(in_size), int(out_size))
     if device is None:
         return b, k, ks
@@ -63,7 +66,110 @@ def resample_coeffs(in_size, out_size, device=None):
     if hit is None:
         hit = (torch.from_numpy(b).to(device), torch.from_numpy(k).to(device), ks)
         _DEV_COEFFS[key] = hit
+        while len(_DEV_COEFFS) > _DEV_COEFFS_MAX:     # an evicted table may still be read by a queued launch: the caching allocator
+            _DEV_COEFFS.popitem(last=False)           # only hands its block to later work of the same stream
+    else:
+        _DEV_COEFFS.move_to_end(key)
     return hit
+
+
+def _box_corners(box):
+    """fvcore Transform.apply_box: the 4 corners of each box as [4N, 2] coordinates (a copy), for numpy arrays and tensors."""
+    idxs = [0, 1, 2, 1, 0, 3, 2, 3]
+    if isinstance(box, torch.Tensor):
+        return box.reshape(-1, 4)[:, idxs].reshape(-1, 2).clone()
+    return np.asarray(box).reshape(-1, 4)[:, idxs].reshape(-1, 2).copy()
+
+
+def _corners_to_box(coords):
+    c = coords.reshape(-1, 4, 2)
+    if isinstance(c, torch.Tensor):
+        return torch.cat([c.min(dim=1).values, c.max(dim=1).values], 1)
+    return np.concatenate([c.min(axis=1), c.max(axis=1)], axis=1)
+
+
+def _scale(col, factor):
+    """col * factor in the column's own precision, the way numpy multiplies an fp32 array by a Python float (the factor is rounded
+    to fp32 first)."""
+    if isinstance(col, torch.Tensor):
+        return col * torch.tensor(factor, dtype=col.dtype, device=col.device)
+    return col * np.asarray(factor, dtype=col.dtype)
+
+
+class NoOpTransform:
+    """fvcore NoOpTransform: every apply_* returns its input."""
+
+    def apply_image(self, img):
+        return img
+
+    def apply_coords(self, coords):
+        return coords
+
+    def apply_box(self, box):
+        return box
+
+    def inverse(self):
+        return self
+
+
+class HFlipTransform:
+    """fvcore HFlipTransform(width): x -> width - x on coordinates (fp32 for fp32 input), the image mirrored along its width."""
+
+    def __init__(self, width):
+        self.width = int(width)
+
+    def apply_image(self, img):
+        """HWC (or NHWC) array / tensor mirrored along W, as fvcore does for numpy images."""
+        if isinstance(img, torch.Tensor):
+            return img.flip(1 if img.dim() <= 3 else -2)
+        return np.flip(img, axis=1) if img.ndim <= 3 else np.flip(img, axis=-2)
+
+    def apply_coords(self, coords):
+        coords[:, 0] = self.width - coords[:, 0]
+        return coords
+
+    def apply_box(self, box):
+        return _corners_to_box(self.apply_coords(_box_corners(box)))
+
+    def inverse(self):
+        return self
+
+
+class TransformList:
+    """fvcore TransformList: a flat sequence of transforms; `apply_*` runs them in order (each transform's own apply_box, so every
+    step maps corners and takes min / max), `inverse` is the reversed list of inverses, `+` concatenates."""
+
+    def __init__(self, transforms):
+        flat = []
+        for t in transforms:
+            flat.extend(t.transforms if isinstance(t, TransformList) else [t])
+        self.transforms = flat
+
+    def _apply(self, x, meth):
+        for t in self.transforms:
+            x = getattr(t, meth)(x)
+        return x
+
+    def apply_image(self, img):
+        return self._apply(img, "apply_image")
+
+    def apply_coords(self, coords):
+        return self._apply(coords, "apply_coords")
+
+    def apply_box(self, box):
+        return self._apply(box, "apply_box")
+
+    def __add__(self, other):
+        return TransformList(self.transforms + (other.transforms if isinstance(other, TransformList) else [other]))
+
+    def __radd__(self, other):
+        return TransformList((other.transforms if isinstance(other, TransformList) else [other]) + self.transforms)
+
+    def __len__(self):
+        return len(self.transforms)
+
+    def inverse(self):
+        return TransformList([t.inverse() for t in self.transforms[::-1]])
 
 
 class ResizeTransform:
@@ -88,6 +194,11 @@ class ResizeTransform:
         return coords
 
     def apply_box(self, box):
+        if not isinstance(box, torch.Tensor):     # numpy, as fvcore: corners through apply_coords, then min / max
+            coords = _box_corners(box)
+            coords[:, 0] = _scale(coords[:, 0], self.new_w * 1.0 / self.w)
+            coords[:, 1] = _scale(coords[:, 1], self.new_h * 1.0 / self.h)
+            return _corners_to_box(coords)
         box = box.clone().reshape(-1, 4)
         box[:, 0::2] = box[:, 0::2] * (self.new_w * 1.0 / self.w)
         box[:, 1::2] = box[:, 1::2] * (self.new_h * 1.0 / self.h)

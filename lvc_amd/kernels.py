@@ -1599,6 +1599,74 @@ def resize_bilinear_u8(img, new_h, new_w, coeffs_fn, out_slot=None, mean=None, s
     return out
 
 
+def tta_resize_u8(img, H, W, strides, hjobs, vjobs, mean, std):
+    """All ResizeShortestEdge sizes (and their mirrors) of one uint8 device image in two launches (csrc/tta.hip
+    lvc_tta_resize_u8).  img: uint8 device tensor of an H x W image whose element (y, x, c) sits at element strides
+    strides = (sy, sx, sc) from its data pointer (CHW and HWC alike);
+    hjobs: list of (bounds, coefficients, ksize, new_w, tmp) device tensors, one per distinct output width != W; vjobs: list of
+    (hjob index or -1, bounds or None, coefficients or None, ksize, new_h, new_w, u8 or None, mirrored u8 or None, slot or None,
+    mirrored slot or None), slots being [Hp,Wp,4] fp32 contiguous views of batch buffers.  Nothing is returned: the outputs
+    are written in place."""
+    _req_cuda(img)
+    assert img.dtype == torch.uint8
+    hrows = []
+    for xb, xk, ks, nw, tmp in hjobs:
+        _req_cuda(xb, xk, tmp)
+        assert tmp.numel() >= H * nw * 3
+        hrows += [xb.data_ptr(), xk.data_ptr(), ks, nw, tmp.data_ptr()]
+    vrows = []
+    for hj, yb, yk, ks, nh, nw, u8, u8m, f, fm in vjobs:
+        for o in (u8, u8m):
+            assert o is None or (o.is_cuda and o.is_contiguous() and tuple(o.shape) == (nh, nw, 3) and o.dtype == torch.uint8)
+        for o in (f, fm):
+            assert o is None or (o.is_cuda and o.is_contiguous() and o.dim() == 3 and o.shape[2] == 4 and o.dtype == torch.float32)
+        vrows += [hj, yb.data_ptr() if yb is not None else 0, yk.data_ptr() if yk is not None else 0, ks, nh, nw,
+                  u8.data_ptr() if u8 is not None else 0, u8m.data_ptr() if u8m is not None else 0,
+                  f.data_ptr() if f is not None else 0, f.shape[0] if f is not None else 0, f.shape[1] if f is not None else 0,
+                  fm.data_ptr() if fm is not None else 0, fm.shape[0] if fm is not None else 0, fm.shape[1] if fm is not None else 0]
+    hj = (c_longlong * max(1, len(hrows)))(*hrows)
+    vj = (c_longlong * len(vrows))(*vrows)
+    m = (c_float * 3)(*[float(v) for v in mean])
+    s = (c_float * 3)(*[float(v) for v in std])
+    sy, sx, sc = strides
+    rc = _lib.lib().lvc_tta_resize_u8(ptr(img), c_int(H), c_int(W), c_longlong(sy), c_longlong(sx), c_longlong(sc), hj,
+                                      c_int(len(hjobs)), vj, c_int(len(vjobs)), m, s, _stream(img))
+    check(rc, "lvc_tta_resize_u8")
+
+
+TTA_PARAM_STRIDE = 16     # floats per augmentation in lvc_tta_merge's inverse-transform table
+TTA_MAX_STEPS = 4
+
+
+def tta_merge(boxes, scores, classes, counts, params, tab, num_images, nmax, score_thresh, nms_thresh, topk):
+    """Union + inverse transforms + finite filter + clip + score filter + per-class NMS + first `topk` for `num_images` images
+    (csrc/tta.hip lvc_tta_merge).  boxes [A,T,4], scores [A,T], classes [A,T] int32, counts [A] int32: every augmentation's
+    detections; params [A,16] fp32 and tab [B,4] int32 device tables.  Returns (boxes [B,topk,4], scores [B,topk], classes
+    [B,topk] int32, count [B] int32) on the device, no sync."""
+    _req_cuda(boxes, scores, classes, counts, params, tab)
+    A, T = scores.shape
+    assert boxes.shape == (A, T, 4) and classes.shape == (A, T) and counts.shape == (A,) and params.shape == (A, TTA_PARAM_STRIDE)
+    assert tab.shape == (num_images, 4) and tab.dtype == torch.int32 and params.dtype == torch.float32
+    assert classes.dtype == torch.int32 and counts.dtype == torch.int32
+    dev = boxes.device
+    B = num_images
+    ob = torch.empty(B, max(topk, 1), 4, device=dev, dtype=torch.float32)
+    osc = torch.empty(B, max(topk, 1), device=dev, dtype=torch.float32)
+    ocl = torch.empty(B, max(topk, 1), device=dev, dtype=torch.int32)
+    cnt = torch.zeros(B, device=dev, dtype=torch.int32)
+    if topk == 0 or B == 0:
+        return ob[:, :0], osc[:, :0], ocl[:, :0], cnt
+    wsb = _lib.lib().lvc_tta_merge_workspace_bytes(c_int(B), c_int(nmax))
+    ws = torch.empty(wsb + 256, dtype=torch.uint8, device=dev)
+    off = (-ws.data_ptr()) % 256
+    ws = ws[off:off + wsb]
+    rc = _lib.lib().lvc_tta_merge(ptr(boxes.contiguous()), ptr(scores.contiguous()), ptr(classes.contiguous()), ptr(counts), c_int(T),
+                                  ptr(params), ptr(tab), c_int(B), c_int(nmax), c_float(score_thresh), c_double(nms_thresh),
+                                  c_int(topk), ptr(ob), ptr(osc), ptr(ocl), ptr(cnt), ptr(ws), c_longlong(wsb), _stream(boxes))
+    check(rc, "lvc_tta_merge")
+    return ob, osc, ocl, cnt
+
+
 def maxpool2d_nhwc(x, k, stride, pad):
     _req_cuda(x)
     assert x.is_contiguous() and x.dtype == torch.float32

@@ -236,27 +236,37 @@ class GeneralizedRCNN(_RCNNBase):
         return losses
 
     # ------------------------------------------------------------------ device-side fast path
-    def inference_batched(self, batched_inputs, do_postprocess=True):
+    def inference_batched(self, batched_inputs, do_postprocess=True, status=None):
         """Whole forward with device-resident, fixed-shape outputs and no host sync:
-        (boxes [B,topk,4], scores [B,topk], classes [B,topk] int32, count [B] int32, status [1] int32)."""
+        (boxes [B,topk,4], scores [B,topk], classes [B,topk] int32, count [B] int32, status [1] int32).
+        status: an existing status word to OR this pass's conditions into (a new one when None)."""
         assert isinstance(self.proposal_generator, RPN) and isinstance(self.roi_heads, StandardROIHeads)
         images = self.preprocess_image(batched_inputs)
         sizes = images.image_sizes
-        dev = self.device
-        sizes_dev = self._dev_const(sizes, torch.int32)
         N, _, Hp, Wp = images.tensor.shape
         x4 = images.tensor.as_strided((N, Hp, Wp, 4), (Hp * Wp * 4, Wp * 4, 4, 1), images.tensor.storage_offset())
-        feats = self.backbone.forward_nhwc(x4)
-        pboxes, _plogits, pcount = self.proposal_generator.predict_proposals_batched(feats, sizes_dev)
-        post = None
+        post_rows = None
         if do_postprocess:
-            rows = []
+            post_rows = []
             for inp, (h, w) in zip(batched_inputs, sizes):
                 dh, dw = (int(inp["raw"].shape[0]), int(inp["raw"].shape[1])) if "image" not in inp else (h, w)
                 oh, ow = inp.get("height", dh), inp.get("width", dw)   # DatasetMapper: height/width = the file's size
-                rows.append([ow / w, oh / h, float(oh), float(ow)])
-            post = self._dev_const(rows, torch.float32)
-        status = K.new_status(dev)
+                post_rows.append([ow / w, oh / h, float(oh), float(ow)])
+        return self.inference_nhwc(x4, sizes, post_rows, status)
+
+    def inference_nhwc(self, x4, sizes, post_rows=None, status=None):
+        """`inference_batched` after `preprocess_image`: x4 [N,Hp,Wp,4] fp32 the normalised, zero-padded batch (what
+        preprocess_image builds), sizes the N image sizes; post_rows None (no detector_postprocess) or per image
+        [out_w / w, out_h / h, out_h, out_w].  status: a status word to OR into (a new one when None).  Same outputs."""
+        dev = self.device
+        sizes_dev = self._dev_const(sizes, torch.int32)
+        feats = self.backbone.forward_nhwc(x4)
+        pboxes, _plogits, pcount = self.proposal_generator.predict_proposals_batched(feats, sizes_dev)
+        post = None
+        if post_rows is not None:
+            post = self._dev_const(post_rows, torch.float32)
+        if status is None:
+            status = K.new_status(dev)
         ob, osc, ocl, _orow, cnt = self.roi_heads.forward_batched(feats, pboxes, pcount, sizes_dev, post=post, status=status)
         return ob, osc, ocl, cnt, status
 
