@@ -277,6 +277,19 @@ long long lvc_tta_merge_workspace_bytes(int B, int Nmax);
 int lvc_tta_merge(const float* boxes, const float* scores, const int* classes, const int* counts, int topk_in, const float* params,
                   const int* tab, int B, int Nmax, float score_thresh, double nms_thresh, int topk_out, float* ob, float* osc, int* ocl,
                   int* ocount, void* workspace, long long workspace_bytes, void* stream);
+/* Training input of a whole batch (lvc_amd/csrc/train_input.hip; reference lvc/data/dataset_mapper.py:90-209): RandomCrop ->
+ * ResizeShortestEdge (Pillow-exact, as lvc_resize_bilinear_u8, coefficients for the CROPPED size -> the output size) -> RandomFlip
+ * -> normalise + zero-pad, for B uint8 images of different sizes in two launches whatever B is.
+ *   h_blob (host) / d_blob (its device copy), blob_bytes: int64 jobs [B][24] first, the int32 bounds / coefficient tables behind
+ *   them at the byte offsets the jobs name.  Job words: 0 source pointer (element (y,x,c) at src[y*sy + x*sx + c*sc]), 1 H, 2 W,
+ *   3 sy, 4 sx, 5 sc, 6 x0, 7 y0, 8 crop w, 9 crop h, 10 new_h, 11 new_w, 12 xb offset (-1: width unchanged), 13 xk offset,
+ *   14 kxs, 15 yb offset (-1: height unchanged), 16 yk offset, 17 kys, 18 flip, 19 slot, 20 optional uint8 output pointer
+ *   [new_h,new_w,3] (0: none), 21 byte offset of the job's [crop h,new_w,3] intermediate in tmp; 22-23 reserved.
+ *   out [n_slots,Hp,Wp,4] fp32 = (v - mean) / std, zero padded; mean3 / std3: host float[3].  The host blob is validated (windows
+ *   inside their images, taps inside their crops, outputs inside their buffers) before anything is launched.  launches: optional,
+ *   receives the number of kernel launches issued (at most two). */
+int lvc_train_input_u8(const void* h_blob, const void* d_blob, long long blob_bytes, int B, unsigned char* tmp, long long tmp_bytes,
+                       float* out, int n_slots, int Hp, int Wp, const float* mean3, const float* std3, int* launches, void* stream);
 /* F.max_pool2d on NHWC (BasicStem resnet.py:591: k3 s2 p1; LastLevelMaxPool fpn.py:176: k1 s2 p0). */
 int lvc_maxpool2d_nhwc(const float* x, float* y, int N, int H, int W, int C, int k, int stride, int pad,
                        void* stream);

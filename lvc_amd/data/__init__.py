@@ -1,4 +1,10 @@
-"""Test-time input transform of the detector (the part of detectron2/data that sits on the device here)."""
-from .transforms import HFlipTransform, NoOpTransform, ResizeShortestEdge, ResizeTransform, TransformList, resample_coeffs
+"""Input transforms of the detector (the part of detectron2/data that sits on the device here): the test-time resize, and the
+training input -- crop, resize, flip, annotations, batching (dataset_mapper.py, build.py)."""
+from .transforms import (AugmentationList, CropTransform, HFlipTransform, NoOpTransform, RandomCrop, RandomFlip, ResizeShortestEdge,
+                         ResizeTransform, TrainInputParams, TransformList, resample_coeffs)
+from .dataset_mapper import DatasetMapper, DatasetMapperIgnore, build_augmentation
+from .build import AspectRatioGrouper, TrainingSampler, build_detection_train_loader
 
-__all__ = ["HFlipTransform", "NoOpTransform", "ResizeShortestEdge", "ResizeTransform", "TransformList", "resample_coeffs"]
+__all__ = ["AugmentationList", "CropTransform", "HFlipTransform", "NoOpTransform", "RandomCrop", "RandomFlip", "ResizeShortestEdge",
+           "ResizeTransform", "TrainInputParams", "TransformList", "resample_coeffs", "DatasetMapper", "DatasetMapperIgnore",
+           "build_augmentation", "AspectRatioGrouper", "TrainingSampler", "build_detection_train_loader"]

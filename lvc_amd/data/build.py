@@ -1,0 +1,194 @@
+"""build_detection_train_loader (reference lvc/data/build.py:165-232) with the images prepared on the device.
+
+The reference maps every image on CPU workers (file decode, crop, Pillow resize, flip) and leaves normalising, padding and batching
+to the model.  Here the loader draws the transforms and maps the annotations on the host (dataset_mapper.DatasetMapper.draw), then
+prepares the pixels of the WHOLE batch with one kernel call (csrc/train_input.hip: two launches, every table in one upload) on a side
+stream, straight into the padded NHWC4 fp32 batch the model's trunk reads.  Two batch buffers rotate: batch k+1 is prepared while
+step k runs.  Streams meet through events only -- the model's stream waits for the batch's `ready` event (GeneralizedRCNN.
+preprocess_image, through `PreparedBatch.image_list`), and the side stream waits, before it overwrites a buffer, for the event the
+consumer's stream recorded when the NEXT batch was asked for (by then the step that read the buffer has been queued in full).
+
+Order of images: the reference's TrainingSampler (detectron2/data/samplers/distributed_sampler.py:12-54: seeded torch.randperm
+shuffles, rank-strided) followed by its aspect-ratio grouping (detectron2/data/common.py:115-149: two buckets by w > h, a batch
+leaves when its bucket is full) when DATALOADER.ASPECT_RATIO_GROUPING is set (the default).
+"""
+import itertools
+import os
+
+import torch
+
+from .. import distributed as dist
+from .. import kernels as K
+from ..structures import ImageList
+from .dataset_mapper import DatasetMapper, check_supported
+from .transforms import resample_coeffs
+
+
+class TrainingSampler:
+    """An infinite stream of indices: shuffle(range(size)) + shuffle(range(size)) + ..., every world_size-th one from `rank` on."""
+
+    def __init__(self, size, shuffle=True, seed=None, rank=None, world_size=None):
+        assert size > 0
+        self._size, self._shuffle = int(size), shuffle
+        self._rank = dist.get_rank() if rank is None else int(rank)
+        self._world_size = dist.get_world_size() if world_size is None else int(world_size)
+        if seed is None:
+            if self._world_size > 1:
+                raise ValueError("TrainingSampler: every rank must be given the same seed")
+            seed = int.from_bytes(os.urandom(4), "little")
+        self._seed = int(seed)
+
+    def __iter__(self):
+        yield from itertools.islice(self._infinite_indices(), self._rank, None, self._world_size)
+
+    def _infinite_indices(self):
+        g = torch.Generator()
+        g.manual_seed(self._seed)
+        while True:
+            if self._shuffle:
+                yield from torch.randperm(self._size, generator=g).tolist()
+            else:
+                yield from range(self._size)
+
+
+class AspectRatioGrouper:
+    """AspectRatioGroupedDataset over anything with "width" / "height": bucket 0 holds w > h, bucket 1 the rest; a bucket that
+    reaches batch_size leaves as a batch."""
+
+    def __init__(self, dataset, batch_size):
+        self.dataset, self.batch_size = dataset, int(batch_size)
+        self._buckets = [[] for _ in range(2)]
+
+    def __iter__(self):
+        for d in self.dataset:
+            bucket = self._buckets[0 if d["width"] > d["height"] else 1]
+            bucket.append(d)
+            if len(bucket) == self.batch_size:
+                yield bucket[:]
+                del bucket[:]
+
+
+def _plain_batches(dataset, batch_size):
+    """BatchSampler(drop_last=True) over an infinite stream."""
+    it = iter(dataset)
+    while True:
+        yield [next(it) for _ in range(batch_size)]
+
+
+class PreparedBatch:
+    """A training batch whose images are already normalised, padded and batched on the device.  Every item of the loader's
+    `batched_inputs` carries the same PreparedBatch under "prepared" (and its own "slot" in it, its dataset "index" and the drawn
+    "train_input_params"); GeneralizedRCNN.preprocess_image takes the batch as it is."""
+
+    def __init__(self, buffer, sizes, ready):
+        self.buffer, self.sizes, self.ready = buffer, sizes, ready      # [B,Hp,Wp,4] fp32, [(h, w)], the event that ends its kernels
+
+    def image_list(self, device=None):
+        """The ImageList preprocess_image would have built; the calling stream waits for the batch first."""
+        if self.ready is not None:
+            torch.cuda.current_stream(self.buffer.device).wait_event(self.ready)
+        return ImageList(self.buffer.permute(0, 3, 1, 2)[:, :3], list(self.sizes))
+
+
+class _Slot:
+    def __init__(self, device):
+        self.workspace = K.TrainInputWorkspace(device)
+        self.storage = None          # flat fp32 storage of the batch buffer, grown on demand
+        self.released = None         # recorded on the consumer's stream once the step that read this slot has been queued
+        self.images = None           # the uploaded sources of the batch in flight
+
+
+class TrainInputLoader:
+    """Infinite iterator of `batched_inputs` (see the module docstring).  `sync=True` prepares each batch on the calling stream and
+    waits for it (one buffer would do): the plain order the pipelined one must reproduce."""
+
+    def __init__(self, dataset_dicts, mapper, batch_size, sampler, size_divisibility, aspect_ratio_grouping=True, device="cuda",
+                 sync=False, num_buffers=2):
+        assert len(dataset_dicts) > 0 and batch_size > 0
+        self.dataset_dicts, self.mapper, self.batch_size, self.sampler = dataset_dicts, mapper, int(batch_size), sampler
+        self.size_divisibility, self.grouping, self.sync = int(size_divisibility), bool(aspect_ratio_grouping), bool(sync)
+        self.device = torch.device(device)
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.num_buffers = int(num_buffers)
+        assert self.num_buffers >= 2
+
+    def index_batches(self):
+        """The batches as lists of dataset indices (host only): sampler, then grouping by the dicts' own width / height."""
+        def row(i):
+            d = self.dataset_dicts[i]
+            if "width" in d and "height" in d:
+                return {"index": i, "width": d["width"], "height": d["height"]}
+            return {"index": i, "width": int(d["raw"].shape[1]), "height": int(d["raw"].shape[0])}
+
+        rows = (row(i) for i in self.sampler)
+        batches = AspectRatioGrouper(rows, self.batch_size) if self.grouping else _plain_batches(rows, self.batch_size)
+        for b in batches:
+            yield [r["index"] for r in b]
+
+    def _prepare(self, indices, slot, stream):
+        drawn = [self.mapper.draw(self.dataset_dicts[i]) for i in indices]
+        sizes = [p.new_size for _, _, p in drawn]
+        Hp, Wp = ImageList.padded_size(sizes, self.size_divisibility)
+        B = len(drawn)
+        with torch.cuda.stream(stream):
+            if slot.released is not None:
+                stream.wait_event(slot.released)
+            n = B * Hp * Wp * 4
+            if slot.storage is None or slot.storage.numel() < n:
+                slot.storage = torch.empty(n * 5 // 4, dtype=torch.float32, device=self.device)
+            buf = slot.storage[:n].view(B, Hp, Wp, 4)
+            slot.images = [raw.to(self.device, non_blocking=True) for _, raw, _ in drawn]
+            K.train_input_u8(slot.images, [p.job() for _, _, p in drawn], buf, self.mapper.pixel_mean, self.mapper.pixel_std,
+                             resample_coeffs, workspace=slot.workspace)
+            ready = torch.cuda.Event()
+            ready.record(stream)
+        batch = PreparedBatch(buf, sizes, ready)
+        return [dict(d, prepared=batch, index=i, slot=s, train_input_params=p) for s, ((d, _, p), i) in enumerate(zip(drawn, indices))]
+
+    def __iter__(self):
+        batches = self.index_batches()
+        if self.sync:
+            slot = _Slot(self.device)
+            for indices in batches:
+                out = self._prepare(indices, slot, torch.cuda.current_stream(self.device))
+                out[0]["prepared"].ready.synchronize()
+                yield out
+            return
+        side = torch.cuda.Stream(self.device)
+        side.wait_stream(torch.cuda.current_stream(self.device))      # device-resident sources the caller has just produced
+        slots = [_Slot(self.device) for _ in range(self.num_buffers)]
+        k = 0
+        pending = self._prepare(next(batches), slots[0], side)
+        while True:
+            current, cur_slot = pending, slots[k % self.num_buffers]
+            k += 1
+            nxt = slots[k % self.num_buffers]
+            # whoever read `nxt` (the batch handed out num_buffers - 1 requests ago) has queued its step: `released` is set
+            pending = self._prepare(next(batches), nxt, side)
+            yield current
+            # the consumer is back for the next batch: everything that reads `cur_slot` is on its stream already
+            cur_slot.released = torch.cuda.Event()
+            cur_slot.released.record(torch.cuda.current_stream(self.device))
+
+
+def build_detection_train_loader(cfg, dataset_dicts, mapper=None, seed=None, size_divisibility=None, sync=False):
+    """An infinite iterator of batches of SOLVER.IMS_PER_BATCH // world_size items for `model(batched_inputs)` in training mode.
+    dataset_dicts: the reference's dataset format with the decoded image under "raw" (uint8 [H,W,3], pinned host memory makes the
+    upload asynchronous).  seed: the sampler's (the same on every rank); the augmentations draw from numpy's global generator.
+    size_divisibility: the backbone's (default: 32 for the FPN backbones, else 0)."""
+    check_supported(cfg)
+    name = cfg.DATALOADER.SAMPLER_TRAIN
+    if name != "TrainingSampler":
+        raise NotImplementedError("DATALOADER.SAMPLER_TRAIN = {} is not implemented (TrainingSampler only)".format(name))
+    world = dist.get_world_size()
+    total = int(cfg.SOLVER.IMS_PER_BATCH)
+    assert total > 0 and total % world == 0, "Total batch size ({}) must be divisible by the number of gpus ({}).".format(total, world)
+    if mapper is None:
+        mapper = DatasetMapper.from_config(cfg, True)
+    if size_divisibility is None:
+        size_divisibility = 32 if "fpn" in cfg.MODEL.BACKBONE.NAME.lower() else 0
+    sampler = TrainingSampler(len(dataset_dicts), seed=seed)
+    loader = TrainInputLoader(dataset_dicts, mapper, total // world, sampler, size_divisibility,
+                              aspect_ratio_grouping=cfg.DATALOADER.ASPECT_RATIO_GROUPING, device=cfg.MODEL.DEVICE, sync=sync)
+    return iter(loader)

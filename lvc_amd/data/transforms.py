@@ -252,3 +252,138 @@ class ResizeShortestEdge:
             return None     # NoOpTransform
         newh, neww = self.output_size(h, w, int(size))
         return ResizeTransform(h, w, newh, neww, self.interp)
+
+
+# ------------------------------------------------------------------------------------------------ training input
+# RandomCrop -> ResizeShortestEdge -> RandomFlip: the training augmentation of the shipped yamls (reference DatasetMapperIgnore.
+# from_config, lvc/data/dataset_mapper.py:90-126).  Only the POLICY lives here -- which window, which size, flip or not, and the
+# matching coordinate transforms; the pixels of a whole batch are produced by one kernel call (csrc/train_input.hip).  Every random
+# number comes from numpy's global generator through the reference's own calls in the reference's order, so `np.random.seed(s)`
+# before a draw gives the reference's window, size and flip decision.
+
+
+class CropTransform:
+    """fvcore CropTransform(x0, y0, w, h): the window img[y0:y0+h, x0:x0+w]; coordinates shift by (-x0, -y0)."""
+
+    def __init__(self, x0, y0, w, h):
+        self.x0, self.y0, self.w, self.h = int(x0), int(y0), int(w), int(h)
+
+    def apply_image(self, img):
+        """HWC array / tensor: a view of the window, as fvcore's slicing."""
+        return img[self.y0:self.y0 + self.h, self.x0:self.x0 + self.w]
+
+    def apply_coords(self, coords):
+        coords[:, 0] -= self.x0
+        coords[:, 1] -= self.y0
+        return coords
+
+    def apply_box(self, box):
+        return _corners_to_box(self.apply_coords(_box_corners(box)))
+
+
+class _Shape:
+    """What an augmentation policy needs of an image: its shape."""
+
+    def __init__(self, h, w):
+        self.shape = (int(h), int(w), 3)
+
+
+class RandomCrop:
+    """reference augmentation_impl.py:291-340, all four INPUT.CROP.TYPE values."""
+
+    def __init__(self, crop_type, crop_size):
+        assert crop_type in ["relative_range", "relative", "absolute", "absolute_range"], crop_type
+        self.crop_type, self.crop_size = crop_type, tuple(crop_size)
+
+    def get_transform(self, img):
+        h, w = int(img.shape[0]), int(img.shape[1])
+        croph, cropw = self.get_crop_size((h, w))
+        assert h >= croph and w >= cropw, "Shape computation in {} has bugs.".format(self)
+        h0 = np.random.randint(h - croph + 1)
+        w0 = np.random.randint(w - cropw + 1)
+        return CropTransform(w0, h0, cropw, croph)
+
+    def get_crop_size(self, image_size):
+        h, w = image_size
+        if self.crop_type == "relative":
+            ch, cw = self.crop_size
+            return int(h * ch + 0.5), int(w * cw + 0.5)
+        if self.crop_type == "relative_range":
+            crop_size = np.asarray(self.crop_size, dtype=np.float32)
+            ch, cw = crop_size + np.random.rand(2) * (1 - crop_size)
+            return int(h * ch + 0.5), int(w * cw + 0.5)
+        if self.crop_type == "absolute":
+            return (min(self.crop_size[0], h), min(self.crop_size[1], w))
+        assert self.crop_size[0] <= self.crop_size[1]      # absolute_range
+        ch = np.random.randint(min(h, self.crop_size[0]), min(h, self.crop_size[1]) + 1)
+        cw = np.random.randint(min(w, self.crop_size[0]), min(w, self.crop_size[1]) + 1)
+        return ch, cw
+
+    def __repr__(self):
+        return "RandomCrop(crop_type={!r}, crop_size={!r})".format(self.crop_type, self.crop_size)
+
+
+class RandomFlip:
+    """reference augmentation_impl.py:91-120, horizontal flips (the only kind build_augmentation creates)."""
+
+    def __init__(self, prob=0.5, *, horizontal=True, vertical=False):
+        if horizontal and vertical:
+            raise ValueError("Cannot do both horiz and vert. Please use two Flip instead.")
+        if not horizontal and not vertical:
+            raise ValueError("At least one of horiz or vert has to be True!")
+        if vertical:
+            raise NotImplementedError("RandomFlip(vertical=True): only the horizontal flip of the shipped configs is implemented")
+        self.prob = prob
+
+    def get_transform(self, img):
+        w = int(img.shape[1])
+        do = np.random.uniform(0, 1.0, []) < self.prob      # Augmentation._rand_range()
+        return HFlipTransform(w) if do else NoOpTransform()
+
+
+class TrainInputParams:
+    """What one draw of the training augmentations decided, as the integers the batch kernel needs: the crop window (x0, y0, w, h)
+    in the source image (the whole image without a crop), the size after the resize, and the flip decision."""
+
+    def __init__(self, h, w):
+        self.crop = (0, 0, int(w), int(h))
+        self.new_size = (int(h), int(w))
+        self.flip = False
+
+    def job(self):
+        return self.crop + self.new_size + (self.flip,)
+
+    def __repr__(self):
+        return "TrainInputParams(crop={}, new_size={}, flip={})".format(self.crop, self.new_size, self.flip)
+
+
+class AugmentationList:
+    """AugInput.apply_augmentations (reference augmentation.py:212-245) for images known by their size alone: asks each policy in
+    turn for its transform, handing the next one the size the previous transform leaves.  `draw(h, w)` -> (TransformList,
+    TrainInputParams).  A crop is only understood in front of the resize and a flip behind it (the order from_config builds)."""
+
+    def __init__(self, augmentations):
+        self.augmentations = list(augmentations)
+
+    def draw(self, h, w):
+        p = TrainInputParams(h, w)
+        tfms = []
+        for aug in self.augmentations:
+            t = aug.get_transform(_Shape(h, w))
+            if t is None:
+                t = NoOpTransform()
+            if isinstance(t, CropTransform):
+                assert not tfms or all(isinstance(u, NoOpTransform) for u in tfms), "a crop must come first"
+                p.crop = (t.x0, t.y0, t.w, t.h)
+                p.new_size = (t.h, t.w)
+                h, w = t.h, t.w
+            elif isinstance(t, ResizeTransform):
+                assert not p.flip, "a resize must come before the flip"
+                p.new_size = (t.new_h, t.new_w)
+                h, w = t.new_h, t.new_w
+            elif isinstance(t, HFlipTransform):
+                p.flip = not p.flip
+            elif not isinstance(t, NoOpTransform):
+                raise NotImplementedError("transform {} is not part of the device training input".format(type(t).__name__))
+            tfms.append(t)
+        return TransformList(tfms), p

@@ -1634,6 +1634,90 @@ def tta_resize_u8(img, H, W, strides, hjobs, vjobs, mean, std):
     check(rc, "lvc_tta_resize_u8")
 
 
+TRAIN_INPUT_LAUNCHES = []  # kernel launches of the last (up to 64) lvc_train_input_u8 calls, as the library counted them
+TRAIN_INPUT_FIELDS = 24   # int64 words per job of lvc_train_input_u8 (include/lvc_amd.h)
+
+
+class TrainInputWorkspace:
+    """Buffers of one lvc_train_input_u8 call, reused from batch to batch (grown, never shrunk): the pinned host blob (job table +
+    coefficient tables), its device copy and the horizontal pass's uint8 intermediate.  `uploaded` is recorded after the blob's
+    copy is queued: the host blob must not be rewritten before it has passed (`wait_host`)."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self.host = self.dev = self.tmp = self.uploaded = None
+
+    def wait_host(self):
+        if self.uploaded is not None:
+            self.uploaded.synchronize()      # this event only: the copy out of the pinned blob, queued two batches ago
+
+    def reserve(self, blob_bytes, tmp_bytes):
+        if self.host is None or self.host.numel() < blob_bytes:
+            n = max(blob_bytes * 3 // 2, 1 << 16)
+            self.host = torch.empty(n, dtype=torch.uint8).pin_memory()
+            self.dev = torch.empty(n, dtype=torch.uint8, device=self.device)
+        if self.tmp is None or self.tmp.numel() < tmp_bytes:
+            self.tmp = torch.empty(max(tmp_bytes * 3 // 2, 1 << 16), dtype=torch.uint8, device=self.device)
+
+
+def train_input_u8(images, jobs, out, mean, std, coeffs_fn, want_u8=False, workspace=None):
+    """RandomCrop -> ResizeShortestEdge -> RandomFlip -> normalise + pad of a whole batch in two launches (csrc/train_input.hip
+    lvc_train_input_u8), on the current stream.  images: uint8 device tensors [H,W,3] (any strides: an HWC view of a CHW tensor
+    is read in place); jobs: per image (x0, y0, crop_w, crop_h, new_h, new_w, flip); out [n_slots,Hp,Wp,4] fp32 contiguous: image i
+    fills slot i completely.  coeffs_fn(in, out) -> (bounds, coefficients, ksize) numpy tables (data.transforms.resample_coeffs).
+    Returns the uint8 [new_h,new_w,3] results when want_u8 (else None).  One host->device copy carries every table."""
+    import numpy as np
+
+    B = len(images)
+    assert B == len(jobs) and B > 0
+    _req_cuda(out, *images)
+    assert out.dim() == 4 and out.shape[3] == 4 and out.is_contiguous() and out.dtype == torch.float32 and out.shape[0] >= B
+    ws = workspace if workspace is not None else TrainInputWorkspace(out.device)
+    tab = np.zeros((B, TRAIN_INPUT_FIELDS), np.int64)
+    tables, off, tmp_off = [], B * TRAIN_INPUT_FIELDS * 8, 0
+    u8 = []
+    for i, (img, (x0, y0, cw, ch, nh, nw, flip)) in enumerate(zip(images, jobs)):
+        assert img.dtype == torch.uint8 and img.dim() == 3 and img.shape[2] == 3 and img.device == out.device
+        row = tab[i]
+        row[0:6] = (img.data_ptr(), img.shape[0], img.shape[1], img.stride(0), img.stride(1), img.stride(2))
+        row[6:12] = (x0, y0, cw, ch, nh, nw)
+        row[12] = row[15] = -1
+        for size_in, size_out, at in ((cw, nw, 12), (ch, nh, 15)):
+            if size_in != size_out:
+                b, k, ks = coeffs_fn(size_in, size_out)
+                row[at], row[at + 1], row[at + 2] = off, off + b.nbytes, ks
+                tables += [b, k]
+                off += b.nbytes + k.nbytes
+        row[18], row[19] = int(bool(flip)), i
+        if want_u8:
+            u8.append(torch.empty(nh, nw, 3, dtype=torch.uint8, device=out.device))
+            row[20] = u8[-1].data_ptr()
+        if nw != cw:
+            row[21] = tmp_off
+            tmp_off += (ch * nw * 3 + 255) & ~255
+    ws.wait_host()
+    ws.reserve(off, tmp_off)
+    hb = ws.host.numpy()
+    hb[:tab.nbytes] = tab.reshape(-1).view(np.uint8)
+    at = tab.nbytes
+    for t in tables:
+        hb[at:at + t.nbytes] = np.ascontiguousarray(t, np.int32).reshape(-1).view(np.uint8)
+        at += t.nbytes
+    ws.dev[:off].copy_(ws.host[:off], non_blocking=True)
+    ws.uploaded = torch.cuda.Event()
+    ws.uploaded.record(torch.cuda.current_stream(out.device))
+    m = (c_float * 3)(*[float(v) for v in mean])
+    s = (c_float * 3)(*[float(v) for v in std])
+    n = c_int(0)
+    rc = _lib.lib().lvc_train_input_u8(ptr(ws.host), ptr(ws.dev), c_longlong(off), c_int(B), ptr(ws.tmp), c_longlong(ws.tmp.numel()),
+                                       ptr(out), c_int(out.shape[0]), c_int(out.shape[1]), c_int(out.shape[2]), m, s, ctypes.byref(n),
+                                       _stream(out))
+    check(rc, "lvc_train_input_u8")
+    TRAIN_INPUT_LAUNCHES.append(n.value)
+    del TRAIN_INPUT_LAUNCHES[:-64]
+    return u8 if want_u8 else None
+
+
 TTA_PARAM_STRIDE = 16     # floats per augmentation in lvc_tta_merge's inverse-transform table
 TTA_MAX_STEPS = 4
 

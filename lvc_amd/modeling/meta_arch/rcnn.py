@@ -53,6 +53,9 @@ class _RCNNBase(nn.Module):
     def preprocess_image(self, batched_inputs):
         """Normalize, pad and batch (reference rcnn.py:324-333).  Storage is NHWC with 4 channel slots;
         `.tensor` is the NCHW-shaped [N,3,Hp,Wp] view of it."""
+        if "prepared" in batched_inputs[0] and "image" not in batched_inputs[0]:
+            # lvc_amd.data.build_detection_train_loader: the batch is already normalised, padded and batched on the device
+            return batched_inputs[0]["prepared"].image_list(self.device)
         if "image" not in batched_inputs[0] and "raw" in batched_inputs[0]:
             return self._preprocess_raw(batched_inputs)
         images = [x["image"].to(self.device, non_blocking=True) for x in batched_inputs]
