@@ -56,8 +56,11 @@ void lvc_set_error(const char* fmt, ...);
  *                             stream-K decomposition); launches on different streams need different workspaces
  */
 long long lvc_conv_workspace_bytes(void);
+/* Byte offset, inside that workspace, of the range / error words described next (behind the partial tiles and the worker
+ * flags; the layout is csrc/conv_common.h's).  Hosts read the words at this offset instead of restating the layout. */
+long long lvc_conv_range_words_offset(void);
 /* Per-layer range words.  The workspace ends in lvc_range_slots() int32 words behind the worker flags (byte offset
- * 1024*256*128*4 + 1024*4).  Word 0 is the shared error word (bit 0: a stream-K worker timed out; bit 1: an operand left a
+ * lvc_conv_range_words_offset()).  Word 0 is the shared error word (bit 0: a stream-K worker timed out; bit 1: an operand left a
  * two-way fp16 split kernel's range).  lvc_set_range_slot(s), 0 < s < lvc_range_slots(), makes the fp16-split conv/GEMM
  * launches that follow ON THE CALLING THREAD raise their bits in word s instead, so the host can re-route exactly the layer
  * that overflowed (lvc_amd.kernels.check_conv_error_word); 0 restores the shared word. */

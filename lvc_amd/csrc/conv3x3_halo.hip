@@ -17,15 +17,9 @@
 // [3][Kpad][Kg] with k order (c/32, r, s, c%32), stream-K workers with partial-tile hand-off, fused
 // scale/shift/residual/ReLU epilogue through LDS -- is the contract of conv_bf16x3.hip, so both kernels are
 // interchangeable on a 3x3 layer (tests/test_gpu_kernels.py runs both against the same oracle).
-#include "common.h"
+#include "conv_common.h"
 #include <stdlib.h>
 #include <type_traits>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 #define HM 256           // output pixels per tile (patch area <= HM)
 #define LROW 40          // bf16 elements per LDS row (32 + 8 pad = 80 B: conflict-free ds_read_b128)
@@ -33,7 +27,6 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 #define NJ 6
 #define PLANE_A (HALO_MAX * LROW)
 #define NT 512
-#define SPIN_LIMIT (1 << 24)
 
 struct HaloArgs {
   const float* x;
@@ -272,25 +265,14 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_halo_kernel(HaloArgs p) {
           }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
-      if (tid == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __hip_atomic_store(p.flags + lw, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
+      if (tid == 0) lvc_publish_partial(p.flags, lw);
       continue;
     }
     if (cc1 < p.nk) {
       const int last_unit = tile * p.nk + p.nk - 1;
       const int last_worker = last_unit / p.units_per_worker;
       for (int pw = lw + 1; pw <= last_worker; ++pw) {
-        if (tid == 0) {
-          int spins = 0;
-          while (__hip_atomic_load(p.flags + pw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) {
-            __builtin_amdgcn_s_sleep(4);
-            if (++spins > SPIN_LIMIT) { atomicOr(p.flags + p.err_index, 1); break; }
-          }
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        }
+        if (tid == 0) lvc_wait_partial(p.flags, pw, p.err_index);
         __syncthreads();
         const float* src = p.partials + (size_t)pw * (NT * 32 * NI);
 #pragma unroll
@@ -304,7 +286,7 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_halo_kernel(HaloArgs p) {
               acc[mi][ni][e4 * 4 + 2] += v[2]; acc[mi][ni][e4 * 4 + 3] += v[3];
             }
         __syncthreads();
-        if (tid == 0) __hip_atomic_store(p.flags + pw, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (tid == 0) lvc_release_partial(p.flags, pw);
       }
     }
 
@@ -366,9 +348,6 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_halo_kernel(HaloArgs p) {
     __syncthreads();
   }
 }
-
-#define LVC_MAX_WORKERS 1024
-static int g_cus_halo = 0;
 
 extern "C" int lvc_conv2d_nhwc_bf16x3(const float* x, const unsigned short* w_split, const float* scale,
                                       const float* shift, const float* residual, float* y, int N, int H, int W, int C,
@@ -436,20 +415,12 @@ extern "C" int lvc_conv3x3_nhwc_bf16x3(const float* x, const unsigned short* w_s
   const long long xb = (long long)N * H * W * C * 4, wb = (long long)(lvc_cdiv(K, 128) * 128) * Kg * 2;   // planes are padded to 128 rows
   LVC_CHECK_ARG(xb < (1ll << 31) && 3 * wb < (1ll << 31), "input / weight tensor must be smaller than 2 GiB");
   a.x_bytes = (int)xb; a.w_plane_bytes = (int)wb;
-  if (g_cus_halo == 0) {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-    g_cus_halo = cus;
-  }
-  int cap = g_cus_halo;  // one worker per CU: 150 KB of LDS per workgroup
+  int cap = lvc_cu_count();  // one worker per CU: 150 KB of LDS per workgroup
   if (cap > LVC_MAX_WORKERS) cap = LVC_MAX_WORKERS;
-  int workers = (int)(units < cap ? units : cap);
-  a.units_per_worker = (int)((units + workers - 1) / workers);
-  a.nworkers = (int)((units + a.units_per_worker - 1) / a.units_per_worker);
+  lvc_plan_workers(units, cap, 1, &a.units_per_worker, &a.nworkers);
   a.partials = (float*)workspace;
-  a.flags = (int*)((char*)workspace + (size_t)LVC_MAX_WORKERS * 256 * 128 * 4);
-  a.err_index = LVC_MAX_WORKERS;
+  a.flags = lvc_ws_flags(workspace);
+  a.err_index = lvc_ws_range_index(0);
   if (ni == 1)
     hipLaunchKernelGGL(conv3x3_halo_kernel<1>, dim3(a.nworkers), dim3(NT), 0, (hipStream_t)stream, a);
   else

@@ -15,16 +15,9 @@
 // (activations of this network are O(1e2); `LVC_CONV_SPLIT=bf16x3` selects the range-free kernels).
 // Everything else (patch tiling, halo staging once per 32-channel chunk, weight planes streamed per tap, stream-K workers,
 // epilogue) is conv3x3_halo.hip's.
-#include "common.h"
+#include "conv_common.h"
 #include <stdlib.h>
 #include <type_traits>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16;
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 #define HM 256           // output pixels per tile (patch area <= HM)
 #define LROW 40          // fp16 elements per LDS row (32 + 8 pad = 80 B: conflict-free ds_read_b128)
@@ -32,7 +25,6 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 #define NJ 6
 #define PLANE_A (HALO_MAX * LROW)
 #define NT 512
-#define SPIN_LIMIT (1 << 24)
 
 struct HaloArgsH {
   const float* x;
@@ -50,11 +42,6 @@ struct HaloArgsH {
                 // tile each, so a halo patch is fetched from the fabric once and served to the others by that XCD's L2
   int x_bytes, w_plane_bytes;
 };
-
-__device__ __forceinline__ void split2h(float a, f16& h, f16& m) {
-  h = (f16)a;
-  m = (f16)((a - (float)h) * 2048.f);
-}
 
 // NI = 32-column MFMA blocks per wave: NI = 2 -> 128 output channels per tile (wave tile 64 x 64), NI = 1 -> 64 output
 // channels per tile (wave tile 64 x 32; the 64-channel res2 layers, which would waste half of a 128-wide tile).
@@ -154,7 +141,7 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_halo_h2_kernel(HaloArgsH p) {
             h[e] = hh; m[e] = mm;
             big = fmaxf(big, fabsf(areg[j][e]));
           }
-          if (!(big <= 65504.f)) range_err = 1;   // beyond fp16 (or NaN): reported through the workspace error word
+          if (!(big <= LVC_F16_MAX)) range_err = 1;   // beyond fp16 (or NaN): reported through the workspace error word
           const int o = (hrow + 64 * j) * LROW + q * 4;
           *reinterpret_cast<f16x4*>(sA + o) = h;
           *reinterpret_cast<f16x4*>(sA + PLANE_A + o) = m;
@@ -284,11 +271,7 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_halo_h2_kernel(HaloArgsH p) {
           }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
-      if (tid == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __hip_atomic_store(p.flags + lw, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
+      if (tid == 0) lvc_publish_partial(p.flags, lw);
       continue;
     }
     if (cc1 < p.nk) {
@@ -296,14 +279,7 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_halo_h2_kernel(HaloArgsH p) {
       const int wstep = p.ngroup > 1 ? p.ngroup : 1;
       const int last_worker = (last_unit / p.units_per_worker) * wstep + wsel;
       for (int pw = lw + wstep; pw <= last_worker; pw += wstep) {
-        if (tid == 0) {
-          int spins = 0;
-          while (__hip_atomic_load(p.flags + pw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) {
-            __builtin_amdgcn_s_sleep(4);
-            if (++spins > SPIN_LIMIT) { atomicOr(p.flags + p.err_index, 1); break; }
-          }
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        }
+        if (tid == 0) lvc_wait_partial(p.flags, pw, p.err_index);
         __syncthreads();
         const float* src = p.partials + (size_t)pw * (NT * 32 * NI);
 #pragma unroll
@@ -317,7 +293,7 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_halo_h2_kernel(HaloArgsH p) {
               acc[mi][ni][e4 * 4 + 2] += v[2]; acc[mi][ni][e4 * 4 + 3] += v[3];
             }
         __syncthreads();
-        if (tid == 0) __hip_atomic_store(p.flags + pw, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (tid == 0) lvc_release_partial(p.flags, pw);
       }
     }
 
@@ -381,9 +357,6 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_halo_h2_kernel(HaloArgsH p) {
   if (range_err) atomicOr(p.flags + p.err_index, 2);
 }
 
-#define LVC_MAX_WORKERS 1024
-static int g_cus_halo_h = 0;
-
 // Patch shape for an H x W output: PH * PW <= 256 pixels, (PH + 2) * (PW + 2) <= HALO_MAX halo pixels, fewest patches
 // (every patch costs a full 256-row MFMA tile whatever its fill); ties go to the smaller halo.
 static void pick_patch_h(int H, int W, int* PH, int* PW) {
@@ -438,13 +411,7 @@ extern "C" int lvc_conv3x3_nhwc_f16x2(const float* x, const unsigned short* w_sp
   const long long xb = (long long)N * H * W * C * 4, wb = (long long)(lvc_cdiv(K, 128) * 128) * Kg * 2;   // planes are padded to 128 rows
   LVC_CHECK_ARG(xb < (1ll << 31) && 2 * wb < (1ll << 31), "input / weight tensor must be smaller than 2 GiB");
   a.x_bytes = (int)xb; a.w_plane_bytes = (int)wb;
-  if (g_cus_halo_h == 0) {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-    g_cus_halo_h = cus;
-  }
-  int cap = g_cus_halo_h;  // one worker per CU: 150 KB of LDS per workgroup
+  int cap = lvc_cu_count();  // one worker per CU: 150 KB of LDS per workgroup
   if (cap > LVC_MAX_WORKERS) cap = LVC_MAX_WORKERS;
   // Two or four output-channel tiles: the workers of a group share their pixel tiles (see HaloArgsH::ngroup); the unit
   // space is then pixel tiles x chunks only.
@@ -455,12 +422,11 @@ extern "C" int lvc_conv3x3_nhwc_f16x2(const float* x, const unsigned short* w_sp
     cap /= a.tiles_n;
     a.total_units = (int)units;
   }
-  int workers = (int)(units < cap ? units : cap);
-  a.units_per_worker = (int)((units + workers - 1) / workers);
-  a.nworkers = (int)((units + a.units_per_worker - 1) / a.units_per_worker) * a.ngroup;
+  lvc_plan_workers(units, cap, 1, &a.units_per_worker, &a.nworkers);
+  a.nworkers *= a.ngroup;
   a.partials = (float*)workspace;
-  a.flags = (int*)((char*)workspace + (size_t)LVC_MAX_WORKERS * 256 * 128 * 4);
-  a.err_index = LVC_MAX_WORKERS + lvc_range_slot();   // the layer's own range word (common.cpp)
+  a.flags = lvc_ws_flags(workspace);
+  a.err_index = lvc_ws_range_index(lvc_range_slot());   // the layer's own range word (common.cpp)
   if (ni == 1)
     hipLaunchKernelGGL((conv3x3_halo_h2_kernel<1>), dim3(a.nworkers), dim3(NT), 0, (hipStream_t)stream, a);
   else

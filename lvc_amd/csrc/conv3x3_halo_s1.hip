@@ -24,24 +24,15 @@
 //     under the MFMAs of taps 4..6 -- no refill phase between chunks, the tap pipeline runs through.
 // Tiling (<= 256-pixel patches x 64 NI channels, 8 waves as 4 x 2), stream-K workers with grouped channel tiles, partial-tile
 // hand-off and the epilogue through LDS are conv3x3_halo_h2.hip's.
-#include "common.h"
+#include "conv_common.h"
 #include <type_traits>
 #include <stdlib.h>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16;
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
 #define HM 256            // output pixels per tile (patch area <= HM)
 #define LROW 40           // fp16 elements per halo row in LDS (32 + 8 pad = 80 B: conflict-free ds_read_b128)
 #define HALO_S1 340       // halo pixels per tile: two buffers x two planes x 340 x 80 B = 108,800 B
 #define NJ 6              // halo pixels per thread (6 x 64 pixel slots x 8 float4 slots)
 #define NT 512
-#define SPIN_LIMIT (1 << 24)
-#define ACT_SCALE 16.f    // activations x 2^4 before the split (see the header)
-#define ACT_MAX 4094.f    // 65504 / 16
 #define HALO_MAX_LEVELS 6
 
 struct HaloArgsS {
@@ -82,14 +73,6 @@ struct HaloArgsS {
   long long pred_plane_elems;
   int pred_K, pred_err_index;
 };
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* glb_ptr_t;
-__device__ __forceinline__ void glds16(const void* g, void* l) {
-  __builtin_amdgcn_global_load_lds((glb_ptr_t)g, (lds_ptr_t)l, 16, 0, 0);
-}
-
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // ONEACC = true: the single-accumulator numerics of the header (row-scaled weight planes, activations x 2^4, residual planes unscaled).
 // ONEACC = false: conv3x3_halo_h2.hip's numerics in this kernel's pipeline -- residual planes x 2^11, a main (a1 b1) and a cross
@@ -204,7 +187,6 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_halo_s1_kernel(HaloArgsS p) {
   int u = wq * p.units_per_worker;
   const int u_end = min(u + p.units_per_worker, p.total_units);
 
-
   // fragment offsets.  A (halves): halo pixel of output pixel m at tap (0,0); rows past the patch read pixel 0.
   // B (bytes within a plane): row * 64 + swizzled granule of k16 step s2: ((s2 * 2 + fh) ^ ((row >> 2) & 3)) * 16
   int a_frag[2];
@@ -297,7 +279,7 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_halo_s1_kernel(HaloArgsS p) {
       f16x4 h, m;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const float a = ONEACC ? areg[j][e] * ACT_SCALE : areg[j][e];
+        const float a = ONEACC ? areg[j][e] * LVC_ACT_SCALE : areg[j][e];
         const f16 hh = (f16)a;
         h[e] = hh;
         m[e] = ONEACC ? (f16)(a - (float)hh) : (f16)((a - (float)hh) * 2048.f);
@@ -524,11 +506,7 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_halo_s1_kernel(HaloArgsS p) {
           }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
-      if (tid == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __hip_atomic_store(p.flags + lw, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
+      if (tid == 0) lvc_publish_partial(p.flags, lw);
       continue;
     }
     if (cc1 < p.nk) {
@@ -536,14 +514,7 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_halo_s1_kernel(HaloArgsS p) {
       const int wstep = p.ngroup > 1 ? p.ngroup : 1;
       const int last_worker = (last_unit / p.units_per_worker) * wstep + wsel;
       for (int pw = lw + wstep; pw <= last_worker; pw += wstep) {
-        if (tid == 0) {
-          int spins = 0;
-          while (__hip_atomic_load(p.flags + pw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) {
-            __builtin_amdgcn_s_sleep(4);
-            if (++spins > SPIN_LIMIT) { atomicOr(p.flags + p.err_index, 1); break; }
-          }
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        }
+        if (tid == 0) lvc_wait_partial(p.flags, pw, p.err_index);
         __syncthreads();
         const float* src = p.partials + (size_t)pw * (NT * 32 * NI);
 #pragma unroll
@@ -557,7 +528,7 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_halo_s1_kernel(HaloArgsS p) {
               acc[mi][ni][e4 * 4 + 2] += v[2]; acc[mi][ni][e4 * 4 + 3] += v[3];
             }
         __syncthreads();
-        if (tid == 0) __hip_atomic_store(p.flags + pw, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (tid == 0) lvc_release_partial(p.flags, pw);
       }
     }
 
@@ -640,7 +611,7 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_halo_s1_kernel(HaloArgsS p) {
         }
       }
       // the pointwise layer's own range word: a hidden value beyond fp16
-      if (!(bigp <= 65504.f)) atomicOr(p.flags + p.pred_err_index, bigp < INFINITY ? 2 : 4);
+      lvc_report_range(p.flags, p.pred_err_index, bigp, LVC_F16_MAX);
       __syncthreads();
       continue;
     }
@@ -710,7 +681,7 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_halo_s1_kernel(HaloArgsS p) {
               f16x4s h, l;
 #pragma unroll
               for (int e = 0; e < 4; ++e) {
-                const float a = v[e] * ACT_SCALE;
+                const float a = v[e] * LVC_ACT_SCALE;
                 const f16 hh = (f16)a;
                 h[e] = hh;
                 l[e] = (f16)(a - (float)hh);
@@ -727,7 +698,8 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_halo_s1_kernel(HaloArgsS p) {
       using T0 = std::integral_constant<int, 0>; using T1 = std::integral_constant<int, 1>; using T2 = std::integral_constant<int, 2>;
       if (p.presplit) {      // (the entry point admits it without residual, with ReLU)
         rows(T0{}, std::true_type{}, std::true_type{});
-        if (!(bigq * ACT_SCALE <= ACT_MAX)) atomicOr(p.flags + p.next_err_index, bigq < INFINITY ? 2 : 4);
+        // not lvc_report_range: this copy compares the SCALED value, unlike every other one (the presplit range check); kept as it is
+        if (!(bigq * LVC_ACT_SCALE <= LVC_ACT_MAX)) atomicOr(p.flags + p.next_err_index, bigq < INFINITY ? 2 : 4);
       }
       else if (p.res_mode == 0) { if (p.relu) rows(T0{}, std::true_type{}, std::false_type{}); else rows(T0{}, std::false_type{}, std::false_type{}); }
       else if (p.res_mode == 1) { if (p.relu) rows(T1{}, std::true_type{}, std::false_type{}); else rows(T1{}, std::false_type{}, std::false_type{}); }
@@ -740,18 +712,13 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_halo_s1_kernel(HaloArgsS p) {
   }
 #ifdef HALO_TIMELINE
   if (lane == 0 && (blockIdx.x & 15) == 0) {
-    unsigned long long* d = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(p.partials) + (size_t)512 * 256 * 128 * 4) + ((blockIdx.x >> 4) * 8 + wave) * 16;
+    unsigned long long* d = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(p.partials) + LVC_WS_DIAG_OFFSET) + ((blockIdx.x >> 4) * 8 + wave) * 16;
     d[0] = tl_run; d[1] = tl_vm; d[2] = tl_bar; d[3] = tl_n; d[4] = tl_pro; d[5] = tl_epi; d[6] = __builtin_readcyclecounter() - tl_t0; d[7] = 1;
     d[8] = tl_hand; d[9] = tl_cs;
   }
 #endif
-  // bit 1: a FINITE activation beyond the form's range; bit 2: a non-finite one (usually what an upstream layer that left ITS range
-  // in this pass handed down: kernels.check_conv_error_word does not move this layer for it while another layer reports bit 1)
-  if (!(big <= (ONEACC ? ACT_MAX : 65504.f))) atomicOr(p.flags + p.err_index, big < INFINITY ? 2 : 4);
+  lvc_report_range(p.flags, p.err_index, big, ONEACC ? LVC_ACT_MAX : LVC_F16_MAX);
 }
-
-#define LVC_MAX_WORKERS 1024
-static int g_cus_halo_s = 0;
 
 // Patch shape for an H x W output: PH * PW <= 256 pixels, (PH + 2) * (PW + 2) <= HALO_S1 halo pixels, fewest patches
 // (every patch costs a full 256-row MFMA tile whatever its fill); ties go to the smaller halo.
@@ -780,13 +747,7 @@ static int halo_s1_finish(HaloArgsS& a, bool oneacc, long long tiles_m_total, in
   LVC_CHECK_ARG(units < (1ll << 31), "iteration space too large");
   a.total_units = (int)units;
   a.w_plane_elems = (long long)(lvc_cdiv(a.K, 128) * 128) * Kg;   // planes are padded to 128 rows
-  if (g_cus_halo_s == 0) {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-    g_cus_halo_s = cus;
-  }
-  int cap = g_cus_halo_s;  // one worker per CU (154 KB of LDS per workgroup)
+  int cap = lvc_cu_count();  // one worker per CU (154 KB of LDS per workgroup)
   if (cap > LVC_MAX_WORKERS) cap = LVC_MAX_WORKERS;
   a.ngroup = 1;
   if ((a.tiles_n == 2 || a.tiles_n == 4) && cap % a.tiles_n == 0 && units / a.tiles_n >= cap / a.tiles_n) {
@@ -795,12 +756,11 @@ static int halo_s1_finish(HaloArgsS& a, bool oneacc, long long tiles_m_total, in
     cap /= a.tiles_n;
     a.total_units = (int)units;
   }
-  int workers = (int)(units < cap ? units : cap);
-  a.units_per_worker = (int)((units + workers - 1) / workers);
-  a.nworkers = (int)((units + a.units_per_worker - 1) / a.units_per_worker) * a.ngroup;
+  lvc_plan_workers(units, cap, 1, &a.units_per_worker, &a.nworkers);
+  a.nworkers *= a.ngroup;
   a.partials = (float*)workspace;
-  a.flags = (int*)((char*)workspace + (size_t)LVC_MAX_WORKERS * 256 * 128 * 4);
-  a.err_index = LVC_MAX_WORKERS + lvc_range_slot();   // the layer's own range word (common.cpp)
+  a.flags = lvc_ws_flags(workspace);
+  a.err_index = lvc_ws_range_index(lvc_range_slot());   // the layer's own range word (common.cpp)
   hipStream_t st = (hipStream_t)stream;
   if (a.pred_w) {
     LVC_CHECK_ARG(!oneacc && ni == 2, "pointwise layer on top: the two-accumulator form with >= 128 hidden channels");
@@ -855,7 +815,7 @@ static int halo_s1_launch(bool oneacc, const float* x, const unsigned short* w_s
                     ((uintptr_t)workspace & 15) == 0 && ((uintptr_t)scale & 15) == 0, "pointers must be 16-byte aligned");
   if (presplit) LVC_CHECK_ARG(oneacc && relu == 1 && res_mode == 0 && K % 32 == 0 && a.ldy == K, "pre-split output: single accumulator, ReLU, no residual, K % 32 == 0, dense rows");
   if (presplit) LVC_CHECK_ARG(next_slot > 0 && next_slot < lvc_range_slots(), "pre-split output: the consumer's range slot");
-  a.presplit = presplit; a.next_err_index = LVC_MAX_WORKERS + next_slot;
+  a.presplit = presplit; a.next_err_index = lvc_ws_range_index(next_slot);
   halo_s1_patch(a, H, W);
   a.tiles_x = lvc_cdiv(W, a.PW); a.tiles_y = lvc_cdiv(H, a.PH);
   const long long xb = (long long)N * H * W * C * 4;
@@ -892,7 +852,7 @@ static int halo_s1_levels(int oneacc, const float* const* xs, float* const* ys, 
     LVC_CHECK_ARG(pred->slot > 0 && pred->slot < lvc_range_slots(), "pointwise layer on top: its range slot");
     a.pred_w = pred->w; a.pred_scale = pred->scale; a.pred_shift = pred->shift; a.pred_K = pred->K;
     a.pred_plane_elems = (long long)pred->rows * K;
-    a.pred_err_index = LVC_MAX_WORKERS + pred->slot;
+    a.pred_err_index = lvc_ws_range_index(pred->slot);
     a.ldy = pred->ld;
   }
   int big = 0;      // the patch shape is chosen for the largest map, wherever it stands in the list
@@ -1022,7 +982,7 @@ __global__ __launch_bounds__(256) void split_rowscaled_kernel(const float* __res
 extern "C" int lvc_split_weights_rowscaled(const float* wp, int rows, int Kg, void* planes_out, float* row_factor, void* stream) {
   LVC_CHECK_ARG(wp && planes_out && row_factor && rows > 0 && Kg > 0, "bad arguments");
   hipLaunchKernelGGL(split_rowscaled_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, wp, Kg, (long long)rows * Kg,
-                     (unsigned short*)planes_out, row_factor, 1.f / ACT_SCALE);
+                     (unsigned short*)planes_out, row_factor, 1.f / LVC_ACT_SCALE);
   LVC_CHECK_LAUNCH();
   return LVC_OK;
 }

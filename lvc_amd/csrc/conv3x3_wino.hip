@@ -20,16 +20,9 @@
 // is multiplied; the transformed weight planes of a (filter row, chunk) -- 4 positions x 2 planes x 128 channels x 32 B = 32 KB, stored
 // in exactly that order by lvc_amd.kernels.pack_wino -- arrive by LDS-DMA one stage ahead into a ring of two.  A stage = (chunk, filter
 // row): 24 MFMAs per wave, one barrier.
-#include "common.h"
+#include "conv_common.h"
 #include <stdlib.h>
 #include <type_traits>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16;
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 #define WN_NT 512
 #define WN_PAIRS 128
@@ -39,9 +32,6 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 #define WN_VBUF (8 * WN_PP)                // 40,960 B: 2 planes x 4 positions
 #define WN_USLOT (8 * WN_CH * 32)          // 32,768 B: 4 positions x 2 planes x 128 channel rows x 32 B
 #define WN_SMEM (2 * WN_VBUF + 2 * WN_USLOT)
-#define ACT_SCALE 16.f
-#define ACT_MAX 4094.f
-#define LVC_MAX_WORKERS 1024
 
 struct WinoArgs {
   const float* x;              // [N,H,W,C]
@@ -63,14 +53,9 @@ struct WinoArgs {
   int pred_K, pred_err_index;
 };
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* glb_ptr_t;
-__device__ __forceinline__ void wn_glds16(const void* g, void* l) { __builtin_amdgcn_global_load_lds((glb_ptr_t)g, (lds_ptr_t)l, 16, 0, 0); }
-// behind it: at most N vector-memory operations outstanding and every LDS operation of this wave complete
-template <int N> __device__ __forceinline__ void wn_wait_vm_lds() { asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory"); }
 // One tile segment: chunks [cc0, cc1) of tile t.  Whole tiles (cc0 = 0, cc1 = nk) go straight to the epilogue.  Stream-K (SK): a worker
 // whose segment does not hold the tile's first chunk hands its partial sums (still in the transformed domain: the output transform is
-// linear) to the worker that does -- the protocol of conv3x3_halo_s1.hip: partials [worker][128 values][512 threads], a flag per
+// linear) to the worker that does -- the hand-off of conv_common.h: partials [worker][128 values][512 threads], a flag per
 // worker, the owner adds the later workers' parts in worker order (deterministic) and runs the epilogue.  lw = this worker.
 template <bool PRED, bool SK>
 __device__ __forceinline__ void wino_tile(const WinoArgs& p, const int t, const int cc0, const int cc1, const int lw, unsigned char* const smem) {
@@ -157,7 +142,7 @@ __device__ __forceinline__ void wino_tile(const WinoArgs& p, const int t, const 
   auto split = [&](f32x4 v, f16x4& h, f16x4& l) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      const float a = v[e] * ACT_SCALE;
+      const float a = v[e] * LVC_ACT_SCALE;
       const f16 hh = (f16)a;
       h[e] = hh;
       l[e] = (f16)(a - (float)hh);
@@ -195,7 +180,7 @@ __device__ __forceinline__ void wino_tile(const WinoArgs& p, const int t, const 
   auto dma_u = [&](int kc, int r, int slot) {
     const unsigned short* s = u_src + (size_t)((r * nk + kc) * 8) * u_img;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) wn_glds16(s + j * 32 * 16, sU + slot * WN_USLOT + wave * 4096 + j * 1024);
+    for (int j = 0; j < 4; ++j) glds16(s + j * 32 * 16, sU + slot * WN_USLOT + wave * 4096 + j * 1024);
   };
 
   // ---- fragments.  A: V row m + r PWP of (plane, position); B: channel row of (position, plane)
@@ -292,7 +277,7 @@ __device__ __forceinline__ void wino_tile(const WinoArgs& p, const int t, const 
     prep1();                              // (chunk 0: the prologue's values once more)
     write1(vb);
     __builtin_amdgcn_sched_barrier(0);
-    wn_wait_vm_lds<4>();                  // the DMA; round 0's loads stay in flight
+    wait_vm_lds<4>();                  // the DMA; round 0's loads stay in flight
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
     // r = 1: round 1 of the next chunk is requested
@@ -300,7 +285,7 @@ __device__ __forceinline__ void wino_tile(const WinoArgs& p, const int t, const 
     load1(kn);
     stage_mma(vb, sU + (1 - s0) * WN_USLOT, 1);
     __builtin_amdgcn_sched_barrier(0);
-    wn_wait_vm_lds<2>();
+    wait_vm_lds<2>();
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
     // r = 2: round 0 of the next chunk is converted and written
@@ -309,11 +294,11 @@ __device__ __forceinline__ void wino_tile(const WinoArgs& p, const int t, const 
     prep0();
     write0(vnext);
     __builtin_amdgcn_sched_barrier(0);
-    wn_wait_vm_lds<0>();
+    wait_vm_lds<0>();
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
   }
-  if (!(big <= ACT_MAX)) atomicOr(p.flags + p.err_index, big < INFINITY ? 2 : 4);      // finite / non-finite: see conv3x3_halo_s1.hip
+  lvc_report_range(p.flags, p.err_index, big, LVC_ACT_MAX);
 
   if constexpr (SK) {
     if (cc0 != 0) {          // not the tile's owner: publish the partial sums, done
@@ -333,25 +318,14 @@ __device__ __forceinline__ void wino_tile(const WinoArgs& p, const int t, const 
             }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
-      if (tid == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __hip_atomic_store(p.flags + lw, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
+      if (tid == 0) lvc_publish_partial(p.flags, lw);
       return;
     }
     if (cc1 < nk) {          // the owner of a split tile: add the later workers' parts in worker order
       const int last_worker = (t * nk + nk - 1) / p.units_per_worker;
 #pragma unroll 1
       for (int pw = lw + 1; pw <= last_worker; ++pw) {
-        if (tid == 0) {
-          int spins = 0;
-          while (__hip_atomic_load(p.flags + pw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) {
-            __builtin_amdgcn_s_sleep(4);
-            if (++spins > (1 << 24)) { atomicOr(p.flags + p.err_index, 1); break; }
-          }
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        }
+        if (tid == 0) lvc_wait_partial(p.flags, pw, p.err_index);
         __syncthreads();
         const __amdgpu_buffer_rsrc_t pres = __builtin_amdgcn_make_buffer_rsrc((void*)(p.partials + (size_t)pw * (WN_NT * 128)), 0, WN_NT * 128 * 4, 0x00020000);
         const unsigned toff = (unsigned)tid * 16u;
@@ -373,7 +347,7 @@ __device__ __forceinline__ void wino_tile(const WinoArgs& p, const int t, const 
               __builtin_amdgcn_sched_barrier(0);
             }
         __syncthreads();
-        if (tid == 0) __hip_atomic_store(p.flags + pw, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (tid == 0) lvc_release_partial(p.flags, pw);
       }
     }
   }
@@ -501,7 +475,7 @@ __device__ __forceinline__ void wino_tile(const WinoArgs& p, const int t, const 
         if (oy < p.H && ox < p.W) unsafeAtomicAdd(p.y + ((size_t)((long long)img * p.H + oy) * p.W + ox) * p.ldy + fi, v * psc + psh);
       }
     }
-    if (!(bigp <= 65504.f)) atomicOr(p.flags + p.pred_err_index, bigp < INFINITY ? 2 : 4);      // the pointwise layer's own range word
+    lvc_report_range(p.flags, p.pred_err_index, bigp, LVC_F16_MAX);      // the pointwise layer's own range word
   }
 }
 
@@ -544,14 +518,8 @@ static int g_wino_streamk = 0;
 extern "C" void lvc_set_wino_streamk(int mode) { g_wino_streamk = mode; }
 
 static int wn_cus() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    cus = n / 8 * 8;
-    if (cus < 8) cus = 8;
-  }
-  return cus;
+  const int cus = lvc_cu_count() / 8 * 8;
+  return cus < 8 ? 8 : cus;
 }
 
 static int wino_launch(const float* x, const unsigned short* u, const float* scale, const float* shift, float* y, int N, int H, int W, int C,
@@ -574,11 +542,11 @@ static int wino_launch(const float* x, const unsigned short* u, const float* sca
   LVC_CHECK_ARG(nt < (1ll << 31), "too many tiles");
   a.ntiles = (int)nt;
   a.nk = C / 16;
-  a.flags = (int*)((char*)workspace + (size_t)LVC_MAX_WORKERS * 256 * 128 * 4);
-  a.err_index = LVC_MAX_WORKERS + lvc_range_slot();
+  a.flags = lvc_ws_flags(workspace);
+  a.err_index = lvc_ws_range_index(lvc_range_slot());
   a.pred_w = pred_w; a.pred_scale = pred_scale; a.pred_shift = pred_shift; a.pred_K = pred_K;
   a.pred_plane = (long long)pred_rows * K;
-  a.pred_err_index = LVC_MAX_WORKERS + pred_slot;
+  a.pred_err_index = lvc_ws_range_index(pred_slot);
   if (pred_w) {
     LVC_CHECK_ARG(K % WN_CH == 0 && K <= 2 * WN_CH, "the pointwise layer on top needs 128 or 256 hidden channels (at most two slices per output)");
     LVC_CHECK_ARG(pred_K >= 1 && pred_K <= 32 && pred_rows >= 32 && pred_slot >= 0 && pred_slot < lvc_range_slots(), "bad pointwise layer");
@@ -590,12 +558,12 @@ static int wino_launch(const float* x, const unsigned short* u, const float* sca
   bool sk = g_wino_streamk != 0 && nunits < (1ll << 31) && a.ntiles % cus != 0;
   if (sk) {
     constexpr int min_units = 4;        // a segment restarts the pipeline: at least four chunks (12 stages) per worker
-    long long workers = (nunits + min_units - 1) / min_units;
-    if (workers > cus) workers = cus;
-    a.units_per_worker = (int)((nunits + workers - 1) / workers);
+    lvc_plan_workers(nunits, cus, min_units, &a.units_per_worker, &a.nworkers);
     const bool whole = g_wino_streamk == 2;
-    if (whole) a.units_per_worker = (a.units_per_worker + a.nk - 1) / a.nk * a.nk;      // whole tiles per worker: persistent workgroups, no hand-off
-    a.nworkers = (int)((nunits + a.units_per_worker - 1) / a.units_per_worker);
+    if (whole) {      // whole tiles per worker: persistent workgroups, no hand-off
+      a.units_per_worker = (a.units_per_worker + a.nk - 1) / a.nk * a.nk;
+      a.nworkers = (int)((nunits + a.units_per_worker - 1) / a.units_per_worker);
+    }
     if (pred_w) {
       if (whole) hipLaunchKernelGGL((conv3x3_wino_sk_kernel<true, false>), dim3(a.nworkers), dim3(WN_NT), 0, (hipStream_t)stream, a);
       else hipLaunchKernelGGL((conv3x3_wino_sk_kernel<true, true>), dim3(a.nworkers), dim3(WN_NT), 0, (hipStream_t)stream, a);

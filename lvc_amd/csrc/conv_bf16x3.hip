@@ -16,15 +16,9 @@
 //
 // Weights are split once on the host into three bf16 planes [3][Kpad][Kg]; activations stay fp32 in HBM and are
 // split on the fly when a staged chunk is written to LDS (LDS holds bf16 planes, k-contiguous rows of 32 + 8 pad).
-#include "common.h"
+#include "conv_common.h"
 #include <stdlib.h>
 #include <type_traits>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 #define BM 128
 #define BN 128
@@ -32,7 +26,6 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 #define LROW 40          // bf16 elements per LDS row (32 + 8 pad = 80 B: conflict-free ds_read_b128)
 #define PLANE_A (BM * LROW)
 #define PLANE_B (BN * LROW)
-#define SPIN_LIMIT (1 << 24)
 
 struct ConvArgsB {
   const float* x;
@@ -264,25 +257,14 @@ __global__ __launch_bounds__(NT, 2) void conv_bf16x3_kernel(ConvArgsB p) {
         }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
-      if (tid == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __hip_atomic_store(p.flags + lw, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
+      if (tid == 0) lvc_publish_partial(p.flags, lw);
       continue;
     }
     if (kc1 < p.nk) {
       const int last_unit = tile * p.nk + p.nk - 1;
       const int last_worker = last_unit / p.units_per_worker;
       for (int pw = lw + 1; pw <= last_worker; ++pw) {
-        if (tid == 0) {
-          int spins = 0;
-          while (__hip_atomic_load(p.flags + pw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) {
-            __builtin_amdgcn_s_sleep(4);
-            if (++spins > SPIN_LIMIT) { atomicOr(p.flags + p.err_index, 1); break; }
-          }
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        }
+        if (tid == 0) lvc_wait_partial(p.flags, pw, p.err_index);
         __syncthreads();
         const float* src = p.partials + (size_t)pw * (NT * 32);
 #pragma unroll
@@ -294,7 +276,7 @@ __global__ __launch_bounds__(NT, 2) void conv_bf16x3_kernel(ConvArgsB p) {
             acc[mi][0][e4 * 4 + 2] += v[2]; acc[mi][0][e4 * 4 + 3] += v[3];
           }
         __syncthreads();
-        if (tid == 0) __hip_atomic_store(p.flags + pw, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (tid == 0) lvc_release_partial(p.flags, pw);
       }
     }
 
@@ -606,25 +588,14 @@ __global__ __launch_bounds__(NT, 2) void conv_pw_bf16x3_kernel(ConvArgsB p) {
         }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
-      if (tid == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __hip_atomic_store(p.flags + lw, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
+      if (tid == 0) lvc_publish_partial(p.flags, lw);
       continue;
     }
     if (kc1 < p.nk) {
       const int last_unit = tile * p.nk + p.nk - 1;
       const int last_worker = last_unit / p.units_per_worker;
       for (int pw = lw + 1; pw <= last_worker; ++pw) {
-        if (tid == 0) {
-          int spins = 0;
-          while (__hip_atomic_load(p.flags + pw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) {
-            __builtin_amdgcn_s_sleep(4);
-            if (++spins > SPIN_LIMIT) { atomicOr(p.flags + p.err_index, 1); break; }
-          }
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        }
+        if (tid == 0) lvc_wait_partial(p.flags, pw, p.err_index);
         __syncthreads();
         const float* src = p.partials + (size_t)pw * (NT * 32);
 #pragma unroll
@@ -636,7 +607,7 @@ __global__ __launch_bounds__(NT, 2) void conv_pw_bf16x3_kernel(ConvArgsB p) {
             acc[mi][0][e4 * 4 + 2] += v[2]; acc[mi][0][e4 * 4 + 3] += v[3];
           }
         __syncthreads();
-        if (tid == 0) __hip_atomic_store(p.flags + pw, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (tid == 0) lvc_release_partial(p.flags, pw);
       }
     }
 
@@ -674,7 +645,6 @@ __global__ __launch_bounds__(NT, 2) void conv_pw_bf16x3_kernel(ConvArgsB p) {
     __syncthreads();
   }
 }
-
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Pointwise shape for LONG reductions (1x1 convolutions with >= 1024 input channels, the box-head FC layers): these are
@@ -908,25 +878,14 @@ __global__ __launch_bounds__(NT, 2) void conv_pw256_bf16x3_kernel(ConvArgsB p) {
           }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
-      if (tid == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __hip_atomic_store(p.flags + lw, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
+      if (tid == 0) lvc_publish_partial(p.flags, lw);
       continue;
     }
     if (kc1 < p.nk) {
       const int last_unit = tile * p.nk + p.nk - 1;
       const int last_worker = last_unit / p.units_per_worker;
       for (int pw = lw + 1; pw <= last_worker; ++pw) {
-        if (tid == 0) {
-          int spins = 0;
-          while (__hip_atomic_load(p.flags + pw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) {
-            __builtin_amdgcn_s_sleep(4);
-            if (++spins > SPIN_LIMIT) { atomicOr(p.flags + p.err_index, 1); break; }
-          }
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        }
+        if (tid == 0) lvc_wait_partial(p.flags, pw, p.err_index);
         __syncthreads();
         const float* src = p.partials + (size_t)pw * (NT * 16 * MI * NI);
 #pragma unroll
@@ -940,7 +899,7 @@ __global__ __launch_bounds__(NT, 2) void conv_pw256_bf16x3_kernel(ConvArgsB p) {
               acc[mi][ni][e4 * 4 + 2] += v[2]; acc[mi][ni][e4 * 4 + 3] += v[3];
             }
         __syncthreads();
-        if (tid == 0) __hip_atomic_store(p.flags + pw, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (tid == 0) lvc_release_partial(p.flags, pw);
       }
     }
 
@@ -1012,9 +971,6 @@ __global__ __launch_bounds__(NT, 2) void conv_pw256_bf16x3_kernel(ConvArgsB p) {
   }
 }
 
-#define LVC_MAX_WORKERS 1024
-static int g_cus = 0;
-
 // Same argument meaning as lvc_conv2d_nhwc_f32 (mode 0 only) except `w_split`: three bf16 planes [3][Kpad][Kg]
 // (hi, mid, lo parts of the packed fp32 weights, k order (c/32, r, s, c%32)).  Requires K % 4 == 0, ldy % 4 == 0,
 // ldr % 4 == 0.  workspace: the lvc_conv_workspace_bytes() scratch shared with the fp32 kernel.
@@ -1065,22 +1021,13 @@ extern "C" int lvc_conv2d_nhwc_bf16x3(const float* x, const unsigned short* w_sp
   const long long xb = (long long)N * H * W * C * 4, wb = (long long)(lvc_cdiv(K, BN) * BN) * Kg * 2;   // planes are padded to 128 rows
   LVC_CHECK_ARG(xb < (1ll << 31) && 3 * wb < (1ll << 31), "input / weight tensor must be smaller than 2 GiB");
   a.x_bytes = (int)xb; a.w_plane_bytes = (int)wb;
-  if (g_cus == 0) {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-    g_cus = cus;
-  }
-  int cap = g_cus;  // one worker per CU: 120 KB of LDS per workgroup
+  int cap = lvc_cu_count();  // one worker per CU: 120 KB of LDS per workgroup
   if (cap > LVC_MAX_WORKERS) cap = LVC_MAX_WORKERS;
   const int min_units = 4;
-  int workers = (int)((units + min_units - 1) / min_units);
-  if (workers > cap) workers = cap;
-  a.units_per_worker = (int)((units + workers - 1) / workers);
-  a.nworkers = (int)((units + a.units_per_worker - 1) / a.units_per_worker);
+  lvc_plan_workers(units, cap, min_units, &a.units_per_worker, &a.nworkers);
   a.partials = (float*)workspace;
-  a.flags = (int*)((char*)workspace + (size_t)LVC_MAX_WORKERS * 256 * 128 * 4);
-  a.err_index = LVC_MAX_WORKERS;
+  a.flags = lvc_ws_flags(workspace);
+  a.err_index = lvc_ws_range_index(0);
   if (shape == 2 && gbn == 32)
     hipLaunchKernelGGL((conv_pw256_bf16x3_kernel<1, 1>), dim3(a.nworkers), dim3(NT), 0, (hipStream_t)stream, a);
   else if (shape == 2 && gbn == 64)

@@ -32,19 +32,10 @@
 // conflict-free; the contraction index is permuted within every 16 (0-3, 8-11, 4-7, 12-15) as in conv_pw_chain.hip.
 // Numerics: the single-accumulator two-way fp16 split of conv3x3_halo_s1.hip / conv_pw_chain.hip (row-scaled weight planes,
 // activations x 2^4, |a| <= 4094 for x, t1 and t2, else bit 1 of the layer's range word is raised and the host re-routes the block).
-#include "common.h"
+#include "conv_common.h"
 #include <stdlib.h>
 #include <type_traits>
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16;
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-#define ACT_SCALE 16.f
-#define ACT_MAX 4094.f
-#define LVC_MAX_WORKERS 1024
 #define BN_MARK 0xFFFF0000u      // a byte offset beyond every tensor's buffer range: loads return zeros, stores are dropped
 
 struct BneckArgs {
@@ -56,32 +47,8 @@ struct BneckArgs {
   int N, H, W, ldx, ldy, tiles_x, tiles_y, ntiles, err_index;
 };
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* glb_ptr_t;
-__device__ __forceinline__ void glds16(const void* g, void* l) {
-  __builtin_amdgcn_global_load_lds((glb_ptr_t)g, (lds_ptr_t)l, 16, 0, 0);
-}
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 __device__ __forceinline__ void wait_lgkm0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-// loads the compiler does not track (see conv_pw_chain.hip): completion through the waits below, which are tied to the registers
-template <int IMM> __device__ __forceinline__ f32x4 load_untracked(u32x4 rsrc, unsigned voff, unsigned soff) {
-  f32x4 v;
-  asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen offset:%4" : "=v"(v) : "v"(voff), "s"(rsrc), "s"(soff), "n"(IMM) : "memory");
-  return v;
-}
-__device__ __forceinline__ void track_abs(float& big, float a, float b) {
-  asm volatile("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(big) : "v"(a), "v"(b));
-}
 __device__ __forceinline__ void tie4(f32x4& a, f32x4& b, f32x4& c, f32x4& d) { asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d)); }
-__device__ __forceinline__ u32x4 make_rsrc(const void* base, unsigned bytes) {
-  const unsigned long long b = (unsigned long long)base;
-  return u32x4{(unsigned)__builtin_amdgcn_readfirstlane((unsigned)b), (unsigned)__builtin_amdgcn_readfirstlane((unsigned)(b >> 32) & 0xffffu),
-               (unsigned)__builtin_amdgcn_readfirstlane(bytes), 0x00020000u};
-}
-// soffset of a store is always the literal 0 (conv_pw_chain.hip: the >64-bit store data hazard with an SGPR soffset)
-__device__ __forceinline__ void store_b128(f32x4 v, __amdgpu_buffer_rsrc_t rsrc, unsigned voff) {
-  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsrc, voff, 0, 0);
-}
 template <int I, int N, class F> __device__ __forceinline__ void static_for(F&& f) {
   if constexpr (I < N) {
     f(std::integral_constant<int, I>{});
@@ -91,7 +58,7 @@ template <int I, int N, class F> __device__ __forceinline__ void static_for(F&& 
 __device__ __forceinline__ void split8(const f32x4& a, const f32x4& b, f16x8& h, f16x8& l) {
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
-    const float u = a[c] * ACT_SCALE, v = b[c] * ACT_SCALE;
+    const float u = a[c] * LVC_ACT_SCALE, v = b[c] * LVC_ACT_SCALE;
     const f16 uh = (f16)u, vh = (f16)v;
     h[c] = uh; h[4 + c] = vh;
     l[c] = (f16)(u - (float)uh); l[4 + c] = (f16)(v - (float)vh);
@@ -184,7 +151,7 @@ __global__ __launch_bounds__(BN_NW * 64) void conv_bneck_kernel(BneckArgs p) {
   // TWO stages back (phases 1 and 3 issue a stage's MFMAs one stage late, under the next one's vector work), which takes the stage
   // BN_NSLOT - 2 ahead; returns this stage's fragment base for the lane
 #ifdef BN_DIAG_TIMELINE      // wave 0 of four workgroups stamps every stage of its first tiles into the head of the workspace
-  unsigned long long* const tl_base = reinterpret_cast<unsigned long long*>(p.flags) - (size_t)LVC_MAX_WORKERS * 256 * 128 / 2;
+  unsigned long long* const tl_base = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(p.flags) - LVC_WS_FLAGS_OFFSET);
   const int tl_slot = blockIdx.x == 0 ? 0 : blockIdx.x == (gridDim.x >> 1) ? 1 : blockIdx.x == 8 ? 2 : blockIdx.x == (gridDim.x >> 1) + 8 ? 3 : -1;
   int tl_iter = 0;
 #endif
@@ -430,7 +397,7 @@ __global__ __launch_bounds__(BN_NW * 64) void conv_bneck_kernel(BneckArgs p) {
           constexpr int gi = h / 8, k = (h / 2) % 4, e0 = 2 * (h % 2);
           if (NGR == 2 && h == 8 && NM == 0) load_xb(1);
           const float a = xb[k][e0], b2 = xb[k][e0 + 1];
-          const float u = a * ACT_SCALE, v = b2 * ACT_SCALE;
+          const float u = a * LVC_ACT_SCALE, v = b2 * LVC_ACT_SCALE;
           const f16 uh = (f16)u, vh = (f16)v;
           constexpr int d0 = 4 * (k & 1) + e0;
           zh[XS][gi][k >> 1][d0] = uh; zh[XS][gi][k >> 1][d0 + 1] = vh;
@@ -502,7 +469,7 @@ __global__ __launch_bounds__(BN_NW * 64) void conv_bneck_kernel(BneckArgs p) {
             for (int e = 0; e < 4; ++e) {
               const float o = fmaxf(acc1[gi][cb][4 * i + e] * sc[e] + sh[e], 0.f) * msk[gi];
               v[e] = o;
-              const float a = o * ACT_SCALE;
+              const float a = o * LVC_ACT_SCALE;
               const f16 hh = (f16)a;
               yh[i >> 1][4 * (i & 1) + e] = hh;
               yl[i >> 1][4 * (i & 1) + e] = (f16)(a - (float)hh);
@@ -626,7 +593,7 @@ __global__ __launch_bounds__(BN_NW * 64) void conv_bneck_kernel(BneckArgs p) {
         for (int e = 0; e < 4; ++e) {
           const float o = fmaxf(acc2[cb][4 * i + e] * sc[e] + sh[e], 0.f);
           v[e] = o;
-          const float a = o * ACT_SCALE;
+          const float a = o * LVC_ACT_SCALE;
           const f16 hh = (f16)a;
           t2h[2 * cb + (i >> 1)][4 * (i & 1) + e] = hh;
           t2l[2 * cb + (i >> 1)][4 * (i & 1) + e] = (f16)(a - (float)hh);
@@ -730,10 +697,8 @@ __global__ __launch_bounds__(BN_NW * 64) void conv_bneck_kernel(BneckArgs p) {
   };
   if (wave < BN_NG1 - BN_NW) tiles(std::true_type{}); else tiles(std::false_type{});
   wait_vm<0>();
-  if (!(big <= ACT_MAX)) atomicOr(p.flags + p.err_index, big < INFINITY ? 2 : 4);
+  lvc_report_range(p.flags, p.err_index, big, LVC_ACT_MAX);
 }
-
-static int g_cus_bneck = 0;
 
 // One bottleneck block, 64 mid and 256 output channels, stride 1 (detectron2/modeling/backbone/resnet.py:195-211):
 // y = relu(bn3(conv3(relu(bn2(conv2(relu(bn1(conv1(x)))))))) + shortcut(x)).  x [N][H][W][ldx] (cin channels used), y [N][H][W][ldy].
@@ -758,18 +723,12 @@ extern "C" int lvc_bottleneck_nhwc_f16s1(const float* x, int ldx, float* y, int 
   a.N = N; a.H = H; a.W = W; a.ldx = ldx; a.ldy = ldy;
   a.tiles_x = lvc_cdiv(W, BN_TW); a.tiles_y = lvc_cdiv(H, BN_TH);
   a.ntiles = N * a.tiles_x * a.tiles_y;
-  a.flags = (int*)((char*)workspace + (size_t)LVC_MAX_WORKERS * 256 * 128 * 4);
-  a.err_index = LVC_MAX_WORKERS + lvc_range_slot();
-  if (g_cus_bneck == 0) {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-    g_cus_bneck = cus;
-  }
+  a.flags = lvc_ws_flags(workspace);
+  a.err_index = lvc_ws_range_index(lvc_range_slot());
 #ifdef BN_DIAG_WGS1
-  int grid = g_cus_bneck;
+  int grid = lvc_cu_count();
 #else
-  int grid = g_cus_bneck;
+  int grid = lvc_cu_count();
 #endif
 #ifdef BN_DIAG_GRID
   grid = BN_DIAG_GRID;

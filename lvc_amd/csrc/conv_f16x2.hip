@@ -4,16 +4,9 @@
 // fp16's range raise bit 1 of the workspace error word).  Kernel structure, tiling, loaders, stream-K protocol and
 // epilogues are those of conv_bf16x3.hip's conv_pw_f16x2_kernel / conv_pw256_f16x2_kernel; weights are the two fp16
 // planes [2][Kpad][Kg] of PackedConv.split2h().  Layers that are not pointwise stay on the bf16 kernels.
-#include "common.h"
+#include "conv_common.h"
 #include <stdlib.h>
 #include <type_traits>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16;
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 #define BM 128
 #define BN 128
@@ -21,7 +14,6 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 #define LROW 40          // bf16 elements per LDS row (32 + 8 pad = 80 B: conflict-free ds_read_b128)
 #define PLANE_A (BM * LROW)
 #define PLANE_B (BN * LROW)
-#define SPIN_LIMIT (1 << 24)
 
 struct ConvArgsH {
   const float* x;
@@ -37,11 +29,6 @@ struct ConvArgsH {
   int ngroup;                   // conv_pw256_f16x2_kernel: workers per row-tile group (1 = ungrouped)
   int x_bytes, w_plane_bytes;   // bytes of the input tensor / of ONE weight plane
 };
-
-__device__ __forceinline__ void split2h(float a, f16& h, f16& m) {
-  h = (f16)a;
-  m = (f16)((a - (float)h) * 2048.f);
-}
 
 #define NT 512   // 8 waves: two per SIMD, one workgroup per CU
 
@@ -159,7 +146,7 @@ __global__ __launch_bounds__(NT, 2) void conv_pw_f16x2_kernel(ConvArgsH p) {
         h[e] = hh; m[e] = mm;
         big = fmaxf(big, fabsf(areg[SL][j][e]));
       }
-      if (!(big <= 65504.f)) range_err = 1;   // beyond fp16 (or NaN): reported through the workspace error word
+      if (!(big <= LVC_F16_MAX)) range_err = 1;   // beyond fp16 (or NaN): reported through the workspace error word
       const int o = (row0 + 64 * j) * LROW + q * 4;
       *reinterpret_cast<f16x4*>(sa + o) = h;
       *reinterpret_cast<f16x4*>(sa + PLANE_A + o) = m;
@@ -302,25 +289,14 @@ __global__ __launch_bounds__(NT, 2) void conv_pw_f16x2_kernel(ConvArgsH p) {
         }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
-      if (tid == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __hip_atomic_store(p.flags + lw, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
+      if (tid == 0) lvc_publish_partial(p.flags, lw);
       continue;
     }
     if (kc1 < p.nk) {
       const int last_unit = tile * p.nk + p.nk - 1;
       const int last_worker = last_unit / p.units_per_worker;
       for (int pw = lw + 1; pw <= last_worker; ++pw) {
-        if (tid == 0) {
-          int spins = 0;
-          while (__hip_atomic_load(p.flags + pw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) {
-            __builtin_amdgcn_s_sleep(4);
-            if (++spins > SPIN_LIMIT) { atomicOr(p.flags + p.err_index, 1); break; }
-          }
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        }
+        if (tid == 0) lvc_wait_partial(p.flags, pw, p.err_index);
         __syncthreads();
         const float* src = p.partials + (size_t)pw * (NT * 32);
 #pragma unroll
@@ -332,7 +308,7 @@ __global__ __launch_bounds__(NT, 2) void conv_pw_f16x2_kernel(ConvArgsH p) {
             acc[mi][0][e4 * 4 + 2] += v[2]; acc[mi][0][e4 * 4 + 3] += v[3];
           }
         __syncthreads();
-        if (tid == 0) __hip_atomic_store(p.flags + pw, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (tid == 0) lvc_release_partial(p.flags, pw);
       }
     }
 
@@ -371,7 +347,6 @@ __global__ __launch_bounds__(NT, 2) void conv_pw_f16x2_kernel(ConvArgsH p) {
   }
   if (range_err) atomicOr(p.flags + p.err_index, 2);
 }
-
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Pointwise shape for LONG reductions (1x1 convolutions with >= 1024 input channels, the box-head FC layers): these are
@@ -510,7 +485,7 @@ __global__ __launch_bounds__(NT, 2) void conv_pw256_f16x2_kernel(ConvArgsH p) {
         h[e] = hh; m[e] = mm;
         big = fmaxf(big, fabsf(areg[SL][j][e]));
       }
-      if (!(big <= 65504.f)) range_err = 1;   // beyond fp16 (or NaN): reported through the workspace error word
+      if (!(big <= LVC_F16_MAX)) range_err = 1;   // beyond fp16 (or NaN): reported through the workspace error word
       const int o = (rslot + 64 * j) * 32 + a_st;
       *reinterpret_cast<f16x4*>(sa + o) = h;
       *reinterpret_cast<f16x4*>(sa + G_PA + o) = m;
@@ -626,11 +601,7 @@ __global__ __launch_bounds__(NT, 2) void conv_pw256_f16x2_kernel(ConvArgsH p) {
           }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
-      if (tid == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __hip_atomic_store(p.flags + lw, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
+      if (tid == 0) lvc_publish_partial(p.flags, lw);
       continue;
     }
     if (kc1 < p.nk) {
@@ -638,14 +609,7 @@ __global__ __launch_bounds__(NT, 2) void conv_pw256_f16x2_kernel(ConvArgsH p) {
       const int wstep = p.ngroup > 1 ? p.ngroup : 1;
       const int last_worker = (last_unit / p.units_per_worker) * wstep + wsel;
       for (int pw = lw + wstep; pw <= last_worker; pw += wstep) {
-        if (tid == 0) {
-          int spins = 0;
-          while (__hip_atomic_load(p.flags + pw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) {
-            __builtin_amdgcn_s_sleep(4);
-            if (++spins > SPIN_LIMIT) { atomicOr(p.flags + p.err_index, 1); break; }
-          }
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        }
+        if (tid == 0) lvc_wait_partial(p.flags, pw, p.err_index);
         __syncthreads();
         const float* src = p.partials + (size_t)pw * (NT * 16 * MI * NI);
 #pragma unroll
@@ -659,7 +623,7 @@ __global__ __launch_bounds__(NT, 2) void conv_pw256_f16x2_kernel(ConvArgsH p) {
               acc[mi][ni][e4 * 4 + 2] += v[2]; acc[mi][ni][e4 * 4 + 3] += v[3];
             }
         __syncthreads();
-        if (tid == 0) __hip_atomic_store(p.flags + pw, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (tid == 0) lvc_release_partial(p.flags, pw);
       }
     }
 
@@ -732,9 +696,6 @@ __global__ __launch_bounds__(NT, 2) void conv_pw256_f16x2_kernel(ConvArgsH p) {
   if (range_err) atomicOr(p.flags + p.err_index, 2);
 }
 
-#define LVC_MAX_WORKERS 1024
-static int g_cus_h = 0;
-
 // Pointwise layers (R = S = 1, pad 0) only; same arguments as lvc_conv2d_nhwc_bf16x3 except `w_split`: two fp16 planes
 // [2][Kpad][Kg] (w1 = fp16(w), w2 = fp16((w - w1) * 2048)).  Returns LVC_ERR_INVALID for anything the pointwise shapes do
 // not cover (the caller keeps those on the bf16 kernels).
@@ -786,17 +747,9 @@ extern "C" int lvc_conv2d_nhwc_f16x2(const float* x, const unsigned short* w_spl
   const long long xb = (long long)N * H * W * C * 4, wb = (long long)(lvc_cdiv(K, BN) * BN) * Kg * 2;   // planes are padded to 128 rows
   LVC_CHECK_ARG(xb < (1ll << 31) && 2 * wb < (1ll << 31), "input / weight tensor must be smaller than 2 GiB");
   a.x_bytes = (int)xb; a.w_plane_bytes = (int)wb;
-  if (g_cus_h == 0) {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-    g_cus_h = cus;
-  }
-  int cap = g_cus_h;  // one worker per CU
+  int cap = lvc_cu_count();  // one worker per CU
   if (cap > LVC_MAX_WORKERS) cap = LVC_MAX_WORKERS;
   const int min_units = 4;
-  int workers = (int)((units + min_units - 1) / min_units);
-  if (workers > cap) workers = cap;
   // two output-channel tiles on a chip-filling layer: pair the workers (ConvArgsH::ngroup); the unit space is then row
   // tiles x chunks.  Measured per layer (scripts/probe_layers_list.py): pairs gain 2 % on the 256-channel outputs (FPN
   // laterals, res4 reductions); groups of 4 / 8 / 16 lose 1-7 % (sixteen workers in step on one row tile serialise on
@@ -804,18 +757,18 @@ extern "C" int lvc_conv2d_nhwc_f16x2(const float* x, const unsigned short* w_spl
   a.ngroup = 1;
   constexpr int ngroup_on = 1;
   const int tn = a.tiles_n;
-  if (ngroup_on && shape == 2 && workers == cap && (tn == 2 || (ngroup_on > 1 && tn <= 16 && (tn & (tn - 1)) == 0)) && cap % tn == 0 &&
-      units / tn >= (long long)(cap / tn) * min_units) {
+  if (ngroup_on && shape == 2 && (tn == 2 || (ngroup_on > 1 && tn <= 16 && (tn & (tn - 1)) == 0)) && cap % tn == 0 &&
+      units / tn >= (long long)(cap / tn) * min_units) {      // (which also says that the ungrouped split would use all `cap` workers)
     a.ngroup = tn;
     units /= tn;
-    workers = cap / tn;
+    cap /= tn;
     a.total_units = (int)units;
   }
-  a.units_per_worker = (int)((units + workers - 1) / workers);
-  a.nworkers = (int)((units + a.units_per_worker - 1) / a.units_per_worker) * a.ngroup;
+  lvc_plan_workers(units, cap, min_units, &a.units_per_worker, &a.nworkers);
+  a.nworkers *= a.ngroup;
   a.partials = (float*)workspace;
-  a.flags = (int*)((char*)workspace + (size_t)LVC_MAX_WORKERS * 256 * 128 * 4);
-  a.err_index = LVC_MAX_WORKERS + lvc_range_slot();   // the layer's own range word (common.cpp)
+  a.flags = lvc_ws_flags(workspace);
+  a.err_index = lvc_ws_range_index(lvc_range_slot());   // the layer's own range word (common.cpp)
   if (shape == 2 && gbn == 32)
     hipLaunchKernelGGL((conv_pw256_f16x2_kernel<1, 1>), dim3(a.nworkers), dim3(NT), 0, (hipStream_t)stream, a);
   else if (shape == 2 && gbn == 64)

@@ -36,16 +36,12 @@
 // Lane/fragment map for 32x32x2 (A: lane l holds A[i=l&31][k=l>>5]; B: B[k=l>>5][j=l&31]):
 // lane (i,h) ds_read_b128's 4 consecutive k (= 8*kk + 4*h + t, t=0..3) from row i; MFMA step t then
 // contracts k in {8kk+t, 8kk+4+t}; A and B use the same permutation so every k is used exactly once.
-#include "common.h"
+#include "conv_common.h"
 #include <stdlib.h>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #define BM 128
 #define BK 32
 #define LDS_STRIDE 36   // floats per staged tile row (BK + 4 pad)
-#define SPIN_LIMIT (1 << 24)
 
 struct ConvArgs {
   const float* x;      // input  [N,H,W,C]   (C = physical channel count, multiple of 4)
@@ -281,11 +277,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_f32_kernel(ConvArgs p) {
           }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
-      if (tid == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __hip_atomic_store(p.flags + lw, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
+      if (tid == 0) lvc_publish_partial(p.flags, lw);
       continue;  // the finisher owns the epilogue
     }
     if (kc1 < p.nk) {
@@ -293,14 +285,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_f32_kernel(ConvArgs p) {
       const int last_unit = tile * p.nk + p.nk - 1;
       const int last_worker = last_unit / p.units_per_worker;
       for (int pw = lw + 1; pw <= last_worker; ++pw) {
-        if (tid == 0) {
-          int spins = 0;
-          while (__hip_atomic_load(p.flags + pw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) {
-            __builtin_amdgcn_s_sleep(4);
-            if (++spins > SPIN_LIMIT) { atomicOr(p.flags + p.err_index, 1); break; }
-          }
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        }
+        if (tid == 0) lvc_wait_partial(p.flags, pw, p.err_index);
         __syncthreads();
         const float* src = p.partials + (size_t)pw * (256 * 32 * NI);
 #pragma unroll
@@ -314,7 +299,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_f32_kernel(ConvArgs p) {
               acc[mi][ni][e4 * 4 + 2] += v[2]; acc[mi][ni][e4 * 4 + 3] += v[3];
             }
         __syncthreads();
-        if (tid == 0) __hip_atomic_store(p.flags + pw, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (tid == 0) lvc_release_partial(p.flags, pw);
       }
     }
 
@@ -395,25 +380,11 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_f32_kernel(ConvArgs p) {
   }
 }
 
-static int g_capacity = 0;  // co-resident workers (2 per CU)
-static int worker_capacity() {
-  if (g_capacity == 0) {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-    const int per_cu = 2;     // the LDS / VGPR residency limit
-    g_capacity = per_cu * cus;
-  }
-  return g_capacity;
-}
-#define LVC_MAX_WORKERS 1024
-
-// Persistent per-device scratch for split tiles: partial accumulators + flags (+1 error word).  Must be
+// Persistent per-device scratch for split tiles: partial accumulators, worker flags, range / error words (conv_common.h).  Must be
 // zero-initialised once by the caller and must not be shared by launches that run concurrently on
 // different streams.
-extern "C" long long lvc_conv_workspace_bytes(void) {
-  return (long long)LVC_MAX_WORKERS * 256 * 128 * 4 + (LVC_MAX_WORKERS + 1024) * 4 + 256;   // worker flags, then 1024 range / error words
-}
+extern "C" long long lvc_conv_workspace_bytes(void) { return (long long)LVC_WS_BYTES; }
+extern "C" long long lvc_conv_range_words_offset(void) { return (long long)LVC_WS_RANGE_OFFSET; }
 
 // C ABI -- see include/lvc_amd.h for the contract of each argument.
 extern "C" int lvc_conv2d_nhwc_f32(const float* x, const float* w_packed, const float* scale,
@@ -456,22 +427,19 @@ extern "C" int lvc_conv2d_nhwc_f32(const float* x, const float* w_packed, const 
   long long units = (long long)tiles_m * a.tiles_n * a.nk;
   LVC_CHECK_ARG(units < (1ll << 31), "iteration space too large");
   a.total_units = (int)units;
-  int cap = worker_capacity();
+  const int per_cu = 2;     // co-resident workers per CU: the LDS / VGPR residency limit
+  int cap = per_cu * lvc_cu_count();
   if (cap > LVC_MAX_WORKERS) cap = LVC_MAX_WORKERS;
   const int min_units = 4;  // do not cut below 4 chunks per worker: the split-tile hand-off costs microseconds
-  int workers = (int)((units + min_units - 1) / min_units);
-  if (workers > cap) workers = cap;
-  if (workers < 1) workers = 1;
-  a.units_per_worker = (int)((units + workers - 1) / workers);
-  a.nworkers = (int)((units + a.units_per_worker - 1) / a.units_per_worker);
+  lvc_plan_workers(units, cap, min_units, &a.units_per_worker, &a.nworkers);
   {
     const long long xb = (long long)N * H * W * C * 4, wb = (long long)(a.tiles_n * bn) * Kg * 4;
     LVC_CHECK_ARG(xb < (1ll << 31) && wb < (1ll << 31), "input / weight tensor must be smaller than 2 GiB (32-bit buffer offsets)");
     a.x_bytes = (int)xb; a.w_bytes = (int)wb;
   }
   a.partials = (float*)workspace;
-  a.flags = (int*)((char*)workspace + (size_t)LVC_MAX_WORKERS * 256 * 128 * 4);
-  a.err_index = LVC_MAX_WORKERS;
+  a.flags = lvc_ws_flags(workspace);
+  a.err_index = lvc_ws_range_index(0);
   dim3 grid(a.nworkers), block(256);
   hipStream_t st = (hipStream_t)stream;
   if (mode == 0) {

@@ -24,18 +24,9 @@
 //     Wb's columns 32 j .. 32 j + 31 (all N2 rows), both fp16 planes, by LDS-DMA with the granule XOR swizzle of conv_pw_dma.hip.
 // Numerics: the single-accumulator two-way fp16 split of conv3x3_halo_s1.hip (row-scaled weight planes of
 // lvc_split_weights_rowscaled, activations x 2^4, |a| <= 4094 for x AND for y1 or bit 1 of the workspace error word is raised).
-#include "common.h"
+#include "conv_common.h"
 #include <stdlib.h>
 #include <type_traits>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16;
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-#define ACT_SCALE 16.f
-#define ACT_MAX 4094.f
-#define LVC_MAX_WORKERS 1024
 
 struct ChainArgs {
   const float* x;            // [M][ldx]   first layer's input (K1 channels used)
@@ -53,39 +44,7 @@ struct ChainArgs {
   long long wa_plane, wb_plane;   // elements per plane
 };
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* glb_ptr_t;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void glds16(const void* g, void* l) {
-  __builtin_amdgcn_global_load_lds((glb_ptr_t)g, (lds_ptr_t)l, 16, 0, 0);
-}
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-// buffer_load_dwordx4 the compiler does not track (it would wait for everything in flight, LDS-DMA and stores included, at the
-// first use): rows past the end return zeros; completion through the counted waits below, which are TIED to the registers
-template <int IMM> __device__ __forceinline__ f32x4 load_untracked(u32x4 rsrc, unsigned voff, unsigned soff) {
-  f32x4 v;
-  asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen offset:%4" : "=v"(v) : "v"(voff), "s"(rsrc), "s"(soff), "n"(IMM) : "memory");
-  return v;
-}
-// Range tracking pinned in program order (volatile asm): written as plain fmaxf the compiler sank these maxima far below the
-// split, kept the raw input rows alive for them and SPILLED those registers right after the untracked loads were issued --
-// i.e. before their data had arrived.  (The build fails on any spill in this file: csrc/Makefile.)
-__device__ __forceinline__ void track_abs(float& big, float a, float b) {
-  asm volatile("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(big) : "v"(a), "v"(b));
-}
 __device__ __forceinline__ void tie(f32x4& a, f32x4& b, f32x4& c, f32x4& d) { asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d)); }
-__device__ __forceinline__ u32x4 make_rsrc(const void* base, unsigned bytes) {
-  const unsigned long long b = (unsigned long long)base;
-  return u32x4{(unsigned)__builtin_amdgcn_readfirstlane((unsigned)b), (unsigned)__builtin_amdgcn_readfirstlane((unsigned)(b >> 32) & 0xffffu),
-               (unsigned)__builtin_amdgcn_readfirstlane(bytes), 0x00020000u};
-}
-// The scalar offset of a store is ALWAYS the literal 0.  The compiler inserts the wait state a > 64-bit VMEM store needs before its
-// data registers are overwritten only when soffset is not an SGPR (GCNHazardRecognizer::createsVALUHazard); gfx950 needs it with an
-// SGPR soffset as well: with `buffer_store_dwordx4 v[172:175], .., s93 offen` followed directly by a write of v172, the lanes
-// 12-15 of every 16 stored 0 instead of the value (scripts/dbg_chain.py found exactly the registers that were rewritten next).
-__device__ __forceinline__ void store_b128(f32x4 v, __amdgpu_buffer_rsrc_t rsrc, unsigned voff) {
-  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsrc, voff, 0, 0);
-}
 
 // K1: contraction of the first layer (64 / 128), N1: its outputs = the second layer's contraction, N2: the second layer's outputs.
 // NW waves per workgroup (a wave = 32 pixels), NSLOT ring stages, RES: a residual operand exists.
@@ -231,7 +190,7 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_pw_chain_kernel(ChainArgs p) 
       for (int h = 0; h < 2; ++h)
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-          const float a = xr[s][h][c] * ACT_SCALE;
+          const float a = xr[s][h][c] * LVC_ACT_SCALE;
           const f16 hh = (f16)a;
           zh[s][4 * h + c] = hh;
           zl[s][4 * h + c] = (f16)(a - (float)hh);
@@ -296,7 +255,7 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_pw_chain_kernel(ChainArgs p) 
           if (RES) o += rr[i][c];
           o = fmaxf(o, lo1);
           v[c] = o;
-          const float a = o * ACT_SCALE;
+          const float a = o * LVC_ACT_SCALE;
           const f16 hh = (f16)a;
           yh[i >> 1][4 * (i & 1) + c] = hh;
           yl[i >> 1][4 * (i & 1) + c] = (f16)(a - (float)hh);
@@ -347,14 +306,12 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_pw_chain_kernel(ChainArgs p) 
     px = pxn;
   }
   wait_vm<0>();
-  if (!(big <= ACT_MAX)) atomicOr(p.flags + p.err_index, big < INFINITY ? 2 : 4);      // finite / non-finite: see conv3x3_halo_s1.hip
+  lvc_report_range(p.flags, p.err_index, big, LVC_ACT_MAX);
 }
-
-static int g_cus_chain = 0;
 
 template <int K1, int N1, int N2, int NW, int NSLOT>
 static void chain_launch(const ChainArgs& a, int wgs_per_cu, hipStream_t st) {
-  int grid = g_cus_chain * wgs_per_cu;
+  int grid = lvc_cu_count() * wgs_per_cu;
   if (grid > a.ngroups) grid = a.ngroups;
   if (a.res) hipLaunchKernelGGL((conv_pw_chain_kernel<K1, N1, N2, NW, NSLOT, true>), dim3(grid), dim3(NW * 64), 0, st, a);
   else hipLaunchKernelGGL((conv_pw_chain_kernel<K1, N1, N2, NW, NSLOT, false>), dim3(grid), dim3(NW * 64), 0, st, a);
@@ -382,14 +339,8 @@ extern "C" int lvc_conv1x1_chain_nhwc_f16s1(const float* x, int ldx, const unsig
   a.x = x; a.wa = wa; a.sa = sa; a.ta = ta; a.res = residual; a.y1 = y1; a.wb = wb; a.sb = sb; a.tb = tb; a.y2 = y2;
   a.M = M; a.ldx = ldx; a.ldr = ldr; a.ldy1 = ldy1; a.ldy2 = ldy2; a.relu1 = relu1; a.relu2 = relu2;
   a.wa_plane = (long long)wa_rows * K1; a.wb_plane = (long long)wb_rows * N1;
-  a.flags = (int*)((char*)workspace + (size_t)LVC_MAX_WORKERS * 256 * 128 * 4);
-  a.err_index = LVC_MAX_WORKERS + lvc_range_slot();   // the layer's own range word (common.cpp)
-  if (g_cus_chain == 0) {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-    g_cus_chain = cus;
-  }
+  a.flags = lvc_ws_flags(workspace);
+  a.err_index = lvc_ws_range_index(lvc_range_slot());   // the layer's own range word (common.cpp)
   hipStream_t st = (hipStream_t)stream;
   constexpr int NW = 4;
   a.ngroups = lvc_cdiv(M, 32 * NW);

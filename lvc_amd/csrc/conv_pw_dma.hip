@@ -20,18 +20,11 @@
 // so that every 16-lane group of a ds_read_b128 covers the 64 banks exactly once.
 // Arithmetic is that of conv_f16x2.hip (a = a1 + 2^-11 a2, three fp16 MFMAs per block into a main and a cross fp32
 // accumulator); the stream-K split of the chunk sequence and its release/acquire hand-off are the same as well.
-#include "common.h"
+#include "conv_common.h"
 #include <stdlib.h>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16;
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 // <NI, 8, 3, 1>: one workgroup of 8 waves per CU on 256-row tiles with a three-stage ring (other shapes were measured and lost:
 // profiles/README.md round 2).
-#define SPIN_LIMIT (1 << 24)
-#define LVC_MAX_WORKERS 1024
 
 struct ConvArgsD {
   const float* x;
@@ -47,13 +40,6 @@ struct ConvArgsD {
   unsigned long long* dbg;   // -DPW_DMA_TIMELINE build (scripts/probe_pw_timeline.py): cycle stamps of every 64th workgroup, else null
   long long w_plane_elems;
 };
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* glb_ptr_t;
-
-__device__ __forceinline__ void glds16(const void* g, void* l) {
-  __builtin_amdgcn_global_load_lds((glb_ptr_t)g, (lds_ptr_t)l, 16, 0, 0);
-}
 
 template <int NI, int NW, int D_NS, int MI>
 __global__ __launch_bounds__(NW * 64, MI == 2 ? 1 : 2) void conv_pw_dma_kernel(ConvArgsD p) {
@@ -292,11 +278,7 @@ __global__ __launch_bounds__(NW * 64, MI == 2 ? 1 : 2) void conv_pw_dma_kernel(C
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       landed = issued;
       __syncthreads();
-      if (tid == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __hip_atomic_store(p.flags + lw, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
+      if (tid == 0) lvc_publish_partial(p.flags, lw);
       STAMP(5);
       continue;
     }
@@ -305,14 +287,7 @@ __global__ __launch_bounds__(NW * 64, MI == 2 ? 1 : 2) void conv_pw_dma_kernel(C
       const int wstep = p.ngroup > 1 ? p.ngroup : 1;
       const int last_worker = (last_unit / p.units_per_worker) * wstep + wsel;
       for (int pw = lw + wstep; pw <= last_worker; pw += wstep) {
-        if (tid == 0) {
-          int spins = 0;
-          while (__hip_atomic_load(p.flags + pw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) {
-            __builtin_amdgcn_s_sleep(4);
-            if (++spins > SPIN_LIMIT) { atomicOr(p.flags + p.err_index, 1); break; }
-          }
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        }
+        if (tid == 0) lvc_wait_partial(p.flags, pw, p.err_index);
         __syncthreads();
         const float* src = p.partials + (size_t)pw * (D_NT * 16 * MI * NI);
 #pragma unroll
@@ -326,7 +301,7 @@ __global__ __launch_bounds__(NW * 64, MI == 2 ? 1 : 2) void conv_pw_dma_kernel(C
               acc[mi][ni][e4 * 4 + 2] += v[2]; acc[mi][ni][e4 * 4 + 3] += v[3];
             }
         __syncthreads();
-        if (tid == 0) __hip_atomic_store(p.flags + pw, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (tid == 0) lvc_release_partial(p.flags, pw);
       }
     }
 
@@ -419,10 +394,8 @@ __global__ __launch_bounds__(NW * 64, MI == 2 ? 1 : 2) void conv_pw_dma_kernel(C
   }
   STAMP(9);
 #undef STAMP
-  if (!(big <= 65504.f)) atomicOr(p.flags + p.err_index, big < INFINITY ? 2 : 4);      // finite / non-finite: see conv3x3_halo_s1.hip
+  lvc_report_range(p.flags, p.err_index, big, LVC_F16_MAX);
 }
-
-static int g_cus_d = 0;
 
 // Same arguments and results as lvc_conv2d_nhwc_f16x2 (conv_f16x2.hip) for the pointwise layers it routes to its 256-row
 // shape (R = S = 1, pad 0, C % 32 == 0, at least 2048 output rows); returns LVC_ERR_INVALID for anything else.
@@ -460,34 +433,26 @@ extern "C" int lvc_conv2d_nhwc_f16x2_dma(const float* x, const unsigned short* w
   LVC_CHECK_ARG(units < (1ll << 31), "iteration space too large");
   a.total_units = (int)units;
   a.w_plane_elems = (long long)(lvc_cdiv(K, 128) * 128) * Kg;   // planes are padded to 128 rows
-  if (g_cus_d == 0) {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-    g_cus_d = cus;
-  }
-  int cap = g_cus_d;   // one resident workgroup per CU
+  int cap = lvc_cu_count();   // one resident workgroup per CU
   if (cap > LVC_MAX_WORKERS) cap = LVC_MAX_WORKERS;
   const int min_units = 4;
-  int workers = (int)((units + min_units - 1) / min_units);
-  if (workers > cap) workers = cap;
   a.ngroup = 1;
   constexpr int ngroup_on = 1;
   const int tn = a.tiles_n;
-  if (ngroup_on && workers == cap && (tn == 2 || (ngroup_on > 1 && tn <= 16 && (tn & (tn - 1)) == 0)) && cap % tn == 0 &&
-      units / tn >= (long long)(cap / tn) * min_units) {
+  if (ngroup_on && (tn == 2 || (ngroup_on > 1 && tn <= 16 && (tn & (tn - 1)) == 0)) && cap % tn == 0 &&
+      units / tn >= (long long)(cap / tn) * min_units) {      // (which also says that the ungrouped split would use all `cap` workers)
     a.ngroup = tn;
     units /= tn;
-    workers = cap / tn;
+    cap /= tn;
     a.total_units = (int)units;
   }
-  a.units_per_worker = (int)((units + workers - 1) / workers);
-  a.nworkers = (int)((units + a.units_per_worker - 1) / a.units_per_worker) * a.ngroup;
+  lvc_plan_workers(units, cap, min_units, &a.units_per_worker, &a.nworkers);
+  a.nworkers *= a.ngroup;
   a.partials = (float*)workspace;
-  a.flags = (int*)((char*)workspace + (size_t)LVC_MAX_WORKERS * 256 * 128 * 4);
-  a.err_index = LVC_MAX_WORKERS + lvc_range_slot();   // the layer's own range word (common.cpp)
+  a.flags = lvc_ws_flags(workspace);
+  a.err_index = lvc_ws_range_index(lvc_range_slot());   // the layer's own range word (common.cpp)
 #ifdef PW_DMA_TIMELINE     // diagnostics build only: stamps into the upper half of the partial-tile area (never used by <= 256 workers)
-  a.dbg = (unsigned long long*)((char*)workspace + (size_t)512 * 256 * 128 * 4);
+  a.dbg = (unsigned long long*)((char*)workspace + LVC_WS_DIAG_OFFSET);
 #else
   a.dbg = nullptr;
 #endif

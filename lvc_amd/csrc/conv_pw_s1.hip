@@ -16,24 +16,15 @@
 // planes and activations x 2^4 as in conv3x3_halo_s1.hip (|a| <= 4094).
 // The asynchronous loads are written as inline asm and waited for with counted vmcnt waits that are TIED to the destination
 // registers (the compiler's own bookkeeping would wait for everything in flight, LDS-DMA included, at the first use).
-#include "common.h"
+#include "conv_common.h"
 #include <type_traits>
 #include <stdlib.h>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16;
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
 #define PM 256            // rows per tile
 #define AROW 64           // bytes per activation row and plane in LDS (32 halves, unpadded: the 16-byte granules are XOR-swizzled
                           // by (row >> 2) & 3 exactly like the weight rows, conflict-free for the ds_read_b128 lane groups)
 #define NJ 4              // float4 slots per thread and chunk (256 rows x 8 slots / 512 threads)
 #define NT 512
-#define SPIN_LIMIT (1 << 24)
-#define ACT_SCALE 16.f
-#define ACT_MAX 4094.f
 
 struct PwArgsS {
   const float* x;
@@ -55,24 +46,6 @@ struct PwArgsS {
   int pl_N, pl_Npad, pl_H;
   float pl_qscale;           // multiplied into q (softmax scale x log2 e)
 };
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* glb_ptr_t;
-__device__ __forceinline__ void glds16(const void* g, void* l) {
-  __builtin_amdgcn_global_load_lds((glb_ptr_t)g, (lds_ptr_t)l, 16, 0, 0);
-}
-// buffer_load_dwordx4 the compiler does not track: out-of-range offsets return zeros; completion through wait_tied
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ f32x4 load_untracked(u32x4 rsrc, unsigned voff, unsigned soff) {
-  f32x4 v;
-  asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(v) : "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-  return v;
-}
-// at most N vector-memory operations outstanding; the four registers become usable only behind it
-template <int N> __device__ __forceinline__ void wait_tied(f32x4& a, f32x4& b, f32x4& c, f32x4& d) {
-  asm volatile("s_waitcnt vmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(N) : "memory");
-}
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // PRE: x holds the pre-split planes of lvc_conv3x3_nhwc_f16s1_presplit (per row and 32-channel chunk 64 B of hi halves, 64 B of lo halves)
 template <int NI, bool ONEACC, bool PLANES = false, bool PRE = false>
@@ -196,7 +169,7 @@ __global__ __launch_bounds__(NT, 2) void conv_pw_s1_kernel(PwArgsS p) {
         f16x4 h, m;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          const float a = ONEACC ? ar[set][j][e] * ACT_SCALE : ar[set][j][e];
+          const float a = ONEACC ? ar[set][j][e] * LVC_ACT_SCALE : ar[set][j][e];
           const f16 hh = (f16)a;
           h[e] = hh;
           m[e] = ONEACC ? (f16)(a - (float)hh) : (f16)((a - (float)hh) * 2048.f);
@@ -374,11 +347,7 @@ __global__ __launch_bounds__(NT, 2) void conv_pw_s1_kernel(PwArgsS p) {
           }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
-      if (tid == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __hip_atomic_store(p.flags + lw, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
+      if (tid == 0) lvc_publish_partial(p.flags, lw);
       continue;
     }
     if (cc1 < p.nk) {
@@ -386,14 +355,7 @@ __global__ __launch_bounds__(NT, 2) void conv_pw_s1_kernel(PwArgsS p) {
       const int wstep = p.ngroup > 1 ? p.ngroup : 1;
       const int last_worker = (last_unit / p.units_per_worker) * wstep + wsel;
       for (int pw = lw + wstep; pw <= last_worker; pw += wstep) {
-        if (tid == 0) {
-          int spins = 0;
-          while (__hip_atomic_load(p.flags + pw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) {
-            __builtin_amdgcn_s_sleep(4);
-            if (++spins > SPIN_LIMIT) { atomicOr(p.flags + p.err_index, 1); break; }
-          }
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        }
+        if (tid == 0) lvc_wait_partial(p.flags, pw, p.err_index);
         __syncthreads();
         const float* src = p.partials + (size_t)pw * (NT * 32 * NI);
 #pragma unroll
@@ -407,7 +369,7 @@ __global__ __launch_bounds__(NT, 2) void conv_pw_s1_kernel(PwArgsS p) {
               acc[mi][ni][e4 * 4 + 2] += v[2]; acc[mi][ni][e4 * 4 + 3] += v[3];
             }
         __syncthreads();
-        if (tid == 0) __hip_atomic_store(p.flags + pw, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (tid == 0) lvc_release_partial(p.flags, pw);
       }
     }
 
@@ -558,7 +520,7 @@ __global__ __launch_bounds__(NT, 2) void conv_pw_s1_kernel(PwArgsS p) {
               *reinterpret_cast<f16x4*>(dst + p.pl_PS) = lo;
             }
           }
-          if (p.pl_err && !(bigp <= 65504.f)) atomicOr(p.pl_err, 2);
+          if (p.pl_err && !(bigp <= LVC_F16_MAX)) atomicOr(p.pl_err, 2);
         } else if (has_res) {
           if (p.relu == 1) rows(std::true_type{}, A1{}); else if (p.relu == 2) rows(std::true_type{}, A2{}); else rows(std::true_type{}, A0{});
         } else {
@@ -677,16 +639,13 @@ __global__ __launch_bounds__(NT, 2) void conv_pw_s1_kernel(PwArgsS p) {
   }
 #ifdef PW_TIMELINE
   if (lane == 0 && (blockIdx.x & 15) == 0) {
-    unsigned long long* d = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(p.partials) + (size_t)512 * 256 * 128 * 4) + ((blockIdx.x >> 4) * 8 + wave) * 16;
+    unsigned long long* d = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(p.partials) + LVC_WS_DIAG_OFFSET) + ((blockIdx.x >> 4) * 8 + wave) * 16;
     d[0] = tl_pro; d[1] = tl_loop; d[2] = tl_hand; d[3] = tl_cs; d[4] = tl_rows; d[5] = tl_tiles; d[6] = tl_chunks; d[7] = __builtin_readcyclecounter() - tl_t0; d[8] = 1; d[9] = tl_wa; d[10] = tl_wv; d[11] = tl_wb;
   }
 #endif
   if (PRE) return;      // the producer raised this layer's range word where its output x 2^4 left fp16's range
-  if (!(big <= (ONEACC ? ACT_MAX : 65504.f))) atomicOr(p.flags + p.err_index, big < INFINITY ? 2 : 4);      // finite / non-finite: see conv3x3_halo_s1.hip
+  lvc_report_range(p.flags, p.err_index, big, ONEACC ? LVC_ACT_MAX : LVC_F16_MAX);
 }
-
-#define LVC_MAX_WORKERS 1024
-static int g_cus_pw_s = 0;
 
 struct PwPlanes { unsigned short* planes; int* err; long long PS; int N, Npad, H; float qscale; };
 
@@ -724,13 +683,7 @@ static int pw_s1_launch(bool oneacc, const float* x, const unsigned short* w_spl
   LVC_CHECK_ARG(units < (1ll << 31), "iteration space too large");
   a.total_units = (int)units;
   a.w_plane_elems = (long long)(lvc_cdiv(K, 128) * 128) * C;
-  if (g_cus_pw_s == 0) {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-    g_cus_pw_s = cus;
-  }
-  int cap = g_cus_pw_s;
+  int cap = lvc_cu_count();
   if (cap > LVC_MAX_WORKERS) cap = LVC_MAX_WORKERS;
   a.ngroup = 1;
   if ((a.tiles_n == 2 || a.tiles_n == 4 || a.tiles_n == 8 || a.tiles_n == 16) && cap % a.tiles_n == 0 && units / a.tiles_n >= (long long)(cap / a.tiles_n) * 4) {
@@ -740,13 +693,11 @@ static int pw_s1_launch(bool oneacc, const float* x, const unsigned short* w_spl
     a.total_units = (int)units;
   }
   const int min_units = 4;     // a worker's pipeline restarts per tile segment: keep segments >= 4 chunks
-  int workers = (int)((units + min_units - 1) / min_units);
-  if (workers > cap) workers = cap;
-  a.units_per_worker = (int)((units + workers - 1) / workers);
-  a.nworkers = (int)((units + a.units_per_worker - 1) / a.units_per_worker) * a.ngroup;
+  lvc_plan_workers(units, cap, min_units, &a.units_per_worker, &a.nworkers);
+  a.nworkers *= a.ngroup;
   a.partials = (float*)workspace;
-  a.flags = (int*)((char*)workspace + (size_t)LVC_MAX_WORKERS * 256 * 128 * 4);
-  a.err_index = LVC_MAX_WORKERS + lvc_range_slot();   // the layer's own range word (common.cpp)
+  a.flags = lvc_ws_flags(workspace);
+  a.err_index = lvc_ws_range_index(lvc_range_slot());   // the layer's own range word (common.cpp)
   hipStream_t st = (hipStream_t)stream;
   a.planes = nullptr; a.pl_err = nullptr; a.pl_PS = 0; a.pl_N = a.pl_Npad = a.pl_H = 0; a.pl_qscale = 1.f;
   if (pl) {

@@ -21,15 +21,9 @@
 //     barrier  : behind `vmcnt` = B(i+2) landed, `lgkmcnt(0)` = this wave's LDS writes done
 // 16-byte granules of a 32-byte row are XOR-swizzled by (row >> 3) & 1: the sixteen lanes of a ds_read_b128 group (rows r .. r+15 of
 // one k half) then touch all 64 banks once.
-#include "common.h"
+#include "conv_common.h"
 #include <type_traits>
 #include <stdlib.h>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16;
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
 #define PM 256            // rows per tile
 #define PN 256            // channels per tile
@@ -41,9 +35,6 @@ typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 #define DPW 2             // DMA instructions per wave and stage (256 rows x 2 planes x 32 B / 1 KB / 8 waves)
 #define NT 512
 #define NI 4
-#define SPIN_LIMIT (1 << 24)
-#define ACT_SCALE 16.f
-#define ACT_MAX 4094.f
 
 struct PwArgsW {
   const float* x;
@@ -59,25 +50,6 @@ struct PwArgsW {
   int x_bytes;
   long long w_plane_elems;
 };
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* glb_ptr_t;
-__device__ __forceinline__ void glds16(const void* g, void* l) {
-  __builtin_amdgcn_global_load_lds((glb_ptr_t)g, (lds_ptr_t)l, 16, 0, 0);
-}
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-// buffer_load_dwordx4 the compiler does not track: out-of-range offsets return zeros; completion through wait_tied
-__device__ __forceinline__ f32x4 load_untracked(u32x4 rsrc, unsigned voff, unsigned soff) {
-  f32x4 v;
-  asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(v) : "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-  return v;
-}
-template <int N> __device__ __forceinline__ void wait_tied(f32x4& a, f32x4& b) {
-  asm volatile("s_waitcnt vmcnt(%2)" : "+v"(a), "+v"(b) : "n"(N) : "memory");
-}
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-// behind it: at most N vector-memory operations outstanding and every LDS operation of this wave complete
-template <int N> __device__ __forceinline__ void wait_vm_lds() { asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory"); }
 
 __global__ __launch_bounds__(NT, 2) void conv_pw_w2_kernel(PwArgsW p) {
   constexpr int PLANE = PM * ROWB;                 // 8 KB: one plane of one operand of one stage
@@ -163,7 +135,7 @@ __global__ __launch_bounds__(NT, 2) void conv_pw_w2_kernel(PwArgsW p) {
         f16x4 h, m;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          const float a = ar[set][j][e] * ACT_SCALE;
+          const float a = ar[set][j][e] * LVC_ACT_SCALE;
           const f16 hh = (f16)a;
           h[e] = hh;
           m[e] = (f16)(a - (float)hh);
@@ -285,7 +257,7 @@ __global__ __launch_bounds__(NT, 2) void conv_pw_w2_kernel(PwArgsW p) {
     wait_vm<0>();
     __syncthreads();
     u += nst;
-    if (!(big <= ACT_MAX)) atomicOr(p.flags + p.err_index, big < INFINITY ? 2 : 4);      // finite / non-finite: see conv3x3_halo_s1.hip
+    lvc_report_range(p.flags, p.err_index, big, LVC_ACT_MAX);
     // A new definition of every accumulator between the stage loop and the tile's tail: the register allocator may then place them
     // differently in the two regions (a few moves here) instead of spilling one whole accumulator -- and reloading / re-spilling it in
     // every stage -- because the tail's pressure peaks above the budget.
@@ -316,11 +288,7 @@ __global__ __launch_bounds__(NT, 2) void conv_pw_w2_kernel(PwArgsW p) {
           }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
-      if (tid_t == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __hip_atomic_store(p.flags + lw, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
+      if (tid_t == 0) lvc_publish_partial(p.flags, lw);
       continue;
     }
     if (cc1 < p.nk) {
@@ -328,14 +296,7 @@ __global__ __launch_bounds__(NT, 2) void conv_pw_w2_kernel(PwArgsW p) {
       const int wstep = p.ngroup > 1 ? p.ngroup : 1;
       const int last_worker = (last_unit / p.units_per_worker) * wstep + wsel;
       for (int pw = lw + wstep; pw <= last_worker; pw += wstep) {
-        if (tid_t == 0) {
-          int spins = 0;
-          while (__hip_atomic_load(p.flags + pw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) {
-            __builtin_amdgcn_s_sleep(4);
-            if (++spins > SPIN_LIMIT) { atomicOr(p.flags + p.err_index, 1); break; }
-          }
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        }
+        if (tid_t == 0) lvc_wait_partial(p.flags, pw, p.err_index);
         __syncthreads();
         const unsigned base = (unsigned)pw * WSLOT;
 #pragma unroll
@@ -352,7 +313,7 @@ __global__ __launch_bounds__(NT, 2) void conv_pw_w2_kernel(PwArgsW p) {
             __builtin_amdgcn_sched_barrier(0);      // one block's four rows in flight: hoisting all 32 loads takes 128 registers
           }
         __syncthreads();
-        if (tid_t == 0) __hip_atomic_store(p.flags + pw, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (tid_t == 0) lvc_release_partial(p.flags, pw);
       }
     }
 
@@ -445,9 +406,6 @@ __global__ __launch_bounds__(NT, 2) void conv_pw_w2_kernel(PwArgsW p) {
   }
 }
 
-#define LVC_MAX_WORKERS 1024
-static int g_cus_pw_w = 0;
-
 // Pointwise (R = S = 1, pad 0) layer y = act(conv(x, w) * scale + shift (+ residual)) on the 256 x 256 tile: x [N,H,W,C] fp32 NHWC with
 // C % 16 == 0, K % 4 == 0 (meant for K >= 256; channel tiles past K compute on zero weight rows), w_split / scale from
 // lvc_split_weights_rowscaled as for lvc_conv1x1_nhwc_f16s1 (single-accumulator form, |a| <= 4094).  relu: 0 none, 1 ReLU, 2 exact GELU.
@@ -485,13 +443,7 @@ extern "C" int lvc_conv1x1_nhwc_f16s1_w2(const float* x, const unsigned short* w
   LVC_CHECK_ARG(units < (1ll << 31), "iteration space too large");
   a.total_units = (int)units;
   a.w_plane_elems = (long long)Kpad * C;
-  if (g_cus_pw_w == 0) {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-    g_cus_pw_w = cus;
-  }
-  int cap = g_cus_pw_w;
+  int cap = lvc_cu_count();
   if (cap > LVC_MAX_WORKERS / 2) cap = LVC_MAX_WORKERS / 2;      // a worker's partial tile takes two 128 KB slots of the workspace
   a.ngroup = 1;
   if ((a.tiles_n == 2 || a.tiles_n == 4 || a.tiles_n == 8) && cap % a.tiles_n == 0 && units / a.tiles_n >= (long long)(cap / a.tiles_n) * 8) {
@@ -501,13 +453,11 @@ extern "C" int lvc_conv1x1_nhwc_f16s1_w2(const float* x, const unsigned short* w
     a.total_units = (int)units;
   }
   const int min_units = 8;     // a worker's pipeline restarts per tile segment: keep segments >= 8 stages
-  int workers = (int)((units + min_units - 1) / min_units);
-  if (workers > cap) workers = cap;
-  a.units_per_worker = (int)((units + workers - 1) / workers);
-  a.nworkers = (int)((units + a.units_per_worker - 1) / a.units_per_worker) * a.ngroup;
+  lvc_plan_workers(units, cap, min_units, &a.units_per_worker, &a.nworkers);
+  a.nworkers *= a.ngroup;
   a.partials = (float*)workspace;
-  a.flags = (int*)((char*)workspace + (size_t)LVC_MAX_WORKERS * 256 * 128 * 4);
-  a.err_index = LVC_MAX_WORKERS + lvc_range_slot();   // the layer's own range word (common.cpp)
+  a.flags = lvc_ws_flags(workspace);
+  a.err_index = lvc_ws_range_index(lvc_range_slot());   // the layer's own range word (common.cpp)
   hipLaunchKernelGGL(conv_pw_w2_kernel, dim3(a.nworkers), dim3(NT), 0, (hipStream_t)stream, a);
   LVC_CHECK_LAUNCH();
   return LVC_OK;

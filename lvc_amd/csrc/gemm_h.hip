@@ -16,11 +16,8 @@
 //     with the column tile fastest: an A tile leaves HBM once and is shared through that XCD's L2;
 //   * the epilogue stores from the accumulators through a buffer descriptor (rows >= M, columns >= N dropped by the bounds
 //     check) while the ring keeps the next tile's first chunks in flight.
-#include "common.h"
+#include "conv_common.h"
 #include <stdlib.h>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 #ifndef GH_NS
 #define GH_NS 4
@@ -36,13 +33,6 @@ struct GemmHArgs {
   unsigned y_bytes;
   int q15;      // 1: y is int16, y[m][n] = rint(32766 * value) clamped to +-32766 (cosine similarities), NaN -> 32767
 };
-
-typedef __attribute__((address_space(3))) void* gh_lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* gh_glb_ptr_t;
-
-__device__ __forceinline__ void gh_glds16(const void* g, void* l) {
-  __builtin_amdgcn_global_load_lds((gh_glb_ptr_t)g, (gh_lds_ptr_t)l, 16, 0, 0);
-}
 
 __global__ __launch_bounds__(512, 1) void gemm_f16_dma_kernel(GemmHArgs p) {
   __shared__ __attribute__((aligned(1024))) unsigned char smem[GH_NS * GH_STAGE];
@@ -98,9 +88,9 @@ __global__ __launch_bounds__(512, 1) void gemm_f16_dma_kernel(GemmHArgs p) {
     unsigned char* st = smem + (issued % GH_NS) * GH_STAGE;
     {
 #pragma unroll
-      for (int j = 0; j < 2; ++j) gh_glds16(asrc[j] + l_kc * 32, st + (wave * 32 + j * 16) * 64);
+      for (int j = 0; j < 2; ++j) glds16(asrc[j] + l_kc * 32, st + (wave * 32 + j * 16) * 64);
 #pragma unroll
-      for (int j = 0; j < 2; ++j) gh_glds16(bsrc[j] + l_kc * 32, st + GH_A_BYTES + (wave * 32 + j * 16) * 64);
+      for (int j = 0; j < 2; ++j) glds16(bsrc[j] + l_kc * 32, st + GH_A_BYTES + (wave * 32 + j * 16) * 64);
     }
     ++issued;
     if (++l_kc == p.nk) {
@@ -132,7 +122,7 @@ __global__ __launch_bounds__(512, 1) void gemm_f16_dma_kernel(GemmHArgs p) {
   struct Half { f16x8 a[2]; f16x8 b[4]; };
   const unsigned a_off = (unsigned)((wm * 64 + fi) * 64), b_off = (unsigned)(GH_A_BYTES + (wn * 128 + fi) * 64);
   const unsigned bo0 = (unsigned)((fh ^ fx3) * 16), bo1 = (unsigned)(((2 + fh) ^ fx3) * 16);
-  const unsigned smem_lds = (unsigned)(size_t)(gh_lds_ptr_t)(void*)smem;
+  const unsigned smem_lds = (unsigned)(size_t)(lds_ptr_t)(void*)smem;
   auto read_half = [&](Half& h, int g, unsigned bo) {
     const unsigned st = smem_lds + (unsigned)(g % GH_NS) * GH_STAGE;
     const unsigned a0 = st + a_off + bo, b0 = st + b_off + bo;
@@ -237,8 +227,6 @@ __global__ __launch_bounds__(512, 1) void gemm_f16_dma_kernel(GemmHArgs p) {
   }
 }
 
-static int g_cus_h = 0;
-
 static int gemm_f16_launch(const unsigned short* a, const unsigned short* b, int ldb, float* y, int M, int N, int C, int ldy,
                            void* stream, int q15 = 0) {
   LVC_CHECK_ARG(M >= 0 && N > 0 && C > 0, "bad shape");
@@ -263,13 +251,7 @@ static int gemm_f16_launch(const unsigned short* a, const unsigned short* b, int
   // launch, groups of five 1.11 GB at the same speed (0.855 vs 0.861 ms), narrower groups no less traffic and 4 - 6 % slower
   g.ngroup = 5;
   if (g.ngroup > g.tiles_n) g.ngroup = g.tiles_n;
-  if (g_cus_h == 0) {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-    g_cus_h = cus;
-  }
-  g.nworkers = g_cus_h / 8 * 8;
+  g.nworkers = lvc_cu_count() / 8 * 8;
   if (g.nworkers < 8) g.nworkers = 8;
   hipLaunchKernelGGL(gemm_f16_dma_kernel, dim3(g.nworkers), dim3(512), 0, (hipStream_t)stream, g);
   LVC_CHECK_LAUNCH();

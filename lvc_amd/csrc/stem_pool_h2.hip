@@ -21,15 +21,8 @@
 //     pads with -inf.
 // Packed weights: the mode-1 stem layout of lvc_conv2d_nhwc_f32 ([Kpad][7 * 32], k = r*32 + s*4 + c, s = 7 and c = 3
 // zero), split into [3][Kpad][224] bf16 planes.
-#include "common.h"
+#include "conv_common.h"
 #include <stdlib.h>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16;
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 #define SP_PH 3                      // pooled rows per patch
 #define SP_PW 17                     // pooled cols per patch
@@ -151,7 +144,7 @@ __global__ __launch_bounds__(SP_NT, 4) void stem_pool_h2_kernel(StemArgsH p) {  
           h[e] = hh; m[e] = mm;
           big = fmaxf(big, fabsf(wreg[j][e]));
         }
-        if (!(big <= 65504.f)) range_err = 1;
+        if (!(big <= LVC_F16_MAX)) range_err = 1;
         const int o = idx * 4;   // (iy * SP_IW + ix) * 4
         *reinterpret_cast<f16x4*>(sIn + o) = h;
         *reinterpret_cast<f16x4*>(sIn + SP_PLANE_IN + o) = m;
@@ -281,8 +274,6 @@ __global__ __launch_bounds__(SP_NT, 4) void stem_pool_h2_kernel(StemArgsH p) {  
   if (range_err && p.err) atomicOr(p.err, 2);
 }
 
-static int g_cus_stem_h = 0;
-
 // x [N,H,W,4] fp32 (NHWC4), w_split [2][Kpad][224] fp16 planes (split2h) of the mode-1 packed stem weights (Kpad >= 64 rows,
 // plane stride = Kpad * 224), scale/shift [64] or NULL, y [N,Hp,Wp,64] with Ho = (H - 1) / 2 + 1, Hp = (Ho - 1) / 2 + 1.
 extern "C" int lvc_stem_conv_pool_nhwc4_f16x2(const float* x, const unsigned short* w_split, const float* scale,
@@ -303,13 +294,7 @@ extern "C" int lvc_stem_conv_pool_nhwc4_f16x2(const float* x, const unsigned sho
   const long long xb = (long long)N * H * W * 16, wb = (long long)Kpad * 224 * 2;
   LVC_CHECK_ARG(nt < (1ll << 31) && xb < (1ll << 31), "input too large");
   a.ntiles = (int)nt; a.x_bytes = (int)xb; a.w_plane_bytes = (int)wb;
-  if (g_cus_stem_h == 0) {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-    g_cus_stem_h = cus;
-  }
-  a.nworkers = a.ntiles < 2 * g_cus_stem_h ? a.ntiles : 2 * g_cus_stem_h;   // two 66.6 KB workgroups per CU, tiles dealt round-robin
+  a.nworkers = a.ntiles < 2 * lvc_cu_count() ? a.ntiles : 2 * lvc_cu_count();   // two 66.6 KB workgroups per CU, tiles dealt round-robin
   hipLaunchKernelGGL(stem_pool_h2_kernel, dim3(a.nworkers), dim3(SP_NT), 0, (hipStream_t)stream, a);
   LVC_CHECK_LAUNCH();
   return LVC_OK;

@@ -320,21 +320,23 @@ def pack_linear(weight, bias=None, split=None, two_acc=True):
 
 
 _CONV_WS = {}
+_ERR_OFF = None      # byte offset of the range / error words (word 0 = shared, words 1.. = per layer): the library's, set by conv_workspace
 
 
 def conv_workspace(device):
     """Per-(device, stream) scratch of the stream-K conv kernel (zeroed once; see include/lvc_amd.h)."""
+    global _ERR_OFF
     key = (device.index, torch.cuda.current_stream(device).cuda_stream)
     ws = _CONV_WS.get(key)
     if ws is None:
         lib = _lib.lib()
         lib.lvc_conv_workspace_bytes.restype = c_longlong
+        if _ERR_OFF is None:
+            lib.lvc_conv_range_words_offset.restype = c_longlong
+            _ERR_OFF = lib.lvc_conv_range_words_offset()
         ws = torch.zeros(lib.lvc_conv_workspace_bytes(), dtype=torch.uint8, device=device)
         _CONV_WS[key] = ws
     return ws
-
-
-_ERR_OFF = 1024 * 256 * 128 * 4 + 1024 * 4      # byte offset of the range / error words: word 0 = shared, words 1.. = per layer
 
 
 def _conv_error_view(device):
@@ -1250,8 +1252,7 @@ def stem_conv_pool(x4, pc, relu=True, second=None):
     if y2 is not None:
         assert y2.shape == out.shape and y2.stride(3) == 1 and y2.stride(1) == Wp * y2.stride(2) and y2.stride(0) == Hp * y2.stride(1)
     if CONV_SPLIT == "f16x2":
-        ws = conv_workspace(x4.device)
-        err = ws[1024 * 256 * 128 * 4 + 1024 * 4: 1024 * 256 * 128 * 4 + 1024 * 4 + 4]   # the conv error word
+        err = _conv_error_view(x4.device)   # the conv error word
         st = _lib.lib().lvc_stem_conv_pool_nhwc4_f16x2(ptr(x4), ptr(pc.split2h()), ptr(pc.scale), ptr(pc.shift), ptr(out),
                                                        c_int(N), c_int(H), c_int(W), c_int(pc.w.shape[0]),
                                                        c_int(1 if relu else 0), ptr(err), ptr(y2),
