@@ -3,6 +3,7 @@ include/lvc_amd.h).  torch is used for device memory and streams only; all arith
 hot path happens inside liblvc_amd.so.  Every function requires CUDA(HIP) tensors and raises if
 the native library is missing -- there is deliberately no CPU path here.
 """
+import collections
 import ctypes
 
 import torch
@@ -469,7 +470,7 @@ class LaunchTimer:
     Events are recorded on the stream the kernel is launched on (torch's current stream)."""
 
     def __init__(self, only=None, every=1):
-        self.records = []  # (algorithmic flops, start event, end event, engine)
+        self.records = []  # (algorithmic flops, start event, end event, engine, algorithmic bytes)
         self.only = only   # None = bracket every launch; else the set of engine tags to bracket
         self.every = max(1, int(every))   # bracket the launches of every `every`-th step only (`next_step` counts them): an
         self.step = 0                     # event pair costs ~6 us of stream bubbles around a launch
@@ -494,7 +495,7 @@ class LaunchTimer:
         return fl, ms, len(recs)
 
 
-CONV_TIMER = None  # set to a LaunchTimer to instrument lvc_conv2d_nhwc_f32 launches
+CONV_TIMER = None  # set to a LaunchTimer to instrument the conv/GEMM launches (`_launch`)
 # Inner-product engine of the conv/GEMM layers with >= 128 output channels:
 #   "bf16x3" = fp32-accurate 3-way bf16 operand split on the bf16 matrix cores (csrc/conv_bf16x3.hip)
 #   "f32"    = v_mfma_f32_32x32x2_f32 (csrc/conv_igemm.hip); always used for the stem and the 64-channel layers
@@ -558,24 +559,147 @@ _HALO_H2_MIN_TILES = 64    # smaller 3x3 layers (p6; p5 of fewer than seven imag
 PRESPLIT = _os.environ.get("LVC_PRESPLIT", "0") == "1"
 
 
+def _launch(tag, flops, nbytes, slot, what, call):
+    """The bracket around every conv/GEMM launch.  tag: the engine the LaunchTimer files it under (None: never timed) with its
+    algorithmic flops and bytes; slot: the range slot the launch raises its range word on (None: the shared word); what: the entry
+    point `call()` calls and returns the status of.  The thread's slot is back to 0 whatever `call` does."""
+    timer = CONV_TIMER
+    if timer is not None and (tag is None or not timer.active or (timer.only is not None and tag not in timer.only)):
+        timer = None
+    if timer is not None:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+    if slot is None:
+        st = call()
+    else:
+        _lib.lib().lvc_set_range_slot(c_int(slot))
+        try:
+            st = call()
+        finally:
+            _lib.lib().lvc_set_range_slot(c_int(0))
+    check(st, what)
+    if timer is not None:
+        e1.record()
+        timer.records.append((flops, e0, e1, tag, nbytes))
+
+
+def halo_tiles(N, HW, K):
+    """256-pixel x 128-channel tiles of a direct 3x3 launch over N maps of (at most) HW pixels (see _HALO_H2_MIN_TILES)."""
+    return N * ((HW + 255) // 256) * ((K + 127) // 128)
+
+
+def wino_sized(N, H, W, K):
+    """The map fills the chip with the Winograd kernel's one-workgroup tiles (see _WINO_MIN_TILES)."""
+    return CONV_WINO and K >= 128 and wino_tiles(N, H, W, K) >= _WINO_MIN_TILES
+
+
+def _out_hw(pc, H, W):
+    return (H + 2 * pc.pad - pc.R) // pc.stride + 1, (W + 2 * pc.pad - pc.S) // pc.stride + 1
+
+
+# engine: the LaunchTimer's tag; entry: the C-ABI function; one: the single-accumulator form (|a| <= 4094: what `last_one` becomes);
+# slotted: the launch raises the LAYER's range word (and sets `last_one`), not the shared one
+ConvRoute = collections.namedtuple("ConvRoute", "engine entry one slotted")
+
+
+def conv_route(pc, N, H, W, ldo=None, out_contiguous=True, out_numel=None, ldr=None, res_numel=0, split=None):
+    """Which kernel `conv2d_nhwc` runs layer `pc` on for an [N,H,W,pc.C] input, under the module's switches as they are now.
+    pc: anything with R, S, C, K, stride, pad, mode, two_acc and state["tier"] (a PackedConv); ldo / out_contiguous / out_numel: last
+    dimension, contiguity and element count of the output buffer (default: a fresh [N,Ho,Wo,K]); ldr / res_numel: last dimension and
+    element count of the residual operand (ldr None: no residual); split: the caller's explicit operand split.
+    Pure: no tensor, no library call -- it answers on a machine without a GPU."""
+    Ho, Wo = _out_hw(pc, H, W)
+    rows = N * Ho * Wo
+    if ldo is None:
+        ldo = pc.K
+    if out_numel is None:
+        out_numel = rows * ldo
+    has_res = ldr is not None
+    # this layer's range tier (check_conv_error_word): 1 = two accumulators, 2 = the range-free bf16x3 kernels
+    tier = pc.state["tier"] if split is None else 0
+    two_acc = pc.two_acc or tier >= 1
+    configured = split is None and tier < 2      # the configured fp16 split: launches raise the LAYER's range word
+    f16 = tier < 2 and (split or CONV_SPLIT) == "f16x2"
+    pw = pc.R == 1 and pc.S == 1 and pc.pad == 0
+    halo = CONV_HALO and pc.R == 3 and pc.S == 3 and pc.stride == 1 and pc.pad == 1 and pc.C % 32 == 0
+    # narrow 1x1 layers (256 -> 64 reductions, the 15-channel RPN predictors) go to the 64- / 32-channel tiles of the
+    # 256-row pointwise shape
+    pw_narrow = _PW_NARROW and pw and pc.C >= _PW_NARROW_MIN_C and pc.C % 32 == 0 and rows >= 2048
+    if not (CONV_ENGINE == "bf16x3" and pc.mode == 0 and pc.K >= (64 if halo else 4 if pw_narrow else _BF16X3_MIN_K)
+            and pc.K % 4 == 0 and ldo % 4 == 0 and (ldr or 0) % 4 == 0):
+        return ConvRoute("f32", "lvc_conv2d_nhwc_f32", False, False)
+    if halo:
+        if not (f16 and halo_tiles(N, H * W, pc.K) >= _HALO_H2_MIN_TILES):
+            return ConvRoute("bf16x3_halo", "lvc_conv3x3_nhwc_bf16x3", False, False)
+        if configured and HALO_S1 == 2:
+            # Winograd F(2,3) along x on the maps that fill the chip with its one-workgroup tiles (csrc/conv3x3_wino.hip)
+            if (tier == 0 and (not pc.two_acc or WINO_RPN) and not has_res and out_contiguous and ldo == pc.K
+                    and wino_sized(N, H, W, pc.K)):
+                return ConvRoute("f16x2_wino", "lvc_conv3x3_nhwc_wino", True, True)
+            if not two_acc:
+                return ConvRoute("f16x2_halo", "lvc_conv3x3_nhwc_f16s1", True, True)
+        if configured and HALO_S1 >= 1:
+            return ConvRoute("f16x2_halo", "lvc_conv3x3_nhwc_f16x2_pipe", False, True)
+        return ConvRoute("f16x2_halo", "lvc_conv3x3_nhwc_f16x2", False, configured)
+    # the 256-row pointwise shape; 64-channel streams stay bf16x3 (f16x2 there: 0.312 vs 0.335 ms alone, no gain end to end)
+    if f16 and pw and pc.C >= _H2_PW_MIN_C and rows >= 2048:
+        if configured and PW_S1 and pc.C >= _PW_S1_MIN_C and pc.K >= 64 and (not has_res or _PW_S1_RES) and out_numel < (1 << 29):
+            # pointwise layers with >= 64 input channels on the pipelined kernel (csrc/conv_pw_s1.hip: fc1 0.75 -> 0.59 ms, res4 / res5
+            # conv1 -10..15 %, the memory-bound res2 / res3 conv3 -2..9 % since its epilogue stopped serialising rows:
+            # scripts/probe_pw_set.py); precision policy as for the 3x3 layers, and the layers with < 256 input channels keep the
+            # two-accumulator form -- bit-identical to the LDS-DMA kernel they ran on before (they are memory-bound: the form costs nothing)
+            one = PW_S1 == 2 and not two_acc and pc.C >= _PW_S1_ONE_MIN_C
+            if one and PW_W2 and pc.C >= _PW_W2_MIN_C and pc.K >= 256 and pc.K % 256 == 0 and rows >= _PW_W2_MIN_ROWS:
+                # >= 256 input and output channels: the 256 x 256 tile (csrc/conv_pw_w2.hip; same operands, 0.67 x the bytes per MFMA)
+                return ConvRoute("f16x2_pws1", "lvc_conv1x1_nhwc_f16s1_w2", True, True)
+            return ConvRoute("f16x2_pws1", "lvc_conv1x1_nhwc_f16s1" if one else "lvc_conv1x1_nhwc_f16x2_pipe", one, True)
+        # the LDS-DMA kernel addresses outputs / residuals through 32-bit buffer descriptors (< 2^29 elements) and moves
+        # residual rows in 32-channel chunks; anything else stays on the register-staged kernel
+        dma_ok = out_numel < (1 << 29) and (not has_res or (res_numel < (1 << 29) and pc.K % 32 == 0))
+        return ConvRoute("f16x2_pw", "lvc_conv2d_nhwc_f16x2_dma" if dma_ok else "lvc_conv2d_nhwc_f16x2", False, configured)
+    return ConvRoute("bf16x3", "lvc_conv2d_nhwc_bf16x3", False, False)
+
+
+# Every entry point of `conv_route` but the Winograd one is called as
+#   (x, weights, scale, shift, residual, out, N, H, W, C, K, <tail>, activation code, res_mode, ldo, ldr, <last>, workspace, stream).
+# entry point: (weight operand -- "w" packed fp32, "3" bf16 planes, "h" fp16 planes, "s" row-scaled fp16 planes with their own scale --,
+#               tail(pc, weights), last(pc)).  A new kernel of that shape is one ConvRoute in `conv_route` and one row here.
+_TAIL_GENERIC = lambda pc, wts: (pc.R, pc.S, pc.stride, pc.pad, pc.Kg)
+_TAIL_3X3 = lambda pc, wts: (pc.Kg,)
+_TAIL_1X1 = lambda pc, wts: (pc.stride,)
+_NO_LAST = lambda pc: ()
+_CONV_ARGS = {
+    "lvc_conv2d_nhwc_f32": ("w", _TAIL_GENERIC, lambda pc: (pc.mode,)),
+    "lvc_conv2d_nhwc_bf16x3": ("3", _TAIL_GENERIC, _NO_LAST),
+    "lvc_conv2d_nhwc_f16x2": ("h", _TAIL_GENERIC, _NO_LAST),
+    "lvc_conv2d_nhwc_f16x2_dma": ("h", _TAIL_GENERIC, _NO_LAST),
+    "lvc_conv3x3_nhwc_bf16x3": ("3", _TAIL_3X3, _NO_LAST),
+    "lvc_conv3x3_nhwc_f16x2": ("h", _TAIL_3X3, _NO_LAST),
+    "lvc_conv3x3_nhwc_f16x2_pipe": ("h", _TAIL_3X3, _NO_LAST),
+    "lvc_conv3x3_nhwc_f16s1": ("s", _TAIL_3X3, _NO_LAST),
+    "lvc_conv1x1_nhwc_f16x2_pipe": ("h", _TAIL_1X1, _NO_LAST),
+    "lvc_conv1x1_nhwc_f16s1": ("s", _TAIL_1X1, _NO_LAST),
+    "lvc_conv1x1_nhwc_f16s1_w2": ("s", lambda pc, wts: (wts.shape[1], pc.stride), _NO_LAST),
+}
+# the kernels with torch.nn.GELU() in their epilogue (activation code 2)
+_GELU_EPILOGUE = ("lvc_conv1x1_nhwc_f16x2_pipe", "lvc_conv1x1_nhwc_f16s1", "lvc_conv1x1_nhwc_f16s1_w2", "lvc_conv2d_nhwc_f16x2_dma")
+
+
 def presplit_pair_ok(x, pc2, pc3, residual=None):
-    """True where `conv2d_nhwc` would run pc2 on lvc_conv3x3_nhwc_f16s1 and pc3 on lvc_conv1x1_nhwc_f16s1 (both on tier 0): the pair
-    `conv3x3_conv1x1_presplit` replaces launch for launch.  (The routing conditions of conv2d_nhwc, restated; the bit-identity test
-    in tests/test_gpu_kernels.py fails if the two ever disagree.)"""
-    if not (PRESPLIT and CONV_ENGINE == "bf16x3" and CONV_SPLIT == "f16x2" and CONV_HALO and HALO_S1 == 2 and PW_S1 == 2):
+    """True where `conv2d_nhwc` would run pc2 on lvc_conv3x3_nhwc_f16s1 and pc3 on lvc_conv1x1_nhwc_f16s1: the pair
+    `conv3x3_conv1x1_presplit` replaces launch for launch."""
+    if not (PRESPLIT and pc3.C == pc2.K and pc2.K % 32 == 0):
         return False
     N, H, W, C = x.shape
     rows = N * H * W
-    return (pc2.mode == 0 and pc3.mode == 0 and C == pc2.C
-            and pc2.R == 3 and pc2.S == 3 and pc2.stride == 1 and pc2.pad == 1 and pc2.C % 32 == 0 and pc2.K % 32 == 0 and pc2.K >= 64
-            and pc3.R == 1 and pc3.S == 1 and pc3.stride == 1 and pc3.pad == 0 and pc3.C == pc2.K and pc3.K > 64 and pc3.K % 4 == 0
-            and pc3.C >= max(_H2_PW_MIN_C, _PW_S1_MIN_C, _PW_S1_ONE_MIN_C)
-            and pc2.state["tier"] == 0 and pc3.state["tier"] == 0 and not pc2.two_acc and not pc3.two_acc
-            and N * ((H * W + 255) // 256) * ((pc2.K + 127) // 128) >= _HALO_H2_MIN_TILES
-            and not (CONV_WINO and pc2.K >= 128 and wino_tiles(N, H, W, pc2.K) >= _WINO_MIN_TILES)
-            and rows >= 2048 and rows * pc3.K < (1 << 29) and x.numel() < (1 << 29) and rows * pc2.K < (1 << 29)
-            and (residual is None or (_PW_S1_RES and residual.shape[-1] % 4 == 0))
-            and not (PW_W2 and pc3.C >= _PW_W2_MIN_C and pc3.K >= 256 and pc3.K % 256 == 0 and rows >= _PW_W2_MIN_ROWS))
+    # the pair's own limits: no image-group split, no small-row shape, more than 64 outputs, a conv3 that keeps the map
+    if not (C == pc2.C and 2048 <= rows and max(x.numel(), rows * pc2.K, rows * pc3.K) < (1 << 29) and pc3.K > 64
+            and _out_hw(pc3, H, W) == (H, W)):
+        return False
+    r2 = conv_route(pc2, N, H, W)
+    r3 = conv_route(pc3, N, H, W, ldr=None if residual is None else residual.shape[-1],
+                    res_numel=0 if residual is None else residual.numel())
+    return r2.entry == "lvc_conv3x3_nhwc_f16s1" and r3.entry == "lvc_conv1x1_nhwc_f16s1"
 
 
 def conv3x3_conv1x1_presplit(x, pc2, pc3, residual=None, relu=True):
@@ -590,52 +714,36 @@ def conv3x3_conv1x1_presplit(x, pc2, pc3, residual=None, relu=True):
         assert residual.is_contiguous() and residual.dtype == torch.float32 and residual.shape[:3] == out.shape[:3]
     ldr = residual.shape[-1] if residual is not None else 0
     ws = ptr(conv_workspace(x.device))
-
-    def timed(engine, flops, nbytes, launch):
-        timer = CONV_TIMER
-        if timer is not None and (not timer.active or (timer.only is not None and engine not in timer.only)):
-            timer = None
-        if timer is None:
-            return launch()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        launch()
-        e1.record()
-        timer.records.append((flops, e0, e1, engine, nbytes))
-
     planes2, scale2 = pc2.split2s()
     planes3, scale3 = pc3.split2s()
     rows = N * H * W
     pc2.last_one = True
     pc3.last_one = True
-    _lib.lib().lvc_set_range_slot(c_int(pc2.slot))
-    timed("f16x2_halo", 2.0 * rows * pc2.K * C * 9, 4.0 * (rows * C + rows * pc2.K + pc2.K * C * 9),
-          lambda: check(_lib.lib().lvc_conv3x3_nhwc_f16s1_presplit(
-              ptr(x), ptr(planes2), ptr(scale2), ptr(pc2.shift), ptr(mid), c_int(N), c_int(H), c_int(W), c_int(C), c_int(pc2.K),
-              c_int(pc2.Kg), c_int(pc3.slot), ws, _stream(x)), "lvc_conv3x3_nhwc_f16s1_presplit"))
-    _lib.lib().lvc_set_range_slot(c_int(pc3.slot))
-    timed("f16x2_pws1", 2.0 * rows * pc3.K * pc3.C, 4.0 * (rows * pc3.C + rows * pc3.K + (residual.numel() if residual is not None else 0) + pc3.K * pc3.C),
-          lambda: check(_lib.lib().lvc_conv1x1_nhwc_f16s1_presplit(
-              ptr(mid), ptr(planes3), ptr(scale3), ptr(pc3.shift), ptr(residual), ptr(out), c_int(N), c_int(H), c_int(W), c_int(pc3.C),
-              c_int(pc3.K), c_int(1 if relu else 0), c_int(1 if residual is not None else 0), c_int(pc3.K), c_int(ldr), ws, _stream(x)),
-              "lvc_conv1x1_nhwc_f16s1_presplit"))
-    _lib.lib().lvc_set_range_slot(c_int(0))
+    _launch("f16x2_halo", 2.0 * rows * pc2.K * C * 9, 4.0 * (rows * C + rows * pc2.K + pc2.K * C * 9), pc2.slot,
+            "lvc_conv3x3_nhwc_f16s1_presplit", lambda: _lib.lib().lvc_conv3x3_nhwc_f16s1_presplit(
+                ptr(x), ptr(planes2), ptr(scale2), ptr(pc2.shift), ptr(mid), c_int(N), c_int(H), c_int(W), c_int(C), c_int(pc2.K),
+                c_int(pc2.Kg), c_int(pc3.slot), ws, _stream(x)))
+    _launch("f16x2_pws1", 2.0 * rows * pc3.K * pc3.C,
+            4.0 * (rows * pc3.C + rows * pc3.K + (residual.numel() if residual is not None else 0) + pc3.K * pc3.C), pc3.slot,
+            "lvc_conv1x1_nhwc_f16s1_presplit", lambda: _lib.lib().lvc_conv1x1_nhwc_f16s1_presplit(
+                ptr(mid), ptr(planes3), ptr(scale3), ptr(pc3.shift), ptr(residual), ptr(out), c_int(N), c_int(H), c_int(W), c_int(pc3.C),
+                c_int(pc3.K), c_int(1 if relu else 0), c_int(1 if residual is not None else 0), c_int(pc3.K), c_int(ldr), ws, _stream(x)))
     return out
 
 
 def conv2d_nhwc(x, pc, relu=False, residual=None, res_mode=0, out=None, split=None, act=None):
     """x: [N,H,W,C] fp32 contiguous (NHWC).  Returns [N,Ho,Wo,K].
-    act="gelu": torch.nn.GELU() (erf form) on the result -- in the epilogue of the LDS-DMA pointwise kernel where the layer
-    runs on it (bit-identical to a separate lvc_gelu pass), as a second launch otherwise.
+    act="gelu": torch.nn.GELU() (erf form) on the result -- in the epilogue of the pointwise kernels that have it, where the layer
+    runs on one (bit-identical to a separate lvc_gelu pass), as a second launch otherwise.
     split: None = the configured split (LVC_CONV_SPLIT); "bf16x3" keeps the fp32 exponent range (gradients).
     res_mode 1: residual has the output's shape; 2: residual is [N,Ho/2,Wo/2,K] and is
-    nearest-x2-upsampled on the fly (FPN top-down path, reference fpn.py:131-133)."""
+    nearest-x2-upsampled on the fly (FPN top-down path, reference fpn.py:131-133).
+    Which kernel runs is `conv_route`'s answer; its arguments are `_CONV_ARGS`' row."""
     _req_cuda(x, residual)
     assert x.dim() == 4 and x.is_contiguous() and x.dtype == torch.float32
     N, H, W, C = x.shape
     assert C == pc.C, "channel mismatch: tensor {} vs packed {}".format(C, pc.C)
-    Ho = (H + 2 * pc.pad - pc.R) // pc.stride + 1
-    Wo = (W + 2 * pc.pad - pc.S) // pc.stride + 1
+    Ho, Wo = _out_hw(pc, H, W)
     if out is None:
         out = torch.empty(N, Ho, Wo, pc.K, device=x.device, dtype=torch.float32)
     if residual is not None:
@@ -645,7 +753,8 @@ def conv2d_nhwc(x, pc, relu=False, residual=None, res_mode=0, out=None, split=No
     # The split-precision kernels address their operands through 32-bit buffer descriptors (< 2 GiB per tensor).  A batch whose
     # input / output / residual reaches 2^29 elements (32 images on the p2 map) is run in image groups that stay below it --
     # same kernels, same values (a tile never spans two images) -- instead of failing (logged once)
-    big = max(x.numel(), out.numel(), residual.numel() if residual is not None else 0)
+    res_numel = residual.numel() if residual is not None else 0
+    big = max(x.numel(), out.numel(), res_numel)
     if big >= (1 << 29) and N > 1 and out.is_contiguous() and out.shape[-1] == pc.K:
         per_image = (big + N - 1) // N
         nb = max(1, ((1 << 29) - 1) // per_image)
@@ -656,142 +765,36 @@ def conv2d_nhwc(x, pc, relu=False, residual=None, res_mode=0, out=None, split=No
             conv2d_nhwc(x[n0:n1], pc, relu=relu, residual=residual[n0:n1] if residual is not None else None, res_mode=res_mode,
                         out=out[n0:n1], split=split, act=act)
         return out
+    ldo = out.shape[-1]
     ldr = residual.shape[-1] if residual is not None else 0
-    # this layer's range tier (check_conv_error_word): 1 = two accumulators, 2 = the range-free bf16x3 kernels
-    tier = pc.state["tier"] if split is None else 0
-    two_acc = pc.two_acc or tier >= 1
-    if tier >= 2:
-        split = "bf16x3"
-    slotted = False
-    engine = "f32"
-    halo = CONV_HALO and pc.R == 3 and pc.S == 3 and pc.stride == 1 and pc.pad == 1 and pc.C % 32 == 0
-    # narrow 1x1 layers (256 -> 64 reductions, the 15-channel RPN predictors) go to the 64- / 32-channel tiles of the
-    # 256-row pointwise shape
-    pw_narrow = _PW_NARROW and pc.R == 1 and pc.S == 1 and pc.pad == 0 and pc.C >= _PW_NARROW_MIN_C and pc.C % 32 == 0 and N * Ho * Wo >= 2048
-    if (CONV_ENGINE == "bf16x3" and pc.mode == 0 and pc.K >= (64 if halo else 4 if pw_narrow else _BF16X3_MIN_K)
-            and pc.K % 4 == 0 and out.shape[-1] % 4 == 0 and ldr % 4 == 0):
-        h2_halo = halo and (split or CONV_SPLIT) == "f16x2" and N * ((H * W + 255) // 256) * ((pc.K + 127) // 128) >= _HALO_H2_MIN_TILES
-        h2_pw = (not halo and (split or CONV_SPLIT) == "f16x2" and pc.R == 1 and pc.S == 1 and pc.pad == 0 and pc.C >= _H2_PW_MIN_C
-                 and N * Ho * Wo >= 2048)   # the 256-row pointwise shape; 64-channel streams stay bf16x3 (f16x2 there: 0.312 vs 0.335 ms alone, no gain end to end)
-        engine = "f16x2_halo" if h2_halo else "f16x2_pw" if h2_pw else "bf16x3_halo" if halo else "bf16x3"
-        if engine.startswith("f16x2") and tier < 2 and split is None:
-            _lib.lib().lvc_set_range_slot(c_int(pc.slot))     # this launch raises the LAYER's range word
-            slotted = True
-            pc.last_one = False
-        if (engine == "f16x2_pw" and PW_S1 and split is None and pc.C >= _PW_S1_MIN_C and pc.K >= 64 and (residual is None or _PW_S1_RES)
-                and out.numel() < (1 << 29)):
-            engine = "f16x2_pws1"     # >= 64 input channels: the pipelined pointwise kernel (csrc/conv_pw_s1.hip)
-    if (engine == "f16x2_halo" and HALO_S1 == 2 and split is None and tier == 0 and (not pc.two_acc or WINO_RPN) and CONV_WINO and residual is None and pc.K >= 128
-            and out.is_contiguous() and out.shape[-1] == pc.K and wino_tiles(N, H, W, pc.K) >= _WINO_MIN_TILES):
-        engine = "f16x2_wino"      # (decided before the timer's engine filter: bench.py brackets the launches of ONE engine in the timed region)
-    timer = CONV_TIMER
-    if timer is not None and (not timer.active or (timer.only is not None and engine not in timer.only)):
-        timer = None
-    if timer is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    if engine != "f32":
-        if engine == "f16x2_wino":
-            # Winograd F(2,3) along x on the maps that fill the chip with its one-workgroup tiles (csrc/conv3x3_wino.hip)
-            pc.last_one = True
-            conv3x3_wino(x, pc, relu=relu, out=out)
-        elif engine == "f16x2_halo" and HALO_S1 == 2 and split is None and not two_acc:
-            planes, scale2 = pc.split2s()
-            pc.last_one = True
-            st = _lib.lib().lvc_conv3x3_nhwc_f16s1(
-                ptr(x), ptr(planes), ptr(scale2), ptr(pc.shift), ptr(residual), ptr(out),
-                c_int(N), c_int(H), c_int(W), c_int(C), c_int(pc.K), c_int(pc.Kg), c_int(1 if relu else 0),
-                c_int(res_mode), c_int(out.shape[-1]), c_int(ldr), ptr(conv_workspace(x.device)), _stream(x))
-            check(st, "lvc_conv3x3_nhwc_f16s1")
-        elif engine == "f16x2_halo" and HALO_S1 >= 1 and split is None:
-            st = _lib.lib().lvc_conv3x3_nhwc_f16x2_pipe(
-                ptr(x), ptr(pc.split2h()), ptr(pc.scale), ptr(pc.shift), ptr(residual), ptr(out),
-                c_int(N), c_int(H), c_int(W), c_int(C), c_int(pc.K), c_int(pc.Kg), c_int(1 if relu else 0),
-                c_int(res_mode), c_int(out.shape[-1]), c_int(ldr), ptr(conv_workspace(x.device)), _stream(x))
-            check(st, "lvc_conv3x3_nhwc_f16x2_pipe")
-        elif engine == "f16x2_halo":
-            st = _lib.lib().lvc_conv3x3_nhwc_f16x2(
-                ptr(x), ptr(pc.split2h()), ptr(pc.scale), ptr(pc.shift), ptr(residual), ptr(out),
-                c_int(N), c_int(H), c_int(W), c_int(C), c_int(pc.K), c_int(pc.Kg), c_int(1 if relu else 0),
-                c_int(res_mode), c_int(out.shape[-1]), c_int(ldr), ptr(conv_workspace(x.device)), _stream(x))
-            check(st, "lvc_conv3x3_nhwc_f16x2")
-        elif halo:
-            st = _lib.lib().lvc_conv3x3_nhwc_bf16x3(
-                ptr(x), ptr(pc.split3()), ptr(pc.scale), ptr(pc.shift), ptr(residual), ptr(out),
-                c_int(N), c_int(H), c_int(W), c_int(C), c_int(pc.K), c_int(pc.Kg), c_int(1 if relu else 0),
-                c_int(res_mode), c_int(out.shape[-1]), c_int(ldr), ptr(conv_workspace(x.device)), _stream(x))
-            check(st, "lvc_conv3x3_nhwc_bf16x3")
-        elif engine == "f16x2_pws1":
-            # pointwise layers with >= 64 input channels on the pipelined kernel (csrc/conv_pw_s1.hip: fc1 0.75 -> 0.59 ms, res4 / res5
-            # conv1 -10..15 %, the memory-bound res2 / res3 conv3 -2..9 % since its epilogue stopped serialising rows:
-            # scripts/probe_pw_set.py); precision policy as for the 3x3 layers, and the layers with < 256 input channels keep the
-            # two-accumulator form -- bit-identical to the LDS-DMA kernel they ran on before (they are memory-bound: the form costs nothing)
-            one = PW_S1 == 2 and not two_acc and C >= _PW_S1_ONE_MIN_C
-            pc.last_one = one
-            fused_act = act == "gelu" and not relu
-            if fused_act:
-                act = None
-            code = c_int(2 if fused_act else 1 if relu else 0)
-            if one and PW_W2 and C >= _PW_W2_MIN_C and pc.K >= 256 and pc.K % 256 == 0 and N * Ho * Wo >= _PW_W2_MIN_ROWS:
-                # >= 256 input and output channels: the 256 x 256 tile (csrc/conv_pw_w2.hip; same operands, 0.67 x the bytes per MFMA)
-                planes, scale2 = pc.split2s()
-                st = _lib.lib().lvc_conv1x1_nhwc_f16s1_w2(
-                    ptr(x), ptr(planes), ptr(scale2), ptr(pc.shift), ptr(residual), ptr(out), c_int(N), c_int(H), c_int(W), c_int(C),
-                    c_int(pc.K), c_int(planes.shape[1]), c_int(pc.stride), code, c_int(res_mode), c_int(out.shape[-1]), c_int(ldr),
-                    ptr(conv_workspace(x.device)), _stream(x))
-            elif one:
-                planes, scale2 = pc.split2s()
-                st = _lib.lib().lvc_conv1x1_nhwc_f16s1(
-                    ptr(x), ptr(planes), ptr(scale2), ptr(pc.shift), ptr(residual), ptr(out), c_int(N), c_int(H), c_int(W), c_int(C),
-                    c_int(pc.K), c_int(pc.stride), code, c_int(res_mode), c_int(out.shape[-1]), c_int(ldr),
-                    ptr(conv_workspace(x.device)), _stream(x))
-            else:
-                st = _lib.lib().lvc_conv1x1_nhwc_f16x2_pipe(
-                    ptr(x), ptr(pc.split2h()), ptr(pc.scale), ptr(pc.shift), ptr(residual), ptr(out), c_int(N), c_int(H), c_int(W), c_int(C),
-                    c_int(pc.K), c_int(pc.stride), code, c_int(res_mode), c_int(out.shape[-1]), c_int(ldr),
-                    ptr(conv_workspace(x.device)), _stream(x))
-            check(st, "lvc_conv1x1_nhwc_f16s1" if one else "lvc_conv1x1_nhwc_f16x2_pipe")
-        elif engine == "f16x2_pw":
-            # the LDS-DMA kernel addresses outputs / residuals through 32-bit buffer descriptors (< 2^29 elements) and moves
-            # residual rows in 32-channel chunks; anything else stays on the register-staged kernel (logged once)
-            dma_ok = out.numel() < (1 << 29) and (residual is None or (residual.numel() < (1 << 29) and pc.K % 32 == 0))
-            if not dma_ok:
-                _log_once("pw_dma_fallback", "pointwise layer %dx%d->%d (%d output elements, residual %s) is outside the LDS-DMA "
-                          "kernel's range; it runs on the register-staged fp16x2 kernel", N * H * W, C, pc.K, out.numel(),
-                          "yes" if residual is not None else "no")
-            fn = "lvc_conv2d_nhwc_f16x2_dma" if dma_ok else "lvc_conv2d_nhwc_f16x2"
-            fused_act = act == "gelu" and fn.endswith("_dma") and not relu
-            if fused_act:
-                act = None
-            st = getattr(_lib.lib(), fn)(
-                ptr(x), ptr(pc.split2h()), ptr(pc.scale), ptr(pc.shift), ptr(residual), ptr(out),
-                c_int(N), c_int(H), c_int(W), c_int(C), c_int(pc.K), c_int(pc.R), c_int(pc.S),
-                c_int(pc.stride), c_int(pc.pad), c_int(pc.Kg), c_int(2 if fused_act else 1 if relu else 0), c_int(res_mode),
-                c_int(out.shape[-1]), c_int(ldr), ptr(conv_workspace(x.device)), _stream(x))
-            check(st, "lvc_conv2d_nhwc_f16x2")
-        else:
-            st = _lib.lib().lvc_conv2d_nhwc_bf16x3(
-                ptr(x), ptr(pc.split3()), ptr(pc.scale), ptr(pc.shift), ptr(residual), ptr(out),
-                c_int(N), c_int(H), c_int(W), c_int(C), c_int(pc.K), c_int(pc.R), c_int(pc.S),
-                c_int(pc.stride), c_int(pc.pad), c_int(pc.Kg), c_int(1 if relu else 0), c_int(res_mode),
-                c_int(out.shape[-1]), c_int(ldr), ptr(conv_workspace(x.device)), _stream(x))
-            check(st, "lvc_conv2d_nhwc_bf16x3")
+    route = conv_route(pc, N, H, W, ldo, out.is_contiguous(), out.numel(), None if residual is None else ldr, res_numel, split)
+    entry = route.entry
+    if route.slotted:
+        pc.last_one = route.one
+    if entry == "lvc_conv3x3_nhwc_wino":
+        def call():
+            return _wino_launch(x, pc, relu, out)
     else:
-        st = _lib.lib().lvc_conv2d_nhwc_f32(
-            ptr(x), ptr(pc.w), ptr(pc.scale), ptr(pc.shift), ptr(residual), ptr(out),
-            c_int(N), c_int(H), c_int(W), c_int(C), c_int(pc.K), c_int(pc.R), c_int(pc.S),
-            c_int(pc.stride), c_int(pc.pad), c_int(pc.Kg), c_int(1 if relu else 0), c_int(res_mode),
-            c_int(out.shape[-1]), c_int(ldr), c_int(pc.mode), ptr(conv_workspace(x.device)), _stream(x))
-        check(st, "lvc_conv2d_nhwc_f32")
-    if slotted:
-        _lib.lib().lvc_set_range_slot(c_int(0))
-    if timer is not None:
-        e1.record()
-        c_real = 3 if pc.mode == 1 else C
-        # algorithmic bytes of the launch: the input pixels it needs, its output, the residual operand, the weights -- each once
-        nbytes = 4.0 * (N * (Ho * Wo if (pc.R == 1 and pc.S == 1) else H * W) * c_real + N * Ho * Wo * pc.K
-                        + (residual.numel() if residual is not None else 0) + pc.K * c_real * pc.R * pc.S)
-        timer.records.append((2.0 * N * Ho * Wo * pc.K * c_real * pc.R * pc.S, e0, e1, engine, nbytes))
+        if entry == "lvc_conv2d_nhwc_f16x2" and route.engine == "f16x2_pw":
+            _log_once("pw_dma_fallback", "pointwise layer %dx%d->%d (%d output elements, residual %s) is outside the LDS-DMA "
+                      "kernel's range; it runs on the register-staged fp16x2 kernel", N * H * W, C, pc.K, out.numel(),
+                      "yes" if residual is not None else "no")
+        code = 1 if relu else 0
+        if act == "gelu" and not relu and entry in _GELU_EPILOGUE:
+            code, act = 2, None
+        operand, tail, last = _CONV_ARGS[entry]
+
+        def call():
+            wts, scale = (pc.split2s() if operand == "s" else
+                          ((pc.split2h() if operand == "h" else pc.split3() if operand == "3" else pc.w), pc.scale))
+            ints = (N, H, W, C, pc.K) + tail(pc, wts) + (code, res_mode, ldo, ldr) + last(pc)
+            return getattr(_lib.lib(), entry)(ptr(x), ptr(wts), ptr(scale), ptr(pc.shift), ptr(residual), ptr(out),
+                                              *[c_int(v) for v in ints], ptr(conv_workspace(x.device)), _stream(x))
+    c_real = 3 if pc.mode == 1 else C
+    # algorithmic bytes of the launch: the input pixels it needs, its output, the residual operand, the weights -- each once
+    nbytes = 4.0 * (N * (Ho * Wo if (pc.R == 1 and pc.S == 1) else H * W) * c_real + N * Ho * Wo * pc.K + res_numel
+                    + pc.K * c_real * pc.R * pc.S)
+    _launch(route.engine, 2.0 * N * Ho * Wo * pc.K * c_real * pc.R * pc.S, nbytes, pc.slot if route.slotted else None, entry, call)
     if act == "gelu":
         check(_lib.lib().lvc_gelu(ptr(out), ptr(out), c_longlong(out.numel()), _stream(out)), "lvc_gelu")
     elif act is not None:
@@ -870,21 +873,43 @@ def pack_wino(pc):
     return u, scale
 
 
-def conv3x3_wino(x, pc, relu=False, out=None):
-    """y = act(conv3x3(x) * scale + shift) on the Winograd F(2,3) kernel.  x [N,H,W,C] fp32 NHWC contiguous."""
+def _wino_launch(x, pc, relu, out):
     _req_cuda(x)
     N, H, W, C = x.shape
     u, scale = pack_wino(pc)
+    return _lib.lib().lvc_conv3x3_nhwc_wino(ptr(x), ptr(u), ptr(scale), ptr(pc.shift), ptr(out), c_int(N), c_int(H), c_int(W), c_int(C), c_int(pc.K),
+                                            c_int(u.shape[4]), c_int(1 if relu else 0), c_int(out.stride(2)), ptr(conv_workspace(x.device)), _stream(x))
+
+
+def conv3x3_wino(x, pc, relu=False, out=None):
+    """y = act(conv3x3(x) * scale + shift) on the Winograd F(2,3) kernel.  x [N,H,W,C] fp32 NHWC contiguous."""
     if out is None:
-        out = torch.empty(N, H, W, pc.K, device=x.device, dtype=torch.float32)
-    check(_lib.lib().lvc_conv3x3_nhwc_wino(ptr(x), ptr(u), ptr(scale), ptr(pc.shift), ptr(out), c_int(N), c_int(H), c_int(W), c_int(C), c_int(pc.K),
-                                           c_int(u.shape[4]), c_int(1 if relu else 0), c_int(out.stride(2)), ptr(conv_workspace(x.device)), _stream(x)),
-          "lvc_conv3x3_nhwc_wino")
+        out = torch.empty(x.shape[0], x.shape[1], x.shape[2], pc.K, device=x.device, dtype=torch.float32)
+    check(_wino_launch(x, pc, relu, out), "lvc_conv3x3_nhwc_wino")
     return out
 
 
 def wino_tiles(N, H, W, K):
     return N * ((H + 7) // 8) * ((W + 31) // 32) * ((K + 127) // 128)
+
+
+def _direct_f16_3x3(pc, C):
+    """pc is a 3x3 / stride 1 / pad 1 layer over C channels that the switches and its range tier put on the direct fp16-split kernels."""
+    return (CONV_ENGINE == "bf16x3" and CONV_SPLIT == "f16x2" and CONV_HALO and HALO_S1 >= 1 and pc.state["tier"] < 2 and pc.mode == 0
+            and pc.R == 3 and pc.S == 3 and pc.stride == 1 and pc.pad == 1 and pc.C == C and C % 32 == 0)
+
+
+def _level_maps_ok(xs, N, C, K):
+    """The maps of a grouped 3x3 launch: [N,H_l,W_l,C] fp32 below 2 GiB each, the largest with enough tiles for the fp16-split kernel."""
+    return (all(x.dim() == 4 and x.is_contiguous() and x.dtype == torch.float32 and x.shape[0] == N and x.shape[3] == C
+                and x.numel() < (1 << 29) for x in xs)
+            and halo_tiles(N, max(x.shape[1] * x.shape[2] for x in xs), K) >= _HALO_H2_MIN_TILES)
+
+
+def _wino_levels(xs, K):
+    """(big, rest): indices of the maps large enough for the Winograd kernel, each launched alone, and of those that stay grouped."""
+    big = [i for i, x in enumerate(xs) if wino_sized(x.shape[0], x.shape[1], x.shape[2], K)]
+    return big, [i for i in range(len(xs)) if i not in big]
 
 
 _GROUP_SLOTS = {}
@@ -928,14 +953,10 @@ def conv3x3_levels(xs, pc, relu=False, outs=None):
     if outs is None:
         outs = [torch.empty(x.shape[0], x.shape[1], x.shape[2], q.K, device=x.device, dtype=torch.float32) for x, q in zip(xs, pcs)]
     forms = {(q.two_acc or q.state["tier"] >= 1) for q in pcs}
-    ok = (len(xs) > 1 and len(xs) <= 6 and len(pcs) == len(xs) and CONV_ENGINE == "bf16x3" and CONV_SPLIT == "f16x2" and CONV_HALO and HALO_S1 >= 1
-          and len(forms) == 1 and all(q.state["tier"] < 2 and q.mode == 0 and q.R == 3 and q.S == 3 and q.stride == 1 and q.pad == 1 and q.C == C
-                                      and q.K == p0.K and q.Kg == p0.Kg for q in pcs)
-          and C % 32 == 0 and p0.K >= 64 and p0.K % 4 == 0
-          and all(x.dim() == 4 and x.is_contiguous() and x.dtype == torch.float32 and x.shape[0] == N and x.shape[3] == C
-                  and x.numel() < (1 << 29) for x in xs)
-          and all(o.is_contiguous() and o.shape == (x.shape[0], x.shape[1], x.shape[2], p0.K) for o, x in zip(outs, xs))
-          and N * ((max(x.shape[1] * x.shape[2] for x in xs) + 255) // 256) * ((p0.K + 127) // 128) >= _HALO_H2_MIN_TILES)
+    ok = (len(xs) > 1 and len(xs) <= 6 and len(pcs) == len(xs) and len(forms) == 1
+          and all(_direct_f16_3x3(q, C) and q.K == p0.K and q.Kg == p0.Kg for q in pcs) and p0.K >= 64 and p0.K % 4 == 0
+          and _level_maps_ok(xs, N, C, p0.K)
+          and all(o.is_contiguous() and o.shape == (x.shape[0], x.shape[1], x.shape[2], p0.K) for o, x in zip(outs, xs)))
     if not ok:
         for x, q, o in zip(xs, pcs, outs):
             conv2d_nhwc(x, q, relu=relu, out=o)
@@ -946,45 +967,30 @@ def conv3x3_levels(xs, pc, relu=False, outs=None):
     if CONV_WINO and HALO_S1 == 2 and all(q.state["tier"] == 0 and (not q.two_acc or WINO_RPN) for q in pcs):
         # maps large enough to fill the chip with one-workgroup tiles run on the Winograd F(2,3) kernel (two thirds of the MFMAs), each
         # alone; the small ones stay one grouped launch of the direct kernel
-        big = [i for i, (x, q) in enumerate(zip(xs, pcs)) if wino_tiles(x.shape[0], x.shape[1], x.shape[2], q.K) >= _WINO_MIN_TILES and q.K >= 128]
+        big, rest = _wino_levels(xs, p0.K)
         if big:
             for i in big:
                 conv2d_nhwc(xs[i], pcs[i], relu=relu, out=outs[i])
-            rest = [i for i in range(len(xs)) if i not in big]
             if rest:
                 conv3x3_levels([xs[i] for i in rest], pc if shared else [pcs[i] for i in rest], relu=relu, outs=[outs[i] for i in rest])
             return outs
     L = len(xs)
-    timer = CONV_TIMER
-    if timer is not None and (not timer.active or (timer.only is not None and "f16x2_halo" not in timer.only)):
-        timer = None
-    if timer is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
     XP, IP = c_void_p * L, c_int * L
     xp, yp = XP(*[x.data_ptr() for x in xs]), XP(*[o.data_ptr() for o in outs])
     hs, ws = IP(*[x.shape[1] for x in xs]), IP(*[x.shape[2] for x in xs])
     for q in pcs:
         q.last_one = one
     ops = [q.split2s() if one else (q.split2h(), q.scale) for q in (pcs[:1] if shared else pcs)]
-    _lib.lib().lvc_set_range_slot(c_int(p0.slot if shared else _group_slot(pcs)))
     if shared:
-        st = _lib.lib().lvc_conv3x3_nhwc_f16_levels(c_int(1 if one else 0), xp, yp, hs, ws, c_int(L), ptr(ops[0][0]), ptr(ops[0][1]), ptr(p0.shift),
-                                                    c_int(N), c_int(C), c_int(p0.K), c_int(p0.Kg), c_int(1 if relu else 0),
-                                                    ptr(conv_workspace(xs[0].device)), _stream(xs[0]))
+        weights = (ptr(ops[0][0]), ptr(ops[0][1]), ptr(p0.shift))
     else:
-        def table(ts):
-            return XP(*[0 if t is None else t.data_ptr() for t in ts])
-        st = _lib.lib().lvc_conv3x3_nhwc_f16_layers(c_int(1 if one else 0), xp, yp, hs, ws, c_int(L), table([o[0] for o in ops]),
-                                                    table([o[1] for o in ops]), table([q.shift for q in pcs]),
-                                                    c_int(N), c_int(C), c_int(p0.K), c_int(p0.Kg), c_int(1 if relu else 0),
-                                                    ptr(conv_workspace(xs[0].device)), _stream(xs[0]))
-    _lib.lib().lvc_set_range_slot(c_int(0))
-    check(st, "lvc_conv3x3_nhwc_f16_levels")
-    if timer is not None:
-        e1.record()
-        px = sum(x.shape[0] * x.shape[1] * x.shape[2] for x in xs)
-        timer.records.append((2.0 * px * p0.K * C * 9, e0, e1, "f16x2_halo", 4.0 * (px * C + px * p0.K + (1 if shared else L) * p0.K * C * 9)))
+        weights = [XP(*[0 if t is None else t.data_ptr() for t in ts]) for ts in ([o[0] for o in ops], [o[1] for o in ops], [q.shift for q in pcs])]
+    entry = "lvc_conv3x3_nhwc_f16_levels" if shared else "lvc_conv3x3_nhwc_f16_layers"
+    px = sum(x.shape[0] * x.shape[1] * x.shape[2] for x in xs)
+    _launch("f16x2_halo", 2.0 * px * p0.K * C * 9, 4.0 * (px * C + px * p0.K + (1 if shared else L) * p0.K * C * 9),
+            p0.slot if shared else _group_slot(pcs), entry, lambda: getattr(_lib.lib(), entry)(
+                c_int(1 if one else 0), xp, yp, hs, ws, c_int(L), *weights, c_int(N), c_int(C), c_int(p0.K), c_int(p0.Kg),
+                c_int(1 if relu else 0), ptr(conv_workspace(xs[0].device)), _stream(xs[0])))
     return outs
 
 
@@ -996,15 +1002,12 @@ def conv3x3_levels_pred(xs, pc, pred, relu=True, _outs=None):
     buffer), or None where the launch does not apply (the caller runs the two layers one after the other)."""
     _req_cuda(*xs)
     N, C = xs[0].shape[0], xs[0].shape[3]
-    ok = (1 <= len(xs) <= 6 and CONV_ENGINE == "bf16x3" and CONV_SPLIT == "f16x2" and CONV_HALO and HALO_S1 >= 1
-          and pc.state["tier"] < 2 and (pc.two_acc or pc.state["tier"] == 1 or HALO_S1 == 1)      # the two-accumulator instance
-          and pc.mode == 0 and pc.R == 3 and pc.S == 3 and pc.stride == 1 and pc.pad == 1 and pc.C == C and C % 32 == 0
+    ok = (1 <= len(xs) <= 6 and _direct_f16_3x3(pc, C)
+          and (pc.two_acc or pc.state["tier"] == 1 or HALO_S1 == 1)      # the two-accumulator instance
           and pc.K in (128, 256) and pc.Kg == 9 * C
           and pred.mode == 0 and pred.R == 1 and pred.S == 1 and pred.stride == 1 and pred.pad == 0 and pred.C == pc.K and pred.Kg == pc.K
           and 1 <= pred.K <= 32 and pred.w.shape[0] >= 32 and pred.state["tier"] < 2
-          and all(x.dim() == 4 and x.is_contiguous() and x.dtype == torch.float32 and x.shape[0] == N and x.shape[3] == C
-                  and x.numel() < (1 << 29) for x in xs)
-          and N * ((max(x.shape[1] * x.shape[2] for x in xs) + 255) // 256) * ((pc.K + 127) // 128) >= _HALO_H2_MIN_TILES)
+          and _level_maps_ok(xs, N, C, pc.K))
     if not ok:
         return None
     ms = [x.shape[0] * x.shape[1] * x.shape[2] for x in xs]
@@ -1021,60 +1024,39 @@ def conv3x3_levels_pred(xs, pc, pred, relu=True, _outs=None):
         # ones stay one grouped launch of the two-accumulator direct kernel.  (The head is packed `two_acc`: its logits decide top-k and
         # NMS.  The Winograd form's measured error lies between the two direct forms' -- rms 4.8e-8 of the output scale against 6.7e-8
         # one accumulator / ~4e-8 two -- but its largest box errors miss the post-trunk chain test's bar: off by default, see WINO_RPN.)
-        big = [i for i, x in enumerate(xs) if wino_tiles(x.shape[0], x.shape[1], x.shape[2], pc.K) >= _WINO_MIN_TILES]
+        big, rest = _wino_levels(xs, pc.K)
         if big:
             u, scale = pack_wino(pc)
             pplanes = pred.split2h()
             pc.last_one = True
             pred.last_one = False
-            wt = CONV_TIMER
-            if wt is not None and (not wt.active or (wt.only is not None and "f16x2_wino" not in wt.only)):
-                wt = None
             for i in big:
-                x = xs[i]
-                if wt is not None:
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                _lib.lib().lvc_set_range_slot(c_int(pc.slot))
-                st = _lib.lib().lvc_conv3x3_nhwc_wino_pred(ptr(x), ptr(u), ptr(scale), ptr(pc.shift), ptr(outs[i]), c_int(N), c_int(x.shape[1]), c_int(x.shape[2]),
-                                                          c_int(C), c_int(pc.K), c_int(u.shape[4]), c_int(1 if relu else 0), c_int(pred.K), ptr(pplanes),
-                                                          ptr(pred.scale), ptr(pred.shift), c_int(pred.K), c_int(pred.w.shape[0]), c_int(pred.slot),
-                                                          ptr(conv_workspace(x.device)), _stream(x))
-                _lib.lib().lvc_set_range_slot(c_int(0))
-                check(st, "lvc_conv3x3_nhwc_wino_pred")
-                if wt is not None:
-                    e1.record()
-                    px = x.shape[0] * x.shape[1] * x.shape[2]
-                    wt.records.append((2.0 * px * pc.K * (C * 9 + pred.K), e0, e1, "f16x2_wino", 4.0 * (px * C + px * pred.K + pc.K * (C * 9 + pred.K))))
-            rest = [i for i in range(len(xs)) if i not in big]
+                x, o = xs[i], outs[i]
+                px = x.shape[0] * x.shape[1] * x.shape[2]
+                _launch("f16x2_wino", 2.0 * px * pc.K * (C * 9 + pred.K), 4.0 * (px * C + px * pred.K + pc.K * (C * 9 + pred.K)), pc.slot,
+                        "lvc_conv3x3_nhwc_wino_pred", lambda: _lib.lib().lvc_conv3x3_nhwc_wino_pred(
+                            ptr(x), ptr(u), ptr(scale), ptr(pc.shift), ptr(o), c_int(N), c_int(x.shape[1]), c_int(x.shape[2]),
+                            c_int(C), c_int(pc.K), c_int(u.shape[4]), c_int(1 if relu else 0), c_int(pred.K), ptr(pplanes),
+                            ptr(pred.scale), ptr(pred.shift), c_int(pred.K), c_int(pred.w.shape[0]), c_int(pred.slot),
+                            ptr(conv_workspace(x.device)), _stream(x)))
             if rest:
                 sub = conv3x3_levels_pred([xs[i] for i in rest], pc, pred, relu=relu, _outs=[outs[i] for i in rest])
                 assert sub is not None
             return outs
     L = len(xs)
-    timer = CONV_TIMER
-    if timer is not None and (not timer.active or (timer.only is not None and "f16x2_halo" not in timer.only)):
-        timer = None
-    if timer is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
     XP, IP = c_void_p * L, c_int * L
     xp, yp = XP(*[x.data_ptr() for x in xs]), XP(*[o.data_ptr() for o in outs])
     hs, ws = IP(*[x.shape[1] for x in xs]), IP(*[x.shape[2] for x in xs])
     pc.last_one = False
     pred.last_one = False
     planes, pplanes = pc.split2h(), pred.split2h()
-    _lib.lib().lvc_set_range_slot(c_int(pc.slot))
-    st = _lib.lib().lvc_conv3x3_nhwc_f16_levels_pred(c_int(0), xp, yp, hs, ws, c_int(L), ptr(planes), ptr(pc.scale), ptr(pc.shift), c_int(N),
-                                                     c_int(C), c_int(pc.K), c_int(pc.Kg), c_int(1 if relu else 0), ptr(pplanes),
-                                                     ptr(pred.scale), ptr(pred.shift), c_int(pred.K), c_int(pred.w.shape[0]),
-                                                     c_int(pred.K), c_int(pred.slot), ptr(conv_workspace(xs[0].device)), _stream(xs[0]))
-    _lib.lib().lvc_set_range_slot(c_int(0))
-    check(st, "lvc_conv3x3_nhwc_f16_levels_pred")
-    if timer is not None:
-        e1.record()
-        px = sum(ms)
-        timer.records.append((2.0 * px * pc.K * (C * 9 + pred.K), e0, e1, "f16x2_halo", 4.0 * (px * C + px * pred.K + pc.K * (C * 9 + pred.K))))
+    px = sum(ms)
+    _launch("f16x2_halo", 2.0 * px * pc.K * (C * 9 + pred.K), 4.0 * (px * C + px * pred.K + pc.K * (C * 9 + pred.K)), pc.slot,
+            "lvc_conv3x3_nhwc_f16_levels_pred", lambda: _lib.lib().lvc_conv3x3_nhwc_f16_levels_pred(
+                c_int(0), xp, yp, hs, ws, c_int(L), ptr(planes), ptr(pc.scale), ptr(pc.shift), c_int(N),
+                c_int(C), c_int(pc.K), c_int(pc.Kg), c_int(1 if relu else 0), ptr(pplanes),
+                ptr(pred.scale), ptr(pred.shift), c_int(pred.K), c_int(pred.w.shape[0]),
+                c_int(pred.K), c_int(pred.slot), ptr(conv_workspace(xs[0].device)), _stream(xs[0])))
     return outs
 
 
@@ -1106,24 +1088,13 @@ def conv1x1_chain(x, ch, residual=None, relu1=True, relu2=True, out1=None, out2=
         out2 = torch.empty(lead + (ch.N2,), device=x.device, dtype=torch.float32)
     if residual is not None:
         assert residual.is_contiguous() and residual.dtype == torch.float32 and residual.numel() // residual.shape[-1] == M
-    timer = CONV_TIMER
-    if timer is not None and (not timer.active or (timer.only is not None and "f16s1_chain" not in timer.only)):
-        timer = None
-    if timer is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    _lib.lib().lvc_set_range_slot(c_int(ch.slot))
-    st = _lib.lib().lvc_conv1x1_chain_nhwc_f16s1(
-        ptr(x), c_int(x.shape[-1]), ptr(ch.wa), c_int(ch.wa.shape[1]), ptr(ch.sa), ptr(ch.ta), ptr(residual),
-        c_int(residual.shape[-1] if residual is not None else 0), ptr(out1), c_int(out1.shape[-1]), c_int(1 if relu1 else 0),
-        ptr(ch.wb), c_int(ch.wb.shape[1]), ptr(ch.sb), ptr(ch.tb), ptr(out2), c_int(out2.shape[-1]), c_int(1 if relu2 else 0),
-        c_int(M), c_int(ch.K1), c_int(ch.N1), c_int(ch.N2), ptr(conv_workspace(x.device)), _stream(x))
-    _lib.lib().lvc_set_range_slot(c_int(0))
-    check(st, "lvc_conv1x1_chain_nhwc_f16s1")
-    if timer is not None:
-        e1.record()
-        nbytes = 4.0 * (M * (ch.K1 + ch.N1 + ch.N2 + (ch.N1 if residual is not None else 0)) + ch.K1 * ch.N1 + ch.N1 * ch.N2)
-        timer.records.append((2.0 * M * (ch.K1 * ch.N1 + ch.N1 * ch.N2), e0, e1, "f16s1_chain", nbytes))
+    nbytes = 4.0 * (M * (ch.K1 + ch.N1 + ch.N2 + (ch.N1 if residual is not None else 0)) + ch.K1 * ch.N1 + ch.N1 * ch.N2)
+    _launch("f16s1_chain", 2.0 * M * (ch.K1 * ch.N1 + ch.N1 * ch.N2), nbytes, ch.slot, "lvc_conv1x1_chain_nhwc_f16s1",
+            lambda: _lib.lib().lvc_conv1x1_chain_nhwc_f16s1(
+                ptr(x), c_int(x.shape[-1]), ptr(ch.wa), c_int(ch.wa.shape[1]), ptr(ch.sa), ptr(ch.ta), ptr(residual),
+                c_int(residual.shape[-1] if residual is not None else 0), ptr(out1), c_int(out1.shape[-1]), c_int(1 if relu1 else 0),
+                ptr(ch.wb), c_int(ch.wb.shape[1]), ptr(ch.sb), ptr(ch.tb), ptr(out2), c_int(out2.shape[-1]), c_int(1 if relu2 else 0),
+                c_int(M), c_int(ch.K1), c_int(ch.N1), c_int(ch.N2), ptr(conv_workspace(x.device)), _stream(x)))
     return out1, out2
 
 
@@ -1208,23 +1179,13 @@ def bottleneck_fused(x, bk, out=None):
     N, H, W, ldx = x.shape
     if out is None:
         out = torch.empty(N, H, W, 256, device=x.device, dtype=torch.float32)
-    timer = CONV_TIMER
-    if timer is not None and (not timer.active or (timer.only is not None and "f16s1_bneck" not in timer.only)):
-        timer = None
-    if timer is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    _lib.lib().lvc_set_range_slot(c_int(bk.slot))
-    st = _lib.lib().lvc_bottleneck_nhwc_f16s1(ptr(x), c_int(ldx), ptr(out), c_int(out.shape[-1]), c_int(N), c_int(H), c_int(W),
-                                              c_int(bk.cin), c_int(1 if bk.proj else 0), ptr(bk.w), ptr(bk.s1), ptr(bk.t1), ptr(bk.s2),
-                                              ptr(bk.t2), ptr(bk.s3), ptr(bk.t3), ptr(conv_workspace(x.device)), _stream(x))
-    _lib.lib().lvc_set_range_slot(c_int(0))
-    check(st, "lvc_bottleneck_nhwc_f16s1")
-    if timer is not None:
-        e1.record()
-        M = N * H * W
-        kk = bk.cin * 64 + 64 * 64 * 9 + 64 * 256 + (bk.cin * 256 if bk.proj else 0)
-        timer.records.append((2.0 * M * kk, e0, e1, "f16s1_bneck", 4.0 * (M * (bk.cin + 256) + kk)))
+    M = N * H * W
+    kk = bk.cin * 64 + 64 * 64 * 9 + 64 * 256 + (bk.cin * 256 if bk.proj else 0)
+    _launch("f16s1_bneck", 2.0 * M * kk, 4.0 * (M * (bk.cin + 256) + kk), bk.slot, "lvc_bottleneck_nhwc_f16s1",
+            lambda: _lib.lib().lvc_bottleneck_nhwc_f16s1(
+                ptr(x), c_int(ldx), ptr(out), c_int(out.shape[-1]), c_int(N), c_int(H), c_int(W),
+                c_int(bk.cin), c_int(1 if bk.proj else 0), ptr(bk.w), ptr(bk.s1), ptr(bk.t1), ptr(bk.s2),
+                ptr(bk.t2), ptr(bk.s3), ptr(bk.t3), ptr(conv_workspace(x.device)), _stream(x)))
     return out
 
 
@@ -2669,13 +2630,9 @@ def qkv_attention(x, pc, B, N, num_heads, scale):
         ws = _MHA_PLANES_WS[key] = torch.zeros(max(16, lib.lvc_mha_workspace_bytes(c_int(B), c_int(N), c_int(num_heads))), dtype=torch.uint8, device=dev)
     planes, scale2 = pc.split2s()
     pc.last_one = True
-    lib.lvc_set_range_slot(c_int(pc.slot))
-    try:
-        check(lib.lvc_conv1x1_qkv_planes_f16s1(ptr(x), ptr(planes), ptr(scale2), ptr(pc.shift), ptr(ws), c_int(B), c_int(N), c_int(pc.C),
-                                               c_int(num_heads), c_float(scale), ptr(_conv_error_view(dev)),
-                                               ptr(conv_workspace(dev)), _stream(x)), "lvc_conv1x1_qkv_planes_f16s1")
-    finally:
-        lib.lvc_set_range_slot(c_int(0))
+    _launch(None, 0.0, 0.0, pc.slot, "lvc_conv1x1_qkv_planes_f16s1", lambda: lib.lvc_conv1x1_qkv_planes_f16s1(
+        ptr(x), ptr(planes), ptr(scale2), ptr(pc.shift), ptr(ws), c_int(B), c_int(N), c_int(pc.C), c_int(num_heads), c_float(scale),
+        ptr(_conv_error_view(dev)), ptr(conv_workspace(dev)), _stream(x)))
     out = torch.empty(B * N, num_heads * 64, device=dev, dtype=torch.float32)
     check(lib.lvc_mha_mfma_planes(ptr(ws), ptr(out), c_int(B), c_int(N), c_int(num_heads), _stream(x)), "lvc_mha_mfma_planes")
     return out
