@@ -652,6 +652,36 @@ int lvc_conv1x1_qkv_planes_f16s1(const float* x, const unsigned short* w_split, 
                                  int B, int N, int C, int H, float softmax_scale, int* err_word, void* workspace, void* stream);
 int lvc_mha_mfma_planes(const void* planes, float* out, int B, int N, int H, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * GroupNorm on NHWC fp32 maps (csrc/group_norm.hip; reference detectron2/layers/batch_norm.py:127-150, NORM "GN" =
+ * nn.GroupNorm(32, C) after the FPN convs and the convs of FastRCNNConvFCHead).
+ * lvc_group_norm_fwd_nhwc: y = act(((x - mean) * rstd) * gamma + beta) (+ residual), mean / rstd [N,G] per (sample, group) over
+ *   H * W * C/G values (biased variance, eps inside the sqrt), written for the backward.  x, y [N,H,W,C]; x_sn..x_sc: the element
+ *   strides of x, which must be those of a contiguous tensor (anything else is an error); C % G == 0 (16-byte accesses where C/G is a
+ *   multiple of 4 and the pointers are 16-byte aligned, scalar ones otherwise).  relu: 0 | 1.  res_mode 0: none; 1: residual
+ *   [N,H,W,C]; 2: residual [N,(H+1)/2,(W+1)/2,C], nearest-x2-upsampled (pixel (h,w) adds residual (h/2,w/2): the conv epilogue's
+ *   res_mode 2, odd sizes included).  relu with a residual is an error.
+ *   tile_rows 0: one workgroup owns whole samples (x held in LDS when a sample fits 64 KB); > 0: statistics over tiles of
+ *   tile_rows image rows, partials in `workspace`, combined in tile order in the prologue of the second launch.
+ *   No float atomics anywhere: repeated calls are bit-identical.
+ * lvc_group_norm_bwd_nhwc: dx [N,H,W,C], dgamma [C], dbeta [C] from dy and the forward's x / mean / rstd; relu 1 rebuilds the
+ *   mask from x, gamma, beta (beta may be NULL when relu == 0).  The gradient of a residual is dy itself (res_mode 1) or its 2x2
+ *   down-sum (res_mode 2, lvc_downsum2x2_nhwc) and is not computed here.  Same two regimes; per-channel partial sums go through
+ *   workspace slabs added in a fixed order.
+ * lvc_upsample2_add_grad_nhwc: the res_mode-2 residual's gradient at ANY fine size: dres [N,(H+1)/2,(W+1)/2,C], dres[n,i,j,:] = sum of
+ *   g[n,2i..2i+1,2j..2j+1,:] inside the map (g [N,H,W,C] contiguous; an even H and W gives lvc_downsum2x2_nhwc's values).
+ * lvc_group_norm_workspace_bytes: bytes of `workspace` for one call (backward != 0: of the backward); 0 = none needed. */
+long long lvc_group_norm_workspace_bytes(int N, int H, int W, int C, int G, int tile_rows, int backward);
+int lvc_group_norm_fwd_nhwc(const float* x, const float* gamma, const float* beta, const float* residual, float* y, float* mean,
+                            float* rstd, int N, int H, int W, int C, int G, long long x_sn, long long x_sh, long long x_sw,
+                            long long x_sc, float eps, int relu, int res_mode, int tile_rows, void* workspace,
+                            long long workspace_bytes, void* stream);
+int lvc_upsample2_add_grad_nhwc(const float* g, float* dres, int N, int H, int W, int C, void* stream);
+int lvc_group_norm_bwd_nhwc(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
+                            const float* beta, float* dx, float* dgamma, float* dbeta, int N, int H, int W, int C, int G,
+                            long long x_sn, long long x_sh, long long x_sw, long long x_sc, int relu, int tile_rows,
+                            void* workspace, long long workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,3 +29,15 @@ def base_rcnn_fpn(depth=50, num_classes=80, device="cuda"):
     M.ROI_BOX_HEAD.NUM_FC = 2
     M.ROI_BOX_HEAD.POOLER_RESOLUTION = 7
     return cfg
+
+
+GN_OVERRIDES = ("MODEL.FPN.NORM", "GN", "MODEL.ROI_BOX_HEAD.NORM", "GN", "MODEL.ROI_BOX_HEAD.NUM_CONV", 4,
+                "MODEL.ROI_BOX_HEAD.NUM_FC", 1)
+
+
+def gn_rcnn_fpn(depth=50, num_classes=80, device="cuda"):
+    """`base_rcnn_fpn` with GroupNorm in the pyramid and the 4conv1fc GroupNorm box head (detectron2's
+    `Misc/scratch_mask_rcnn_R_50_FPN_*_gn.yaml` head and FPN settings; the trunk keeps FrozenBN)."""
+    cfg = base_rcnn_fpn(depth=depth, num_classes=num_classes, device=device)
+    cfg.merge_from_list(list(GN_OVERRIDES))
+    return cfg

@@ -2666,3 +2666,97 @@ def mha(qkv, B, N, num_heads, head_dim, scale, mfma=None):
     check(_lib.lib().lvc_mha(ptr(qkv), ptr(out), c_int(B), c_int(N), c_int(num_heads), c_int(head_dim), c_float(scale), _stream(qkv)),
           "lvc_mha")
     return out
+
+
+# --------------------------------------------------------------------------- GroupNorm (csrc/group_norm.hip)
+GN_SPLIT_MIN_HW = 512     # pixels per sample from which the statistics are split over row tiles (below: one workgroup owns whole samples)
+GN_TILE_ROWS = None       # image rows per tile of the split regime; None: `_gn_tile_rows`
+_GN_TARGET_WGS = 1024     # workgroups a split launch aims for (four per compute unit)
+_GN_MIN_TILE_PIXELS = 128
+
+
+def _gn_tile_rows(N, H, W):
+    """0 = the whole-sample regime; else the tile height of the split regime."""
+    if H * W < GN_SPLIT_MIN_HW:
+        return 0
+    if GN_TILE_ROWS is not None:
+        return max(1, min(int(GN_TILE_ROWS), H))
+    tiles = min(H, max(1, -(-_GN_TARGET_WGS // N)))
+    return min(H, max(-(-H // tiles), -(-_GN_MIN_TILE_PIXELS // W)))
+
+
+def _gn_workspace(x, N, H, W, C, G, rows, backward):
+    nbytes = _lib.lib().lvc_group_norm_workspace_bytes(c_int(N), c_int(H), c_int(W), c_int(C), c_int(G), c_int(rows), c_int(backward))
+    return torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None, nbytes
+
+
+def _gn_strides(x):
+    return tuple(c_longlong(s) for s in x.stride())
+
+
+def group_norm_nhwc(x, gamma, beta, num_groups, eps=1e-5, relu=False, residual=None, res_mode=0):
+    """x [N,H,W,C] fp32 -> (y, mean [N,G], rstd [N,G]);  y = act(GN(x)) (+ residual: res_mode 1 same shape, 2 the coarser map
+    [N,(H+1)//2,(W+1)//2,C] nearest-x2-upsampled, as `conv2d_nhwc`'s res_mode).  Bad arguments (C % G, a non-contiguous x, ReLU
+    with a residual) come back from the library as LvcNativeError."""
+    _req_cuda(x, gamma, beta, residual)
+    assert x.dim() == 4 and x.dtype == torch.float32 and gamma.dtype == torch.float32 and beta.dtype == torch.float32
+    N, H, W, C = x.shape
+    G = int(num_groups)
+    assert gamma.numel() == C and beta.numel() == C and gamma.is_contiguous() and beta.is_contiguous()
+    if residual is not None:
+        if res_mode == 0:
+            res_mode = 1
+        want = (N, H, W, C) if res_mode == 1 else (N, (H + 1) // 2, (W + 1) // 2, C)
+        assert residual.dtype == torch.float32 and residual.is_contiguous() and tuple(residual.shape) == want, \
+            "residual {} for res_mode {} must be {}".format(tuple(residual.shape), res_mode, want)
+    else:
+        res_mode = 0
+    y = torch.empty((N, H, W, C), device=x.device, dtype=torch.float32)
+    mean = torch.empty((N, G), device=x.device, dtype=torch.float32)
+    rstd = torch.empty((N, G), device=x.device, dtype=torch.float32)
+    if N == 0:
+        return y, mean, rstd
+    rows = _gn_tile_rows(N, H, W)
+    ws, nbytes = _gn_workspace(x, N, H, W, C, G, rows, 0)
+    rc = _lib.lib().lvc_group_norm_fwd_nhwc(ptr(x), ptr(gamma), ptr(beta), ptr(residual), ptr(y), ptr(mean), ptr(rstd), c_int(N), c_int(H),
+                                            c_int(W), c_int(C), c_int(G), *_gn_strides(x), c_float(eps), c_int(1 if relu else 0),
+                                            c_int(res_mode), c_int(rows), ptr(ws), c_longlong(nbytes), _stream(x))
+    check(rc, "lvc_group_norm_fwd_nhwc")
+    return y, mean, rstd
+
+
+def group_norm_backward_nhwc(dy, x, mean, rstd, gamma, beta, num_groups, relu=False):
+    """(dx [N,H,W,C], dgamma [C], dbeta [C]) of `group_norm_nhwc`; relu: rebuild the forward's mask from x, gamma, beta."""
+    _req_cuda(dy, x, mean, rstd, gamma, beta)
+    assert x.dim() == 4 and x.dtype == torch.float32 and dy.dtype == torch.float32 and dy.shape == x.shape
+    dy = dy.contiguous()
+    N, H, W, C = x.shape
+    G = int(num_groups)
+    dx = torch.empty((N, H, W, C), device=x.device, dtype=torch.float32)
+    dgamma = torch.empty(C, device=x.device, dtype=torch.float32)
+    dbeta = torch.empty(C, device=x.device, dtype=torch.float32)
+    if N == 0:
+        return dx, dgamma.zero_(), dbeta.zero_()
+    rows = _gn_tile_rows(N, H, W)
+    ws, nbytes = _gn_workspace(x, N, H, W, C, G, rows, 1)
+    rc = _lib.lib().lvc_group_norm_bwd_nhwc(ptr(dy), ptr(x), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(dx), ptr(dgamma), ptr(dbeta),
+                                            c_int(N), c_int(H), c_int(W), c_int(C), c_int(G), *_gn_strides(x), c_int(1 if relu else 0),
+                                            c_int(rows), ptr(ws), c_longlong(nbytes), _stream(x))
+    check(rc, "lvc_group_norm_bwd_nhwc")
+    return dx, dgamma, dbeta
+
+
+def upsample2_residual_grad(g, res_shape):
+    """Gradient of the coarser map of a res_mode-2 add: the 2x2 down-sum of g [N,H,W,C] (`downsum2x2`; with an odd H / W, where the
+    last row / column of the coarser map received one fine row / column only, lvc_upsample2_add_grad_nhwc)."""
+    _req_cuda(g)
+    g = g.contiguous()
+    N, H, W, C = g.shape
+    if H % 2 == 0 and W % 2 == 0 and C % 4 == 0:
+        out = downsum2x2(g)
+    else:
+        out = torch.empty(N, (H + 1) // 2, (W + 1) // 2, C, device=g.device, dtype=torch.float32)
+        check(_lib.lib().lvc_upsample2_add_grad_nhwc(ptr(g), ptr(out), c_int(N), c_int(H), c_int(W), c_int(C), _stream(g)),
+              "lvc_upsample2_add_grad_nhwc")
+    assert tuple(out.shape) == tuple(res_shape)
+    return out

@@ -1,4 +1,4 @@
-from .batch_norm import FrozenBatchNorm2d, get_norm
+from .batch_norm import FrozenBatchNorm2d, GroupNorm, get_norm
 from .nms import batched_nms, nms
 from .roi_align import ROIAlign, roi_align
 from .shape_spec import ShapeSpec

@@ -10,7 +10,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from .. import kernels as K
-from .batch_norm import FrozenBatchNorm2d
+from .batch_norm import FrozenBatchNorm2d, GroupNorm
 from .layout import require_device, to_nchw_view, to_nhwc
 
 
@@ -64,13 +64,20 @@ class Conv2d(nn.Module):
         self._cache_affine = _PackedCache()
         self._range_state = {"tier": 0}      # this layer's range tier survives re-packs (kernels.check_conv_error_word)
 
+    def _folds_norm(self):
+        """True when `norm` is a FrozenBatchNorm2d, whose scale / shift live in the conv kernel's epilogue (and whose scale the
+        gradients carry).  A GroupNorm is a launch of its own after the conv (`forward_nhwc`)."""
+        if self.norm is None or isinstance(self.norm, GroupNorm):
+            return False
+        assert isinstance(self.norm, FrozenBatchNorm2d)
+        return True
+
     def _affine(self):
         """FrozenBN fold / bias of the epilogue; rebuilt only when one of ITS tensors changes (not on every
         optimizer step of the weights)."""
         bn = None
         srcs = [self.bias]
-        if self.norm is not None:
-            assert isinstance(self.norm, FrozenBatchNorm2d)
+        if self._folds_norm():
             bn = (self.norm.weight, self.norm.bias, self.norm.running_mean, self.norm.running_var)
             srcs += list(bn)
         return self._cache_affine.get(srcs, lambda: K.conv_affine(self.bias, bn, self.norm.eps if bn else 1e-5))
@@ -130,7 +137,7 @@ class Conv2d(nn.Module):
                 targets.append((conv._cache, srcs))
                 sig.append((id(conv), 0, conv.weight.data_ptr(), id(aff[0]), jobs[-1]["two_acc"], jobs[-1]["tier"]))
             if dgrad is None or conv in dgrad:
-                scale = aff[0] if conv.norm is not None else None
+                scale = aff[0] if conv._folds_norm() else None
                 srcs = [conv.weight, scale]
                 if conv._stale(conv._cache_dgrad, srcs):
                     jobs.append({"weight": conv.weight, "kind": "dgrad", "stride": conv.stride, "pad": conv.padding, "scale": scale})
@@ -152,13 +159,20 @@ class Conv2d(nn.Module):
 
     def packed_dgrad(self):
         """Packed weights of the data gradient (flipped, transposed, times the FrozenBN scale)."""
-        scale = self._affine()[0] if self.norm is not None else None
+        scale = self._affine()[0] if self._folds_norm() else None
         return self._cache_dgrad.get([self.weight, scale], lambda: K.pack_conv_dgrad(self.weight, scale, self.padding))
 
     def forward_nhwc(self, x, residual=None, res_mode=0, relu=None):
         """x: [N,H,W,C] contiguous.  relu=None -> this layer's own activation."""
         if relu is None:
             relu = self.activation is not None
+        if isinstance(self.norm, GroupNorm):
+            # conv (identity epilogue, bias if any) -> GN -> ReLU | + residual: the reference's order (wrappers.py:83-99, fpn.py:125-133)
+            y = self._conv_nhwc(x, None, 0, False)
+            return self.norm.forward_nhwc(y, relu=relu, residual=residual, res_mode=res_mode)
+        return self._conv_nhwc(x, residual, res_mode, relu)
+
+    def _conv_nhwc(self, x, residual, res_mode, relu):
         if torch.is_grad_enabled() and (x.requires_grad or self.weight.requires_grad
                                         or (self.bias is not None and self.bias.requires_grad)
                                         or (residual is not None and residual.requires_grad)):
@@ -213,7 +227,7 @@ class _ConvFn(torch.autograd.Function):
         if need_w:
             K.wgrad_use_done(conv.weight)
             R = conv.kernel_size[0]
-            scale = conv.packed().scale if conv.norm is not None else None
+            scale = conv.packed().scale if conv._folds_norm() else None
             if K.can_defer_wgrad(x, g) and conv._grad_lands_in_weight():
                 # off the critical path: queued, launched with the other layers' (kernels.flush_wgrad) and written to weight.grad
                 # before backward() returns -- this node hands autograd no gradient for the weight

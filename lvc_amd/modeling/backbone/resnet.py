@@ -135,7 +135,7 @@ class BottleneckBlock(CNNBlockBase):
         if proj and (self.shortcut.stride != 1 or not self.can_fuse_projection()):
             return False
         layers = (self.conv1, self.conv2, self.conv3, self.shortcut) if proj else (self.conv1, self.conv2, self.conv3)
-        return not any(l.norm is None or getattr(l, "two_acc", False) or l._range_state["tier"] for l in layers)
+        return not any(not l._folds_norm() or getattr(l, "two_acc", False) or l._range_state["tier"] for l in layers)
 
     def fused(self):
         """The whole block as ONE launch (csrc/conv_bneck.hip: conv1's output in LDS, conv2's in registers) -- the packed weights, or None
@@ -212,7 +212,7 @@ class BasicStem(CNNBlockBase):
         """x4: [N,H,W,4] (RGB + zero slot).  second: optional callable shape -> [N,Hp,Wp,64] strided view that receives
         a copy of the output (the concat buffer of a fused projection block)."""
         if (K.CONV_ENGINE == "bf16x3" and K.CONV_SPLIT == "f16x2" and K.STEM_FUSED and self.conv1.out_channels == 64
-                and self.conv1.norm is not None):
+                and self.conv1._folds_norm()):
             return K.stem_conv_pool(x4, self.conv1.packed(), relu=True, second=second)   # conv + FrozenBN + ReLU + max-pool, one launch
         y = self.conv1.forward_nhwc(x4)
         y = K.maxpool2d_nhwc(y, 3, 2, 1)
@@ -353,6 +353,9 @@ def build_resnet_backbone(cfg, input_shape):
         unsupported.append("BasicBlock depths 18/34")
     if R.NUM_GROUPS != 1 or R.RES5_DILATION != 1:
         unsupported.append("grouped/dilated res5")
+    if norm != "FrozenBN":
+        # the fused trunk kernels (stem + pool, bottleneck blocks, chained pointwise convs) fold FrozenBN's scale / shift
+        unsupported.append("RESNETS.NORM = '{}' (the trunk implements 'FrozenBN'; GN is built for FPN.NORM and ROI_BOX_HEAD.NORM)".format(norm))
     if unsupported:
         raise NotImplementedError("not on the path of any shipped config: " + ", ".join(unsupported))
     stem = BasicStem(in_channels=input_shape.channels, out_channels=R.STEM_OUT_CHANNELS, norm=norm)

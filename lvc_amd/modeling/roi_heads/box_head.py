@@ -61,8 +61,12 @@ class FastRCNNConvFCHead(nn.Module):
         """x: [M, h, w, C] channels-last pooled features."""
         # dropout (reference box_head.py:88-89, after every FC's ReLU; identity in eval): torch's own nn.Dropout on the
         # device tensor -- its mask comes from torch's generator exactly as the reference's does
+        if self.conv_norm_relus and x.shape[0] == 0:
+            # no RoI: nothing is launched (the conv / GroupNorm kernels take no empty batch)
+            size = self._output_size if isinstance(self._output_size, int) else int(np.prod(self._output_size))
+            return x.new_zeros((0, size))
         for layer in self.conv_norm_relus:
-            x = layer.forward_nhwc(x)
+            x = layer.forward_nhwc(x)           # conv (+ GroupNorm) + ReLU
         if len(self.fcs):
             M = x.shape[0]
             fc = self.fcs[0]
