@@ -293,6 +293,22 @@ int lvc_tta_merge(const float* boxes, const float* scores, const int* classes, c
  *   receives the number of kernel launches issued (at most two). */
 int lvc_train_input_u8(const void* h_blob, const void* d_blob, long long blob_bytes, int B, unsigned char* tmp, long long tmp_bytes,
                        float* out, int n_slots, int Hp, int Wp, const float* mean3, const float* std3, int* launches, void* stream);
+/* The same for images that are mosaics of 1 to 9 tiles (reference lvc/data/mosaic.py get_mosaic / get_mosaic9; a plain image is a
+ * job with one tile), read in place: neither the canvas nor the composite is written to memory; two launches whatever B and the mix.
+ *   A job's source is a canvas: tile t covers the canvas rectangle [x1a,x2a) x [y1a,y2a) with its pixels from (x1b,y1b) on, tiles
+ *   are painted in order (the later one wins where rectangles overlap), what no tile covers is 114.  Arguments as
+ *   lvc_train_input_u8, with int64 jobs [B][128] first in the blob.  Job words: 0 X0, 1 Y0, 2 crop w, 3 crop h (the crop window in
+ *   canvas coordinates), 4 new_h, 5 new_w, 6 xb offset (-1: width unchanged), 7 xk offset, 8 kxs, 9 yb offset (-1: height
+ *   unchanged), 10 yk offset, 11 kys, 12 flip, 13 slot, 14 optional uint8 output pointer [new_h,new_w,3] (0: none), 15 byte offset
+ *   of the job's [crop h,new_w,3] intermediate in tmp (always used: the horizontal pass always runs, as a copy when the width
+ *   stays), 16 number of tiles (1..9), 17-19 reserved; tile t at words 20 + 12 t: 0 source pointer (element (y,x,c) at
+ *   src[y*sy + x*sx + c*sc]), 1 H, 2 W, 3 sy, 4 sx, 5 sc, 6 x1a, 7 y1a, 8 x2a, 9 y2a, 10 x1b, 11 y1b.
+ *   Refused before anything is launched: a tile count outside 1..9, a null tile pointer, non-positive strides, a rectangle with
+ *   negative extent, any pixel of a rectangle inside the window that maps outside its tile, taps outside the window, an output
+ *   outside the padded batch, two jobs on one slot, an intermediate outside tmp. */
+int lvc_train_input_tiles_u8(const void* h_blob, const void* d_blob, long long blob_bytes, int B, unsigned char* tmp,
+                             long long tmp_bytes, float* out, int n_slots, int Hp, int Wp, const float* mean3, const float* std3,
+                             int* launches, void* stream);
 /* F.max_pool2d on NHWC (BasicStem resnet.py:591: k3 s2 p1; LastLevelMaxPool fpn.py:176: k1 s2 p0). */
 int lvc_maxpool2d_nhwc(const float* x, float* y, int N, int H, int W, int C, int k, int stride, int pad,
                        void* stream);

@@ -16,6 +16,9 @@
 // The per-image job table and every coefficient table travel in ONE blob that the caller uploads once; the host copy of the same
 // blob is checked here (windows inside their images, every tap inside its crop, outputs inside their buffers) before anything
 // is launched.  EXACT flags (-ffp-contract=off -fno-fast-math): the normaliser rounds as preprocess_image does.
+//
+// lvc_train_input_tiles_u8 (below, with kernels and a job table of its own): the same for images that are MOSAICS of 1 to 9 tiles
+// (reference lvc/data/mosaic.py get_mosaic / get_mosaic9), read in place -- neither the canvas nor the composite exists in memory.
 #include "common.h"
 
 #define TI_PREC 22
@@ -165,6 +168,197 @@ extern "C" int lvc_train_input_u8(const void* h_blob, const void* d_blob, long l
   }
   hipLaunchKernelGGL(train_input_v_kernel, dim3(lvc_cdiv(Wp, 256), Hp, B), dim3(256), 0, st, db, tmp, out, Hp, Wp, mean3[0], mean3[1],
                      mean3[2], std3[0], std3[1], std3[2]);
+  LVC_CHECK_LAUNCH();
+  if (launches) ++*launches;
+  return LVC_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ tiled sources (mosaic)
+// A job's source is a CANVAS painted from 1..9 tiles: tile t covers the canvas rectangle [x1a, x2a) x [y1a, y2a) with its pixels
+// from (x1b, y1b) on; tiles are painted in order (where rectangles overlap the later one wins) and what no tile covers is 114.  The
+// crop window (X0, Y0, cw, ch) is in canvas coordinates.  Two launches whatever B and whatever the mix of tile counts:
+//   1. horizontal pass, grid (x tiles, rows of the largest window, B), ALWAYS run: a workgroup is one canvas row of one job, so the
+//      tiles that cross it are the same for all its threads: the first wavefront finds them once (<= 9 tests, kept in paint order in
+//      LDS).  A thread walks its taps through contiguous x and keeps the run [.., hi) in which the owner of a pixel does not change,
+//      so the tile list is searched again only where a tap leaves that run.  A width that does not change is a copy (one tap of
+//      weight 1 << 22: what Pillow's skipping the pass gives, byte for byte);
+//   2. vertical pass: train_input_v_kernel's, reading the contiguous [ch][new_w][3] intermediate only.
+#define TT_HEAD 20        // int64 words in front of a job's tiles
+#define TT_TILE 12        // int64 words per tile
+#define TT_MAX_TILES 9
+#define TT_FIELDS (TT_HEAD + TT_MAX_TILES * TT_TILE)   // 128 words = 1 KiB per job (lvc_amd.h)
+#define TT_FILL 114
+#define TT_COORD_MAX (1ll << 30)
+
+enum {
+  TT_X0 = 0, TT_Y0, TT_CW, TT_CH, TT_NEW_H, TT_NEW_W, TT_XB, TT_XK, TT_KXS, TT_YB, TT_YK, TT_KYS, TT_FLIP, TT_SLOT, TT_U8, TT_TMP,
+  TT_NT
+};
+enum { TL_SRC = 0, TL_H, TL_W, TL_SY, TL_SX, TL_SC, TL_X1A, TL_Y1A, TL_X2A, TL_Y2A, TL_X1B, TL_Y1B };
+
+// canvas window row [cw] (through the tile list) -> tmp [ch][new_w][3]
+__global__ __launch_bounds__(256) void train_input_tiles_h_kernel(const char* __restrict__ blob, unsigned char* __restrict__ tmp) {
+  const long long* jb = reinterpret_cast<const long long*>(blob) + (size_t)blockIdx.z * TT_FIELDS;
+  const int y = blockIdx.y, new_w = (int)jb[TT_NEW_W], cw = (int)jb[TT_CW];
+  if (y >= (int)jb[TT_CH] || (int)(blockIdx.x * 256) >= new_w) return;   // the whole workgroup leaves: nobody waits below
+  __shared__ int seg_lo[TT_MAX_TILES], seg_hi[TT_MAX_TILES], n_seg;
+  __shared__ long long seg_sx[TT_MAX_TILES], seg_sc[TT_MAX_TILES];
+  __shared__ const unsigned char* seg_row[TT_MAX_TILES];      // the tile's pixel under window column 0 of this row
+  if (threadIdx.x < 64) {      // the first wavefront: lane t tests tile t; the crossing tiles are compacted in paint order
+    const long long X0 = jb[TT_X0], Y = jb[TT_Y0] + y;
+    const long long* tl = jb + TT_HEAD + (size_t)(threadIdx.x < TT_MAX_TILES ? threadIdx.x : 0) * TT_TILE;
+    long long lo = 0, hi = 0;
+    bool cross = false;
+    if ((long long)threadIdx.x < jb[TT_NT] && Y >= tl[TL_Y1A] && Y < tl[TL_Y2A]) {
+      lo = tl[TL_X1A] > X0 ? tl[TL_X1A] - X0 : 0;
+      hi = tl[TL_X2A] < X0 + cw ? tl[TL_X2A] - X0 : cw;
+      cross = lo < hi;
+    }
+    const unsigned long long m = __ballot(cross);
+    if (cross) {
+      const int p = __popcll(m & ((1ull << threadIdx.x) - 1ull));
+      seg_lo[p] = (int)lo; seg_hi[p] = (int)hi; seg_sx[p] = tl[TL_SX]; seg_sc[p] = tl[TL_SC];
+      seg_row[p] = reinterpret_cast<const unsigned char*>(tl[TL_SRC]) + (Y - tl[TL_Y1A] + tl[TL_Y1B]) * tl[TL_SY] +
+                   (X0 - tl[TL_X1A] + tl[TL_X1B]) * tl[TL_SX];
+    }
+    if (threadIdx.x == 0) n_seg = __popcll(m);
+  }
+  __syncthreads();
+  const int xo = blockIdx.x * 256 + threadIdx.x;
+  if (xo >= new_w) return;
+  int xmin = xo, cnt = 1;
+  const int* k = nullptr;      // width unchanged: one tap of weight 1
+  if (jb[TT_XB] >= 0) {
+    const int* xb = reinterpret_cast<const int*>(blob + jb[TT_XB]);
+    k = reinterpret_cast<const int*>(blob + jb[TT_XK]) + (size_t)xo * (int)jb[TT_KXS];
+    xmin = xb[2 * xo]; cnt = xb[2 * xo + 1];
+  }
+  const int ns = n_seg;
+  int run_hi = -1;                       // taps below run_hi have the owner found last
+  const unsigned char* row = nullptr;    // its row (nullptr: no tile, the fill colour)
+  long long sx = 0, sc = 0;
+  int s0 = 1 << (TI_PREC - 1), s1 = s0, s2 = s0;
+  for (int t = 0; t < cnt; ++t) {
+    const int x = xmin + t;
+    if (x >= run_hi) {      // the last tile that covers x owns it; the run ends where that tile ends or a later one begins
+      row = nullptr; run_hi = cw;
+      for (int i = 0; i < ns; ++i) {
+        const int lo = seg_lo[i], hi = seg_hi[i];
+        if (lo <= x && x < hi) { row = seg_row[i]; sx = seg_sx[i]; sc = seg_sc[i]; run_hi = hi; }
+        else if (lo > x && lo < run_hi) run_hi = lo;
+      }
+    }
+    int p0 = TT_FILL, p1 = TT_FILL, p2 = TT_FILL;
+    if (row) {
+      const unsigned char* p = row + x * sx;
+      p0 = p[0]; p1 = p[sc]; p2 = p[2 * sc];
+    }
+    const int c = k ? k[t] : 1 << TI_PREC;
+    s0 += p0 * c; s1 += p1 * c; s2 += p2 * c;
+  }
+  unsigned char* o = tmp + jb[TT_TMP] + ((size_t)y * new_w + xo) * 3;
+  o[0] = ti_clip8(s0); o[1] = ti_clip8(s1); o[2] = ti_clip8(s2);
+}
+
+// tmp [ch][new_w][3] -> the job's slot (and its optional uint8 output): train_input_v_kernel on the tiled job table
+__global__ __launch_bounds__(256) void train_input_tiles_v_kernel(const char* __restrict__ blob, const unsigned char* __restrict__ tmp,
+                                                                  float* __restrict__ out, int Hp, int Wp, float m0, float m1,
+                                                                  float m2, float d0, float d1, float d2) {
+  const long long* jb = reinterpret_cast<const long long*>(blob) + (size_t)blockIdx.z * TT_FIELDS;
+  const int xo = blockIdx.x * 256 + threadIdx.x, yo = blockIdx.y;
+  if (xo >= Wp) return;
+  const int new_h = (int)jb[TT_NEW_H], new_w = (int)jb[TT_NEW_W];
+  float4 v = {0.f, 0.f, 0.f, 0.f};
+  if (yo < new_h && xo < new_w) {
+    const int xs = jb[TT_FLIP] ? new_w - 1 - xo : xo;   // HFlipTransform(new_w) after the resize
+    const unsigned char* col = tmp + jb[TT_TMP] + (size_t)xs * 3;
+    const long long sy = (long long)new_w * 3;
+    unsigned char r0, r1, r2;
+    if (jb[TT_YB] >= 0) {
+      const int* yb = reinterpret_cast<const int*>(blob + jb[TT_YB]);
+      const int* k = reinterpret_cast<const int*>(blob + jb[TT_YK]) + (size_t)yo * (int)jb[TT_KYS];
+      const int ymin = yb[2 * yo], cnt = yb[2 * yo + 1];
+      int s0 = 1 << (TI_PREC - 1), s1 = s0, s2 = s0;
+      for (int y = 0; y < cnt; ++y) {
+        const unsigned char* p = col + (ymin + y) * sy;
+        const int c = k[y];
+        s0 += p[0] * c; s1 += p[1] * c; s2 += p[2] * c;
+      }
+      r0 = ti_clip8(s0); r1 = ti_clip8(s1); r2 = ti_clip8(s2);
+    } else {   // height unchanged: Pillow skips the vertical pass
+      const unsigned char* p = col + yo * sy;
+      r0 = p[0]; r1 = p[1]; r2 = p[2];
+    }
+    if (jb[TT_U8]) {
+      unsigned char* o = reinterpret_cast<unsigned char*>(jb[TT_U8]) + ((size_t)yo * new_w + xo) * 3;
+      o[0] = r0; o[1] = r1; o[2] = r2;
+    }
+    v.x = ((float)r0 - m0) / d0;
+    v.y = ((float)r1 - m1) / d1;
+    v.z = ((float)r2 - m2) / d2;
+  }
+  *reinterpret_cast<float4*>(out + (((size_t)jb[TT_SLOT] * Hp + yo) * Wp + xo) * 4) = v;
+}
+
+// h_blob / d_blob / blob_bytes as lvc_train_input_u8, with int64 jobs [B][128] first.  Job words: 0 X0, 1 Y0, 2 cw, 3 ch (the crop
+// window in canvas coordinates), 4 new_h, 5 new_w, 6 xb offset (-1: new_w == cw), 7 xk offset, 8 kxs, 9 yb offset (-1: new_h == ch),
+// 10 yk offset, 11 kys, 12 flip, 13 slot, 14 optional uint8 output pointer [new_h][new_w][3] (0: none), 15 byte offset of the job's
+// [ch][new_w][3] intermediate in tmp (always used), 16 number of tiles (1..9), 17-19 reserved; tile t at words 20 + 12 t: 0 source
+// pointer (device uint8, element (y,x,c) at src[y*sy + x*sx + c*sc]), 1 H, 2 W, 3 sy, 4 sx, 5 sc, 6 x1a, 7 y1a, 8 x2a, 9 y2a (its
+// canvas rectangle), 10 x1b, 11 y1b (the tile pixel at the rectangle's first corner).  Checked on the host copy before anything is
+// launched: every pixel of a rectangle that the window sees lies inside its tile, every tap inside the window, outputs and intermediates inside
+// their buffers, no slot written twice.  launches: optional, the number of kernel launches issued (two).
+extern "C" int lvc_train_input_tiles_u8(const void* h_blob, const void* d_blob, long long blob_bytes, int B, unsigned char* tmp,
+                                        long long tmp_bytes, float* out, int n_slots, int Hp, int Wp, const float* mean3,
+                                        const float* std3, int* launches, void* stream) {
+  if (launches) *launches = 0;
+  LVC_CHECK_ARG(B >= 0 && n_slots >= B && Hp > 0 && Wp > 0, "bad batch size");
+  if (B == 0) return LVC_OK;
+  LVC_CHECK_ARG(h_blob && d_blob && out && tmp && mean3 && std3, "null argument");
+  LVC_CHECK_ARG(((uintptr_t)h_blob & 7) == 0 && ((uintptr_t)d_blob & 7) == 0, "the blob must be 8-byte aligned");
+  LVC_CHECK_ARG(blob_bytes >= (long long)B * TT_FIELDS * 8, "blob smaller than its job table");
+  const long long* jobs = reinterpret_cast<const long long*>(h_blob);
+  const char* hb = reinterpret_cast<const char*>(h_blob);
+  int gw = 0, gh = 0;
+  unsigned long long slots_seen = 0;
+  for (int i = 0; i < B; ++i) {
+    const long long* j = jobs + (size_t)i * TT_FIELDS;
+    const long long X0 = j[TT_X0], Y0 = j[TT_Y0], cw = j[TT_CW], ch = j[TT_CH], nh = j[TT_NEW_H], nw = j[TT_NEW_W];
+    LVC_CHECK_ARG(j[TT_NT] >= 1 && j[TT_NT] <= TT_MAX_TILES, "a job has 1 to 9 tiles");
+    LVC_CHECK_ARG(X0 >= 0 && Y0 >= 0 && cw > 0 && ch > 0 && X0 < TT_COORD_MAX && Y0 < TT_COORD_MAX && cw < TT_COORD_MAX &&
+                  ch < TT_COORD_MAX, "bad crop window");
+    for (int t = 0; t < (int)j[TT_NT]; ++t) {
+      const long long* tl = j + TT_HEAD + (size_t)t * TT_TILE;
+      LVC_CHECK_ARG(tl[TL_SRC] && tl[TL_H] > 0 && tl[TL_W] > 0 && tl[TL_H] < TT_COORD_MAX && tl[TL_W] < TT_COORD_MAX, "bad tile image");
+      LVC_CHECK_ARG(tl[TL_SY] > 0 && tl[TL_SX] > 0 && tl[TL_SC] > 0, "strides must be positive");
+      for (int f = TL_X1A; f <= TL_Y1B; ++f) LVC_CHECK_ARG(tl[f] > -TT_COORD_MAX && tl[f] < TT_COORD_MAX, "tile coordinate out of range");
+      LVC_CHECK_ARG(tl[TL_X2A] >= tl[TL_X1A] && tl[TL_Y2A] >= tl[TL_Y1A], "canvas rectangle with negative extent");
+      const long long lx = tl[TL_X1A] > X0 ? tl[TL_X1A] : X0, hx = tl[TL_X2A] < X0 + cw ? tl[TL_X2A] : X0 + cw;
+      const long long ly = tl[TL_Y1A] > Y0 ? tl[TL_Y1A] : Y0, hy = tl[TL_Y2A] < Y0 + ch ? tl[TL_Y2A] : Y0 + ch;
+      if (lx < hx && ly < hy)      // the part of the tile's rectangle the window sees: read from inside the tile
+        LVC_CHECK_ARG(lx - tl[TL_X1A] + tl[TL_X1B] >= 0 && hx - tl[TL_X1A] + tl[TL_X1B] <= tl[TL_W] &&
+                      ly - tl[TL_Y1A] + tl[TL_Y1B] >= 0 && hy - tl[TL_Y1A] + tl[TL_Y1B] <= tl[TL_H], "a tile is read outside its image");
+    }
+    LVC_CHECK_ARG(nh > 0 && nw > 0 && nh <= Hp && nw <= Wp, "output size outside the padded batch");
+    LVC_CHECK_ARG(j[TT_SLOT] >= 0 && j[TT_SLOT] < n_slots, "bad slot");
+    if (j[TT_SLOT] < 64) {
+      LVC_CHECK_ARG(!(slots_seen >> j[TT_SLOT] & 1ull), "two jobs write one slot");
+      slots_seen |= 1ull << j[TT_SLOT];
+    }
+    LVC_CHECK_ARG((j[TT_XB] >= 0) == (nw != cw) && (j[TT_YB] >= 0) == (nh != ch), "coefficients must match the size change");
+    if (j[TT_XB] >= 0) LVC_CHECK_ARG(ti_check_axis(hb, blob_bytes, j[TT_XB], j[TT_XK], j[TT_KXS], cw, nw), "bad column tables");
+    if (j[TT_YB] >= 0) LVC_CHECK_ARG(ti_check_axis(hb, blob_bytes, j[TT_YB], j[TT_YK], j[TT_KYS], ch, nh), "bad row tables");
+    LVC_CHECK_ARG(j[TT_TMP] >= 0 && j[TT_TMP] <= tmp_bytes && ch * nw * 3 <= tmp_bytes - j[TT_TMP], "intermediate outside the scratch buffer");
+    gw = nw > gw ? (int)nw : gw;
+    gh = ch > gh ? (int)ch : gh;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const char* db = reinterpret_cast<const char*>(d_blob);
+  hipLaunchKernelGGL(train_input_tiles_h_kernel, dim3(lvc_cdiv(gw, 256), gh, B), dim3(256), 0, st, db, tmp);
+  LVC_CHECK_LAUNCH();
+  if (launches) ++*launches;
+  hipLaunchKernelGGL(train_input_tiles_v_kernel, dim3(lvc_cdiv(Wp, 256), Hp, B), dim3(256), 0, st, db, tmp, out, Hp, Wp, mean3[0],
+                     mean3[1], mean3[2], std3[0], std3[1], std3[2]);
   LVC_CHECK_LAUNCH();
   if (launches) ++*launches;
   return LVC_OK;

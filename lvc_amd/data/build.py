@@ -11,6 +11,11 @@ consumer's stream recorded when the NEXT batch was asked for (by then the step t
 Order of images: the reference's TrainingSampler (detectron2/data/samplers/distributed_sampler.py:12-54: seeded torch.randperm
 shuffles, rank-strided) followed by its aspect-ratio grouping (detectron2/data/common.py:115-149: two buckets by w > h, a batch
 leaves when its bucket is full) when DATALOADER.ASPECT_RATIO_GROUPING is set (the default).
+
+Mosaic (INPUT.MOSAIC, INPUT.MOSAIC49SPLIT) has a loader of its own, as in the reference, whose trainer picks
+build_detection_train_mosaic_loader when the key is set (lvc/engine/defaults.py:518): a sampled index becomes, by MapDatasetMosaic's
+draws from Python's `random`, a plain item or a mosaic of 4 or 9 dataset items; the batch -- plain and mosaic items mixed -- is
+still one kernel call (lvc_train_input_tiles_u8: the tiles are read in place, no canvas in memory).
 """
 import itertools
 import os
@@ -126,8 +131,21 @@ class TrainInputLoader:
         for b in batches:
             yield [r["index"] for r in b]
 
+    def _draw(self, indices):
+        """The host half of a batch: per item (mapped dict, source image(s), params)."""
+        return [self.mapper.draw(self.dataset_dicts[i]) for i in indices]
+
+    def _fill(self, drawn, buf, slot):
+        """Upload the sources of a batch and queue its kernel call on the current stream."""
+        slot.images = [raw.to(self.device, non_blocking=True) for _, raw, _ in drawn]
+        K.train_input_u8(slot.images, [p.job() for _, _, p in drawn], buf, self.mapper.pixel_mean, self.mapper.pixel_std,
+                         resample_coeffs, workspace=slot.workspace)
+
+    def _items(self, drawn, indices, batch):
+        return [dict(d, prepared=batch, index=i, slot=s, train_input_params=p) for s, ((d, _, p), i) in enumerate(zip(drawn, indices))]
+
     def _prepare(self, indices, slot, stream):
-        drawn = [self.mapper.draw(self.dataset_dicts[i]) for i in indices]
+        drawn = self._draw(indices)
         sizes = [p.new_size for _, _, p in drawn]
         Hp, Wp = ImageList.padded_size(sizes, self.size_divisibility)
         B = len(drawn)
@@ -138,13 +156,10 @@ class TrainInputLoader:
             if slot.storage is None or slot.storage.numel() < n:
                 slot.storage = torch.empty(n * 5 // 4, dtype=torch.float32, device=self.device)
             buf = slot.storage[:n].view(B, Hp, Wp, 4)
-            slot.images = [raw.to(self.device, non_blocking=True) for _, raw, _ in drawn]
-            K.train_input_u8(slot.images, [p.job() for _, _, p in drawn], buf, self.mapper.pixel_mean, self.mapper.pixel_std,
-                             resample_coeffs, workspace=slot.workspace)
+            self._fill(drawn, buf, slot)
             ready = torch.cuda.Event()
             ready.record(stream)
-        batch = PreparedBatch(buf, sizes, ready)
-        return [dict(d, prepared=batch, index=i, slot=s, train_input_params=p) for s, ((d, _, p), i) in enumerate(zip(drawn, indices))]
+        return self._items(drawn, indices, PreparedBatch(buf, sizes, ready))
 
     def __iter__(self):
         batches = self.index_batches()
@@ -172,23 +187,94 @@ class TrainInputLoader:
             cur_slot.released.record(torch.cuda.current_stream(self.device))
 
 
-def build_detection_train_loader(cfg, dataset_dicts, mapper=None, seed=None, size_divisibility=None, sync=False):
-    """An infinite iterator of batches of SOLVER.IMS_PER_BATCH // world_size items for `model(batched_inputs)` in training mode.
-    dataset_dicts: the reference's dataset format with the decoded image under "raw" (uint8 [H,W,3], pinned host memory makes the
-    upload asynchronous).  seed: the sampler's (the same on every rank); the augmentations draw from numpy's global generator.
-    size_divisibility: the backbone's (default: 32 for the FPN backbones, else 0)."""
-    check_supported(cfg)
+class MosaicTrainInputLoader(TrainInputLoader):
+    """TrainInputLoader whose items are MapDatasetMosaic's: a batch entry is a list of dataset indices, [i] for a plain item (through
+    `mapper`), [i, ...] of 4 or 9 for a mosaic (through `mosaic_mapper`).  The mosaic draws happen in sampler order, before the
+    grouping, which buckets a mosaic by its LAST tile's width / height (what the reference's AspectRatioGroupedDataset sees in the
+    mapped dict).  Items carry "tile_indices" next to "index" (the sampled one)."""
+
+    def __init__(self, dataset_dicts, mapper, mosaic_mapper, map_dataset, *args, **kwargs):
+        super().__init__(dataset_dicts, mapper, *args, **kwargs)
+        self.mosaic_mapper, self.map_dataset = mosaic_mapper, map_dataset
+
+    def index_batches(self):
+        def row(i):
+            idxs = self.map_dataset.draw_indices(i)
+            d = self.dataset_dicts[idxs[-1]]
+            if "width" in d and "height" in d:
+                return {"index": idxs, "width": d["width"], "height": d["height"]}
+            return {"index": idxs, "width": int(d["raw"].shape[1]), "height": int(d["raw"].shape[0])}
+
+        rows = (row(i) for i in self.sampler)
+        batches = AspectRatioGrouper(rows, self.batch_size) if self.grouping else _plain_batches(rows, self.batch_size)
+        for b in batches:
+            yield [r["index"] for r in b]
+
+    def _draw(self, indices):
+        out = []
+        for idxs in indices:
+            if len(idxs) == 1:
+                d, raw, p = self.mapper.draw(self.dataset_dicts[idxs[0]])
+                out.append((d, [raw], p))
+            else:
+                out.append(self.mosaic_mapper.draw([self.dataset_dicts[i] for i in idxs]))
+        return out
+
+    def _fill(self, drawn, buf, slot):
+        from .mosaic import plain_tiles_item
+
+        slot.images = [[r.to(self.device, non_blocking=True) for r in raws] for _, raws, _ in drawn]
+        items = [p.tiles_item(tiles) if len(tiles) > 1 else plain_tiles_item(tiles[0], p) for tiles, (_, _, p) in zip(slot.images, drawn)]
+        K.train_input_tiles_u8(items, buf, self.mapper.pixel_mean, self.mapper.pixel_std, resample_coeffs, workspace=slot.workspace)
+
+    def _items(self, drawn, indices, batch):
+        return [dict(d, prepared=batch, index=idxs[0], tile_indices=list(idxs), slot=s, train_input_params=p)
+                for s, ((d, _, p), idxs) in enumerate(zip(drawn, indices))]
+
+
+def _loader_args(cfg, size_divisibility):
     name = cfg.DATALOADER.SAMPLER_TRAIN
     if name != "TrainingSampler":
         raise NotImplementedError("DATALOADER.SAMPLER_TRAIN = {} is not implemented (TrainingSampler only)".format(name))
     world = dist.get_world_size()
     total = int(cfg.SOLVER.IMS_PER_BATCH)
     assert total > 0 and total % world == 0, "Total batch size ({}) must be divisible by the number of gpus ({}).".format(total, world)
-    if mapper is None:
-        mapper = DatasetMapper.from_config(cfg, True)
     if size_divisibility is None:
         size_divisibility = 32 if "fpn" in cfg.MODEL.BACKBONE.NAME.lower() else 0
+    return total // world, size_divisibility
+
+
+def build_detection_train_mosaic_loader(cfg, dataset_dicts, mapper=None, seed=None, size_divisibility=None, sync=False):
+    """build_detection_train_loader for INPUT.MOSAIC > 0 (reference lvc/data/build.py build_detection_train_mosaic_loader): each
+    sampled item is, by MapDatasetMosaic's draws from Python's `random` module (seed it with `random.seed`), a plain item or a
+    mosaic of 4 / 9 dataset items.  mapper: the plain branch's (default: a DatasetMapper of this cfg); the mosaic branch is
+    DatasetMapperMosaic.from_config(cfg).  With INPUT.MOSAIC == 0 this is the plain loader.  Everything else as
+    build_detection_train_loader."""
+    from .dataset_mapper import MOSAIC_KEYS
+    from .mosaic import DatasetMapperMosaic, MapDatasetMosaic
+
+    check_supported(cfg, allow=MOSAIC_KEYS)
+    batch_size, size_divisibility = _loader_args(cfg, size_divisibility)
+    if mapper is None:
+        mapper = DatasetMapper._from_config(cfg, True, allow=MOSAIC_KEYS)
+    mosaic_mapper = DatasetMapperMosaic.from_config(cfg, True)
     sampler = TrainingSampler(len(dataset_dicts), seed=seed)
-    loader = TrainInputLoader(dataset_dicts, mapper, total // world, sampler, size_divisibility,
+    loader = MosaicTrainInputLoader(dataset_dicts, mapper, mosaic_mapper, MapDatasetMosaic(dataset_dicts, mosaic_mapper, mapper, cfg),
+                                    batch_size, sampler, size_divisibility, aspect_ratio_grouping=cfg.DATALOADER.ASPECT_RATIO_GROUPING,
+                                    device=cfg.MODEL.DEVICE, sync=sync)
+    return iter(loader)
+
+
+def build_detection_train_loader(cfg, dataset_dicts, mapper=None, seed=None, size_divisibility=None, sync=False):
+    """An infinite iterator of batches of SOLVER.IMS_PER_BATCH // world_size items for `model(batched_inputs)` in training mode.
+    dataset_dicts: the reference's dataset format with the decoded image under "raw" (uint8 [H,W,3], pinned host memory makes the
+    upload asynchronous).  seed: the sampler's (the same on every rank); the augmentations draw from numpy's global generator.
+    size_divisibility: the backbone's (default: 32 for the FPN backbones, else 0)."""
+    check_supported(cfg)
+    batch_size, size_divisibility = _loader_args(cfg, size_divisibility)
+    if mapper is None:
+        mapper = DatasetMapper.from_config(cfg, True)
+    sampler = TrainingSampler(len(dataset_dicts), seed=seed)
+    loader = TrainInputLoader(dataset_dicts, mapper, batch_size, sampler, size_divisibility,
                               aspect_ratio_grouping=cfg.DATALOADER.ASPECT_RATIO_GROUPING, device=cfg.MODEL.DEVICE, sync=sync)
     return iter(loader)

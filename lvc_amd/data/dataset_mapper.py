@@ -13,8 +13,11 @@ The image comes from `"raw"`: a uint8 [H,W,3] tensor or array, on any device, al
 files is the caller's business, as in `eval_loop_host_inputs`.
 
 Built: INPUT.CROP (all four types), MIN_SIZE_TRAIN / MAX_SIZE_TRAIN / MIN_SIZE_TRAIN_SAMPLING, the horizontal flip, boxes, classes,
-ignore flags, ids.  Not built (NotImplementedError naming the key): INPUT.COLOR_JITTER, INPUT.BLUR, INPUT.LSJ, INPUT.MOSAIC,
-MODEL.MASK_ON, MODEL.KEYPOINT_ON, MODEL.LOAD_PROPOSALS, QUERY_EXPAND.GET_CROPS; "sem_seg_file_name" in an input dict.
+ignore flags, ids; INPUT.MOSAIC / INPUT.MOSAIC49SPLIT through entry points of their own, as in the reference (mosaic.py:
+`DatasetMapperMosaic`, `MapDatasetMosaic`, build.py `build_detection_train_mosaic_loader`) -- `DatasetMapper.from_config` and
+`build_detection_train_loader` never do mosaic and refuse a cfg that asks for it, pointing there.  Not built (NotImplementedError
+naming the key): INPUT.COLOR_JITTER, INPUT.BLUR, INPUT.LSJ, MODEL.MASK_ON, MODEL.KEYPOINT_ON, MODEL.LOAD_PROPOSALS,
+QUERY_EXPAND.GET_CROPS; "sem_seg_file_name" in an input dict.
 """
 import numpy as np
 import torch
@@ -33,15 +36,22 @@ def _unsupported(cfg):
             ("MODEL.LOAD_PROPOSALS", bool(cfg.MODEL.LOAD_PROPOSALS)), ("QUERY_EXPAND.GET_CROPS", bool(cfg.QUERY_EXPAND.GET_CROPS))]
 
 
-def check_supported(cfg):
+MOSAIC_KEYS = ("INPUT.MOSAIC", "INPUT.MOSAIC49SPLIT")     # built, but only by the mosaic entry points (mosaic.py)
+
+
+def check_supported(cfg, allow=()):
+    """allow: keys the caller handles itself (the mosaic entry points pass MOSAIC_KEYS)."""
     for key, on in _unsupported(cfg):
-        if on:
-            raise NotImplementedError("{} is not implemented by the device training input (crop, resize, flip only)".format(key))
+        if on and key not in allow:
+            if key in MOSAIC_KEYS:
+                raise NotImplementedError("{} is not implemented by this entry point (crop, resize, flip only): mosaic batches come "
+                                          "from build_detection_train_mosaic_loader / DatasetMapperMosaic".format(key))
+            raise NotImplementedError("{} is not implemented by the device training input (crop, resize, flip, mosaic only)".format(key))
 
 
-def build_augmentation(cfg, is_train=True):
+def build_augmentation(cfg, is_train=True, allow=()):
     """detection_utils.build_augmentation (:563-598) with the crop of DatasetMapperIgnore.from_config (:92-99) in front."""
-    check_supported(cfg)
+    check_supported(cfg, allow)
     augs = [ResizeShortestEdge.from_config(cfg, is_train)]
     if is_train:
         augs.append(RandomFlip())
@@ -128,7 +138,11 @@ class DatasetMapper:
 
     @classmethod
     def from_config(cls, cfg, is_train=True):
-        return cls(is_train, augmentations=build_augmentation(cfg, is_train), image_format=cfg.INPUT.FORMAT,
+        return cls._from_config(cfg, is_train)
+
+    @classmethod
+    def _from_config(cls, cfg, is_train=True, allow=()):
+        return cls(is_train, augmentations=build_augmentation(cfg, is_train, allow), image_format=cfg.INPUT.FORMAT,
                    pixel_mean=cfg.MODEL.PIXEL_MEAN, pixel_std=cfg.MODEL.PIXEL_STD, device=cfg.MODEL.DEVICE)
 
     def draw(self, dataset_dict):

@@ -1680,6 +1680,78 @@ def train_input_u8(images, jobs, out, mean, std, coeffs_fn, want_u8=False, works
     return u8 if want_u8 else None
 
 
+TRAIN_INPUT_TILES_LAUNCHES = []   # kernel launches of the last (up to 64) lvc_train_input_tiles_u8 calls, as the library counted them
+TRAIN_INPUT_TILES_HEAD, TRAIN_INPUT_TILES_TILE, TRAIN_INPUT_TILES_MAX = 20, 12, 9   # job layout of lvc_train_input_tiles_u8
+TRAIN_INPUT_TILES_FIELDS = TRAIN_INPUT_TILES_HEAD + TRAIN_INPUT_TILES_MAX * TRAIN_INPUT_TILES_TILE      # (include/lvc_amd.h)
+
+
+def train_input_tiles_u8(items, out, mean, std, coeffs_fn, want_u8=False, workspace=None, table_hook=None):
+    """train_input_u8 for images that are mosaics of 1 to 9 tiles, read in place (csrc/train_input.hip lvc_train_input_tiles_u8: two
+    launches, no canvas in memory), on the current stream.  items: per output slot (tiles, (X0, Y0, crop_w, crop_h), new_h, new_w,
+    flip) with the crop window in canvas coordinates and tiles a list of (uint8 device tensor [H,W,3] of any strides, its canvas
+    rectangle (x1a, y1a, x2a, y2a), the tile pixel (x1b, y1b) at the rectangle's first corner); later tiles are painted over earlier
+    ones, what no tile covers is 114.  A plain image is one tile.  out, coeffs_fn, want_u8, workspace: as train_input_u8.
+    table_hook(tab): called with the int64 job table [B,128] before it is uploaded (tests of the library's refusals)."""
+    import numpy as np
+
+    B = len(items)
+    assert B > 0
+    _req_cuda(out)
+    assert out.dim() == 4 and out.shape[3] == 4 and out.is_contiguous() and out.dtype == torch.float32 and out.shape[0] >= B
+    ws = workspace if workspace is not None else TrainInputWorkspace(out.device)
+    F, HEAD, TILE = TRAIN_INPUT_TILES_FIELDS, TRAIN_INPUT_TILES_HEAD, TRAIN_INPUT_TILES_TILE
+    tab = np.zeros((B, F), np.int64)
+    tables, off, tmp_off = [], B * F * 8, 0
+    u8 = []
+    for i, (tiles, (X0, Y0, cw, ch), nh, nw, flip) in enumerate(items):
+        assert 1 <= len(tiles) <= TRAIN_INPUT_TILES_MAX, "an item has 1 to 9 tiles"
+        row = tab[i]
+        row[0:6] = (X0, Y0, cw, ch, nh, nw)
+        row[6] = row[9] = -1
+        for size_in, size_out, at in ((cw, nw, 6), (ch, nh, 9)):
+            if size_in != size_out:
+                b, k, ks = coeffs_fn(size_in, size_out)
+                row[at], row[at + 1], row[at + 2] = off, off + b.nbytes, ks
+                tables += [b, k]
+                off += b.nbytes + k.nbytes
+        row[12], row[13] = int(bool(flip)), i
+        if want_u8:
+            u8.append(torch.empty(nh, nw, 3, dtype=torch.uint8, device=out.device))
+            row[14] = u8[-1].data_ptr()
+        row[15] = tmp_off
+        tmp_off += (ch * nw * 3 + 255) & ~255
+        row[16] = len(tiles)
+        for t, (img, rect, origin) in enumerate(tiles):
+            assert img.dtype == torch.uint8 and img.dim() == 3 and img.shape[2] == 3 and img.device == out.device
+            at = HEAD + t * TILE
+            row[at:at + 6] = (img.data_ptr(), img.shape[0], img.shape[1], img.stride(0), img.stride(1), img.stride(2))
+            row[at + 6:at + 10] = rect
+            row[at + 10:at + 12] = origin
+    if table_hook is not None:
+        table_hook(tab)
+    ws.wait_host()
+    ws.reserve(off, tmp_off)
+    hb = ws.host.numpy()
+    hb[:tab.nbytes] = tab.reshape(-1).view(np.uint8)
+    at = tab.nbytes
+    for t in tables:
+        hb[at:at + t.nbytes] = np.ascontiguousarray(t, np.int32).reshape(-1).view(np.uint8)
+        at += t.nbytes
+    ws.dev[:off].copy_(ws.host[:off], non_blocking=True)
+    ws.uploaded = torch.cuda.Event()
+    ws.uploaded.record(torch.cuda.current_stream(out.device))
+    m = (c_float * 3)(*[float(v) for v in mean])
+    s = (c_float * 3)(*[float(v) for v in std])
+    n = c_int(0)
+    rc = _lib.lib().lvc_train_input_tiles_u8(ptr(ws.host), ptr(ws.dev), c_longlong(off), c_int(B), ptr(ws.tmp),
+                                             c_longlong(ws.tmp.numel()), ptr(out), c_int(out.shape[0]), c_int(out.shape[1]),
+                                             c_int(out.shape[2]), m, s, ctypes.byref(n), _stream(out))
+    check(rc, "lvc_train_input_tiles_u8")
+    TRAIN_INPUT_TILES_LAUNCHES.append(n.value)
+    del TRAIN_INPUT_TILES_LAUNCHES[:-64]
+    return u8 if want_u8 else None
+
+
 TTA_PARAM_STRIDE = 16     # floats per augmentation in lvc_tta_merge's inverse-transform table
 TTA_MAX_STEPS = 4
 
