@@ -309,6 +309,22 @@ int lvc_train_input_u8(const void* h_blob, const void* d_blob, long long blob_by
 int lvc_train_input_tiles_u8(const void* h_blob, const void* d_blob, long long blob_bytes, int B, unsigned char* tmp,
                              long long tmp_bytes, float* out, int n_slots, int Hp, int Wp, const float* mean3, const float* std3,
                              int* launches, void* stream);
+/* INPUT.COLOR_JITTER (reference ColorJitterPIL: torchvision's ColorJitter on a PIL image, i.e. Pillow's ImageEnhance blends,
+ * convert("L") and RGB <-> HSV conversion) of a whole batch (csrc/color_jitter.hip): per job the crop window of a canvas painted
+ * from 1 to 9 tiles (tiles and painting rule of lvc_train_input_tiles_u8) goes through up to four steps in the job's own order and
+ * leaves as a packed uint8 [crop h][crop w][3] image at the job's byte offset in `out`, which lvc_train_input_u8 then reads as a
+ * plain image.  Two launches whatever B and the mix: the sum of grey levels the contrast step needs (64-bit integer atomics into
+ * word 19 of the job's row in d_blob, which is therefore written), then the pixels.  Bytes equal Pillow's.
+ *   h_blob / d_blob / blob_bytes: int64 jobs [B][128], host copy and device copy.  Job words: 0 X0, 1 Y0, 2 crop w, 3 crop h (canvas
+ *   coordinates), 4 byte offset of the output in `out` (a multiple of 4), 5 n_ops (0..4), 6-9 step ids in the order applied (0
+ *   brightness, 1 contrast, 2 saturation, 3 hue; at most one contrast step), 10-13 their factors (the bits of an fp32 in the low
+ *   half; hue: the hue factor in [-0.5, 0.5]), 14 number of tiles (1..9), 15-18 reserved, 19 zero (the sum); tile t at words
+ *   20 + 12 t as in lvc_train_input_tiles_u8.
+ *   Refused before anything is launched: what lvc_train_input_tiles_u8 refuses of a window and its tiles, a step count outside
+ *   0..4, a step id outside 0..3, a second contrast step, a factor outside its range, a non-zero sum word, an output outside `out`
+ *   or over another job's.  launches: optional, the number of kernel launches issued (two). */
+int lvc_color_jitter_tiles_u8(const void* h_blob, void* d_blob, long long blob_bytes, int B, unsigned char* out, long long out_bytes,
+                              int* launches, void* stream);
 /* F.max_pool2d on NHWC (BasicStem resnet.py:591: k3 s2 p1; LastLevelMaxPool fpn.py:176: k1 s2 p0). */
 int lvc_maxpool2d_nhwc(const float* x, float* y, int N, int H, int W, int C, int k, int stride, int pad,
                        void* stream);

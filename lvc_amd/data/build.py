@@ -16,6 +16,12 @@ Mosaic (INPUT.MOSAIC, INPUT.MOSAIC49SPLIT) has a loader of its own, as in the re
 build_detection_train_mosaic_loader when the key is set (lvc/engine/defaults.py:518): a sampled index becomes, by MapDatasetMosaic's
 draws from Python's `random`, a plain item or a mosaic of 4 or 9 dataset items; the batch -- plain and mosaic items mixed -- is
 still one kernel call (lvc_train_input_tiles_u8: the tiles are read in place, no canvas in memory).
+
+Colour jitter (INPUT.COLOR_JITTER; both builders take `color_jitter=True` to follow the key -- without it a cfg that sets the key is
+refused, as it always was): the items whose draw carries a jitter go through one more call on the side stream
+(lvc_color_jitter_tiles_u8, csrc/color_jitter.hip: two launches for the batch), which writes their jittered crop windows into a
+scratch of the rotating buffer; lvc_train_input_u8 then resizes those as plain images.  A batch without a jitter item takes the
+calls it always took.
 """
 import itertools
 import os
@@ -25,7 +31,7 @@ import torch
 from .. import distributed as dist
 from .. import kernels as K
 from ..structures import ImageList
-from .dataset_mapper import DatasetMapper, check_supported
+from .dataset_mapper import DatasetMapper, check_supported, jitter_allow, jitter_item, plain_tiles
 from .transforms import resample_coeffs
 
 
@@ -98,6 +104,7 @@ class PreparedBatch:
 class _Slot:
     def __init__(self, device):
         self.workspace = K.TrainInputWorkspace(device)
+        self.jitter = K.ColorJitterWorkspace(device)     # job table and scratch of the batch's jittered crop windows
         self.storage = None          # flat fp32 storage of the batch buffer, grown on demand
         self.released = None         # recorded on the consumer's stream once the step that read this slot has been queued
         self.images = None           # the uploaded sources of the batch in flight
@@ -138,8 +145,14 @@ class TrainInputLoader:
     def _fill(self, drawn, buf, slot):
         """Upload the sources of a batch and queue its kernel call on the current stream."""
         slot.images = [raw.to(self.device, non_blocking=True) for _, raw, _ in drawn]
-        K.train_input_u8(slot.images, [p.job() for _, _, p in drawn], buf, self.mapper.pixel_mean, self.mapper.pixel_std,
-                         resample_coeffs, workspace=slot.workspace)
+        images, jobs = list(slot.images), [p.job() for _, _, p in drawn]
+        jit = [i for i, (_, _, p) in enumerate(drawn) if p.jitter is not None]
+        if jit:      # their jittered crop windows become the images the resize reads
+            crops = K.color_jitter_tiles_u8([jitter_item(plain_tiles(images[i]), drawn[i][2].crop, drawn[i][2]) for i in jit],
+                                            workspace=slot.jitter)
+            for i, crop in zip(jit, crops):
+                images[i], jobs[i] = crop, drawn[i][2].crop_job()
+        K.train_input_u8(images, jobs, buf, self.mapper.pixel_mean, self.mapper.pixel_std, resample_coeffs, workspace=slot.workspace)
 
     def _items(self, drawn, indices, batch):
         return [dict(d, prepared=batch, index=i, slot=s, train_input_params=p) for s, ((d, _, p), i) in enumerate(zip(drawn, indices))]
@@ -225,6 +238,16 @@ class MosaicTrainInputLoader(TrainInputLoader):
 
         slot.images = [[r.to(self.device, non_blocking=True) for r in raws] for _, raws, _ in drawn]
         items = [p.tiles_item(tiles) if len(tiles) > 1 else plain_tiles_item(tiles[0], p) for tiles, (_, _, p) in zip(slot.images, drawn)]
+        jit = [i for i, (_, _, p) in enumerate(drawn) if p.jitter is not None]
+        if jit:      # their jittered crop windows (of the painted canvas, 114 fill included) become plain one-tile items
+            crops = K.color_jitter_tiles_u8([jitter_item(items[i][0], items[i][1], drawn[i][2]) for i in jit], workspace=slot.jitter)
+            if len(jit) == len(items):      # every item is a plain image now: the plain entry
+                K.train_input_u8(crops, [p.crop_job() for _, _, p in drawn], buf, self.mapper.pixel_mean, self.mapper.pixel_std,
+                                 resample_coeffs, workspace=slot.workspace)
+                return
+            for i, crop in zip(jit, crops):
+                job = drawn[i][2].crop_job()
+                items[i] = (plain_tiles(crop), job[0:4], job[4], job[5], job[6])
         K.train_input_tiles_u8(items, buf, self.mapper.pixel_mean, self.mapper.pixel_std, resample_coeffs, workspace=slot.workspace)
 
     def _items(self, drawn, indices, batch):
@@ -244,20 +267,21 @@ def _loader_args(cfg, size_divisibility):
     return total // world, size_divisibility
 
 
-def build_detection_train_mosaic_loader(cfg, dataset_dicts, mapper=None, seed=None, size_divisibility=None, sync=False):
+def build_detection_train_mosaic_loader(cfg, dataset_dicts, mapper=None, seed=None, size_divisibility=None, sync=False, *,
+                                        color_jitter=None):
     """build_detection_train_loader for INPUT.MOSAIC > 0 (reference lvc/data/build.py build_detection_train_mosaic_loader): each
     sampled item is, by MapDatasetMosaic's draws from Python's `random` module (seed it with `random.seed`), a plain item or a
     mosaic of 4 / 9 dataset items.  mapper: the plain branch's (default: a DatasetMapper of this cfg); the mosaic branch is
     DatasetMapperMosaic.from_config(cfg).  With INPUT.MOSAIC == 0 this is the plain loader.  Everything else as
-    build_detection_train_loader."""
+    build_detection_train_loader (color_jitter goes to both mappers)."""
     from .dataset_mapper import MOSAIC_KEYS
     from .mosaic import DatasetMapperMosaic, MapDatasetMosaic
 
-    check_supported(cfg, allow=MOSAIC_KEYS)
+    check_supported(cfg, allow=jitter_allow(MOSAIC_KEYS, color_jitter))
     batch_size, size_divisibility = _loader_args(cfg, size_divisibility)
     if mapper is None:
-        mapper = DatasetMapper._from_config(cfg, True, allow=MOSAIC_KEYS)
-    mosaic_mapper = DatasetMapperMosaic.from_config(cfg, True)
+        mapper = DatasetMapper._from_config(cfg, True, allow=MOSAIC_KEYS, color_jitter=color_jitter)
+    mosaic_mapper = DatasetMapperMosaic.from_config(cfg, True, color_jitter=color_jitter)
     sampler = TrainingSampler(len(dataset_dicts), seed=seed)
     loader = MosaicTrainInputLoader(dataset_dicts, mapper, mosaic_mapper, MapDatasetMosaic(dataset_dicts, mosaic_mapper, mapper, cfg),
                                     batch_size, sampler, size_divisibility, aspect_ratio_grouping=cfg.DATALOADER.ASPECT_RATIO_GROUPING,
@@ -265,15 +289,17 @@ def build_detection_train_mosaic_loader(cfg, dataset_dicts, mapper=None, seed=No
     return iter(loader)
 
 
-def build_detection_train_loader(cfg, dataset_dicts, mapper=None, seed=None, size_divisibility=None, sync=False):
+def build_detection_train_loader(cfg, dataset_dicts, mapper=None, seed=None, size_divisibility=None, sync=False, *, color_jitter=None):
     """An infinite iterator of batches of SOLVER.IMS_PER_BATCH // world_size items for `model(batched_inputs)` in training mode.
     dataset_dicts: the reference's dataset format with the decoded image under "raw" (uint8 [H,W,3], pinned host memory makes the
     upload asynchronous).  seed: the sampler's (the same on every rank); the augmentations draw from numpy's global generator.
-    size_divisibility: the backbone's (default: 32 for the FPN backbones, else 0)."""
-    check_supported(cfg)
+    size_divisibility: the backbone's (default: 32 for the FPN backbones, else 0).  color_jitter: None -- a cfg that sets
+    INPUT.COLOR_JITTER is refused; True -- follow the key; a transforms.ColorJitter -- use it (its draws come from torch's default
+    generator: `torch.manual_seed`)."""
+    check_supported(cfg, jitter_allow((), color_jitter))
     batch_size, size_divisibility = _loader_args(cfg, size_divisibility)
     if mapper is None:
-        mapper = DatasetMapper.from_config(cfg, True)
+        mapper = DatasetMapper.from_config(cfg, True, color_jitter=color_jitter)
     sampler = TrainingSampler(len(dataset_dicts), seed=seed)
     loader = TrainInputLoader(dataset_dicts, mapper, batch_size, sampler, size_divisibility,
                               aspect_ratio_grouping=cfg.DATALOADER.ASPECT_RATIO_GROUPING, device=cfg.MODEL.DEVICE, sync=sync)

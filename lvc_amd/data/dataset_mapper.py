@@ -13,10 +13,12 @@ The image comes from `"raw"`: a uint8 [H,W,3] tensor or array, on any device, al
 files is the caller's business, as in `eval_loop_host_inputs`.
 
 Built: INPUT.CROP (all four types), MIN_SIZE_TRAIN / MAX_SIZE_TRAIN / MIN_SIZE_TRAIN_SAMPLING, the horizontal flip, boxes, classes,
-ignore flags, ids; INPUT.MOSAIC / INPUT.MOSAIC49SPLIT through entry points of their own, as in the reference (mosaic.py:
+ignore flags, ids; INPUT.COLOR_JITTER (transforms.ColorJitter; pixels: `kernels.color_jitter_tiles_u8`, csrc/color_jitter.hip, on the
+crop window in front of the resize) for callers that opt in with `color_jitter=True` -- without it the key still raises, as it
+always has; INPUT.MOSAIC / INPUT.MOSAIC49SPLIT through entry points of their own, as in the reference (mosaic.py:
 `DatasetMapperMosaic`, `MapDatasetMosaic`, build.py `build_detection_train_mosaic_loader`) -- `DatasetMapper.from_config` and
 `build_detection_train_loader` never do mosaic and refuse a cfg that asks for it, pointing there.  Not built (NotImplementedError
-naming the key): INPUT.COLOR_JITTER, INPUT.BLUR, INPUT.LSJ, MODEL.MASK_ON, MODEL.KEYPOINT_ON, MODEL.LOAD_PROPOSALS,
+naming the key): INPUT.BLUR, INPUT.LSJ, MODEL.MASK_ON, MODEL.KEYPOINT_ON, MODEL.LOAD_PROPOSALS,
 QUERY_EXPAND.GET_CROPS; "sem_seg_file_name" in an input dict.
 """
 import numpy as np
@@ -24,7 +26,7 @@ import torch
 
 from .. import kernels as K
 from ..structures import Boxes, BoxMode, Instances
-from .transforms import AugmentationList, RandomCrop, RandomFlip, ResizeShortestEdge, resample_coeffs
+from .transforms import AugmentationList, ColorJitter, RandomCrop, RandomFlip, ResizeShortestEdge, resample_coeffs
 
 
 def _unsupported(cfg):
@@ -37,6 +39,7 @@ def _unsupported(cfg):
 
 
 MOSAIC_KEYS = ("INPUT.MOSAIC", "INPUT.MOSAIC49SPLIT")     # built, but only by the mosaic entry points (mosaic.py)
+JITTER_KEY = "INPUT.COLOR_JITTER"                          # built, but only for callers that pass color_jitter
 
 
 def check_supported(cfg, allow=()):
@@ -46,13 +49,29 @@ def check_supported(cfg, allow=()):
             if key in MOSAIC_KEYS:
                 raise NotImplementedError("{} is not implemented by this entry point (crop, resize, flip only): mosaic batches come "
                                           "from build_detection_train_mosaic_loader / DatasetMapperMosaic".format(key))
-            raise NotImplementedError("{} is not implemented by the device training input (crop, resize, flip, mosaic only)".format(key))
+            if key == JITTER_KEY:
+                raise NotImplementedError("{} is not applied by default: pass `color_jitter=True` to the loader builder or to the "
+                                          "mapper's from_config to get the device colour jitter".format(key))
+            raise NotImplementedError("{} is not implemented by the device training input (crop, colour jitter, resize, flip, mosaic only)".format(key))
 
 
-def build_augmentation(cfg, is_train=True, allow=()):
-    """detection_utils.build_augmentation (:563-598) with the crop of DatasetMapperIgnore.from_config (:92-99) in front."""
-    check_supported(cfg, allow)
+def jitter_allow(allow, color_jitter):
+    """The keys a caller handles, with INPUT.COLOR_JITTER among them once it has opted in."""
+    return tuple(allow) + ((JITTER_KEY,) if color_jitter is not None and color_jitter is not False else ())
+
+
+def build_augmentation(cfg, is_train=True, allow=(), color_jitter=None):
+    """detection_utils.build_augmentation (:563-598) with the crop of DatasetMapperIgnore.from_config (:92-99) in front.
+    color_jitter: None -- a cfg that sets INPUT.COLOR_JITTER raises; True -- follow the key (ColorJitter() in front of the resize if
+    it is set, as the reference's list has it, none if not); a transforms.ColorJitter -- use it whatever the key says."""
+    check_supported(cfg, jitter_allow(allow, color_jitter))
+    if not (color_jitter is None or color_jitter is True or color_jitter is False or isinstance(color_jitter, ColorJitter)):
+        raise TypeError("color_jitter is None, True or a ColorJitter, got {!r}".format(color_jitter))
     augs = [ResizeShortestEdge.from_config(cfg, is_train)]
+    if is_train and color_jitter is True and cfg.INPUT.COLOR_JITTER:
+        color_jitter = ColorJitter()
+    if is_train and isinstance(color_jitter, ColorJitter):
+        augs.insert(0, color_jitter)
     if is_train:
         augs.append(RandomFlip())
         if cfg.INPUT.CROP.ENABLED:
@@ -125,6 +144,16 @@ def _raw_of(dataset_dict):
     return raw
 
 
+def plain_tiles(raw):
+    """A plain image as the one tile that covers its canvas."""
+    return [(raw, (0, 0, int(raw.shape[1]), int(raw.shape[0])), (0, 0))]
+
+
+def jitter_item(tiles, window, params):
+    """The job of kernels.color_jitter_tiles_u8 for an item whose params carry a jitter."""
+    return (tiles, tuple(window), params.jitter[0], params.jitter[1])
+
+
 class DatasetMapper:
     """See the module docstring.  `DatasetMapper.from_config(cfg, is_train=True)`; `mapper(dataset_dict)` -> the reference's dict."""
 
@@ -137,12 +166,12 @@ class DatasetMapper:
         self.device = torch.device(device)
 
     @classmethod
-    def from_config(cls, cfg, is_train=True):
-        return cls._from_config(cfg, is_train)
+    def from_config(cls, cfg, is_train=True, *, color_jitter=None):
+        return cls._from_config(cfg, is_train, color_jitter=color_jitter)
 
     @classmethod
-    def _from_config(cls, cfg, is_train=True, allow=()):
-        return cls(is_train, augmentations=build_augmentation(cfg, is_train, allow), image_format=cfg.INPUT.FORMAT,
+    def _from_config(cls, cfg, is_train=True, allow=(), color_jitter=None):
+        return cls(is_train, augmentations=build_augmentation(cfg, is_train, allow, color_jitter), image_format=cfg.INPUT.FORMAT,
                    pixel_mean=cfg.MODEL.PIXEL_MEAN, pixel_std=cfg.MODEL.PIXEL_STD, device=cfg.MODEL.DEVICE)
 
     def draw(self, dataset_dict):
@@ -167,7 +196,10 @@ class DatasetMapper:
         raw = raw.to(self.device, non_blocking=True)
         nh, nw = params.new_size
         slot = torch.empty(1, nh, nw, 4, dtype=torch.float32, device=self.device)
-        u8 = K.train_input_u8([raw], [params.job()], slot, self.pixel_mean, self.pixel_std, resample_coeffs, want_u8=True)[0]
+        job = params.job()
+        if params.jitter is not None:      # the jittered crop window is the image the resize reads
+            raw, job = K.color_jitter_tiles_u8([jitter_item(plain_tiles(raw), params.crop, params)])[0], params.crop_job()
+        u8 = K.train_input_u8([raw], [job], slot, self.pixel_mean, self.pixel_std, resample_coeffs, want_u8=True)[0]
         d["image"] = u8.permute(2, 0, 1).contiguous()
         d["normalized"] = slot[0]       # [new_h,new_w,4] fp32: (image - mean) / std as the model's batch slot holds it
         return d

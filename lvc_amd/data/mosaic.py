@@ -5,7 +5,9 @@ The reference pastes 4 or 9 images into a 2s x 2s / 3s x 3s canvas filled with 1
 the canvas to the painted extent and hands the composite to the usual crop -> resize -> flip.  Here the same split as in
 dataset_mapper.py: the host half computes the integer geometry (`mosaic4_layout` / `mosaic9_layout`), maps the annotations and draws
 the augmentations on the composite's size; the pixels come from `kernels.train_input_tiles_u8` (csrc/train_input.hip), which reads
-the tiles in place -- neither the canvas nor the composite is ever written to memory.
+the tiles in place -- neither the canvas nor the composite is ever written to memory.  With a colour jitter (INPUT.COLOR_JITTER,
+opted into with `color_jitter=True`) the jittered crop window of the canvas is written once (`kernels.color_jitter_tiles_u8`) and
+`kernels.train_input_u8` resizes it as a plain image.
 
 What is reproduced, quirks included:
   * s comes from tile 0 only, later tiles may be larger; source rectangles go through numpy's slice rules (an end past the image is
@@ -26,7 +28,7 @@ import random
 import torch
 
 from .. import kernels as K
-from .dataset_mapper import MOSAIC_KEYS, DatasetMapper, _raw_of, mapped_instances
+from .dataset_mapper import MOSAIC_KEYS, DatasetMapper, _raw_of, jitter_item, mapped_instances
 from .transforms import TrainInputParams, resample_coeffs
 
 FILL = 114      # the canvas colour, all three channels
@@ -214,8 +216,8 @@ class DatasetMapperMosaic(DatasetMapper):
     "normalized" as DatasetMapper.__call__).  `draw(list)` is the host half: (dict, tile images, MosaicInputParams)."""
 
     @classmethod
-    def from_config(cls, cfg, is_train=True):
-        return cls._from_config(cfg, is_train, allow=MOSAIC_KEYS)
+    def from_config(cls, cfg, is_train=True, *, color_jitter=None):
+        return cls._from_config(cfg, is_train, allow=MOSAIC_KEYS, color_jitter=color_jitter)
 
     def draw(self, dataset_dicts):
         raws = [_raw_of(d) for d in dataset_dicts]
@@ -234,7 +236,7 @@ class DatasetMapperMosaic(DatasetMapper):
         h, w = layout.size
         transforms, drawn = self.augmentations.draw(h, w)
         params = MosaicInputParams(h, w, layout)
-        params.crop, params.new_size, params.flip = drawn.crop, drawn.new_size, drawn.flip
+        params.crop, params.new_size, params.flip, params.jitter = drawn.crop, drawn.new_size, drawn.flip, drawn.jitter
         out.pop("annotations", None)
         out["instances"] = mapped_instances(annos, transforms, params.new_size)
         return out, raws, params
@@ -244,7 +246,12 @@ class DatasetMapperMosaic(DatasetMapper):
         tiles = [r.to(self.device, non_blocking=True) for r in raws]
         nh, nw = params.new_size
         slot = torch.empty(1, nh, nw, 4, dtype=torch.float32, device=self.device)
-        u8 = K.train_input_tiles_u8([params.tiles_item(tiles)], slot, self.pixel_mean, self.pixel_std, resample_coeffs, want_u8=True)[0]
+        item = params.tiles_item(tiles)
+        if params.jitter is not None:      # the jittered window of the painted canvas (114 fill included) is the image the resize reads
+            crop = K.color_jitter_tiles_u8([jitter_item(item[0], item[1], params)])[0]
+            u8 = K.train_input_u8([crop], [params.crop_job()], slot, self.pixel_mean, self.pixel_std, resample_coeffs, want_u8=True)[0]
+        else:
+            u8 = K.train_input_tiles_u8([item], slot, self.pixel_mean, self.pixel_std, resample_coeffs, want_u8=True)[0]
         d["image"] = u8.permute(2, 0, 1).contiguous()
         d["normalized"] = slot[0]
         return d

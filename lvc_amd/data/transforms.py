@@ -341,14 +341,73 @@ class RandomFlip:
         return HFlipTransform(w) if do else NoOpTransform()
 
 
+class ColorJitterTransform(NoOpTransform):
+    """What one draw of ColorJitter decided: `ops`, the step ids in the order they are applied (0 brightness, 1 contrast, 2
+    saturation, 3 hue), and `factors`, their fp32 factors as Python floats.  Coordinates and boxes pass unchanged; the pixels are
+    csrc/color_jitter.hip's (`kernels.color_jitter_tiles_u8`), applied to the crop window in front of the resize."""
+
+    def __init__(self, ops, factors):
+        self.ops, self.factors = tuple(int(o) for o in ops), tuple(float(f) for f in factors)
+
+    def apply_image(self, img):
+        raise NotImplementedError("the colour jitter of an image is computed for a whole batch by kernels.color_jitter_tiles_u8")
+
+
+class ColorJitter:
+    """reference ColorJitterPIL (augmentation_impl.py:589-617): torchvision 0.8.2's `ColorJitter(brightness=0.4, contrast=0.4,
+    saturation=0.4, hue=0.2)`, the version the reference pins.  The draws are that version's `forward`: `torch.randperm(4)`, then,
+    walking the permutation, one `torch.tensor(1.0).uniform_(lo, hi).item()` per step AT THE MOMENT the step is reached -- so the
+    order of the draws follows the permutation.  generator=None is torch's default CPU generator: `torch.manual_seed(s)` before a
+    draw gives the reference's permutation and factors.  numpy's generator (crop, size, flip) is not touched."""
+
+    def __init__(self, brightness=0.4, contrast=0.4, saturation=0.4, hue=0.2, generator=None):
+        self.ranges = [self._range(brightness, "brightness"), self._range(contrast, "contrast"), self._range(saturation, "saturation"),
+                       self._range(hue, "hue", center=0, bound=(-0.5, 0.5), clip_first_on_zero=False)]
+        self.generator = generator
+
+    @staticmethod
+    def _range(value, name, center=1, bound=(0, float("inf")), clip_first_on_zero=True):
+        """torchvision's ColorJitter._check_input: a number v means [center - v, center + v]; None where the step does nothing."""
+        if isinstance(value, (int, float)):
+            if value < 0:
+                raise ValueError("If {} is a single number, it must be non negative.".format(name))
+            value = [center - float(value), center + float(value)]
+            if clip_first_on_zero:
+                value[0] = max(value[0], 0.0)
+        elif isinstance(value, (tuple, list)) and len(value) == 2:
+            if not bound[0] <= value[0] <= value[1] <= bound[1]:
+                raise ValueError("{} values should be between {}".format(name, bound))
+        else:
+            raise TypeError("{} should be a single number or a list/tuple with length 2.".format(name))
+        return None if value[0] == value[1] == center else (float(value[0]), float(value[1]))
+
+    def get_transform(self, img):
+        ops, factors = [], []
+        for fn_id in torch.randperm(4, generator=self.generator).tolist():
+            r = self.ranges[fn_id]
+            if r is not None:
+                ops.append(fn_id)
+                factors.append(torch.tensor(1.0).uniform_(r[0], r[1], generator=self.generator).item())
+        return ColorJitterTransform(ops, factors)
+
+    def __repr__(self):
+        return "ColorJitter(ranges={})".format(self.ranges)
+
+
 class TrainInputParams:
     """What one draw of the training augmentations decided, as the integers the batch kernel needs: the crop window (x0, y0, w, h)
-    in the source image (the whole image without a crop), the size after the resize, and the flip decision."""
+    in the source image (the whole image without a crop), the size after the resize, and the flip decision; `jitter`: None, or the
+    (ops, factors) of a ColorJitter draw, applied to the crop window in front of the resize."""
 
     def __init__(self, h, w):
         self.crop = (0, 0, int(w), int(h))
         self.new_size = (int(h), int(w))
         self.flip = False
+        self.jitter = None
+
+    def crop_job(self):
+        """The job of kernels.train_input_u8 on the jittered crop, a plain image of the window's size."""
+        return (0, 0, self.crop[2], self.crop[3]) + self.new_size + (self.flip,)
 
     def job(self):
         return self.crop + self.new_size + (self.flip,)
@@ -360,7 +419,8 @@ class TrainInputParams:
 class AugmentationList:
     """AugInput.apply_augmentations (reference augmentation.py:212-245) for images known by their size alone: asks each policy in
     turn for its transform, handing the next one the size the previous transform leaves.  `draw(h, w)` -> (TransformList,
-    TrainInputParams).  A crop is only understood in front of the resize and a flip behind it (the order from_config builds)."""
+    TrainInputParams).  A crop is only understood in front of the resize and a flip behind it, a colour jitter between the crop and
+    the resize (the order from_config builds)."""
 
     def __init__(self, augmentations):
         self.augmentations = list(augmentations)
@@ -373,7 +433,7 @@ class AugmentationList:
             if t is None:
                 t = NoOpTransform()
             if isinstance(t, CropTransform):
-                assert not tfms or all(isinstance(u, NoOpTransform) for u in tfms), "a crop must come first"
+                assert (not tfms or all(isinstance(u, NoOpTransform) for u in tfms)) and p.jitter is None, "a crop must come first"
                 p.crop = (t.x0, t.y0, t.w, t.h)
                 p.new_size = (t.h, t.w)
                 h, w = t.h, t.w
@@ -383,6 +443,10 @@ class AugmentationList:
                 h, w = t.new_h, t.new_w
             elif isinstance(t, HFlipTransform):
                 p.flip = not p.flip
+            elif isinstance(t, ColorJitterTransform):
+                assert p.jitter is None and not p.flip and p.new_size == (p.crop[3], p.crop[2]), \
+                    "the colour jitter comes once, behind the crop and in front of the resize"
+                p.jitter = (t.ops, t.factors)
             elif not isinstance(t, NoOpTransform):
                 raise NotImplementedError("transform {} is not part of the device training input".format(type(t).__name__))
             tfms.append(t)

@@ -1752,7 +1752,86 @@ def train_input_tiles_u8(items, out, mean, std, coeffs_fn, want_u8=False, worksp
     return u8 if want_u8 else None
 
 
-TTA_PARAM_STRIDE = 16     # floats per augmentation in lvc_tta_merge's inverse-transform table
+COLOR_JITTER_LAUNCHES = []   # kernel launches of the last (up to 64) lvc_color_jitter_tiles_u8 calls, as the library counted them
+COLOR_JITTER_FIELDS = TRAIN_INPUT_TILES_FIELDS      # int64 words per job of lvc_color_jitter_tiles_u8 (include/lvc_amd.h)
+COLOR_JITTER_OPS = ("brightness", "contrast", "saturation", "hue")      # step ids 0..3, torchvision's
+
+
+class ColorJitterWorkspace:
+    """Buffers of one lvc_color_jitter_tiles_u8 call, reused from batch to batch (grown, never shrunk): the pinned host job table,
+    its device copy and the scratch that receives the jittered crops (the results are views of it: they live until the next call
+    on this workspace).  `uploaded` as in TrainInputWorkspace."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self.host = self.dev = self.scratch = self.uploaded = None
+
+    def wait_host(self):
+        if self.uploaded is not None:
+            self.uploaded.synchronize()
+
+    def reserve(self, blob_bytes, scratch_bytes):
+        if self.host is None or self.host.numel() < blob_bytes:
+            n = max(blob_bytes * 3 // 2, 1 << 14)
+            self.host = torch.empty(n, dtype=torch.uint8).pin_memory()
+            self.dev = torch.empty(n, dtype=torch.uint8, device=self.device)
+        if self.scratch is None or self.scratch.numel() < scratch_bytes:
+            self.scratch = torch.empty(max(scratch_bytes * 3 // 2, 1 << 16), dtype=torch.uint8, device=self.device)
+
+
+def color_jitter_tiles_u8(items, workspace=None, table_hook=None, device=None):
+    """INPUT.COLOR_JITTER of a whole batch in two launches (csrc/color_jitter.hip lvc_color_jitter_tiles_u8), on the current stream.
+    items: per image (tiles, (X0, Y0, crop_w, crop_h), ops, factors) -- tiles and window as train_input_tiles_u8 (a plain image is one
+    tile), ops the step ids in the order they are applied (0 brightness, 1 contrast, 2 saturation, 3 hue; at most 4, at most one
+    contrast), factors their fp32 factors.  Returns the jittered windows, uint8 [crop_h, crop_w, 3] views of the workspace's scratch:
+    bytes equal to torchvision's ColorJitter steps on a PIL image of the window.  table_hook(tab): called with the int64 job table
+    [B,128] before it is uploaded (tests of the library's refusals)."""
+    import numpy as np
+
+    B = len(items)
+    assert B > 0
+    if device is None:
+        device = workspace.device if workspace is not None else items[0][0][0][0].device
+    ws = workspace if workspace is not None else ColorJitterWorkspace(device)
+    F, HEAD, TILE = COLOR_JITTER_FIELDS, TRAIN_INPUT_TILES_HEAD, TRAIN_INPUT_TILES_TILE
+    tab = np.zeros((B, F), np.int64)
+    out_off, shapes = 0, []
+    for i, (tiles, (X0, Y0, cw, ch), ops, factors) in enumerate(items):
+        assert 1 <= len(tiles) <= TRAIN_INPUT_TILES_MAX, "an item has 1 to 9 tiles"
+        assert len(ops) == len(factors) <= 4, "an item has at most 4 steps"
+        row = tab[i]
+        row[0:4] = (X0, Y0, cw, ch)
+        row[4], row[5] = out_off, len(ops)
+        row[6:6 + len(ops)] = [int(o) for o in ops]
+        row[10:10 + len(ops)] = np.asarray(factors, np.float32).view(np.uint32)
+        row[14] = len(tiles)
+        shapes.append((out_off, int(ch), int(cw)))
+        out_off += (int(ch) * int(cw) * 3 + 255) & ~255
+        for t, (img, rect, origin) in enumerate(tiles):
+            _req_cuda(img)
+            assert img.dtype == torch.uint8 and img.dim() == 3 and img.shape[2] == 3 and img.device == ws.device
+            at = HEAD + t * TILE
+            row[at:at + 6] = (img.data_ptr(), img.shape[0], img.shape[1], img.stride(0), img.stride(1), img.stride(2))
+            row[at + 6:at + 10] = rect
+            row[at + 10:at + 12] = origin
+    if table_hook is not None:
+        table_hook(tab)
+    ws.wait_host()
+    ws.reserve(tab.nbytes, out_off)
+    ws.host.numpy()[:tab.nbytes] = tab.reshape(-1).view(np.uint8)
+    ws.dev[:tab.nbytes].copy_(ws.host[:tab.nbytes], non_blocking=True)
+    ws.uploaded = torch.cuda.Event()
+    ws.uploaded.record(torch.cuda.current_stream(ws.device))
+    n = c_int(0)
+    rc = _lib.lib().lvc_color_jitter_tiles_u8(ptr(ws.host), ptr(ws.dev), c_longlong(tab.nbytes), c_int(B), ptr(ws.scratch),
+                                              c_longlong(ws.scratch.numel()), ctypes.byref(n), _stream(ws.scratch))
+    check(rc, "lvc_color_jitter_tiles_u8")
+    COLOR_JITTER_LAUNCHES.append(n.value)
+    del COLOR_JITTER_LAUNCHES[:-64]
+    return [ws.scratch[off:off + h * w * 3].view(h, w, 3) for off, h, w in shapes]
+
+
+TTA_PARAM_STRIDE = 16    # floats per augmentation in lvc_tta_merge's inverse-transform table
 TTA_MAX_STEPS = 4
 
 
