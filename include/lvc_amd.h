@@ -580,6 +580,26 @@ int lvc_conv_wgrad_group_bf16x3(int njobs, const float* const* x, const float* c
  * jobs in one launch; shapes: 4 ints per job = K, C, R*S, beta.  (AccumulateGrad's `grad += dw` / first assignment.) */
 int lvc_wgrad_finalize_group(int njobs, const float* const* src, float* const* dst, const int* shapes, void* stream);
 int lvc_scatter_stride2_nhwc(const float* x, float* y, int N, int H, int W, int C, void* stream);
+/* Grouped 3x3 convolution of a ResNeXt bottleneck (reference detectron2/modeling/backbone/resnet.py BottleneckBlock with
+ * num_groups > 1), csrc/conv_grouped.hip: NHWC fp32, pad 1, stride 1 or 2, `groups` groups of cg = C / groups input AND output
+ * channels (C == K), cg in {4, 8, 16, 32, 64}, C a multiple of 64; any other shape returns LVC_ERR_INVALID.  Exact fp32 MFMA
+ * (range-free: no range word is raised).
+ * lvc_conv3x3_grouped_nhwc: y = act(conv(x) * scale + shift (+ residual)); the argument order of the dense entry points, wp from
+ *   lvc_pack_conv3x3_grouped; res_mode 0 or 1 (a residual of the output's shape).  With a mode-1 operand it is the data
+ *   gradient of a stride-1 layer; a stride-2 layer's gradient is zero-stuffed first (lvc_scatter_stride2_nhwc), then the same call.
+ * lvc_pack_conv3x3_grouped: w [K][cg][3][3] (the reference's state_dict layout) -> wp, lvc_conv3x3_grouped_packed_floats(K,
+ *   groups) floats.  mode 0: forward; mode 1: data gradient (taps flipped, per-group transpose, times scale[k] or 1).
+ * lvc_conv3x3_grouped_wgrad_nhwc: dw [K][cg][3][3] = scale[k] * sum dy[n,oy,ox,k] * x[n, oy*stride+r-1, ox*stride+s-1, c] from x
+ *   [N,H,W,C] and dy [N,Ho,Wo,*] (row pitch lddy); scratch: lvc_conv3x3_grouped_wgrad_workspace_bytes(...) bytes.  Partial sums
+ *   over pixel chunks are added in chunk order (no atomics): two runs are bit-identical. */
+int lvc_conv3x3_grouped_nhwc(const float* x, const float* wp, const float* scale, const float* shift, const float* residual,
+                             float* y, int N, int H, int W, int C, int K, int groups, int stride, int relu, int res_mode, int ldy,
+                             int ldr, void* workspace, void* stream);
+long long lvc_conv3x3_grouped_packed_floats(int K, int groups);
+int lvc_pack_conv3x3_grouped(const float* w, const float* scale, float* wp, int K, int groups, int mode, void* stream);
+long long lvc_conv3x3_grouped_wgrad_workspace_bytes(int N, int H, int W, int K, int groups, int stride);
+int lvc_conv3x3_grouped_wgrad_nhwc(const float* x, const float* dy, const float* scale, float* dw, int N, int H, int W, int C,
+                                   int groups, int stride, int lddy, void* scratch, void* stream);
 /* y[n, i, j, 0..C) = x[n, 2i, 2j, :], rows of ldy floats in y (0 = C): the sampling of a stride-2 1x1 convolution as a copy (the
  * block input of res3.0 / res4.0 / res5.0 next to conv2's output: conv3 + projection shortcut as one GEMM, resnet.py:117-160). */
 int lvc_subsample2_nhwc(const float* x, float* y, int N, int H, int W, int C, int ldy, void* stream);

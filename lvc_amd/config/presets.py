@@ -41,3 +41,13 @@ def gn_rcnn_fpn(depth=50, num_classes=80, device="cuda"):
     cfg = base_rcnn_fpn(depth=depth, num_classes=num_classes, device=device)
     cfg.merge_from_list(list(GN_OVERRIDES))
     return cfg
+
+
+def resnext_rcnn_fpn(depth=101, num_groups=32, width_per_group=8, num_classes=80, device="cuda"):
+    """`base_rcnn_fpn` on a ResNeXt trunk: detectron2's `COCO-Detection/faster_rcnn_X_101_32x8d_FPN_3x.yaml` sets exactly these four
+    keys (`STRIDE_IN_1X1: False` is the published X-101 setting; `True` builds too -- the grouped 3x3 is then always stride 1).
+    32x4d, 32x8d and 64x4d are the widths the grouped kernel takes (kernels.grouped_conv_check)."""
+    cfg = base_rcnn_fpn(depth=depth, num_classes=num_classes, device=device)
+    cfg.merge_from_list(["MODEL.RESNETS.NUM_GROUPS", num_groups, "MODEL.RESNETS.WIDTH_PER_GROUP", width_per_group,
+                         "MODEL.RESNETS.STRIDE_IN_1X1", False])
+    return cfg

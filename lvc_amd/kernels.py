@@ -35,7 +35,7 @@ class PackedConv:
     """
 
     __slots__ = ("w", "scale", "shift", "K", "C", "R", "S", "stride", "pad", "Kg", "mode", "_w3", "_w2h", "_w2s", "two_acc",
-                 "slot", "state", "_last_one", "__weakref__")
+                 "slot", "state", "_last_one", "groups", "__weakref__")
 
     def __init__(self, w, scale, shift, K, C, R, S, stride, pad, Kg, mode):
         self.w, self.scale, self.shift = w, scale, shift
@@ -43,6 +43,7 @@ class PackedConv:
         self._w3 = None
         self._w2h = None
         self._w2s = None
+        self.groups = 1        # > 1: a grouped 3x3 layer, `w` is the operand of csrc/conv_grouped.hip (`_pack_grouped`)
         self.two_acc = False   # True: never the single-accumulator form of the 3x3 fp16-split kernel (see HALO_S1)
         # range routing of THIS layer (`check_conv_error_word`): its own range word in the workspace, and the tier it runs on --
         # 0: as configured (one accumulator where the policy allows it, |a| <= 4094), 1: two accumulators (|a| <= 65504),
@@ -187,13 +188,56 @@ def _with_planes(pc, planes, out):
     return pc
 
 
-def pack_conv(weight, bias=None, bn=None, stride=1, pad=0, eps=1e-5, stem=False, affine=None, split=None):
+GROUPED_CG = (4, 8, 16, 32, 64)      # channels per group of csrc/conv_grouped.hip
+
+
+def grouped_conv_check(in_channels, out_channels, groups, kernel_size=3, stride=1, padding=1):
+    """Raise NotImplementedError for a grouped convolution outside csrc/conv_grouped.hip: 3x3, pad 1, stride 1 or 2, as many output
+    as input channels, 4 / 8 / 16 / 32 / 64 channels per group (ResNeXt 32x4d, 32x8d, 64x4d at res2..res5), channels a multiple of 64.
+    Pure: it answers on a machine without a GPU."""
+    if kernel_size != 3 or padding != 1 or stride not in (1, 2):
+        raise NotImplementedError("grouped convolution is built for kernel_size=3, padding=1, stride 1 or 2 (a ResNeXt bottleneck's conv2); "
+                                  "got kernel_size={}, padding={}, stride={}, groups={}".format(kernel_size, padding, stride, groups))
+    cg = in_channels // groups if groups > 0 and in_channels % groups == 0 else 0
+    if in_channels != out_channels or cg not in GROUPED_CG or in_channels % 64:
+        raise NotImplementedError(
+            "grouped 3x3 convolution {} -> {} with groups={}: the kernel takes {} channels per group (in == out, a multiple of 64); "
+            "choose MODEL.RESNETS.NUM_GROUPS / WIDTH_PER_GROUP accordingly (32x4d, 32x8d, 64x4d)".format(
+                in_channels, out_channels, groups, " / ".join(str(c) for c in GROUPED_CG)))
+
+
+def _pack_grouped(weight, scale, groups, mode):
+    """The operand of lvc_conv3x3_grouped_nhwc from the reference's [K, C/G, 3, 3] weight.  mode 0: forward; mode 1: the data gradient
+    (taps flipped, per-group transpose, times `scale`)."""
+    _req_cuda(weight, scale)
+    K, cg, R, S = weight.shape
+    grouped_conv_check(cg * groups, K, groups, R if R == S else 0)
+    w = weight.detach()
+    if w.dtype != torch.float32 or not w.is_contiguous():
+        w = w.float().contiguous()
+    lib = _lib.lib()
+    lib.lvc_conv3x3_grouped_packed_floats.restype = c_longlong
+    wp = torch.empty(lib.lvc_conv3x3_grouped_packed_floats(c_int(K), c_int(groups)), device=w.device, dtype=torch.float32)
+    check(lib.lvc_pack_conv3x3_grouped(ptr(w), ptr(scale), ptr(wp), c_int(K), c_int(groups), c_int(mode), _stream(w)),
+          "lvc_pack_conv3x3_grouped")
+    return wp
+
+
+def pack_conv(weight, bias=None, bn=None, stride=1, pad=0, eps=1e-5, stem=False, affine=None, split=None, groups=1):
     """weight: [K, C, R, S] (OIHW, the reference's state_dict layout) on the target device.
     bn: None or (weight, bias, running_mean, running_var) of a FrozenBatchNorm2d; affine: a precomputed
     `conv_affine(bias, bn, eps)` (the fold only changes when those tensors do, the weights change every step).
     stem=True packs the 3-channel 7x7 stem for the NHWC4 "row mode" of the kernel.
+    groups > 1: weight is [K, C/groups, 3, 3], packed for the grouped kernel (`grouped_conv_check`).
     """
     _req_cuda(weight)
+    if groups != 1:
+        grouped_conv_check(weight.shape[1] * groups, weight.shape[0], groups, weight.shape[2], stride, pad)
+        scale, shift = affine if affine is not None else conv_affine(bias, bn, eps)
+        pc = PackedConv(_pack_grouped(weight, None, groups, 0), scale, shift, weight.shape[0], weight.shape[0], 3, 3, stride, pad,
+                        9 * weight.shape[1], 0)
+        pc.groups = groups
+        return pc
     K, C, R, S = weight.shape
     dev = weight.device
     Kpad = (K + BN - 1) // BN * BN
@@ -608,6 +652,9 @@ def conv_route(pc, N, H, W, ldo=None, out_contiguous=True, out_numel=None, ldr=N
     dimension, contiguity and element count of the output buffer (default: a fresh [N,Ho,Wo,K]); ldr / res_numel: last dimension and
     element count of the residual operand (ldr None: no residual); split: the caller's explicit operand split.
     Pure: no tensor, no library call -- it answers on a machine without a GPU."""
+    if getattr(pc, "groups", 1) != 1:
+        # a grouped 3x3 layer (ResNeXt conv2; forward and data gradient): exact fp32 MFMA, range-free -- no tier, no range word
+        return ConvRoute("f32_grouped", "lvc_conv3x3_grouped_nhwc", False, False)
     Ho, Wo = _out_hw(pc, H, W)
     rows = N * Ho * Wo
     if ldo is None:
@@ -680,6 +727,7 @@ _CONV_ARGS = {
     "lvc_conv1x1_nhwc_f16x2_pipe": ("h", _TAIL_1X1, _NO_LAST),
     "lvc_conv1x1_nhwc_f16s1": ("s", _TAIL_1X1, _NO_LAST),
     "lvc_conv1x1_nhwc_f16s1_w2": ("s", lambda pc, wts: (wts.shape[1], pc.stride), _NO_LAST),
+    "lvc_conv3x3_grouped_nhwc": ("w", lambda pc, wts: (pc.groups, pc.stride), _NO_LAST),
 }
 # the kernels with torch.nn.GELU() in their epilogue (activation code 2)
 _GELU_EPILOGUE = ("lvc_conv1x1_nhwc_f16x2_pipe", "lvc_conv1x1_nhwc_f16s1", "lvc_conv1x1_nhwc_f16s1_w2", "lvc_conv2d_nhwc_f16x2_dma")
@@ -746,6 +794,9 @@ def conv2d_nhwc(x, pc, relu=False, residual=None, res_mode=0, out=None, split=No
     Ho, Wo = _out_hw(pc, H, W)
     if out is None:
         out = torch.empty(N, Ho, Wo, pc.K, device=x.device, dtype=torch.float32)
+    grouped = getattr(pc, "groups", 1) != 1
+    if grouped and out.numel() == 0:
+        return out      # an empty batch: nothing to launch (the grouped kernel's grid is its tile count)
     if residual is not None:
         assert residual.is_contiguous() and residual.dtype == torch.float32
         if res_mode == 0:
@@ -794,6 +845,9 @@ def conv2d_nhwc(x, pc, relu=False, residual=None, res_mode=0, out=None, split=No
     # algorithmic bytes of the launch: the input pixels it needs, its output, the residual operand, the weights -- each once
     nbytes = 4.0 * (N * (Ho * Wo if (pc.R == 1 and pc.S == 1) else H * W) * c_real + N * Ho * Wo * pc.K + res_numel
                     + pc.K * c_real * pc.R * pc.S)
+    if grouped:
+        c_real = C // pc.groups
+        nbytes = 4.0 * (N * H * W * C + N * Ho * Wo * pc.K + res_numel + pc.K * c_real * 9)
     _launch(route.engine, 2.0 * N * Ho * Wo * pc.K * c_real * pc.R * pc.S, nbytes, pc.slot if route.slotted else None, entry, call)
     if act == "gelu":
         check(_lib.lib().lvc_gelu(ptr(out), ptr(out), c_longlong(out.numel()), _stream(out)), "lvc_gelu")
@@ -2324,6 +2378,34 @@ def _conv_wgrad(x, dy, scale, R, S, stride, pad, split=None):
     return dw
 
 
+def conv_wgrad_grouped(x, dy, scale, groups, stride):
+    """dW [K, C/groups, 3, 3] (the parameter's layout) of a grouped 3x3 / pad 1 layer y = conv(x, W) (* scale per output channel):
+    x [N,H,W,C], dy [N,Ho,Wo,K].  One launch of its own per layer (it does not join the deferred launch of the dense layers); partial
+    sums are added in a fixed order -- two runs are bit-identical."""
+    _req_cuda(x, dy, scale)
+    assert x.dim() == 4 and dy.dim() == 4 and x.is_contiguous() and dy.is_contiguous()
+    assert x.dtype == torch.float32 and dy.dtype == torch.float32
+    N, H, W, C = x.shape
+    assert tuple(dy.shape) == (N, (H - 1) // stride + 1, (W - 1) // stride + 1, C), (dy.shape, x.shape, stride)
+    grouped_conv_check(C, C, groups, 3, stride, 1)
+    cg = C // groups
+    dw = torch.empty(C, cg, 3, 3, device=x.device, dtype=torch.float32)
+    if x.numel() == 0:
+        return dw.zero_()
+    lib = _lib.lib()
+    lib.lvc_conv3x3_grouped_wgrad_workspace_bytes.restype = c_longlong
+    nbytes = lib.lvc_conv3x3_grouped_wgrad_workspace_bytes(c_int(N), c_int(H), c_int(W), c_int(C), c_int(groups), c_int(stride))
+    scratch = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
+
+    def run():
+        check(lib.lvc_conv3x3_grouped_wgrad_nhwc(ptr(x), ptr(dy), ptr(scale), ptr(dw), c_int(N), c_int(H), c_int(W), c_int(C), c_int(groups),
+                                                 c_int(stride), c_int(C), ptr(scratch), _stream(x)), "lvc_conv3x3_grouped_wgrad_nhwc")
+        return dw
+
+    return _bwd_timed("wgrad", "f32_grouped", 2.0 * dy.numel() * cg * 9, 4.0 * (x.numel() + dy.numel() + dw.numel()), run,
+                      "grouped %dx%dx%d %d g%d s%d" % (N, H, W, C, groups, stride))
+
+
 # ---- deferred, grouped weight gradients (csrc/conv_wgrad.hip: conv_wgrad_group_bf16x3_kernel) --------------------------------------
 DEFER_WGRAD = _os.environ.get("LVC_DEFER_WGRAD", "1") != "0"
 _WGRAD_GROUP = 24            # jobs per launch (kernel-argument table)
@@ -2579,12 +2661,19 @@ def downsum2x2(x):
     return y
 
 
-def pack_conv_dgrad(weight, scale, pad):
-    """Packed weights of the DATA gradient of y = conv(x, weight, stride 1 after sub-sampling, pad) * scale:
+def pack_conv_dgrad(weight, scale, pad, groups=1):
+    """groups > 1 (weight [K, C/groups, 3, 3], pad 1): the grouped kernel's operand in its data-gradient mode; a stride-2 layer's
+    gradient is zero-stuffed onto the input grid before it (`conv_dgrad`).  Otherwise:
+    Packed weights of the DATA gradient of y = conv(x, weight, stride 1 after sub-sampling, pad) * scale:
     dx = conv(dy, Wt, pad = R-1-pad) with Wt[c][k][r][s] = scale[k] * weight[k][c][R-1-r][S-1-s].  A strided 1x1 is
     the same product on the sub-sampled grid followed by `scatter_stride2`.  Output channels of the forward conv
     (the contraction here) are zero-padded to the kernels' 32-channel chunk."""
     Kout, C, R, S = weight.shape
+    if groups != 1:
+        grouped_conv_check(C * groups, Kout, groups, R, 1, pad)
+        pc = PackedConv(_pack_grouped(weight, scale, groups, 1), None, None, Kout, Kout, 3, 3, 1, 1, 9 * C, 0)
+        pc.groups = groups
+        return pc
     kin_pad = (Kout + 31) // 32 * 32
     rows_pad = (C + BN - 1) // BN * BN
     planes = _planes_hint(R, S, kin_pad, DGRAD_SPLIT)
@@ -2595,6 +2684,14 @@ def pack_conv_dgrad(weight, scale, pad):
 def conv_dgrad(dy, pcd, x_shape, stride):
     """dx [x_shape] of a conv whose `pack_conv_dgrad` is pcd.  dy [N,Ho,Wo,K] contiguous."""
     N, H, W, C = x_shape
+    if pcd.groups != 1:
+        # grouped 3x3: a stride-2 layer's gradient is zero-stuffed onto the input grid, then the stride-1 kernel on the flipped operand
+        g = dy.contiguous() if stride == 1 else scatter_stride2(dy, H, W)
+        fl = 2.0 * g.shape[0] * g.shape[1] * g.shape[2] * pcd.K * (pcd.C // pcd.groups) * 9
+        nb = 4.0 * (dy.numel() + N * H * W * C + pcd.K * (pcd.C // pcd.groups) * 9)
+        dxs = _bwd_timed("dgrad", "f32_grouped", fl, nb, lambda: conv2d_nhwc(g, pcd), "grouped %dx%dx%d %d g%d s%d" % (N, H, W, C, pcd.groups, stride))
+        assert tuple(dxs.shape) == (N, H, W, C), (dxs.shape, x_shape)
+        return dxs
     if dy.shape[3] != pcd.C:   # contraction padded to 32 channels
         dy = torch.nn.functional.pad(dy, (0, pcd.C - dy.shape[3]))
     if BWD_TIMER is not None:

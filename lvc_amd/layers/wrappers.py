@@ -46,13 +46,16 @@ class Conv2d(nn.Module):
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, bias=True, norm=None,
                  activation=None, dilation=1, groups=1):
         super().__init__()
-        if dilation != 1 or groups != 1:
-            raise NotImplementedError("dilation/groups are not used by the shipped configs")
+        if dilation != 1:
+            raise NotImplementedError("dilation is not used by the shipped configs")
         ks = kernel_size if isinstance(kernel_size, (tuple, list)) else (kernel_size, kernel_size)
         assert ks[0] == ks[1]
-        self.in_channels, self.out_channels = in_channels, out_channels
+        if groups != 1:
+            # the 3x3 of a ResNeXt bottleneck (csrc/conv_grouped.hip); grouped 1x1 / 7x7 layers are not built
+            K.grouped_conv_check(in_channels, out_channels, groups, ks[0], stride, padding)
+        self.in_channels, self.out_channels, self.groups = in_channels, out_channels, groups
         self.kernel_size, self.stride, self.padding = ks, stride, padding
-        self.weight = nn.Parameter(torch.empty(out_channels, in_channels, ks[0], ks[1]))
+        self.weight = nn.Parameter(torch.empty(out_channels, in_channels // groups, ks[0], ks[1]))
         self.bias = nn.Parameter(torch.zeros(out_channels)) if bias else None
         nn.init.kaiming_uniform_(self.weight, a=5 ** 0.5)
         self.norm = norm
@@ -87,7 +90,7 @@ class Conv2d(nn.Module):
         srcs = [self.weight, aff[0], aff[1]]
         stem = self.in_channels == 3
         pc = self._cache.get(srcs, lambda: K.pack_conv(self.weight, stride=self.stride, pad=self.padding, stem=stem,
-                                                       affine=aff))
+                                                       affine=aff, groups=self.groups))
         # precision policy of the 3x3 fp16-split kernel (kernels.HALO_S1): a layer whose output feeds discrete decisions sets
         # `two_acc` and keeps the main + cross accumulator form (the RPN head: objectness / deltas -> top-k, NMS)
         pc.two_acc = bool(getattr(self, "two_acc", False))
@@ -127,8 +130,8 @@ class Conv2d(nn.Module):
         set of stale layers is then re-packed into the same buffers (no per-layer host work)."""
         jobs, targets, sig = [], [], []
         for conv in convs:
-            if conv.in_channels == 3 or conv.in_channels % 32:
-                continue
+            if conv.in_channels == 3 or conv.in_channels % 32 or conv.groups != 1:
+                continue      # (grouped layers pack their own operand on first use: `packed` / `packed_dgrad`)
             aff = conv._affine()
             srcs = [conv.weight, aff[0], aff[1]]
             if conv._stale(conv._cache, srcs):
@@ -160,7 +163,7 @@ class Conv2d(nn.Module):
     def packed_dgrad(self):
         """Packed weights of the data gradient (flipped, transposed, times the FrozenBN scale)."""
         scale = self._affine()[0] if self._folds_norm() else None
-        return self._cache_dgrad.get([self.weight, scale], lambda: K.pack_conv_dgrad(self.weight, scale, self.padding))
+        return self._cache_dgrad.get([self.weight, scale], lambda: K.pack_conv_dgrad(self.weight, scale, self.padding, groups=self.groups))
 
     def forward_nhwc(self, x, residual=None, res_mode=0, relu=None):
         """x: [N,H,W,C] contiguous.  relu=None -> this layer's own activation."""
@@ -187,8 +190,9 @@ class Conv2d(nn.Module):
         return to_nchw_view(self.forward_nhwc(xh))
 
     def extra_repr(self):
-        return "{}, {}, kernel_size={}, stride={}, padding={}".format(
+        s = "{}, {}, kernel_size={}, stride={}, padding={}".format(
             self.in_channels, self.out_channels, self.kernel_size, self.stride, self.padding)
+        return s if self.groups == 1 else s + ", groups={}".format(self.groups)
 
 
 class _ConvFn(torch.autograd.Function):
@@ -228,7 +232,9 @@ class _ConvFn(torch.autograd.Function):
             K.wgrad_use_done(conv.weight)
             R = conv.kernel_size[0]
             scale = conv.packed().scale if conv._folds_norm() else None
-            if K.can_defer_wgrad(x, g) and conv._grad_lands_in_weight():
+            if conv.groups != 1:
+                dw = K.conv_wgrad_grouped(x, g, scale, conv.groups, conv.stride)      # a launch of its own, already [K, C/G, 3, 3]
+            elif K.can_defer_wgrad(x, g) and conv._grad_lands_in_weight():
                 # off the critical path: queued, launched with the other layers' (kernels.flush_wgrad) and written to weight.grad
                 # before backward() returns -- this node hands autograd no gradient for the weight
                 K.defer_wgrad(conv.weight, x, g, scale, R, conv.stride, conv.padding)

@@ -6,7 +6,9 @@ detectron2/modeling/backbone/resnet.py:101-211 (BottleneckBlock), :564-592 (Basi
 (+ReLU, +residual add) is one launch of an implicit-GEMM MFMA kernel (fp32 operands split into fp16/bf16
 planes with fp32 accumulation, fp32-accurate: DESIGN.md section 3; `LVC_CONV_ENGINE=f32` selects the exact fp32
 MFMA form); activations stay NHWC fp32 in HBM between layers.  BasicBlock / DeepStem / Dropout / CLIP / Deform variants are not selected by any
-shipped config and are not provided (the builder raises for them).
+shipped config and are not provided (the builder raises for them).  ResNeXt (`RESNETS.NUM_GROUPS` > 1, `WIDTH_PER_GROUP`): conv2 is a
+grouped 3x3 on csrc/conv_grouped.hip; such a block declines the paths that bake in a dense conv2 (the fused block, Winograd, the
+pre-split pair -- `fused_eligible`, `kernels.conv_route`) and keeps the pointwise ones.
 """
 import torch
 import torch.nn.functional as F
@@ -39,8 +41,8 @@ class BottleneckBlock(CNNBlockBase):
     def __init__(self, in_channels, out_channels, *, bottleneck_channels, stride=1, num_groups=1, norm="BN",
                  stride_in_1x1=False, dilation=1):
         super().__init__(in_channels, out_channels, stride)
-        if num_groups != 1 or dilation != 1:
-            raise NotImplementedError("grouped / dilated bottlenecks are not used by the shipped configs")
+        if dilation != 1:
+            raise NotImplementedError("dilated bottlenecks (MODEL.RESNETS.RES5_DILATION != 1) are not built")
         if in_channels != out_channels:
             self.shortcut = Conv2d(in_channels, out_channels, kernel_size=1, stride=stride, bias=False,
                                    norm=get_norm(norm, out_channels))
@@ -50,7 +52,7 @@ class BottleneckBlock(CNNBlockBase):
         self.conv1 = Conv2d(in_channels, bottleneck_channels, kernel_size=1, stride=stride_1x1, bias=False,
                             norm=get_norm(norm, bottleneck_channels), activation=F.relu_)
         self.conv2 = Conv2d(bottleneck_channels, bottleneck_channels, kernel_size=3, stride=stride_3x3, padding=1,
-                            bias=False, norm=get_norm(norm, bottleneck_channels), activation=F.relu_)
+                            bias=False, norm=get_norm(norm, bottleneck_channels), activation=F.relu_, groups=num_groups)
         self.conv3 = Conv2d(bottleneck_channels, out_channels, kernel_size=1, bias=False,
                             norm=get_norm(norm, out_channels))
         for layer in [self.conv1, self.conv2, self.conv3, self.shortcut]:
@@ -123,7 +125,7 @@ class BottleneckBlock(CNNBlockBase):
         decides with it whether the stem writes a second copy of its output BEFORE the stem is launched -- at the top of a step the GPU
         queue is empty and every host microsecond in front of the first launches is exposed."""
         if not (K.BNECK and K.CONV_ENGINE == "bf16x3" and K.CONV_SPLIT == "f16x2" and self.conv1.stride == 1 and self.conv2.stride == 1
-                and self.conv2.out_channels == 64):
+                and self.conv2.out_channels == 64 and self.conv2.groups == 1):      # (the fused kernel's conv2 is dense: ResNeXt blocks decline)
             return False
         proj = self.shortcut is not None
         if (self.in_channels, self.conv2.in_channels, self.out_channels, proj) not in K.BNECK_SHAPES:
@@ -351,8 +353,8 @@ def build_resnet_backbone(cfg, input_shape):
         unsupported.append("RESNETS.DEFORM_ON_PER_STAGE")
     if R.DEPTH in (18, 34):
         unsupported.append("BasicBlock depths 18/34")
-    if R.NUM_GROUPS != 1 or R.RES5_DILATION != 1:
-        unsupported.append("grouped/dilated res5")
+    if R.RES5_DILATION != 1:
+        unsupported.append("RESNETS.RES5_DILATION = {} (dilated res5)".format(R.RES5_DILATION))
     if norm != "FrozenBN":
         # the fused trunk kernels (stem + pool, bottleneck blocks, chained pointwise convs) fold FrozenBN's scale / shift
         unsupported.append("RESNETS.NORM = '{}' (the trunk implements 'FrozenBN'; GN is built for FPN.NORM and ROI_BOX_HEAD.NORM)".format(norm))
@@ -372,7 +374,7 @@ def build_resnet_backbone(cfg, input_shape):
             block_class=BottleneckBlock, num_blocks=num_blocks_per_stage[idx],
             stride_per_block=[first_stride] + [1] * (num_blocks_per_stage[idx] - 1),
             in_channels=in_channels, out_channels=out_channels, norm=norm,
-            bottleneck_channels=bottleneck_channels, stride_in_1x1=R.STRIDE_IN_1X1, dilation=1, num_groups=1)
+            bottleneck_channels=bottleneck_channels, stride_in_1x1=R.STRIDE_IN_1X1, dilation=1, num_groups=R.NUM_GROUPS)
         in_channels = out_channels
         out_channels *= 2
         bottleneck_channels *= 2
