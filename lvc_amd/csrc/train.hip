@@ -102,11 +102,14 @@ extern "C" int lvc_match_boxes(const float* gt, int G, const float* boxes, int N
 
 __device__ __forceinline__ void get_deltas(float sx1, float sy1, float sx2, float sy2, float tx1, float ty1, float tx2,
                                            float ty2, float wx, float wy, float ww, float wh, float* d) {
-  // box_regression.py:40-71
-  const float sw = sx2 - sx1, sh = sy2 - sy1, scx = sx1 + 0.5f * sw, scy = sy1 + 0.5f * sh;
-  const float tw = tx2 - tx1, th = ty2 - ty1, tcx = tx1 + 0.5f * tw, tcy = ty1 + 0.5f * th;
-  d[0] = wx * (tcx - scx) / sw; d[1] = wy * (tcy - scy) / sh;
-  d[2] = ww * logf(tw / sw); d[3] = wh * logf(th / sh);
+  // box_regression.py:40-71, evaluated in fp64 and rounded once.  In fp32 the two centres are rounded at the size of the
+  // coordinates before they are subtracted: an error of ~ulp(coordinate) * weight / box size in the target (3.7e-5 at 700 px,
+  // weight 10, boxes from 8 px), which smooth-L1's 1 / beta multiplies in the gradient -- 30 x the 1e-5 to which the losses and
+  // gradients are held against float64 autograd (tests/test_gpu_train_kernels.py).  Four values per foreground row.
+  const double sw = (double)sx2 - sx1, sh = (double)sy2 - sy1, scx = sx1 + 0.5 * sw, scy = sy1 + 0.5 * sh;
+  const double tw = (double)tx2 - tx1, th = (double)ty2 - ty1, tcx = tx1 + 0.5 * tw, tcy = ty1 + 0.5 * th;
+  d[0] = (float)(wx * (tcx - scx) / sw); d[1] = (float)(wy * (tcy - scy) / sh);
+  d[2] = (float)(ww * log(tw / sw)); d[3] = (float)(wh * log(th / sh));
 }
 __device__ __forceinline__ float smooth_l1(float x, float t, float beta, float* grad) {
   const float n = fabsf(x - t);
@@ -199,7 +202,9 @@ extern "C" int lvc_fast_rcnn_losses(const float* logits, int ld_cls, const float
   return LVC_OK;
 }
 
-// RPN losses over S sampled anchors (labels in {0,1}); rows gathered by the host side index plumbing.
+// RPN losses over S rows of sampled anchors: label 1 = positive, 0 = negative, < 0 = padding (lvc_rpn_gather_sampled writes -1 behind
+// an image's sampled anchors when it could not fill its quota).  A padding row adds nothing to either loss and gets a zero gradient
+// (reference rpn.py:328-400 sums over gt_labels >= 0 only); its logit / delta / anchor / gt values are not read.
 __global__ __launch_bounds__(1024) void rpn_losses_kernel(const float* __restrict__ logits, const float* __restrict__ deltas,
                                                           const float* __restrict__ anchors,
                                                           const float* __restrict__ gt_boxes,
@@ -209,6 +214,12 @@ __global__ __launch_bounds__(1024) void rpn_losses_kernel(const float* __restric
   __shared__ double red[2][16];
   double lc = 0.0, lb = 0.0;
   for (int i = threadIdx.x; i < S; i += 1024) {
+    if (labels[i] < 0) {
+      if (dlogits) dlogits[i] = 0.f;
+      if (ddeltas)
+        for (int j = 0; j < 4; ++j) ddeltas[(size_t)i * 4 + j] = 0.f;
+      continue;
+    }
     const float x = logits[i], y = (float)labels[i];
     // F.binary_cross_entropy_with_logits: max(x,0) - x*y + log1p(exp(-|x|));  d/dx = sigmoid(x) - y
     lc += (double)(fmaxf(x, 0.f) - x * y + log1pf(expf(-fabsf(x))));
@@ -238,6 +249,8 @@ __global__ __launch_bounds__(1024) void rpn_losses_kernel(const float* __restric
   }
 }
 
+// logits [S], deltas / anchors / gt_boxes [S,4], labels int8 [S] (1 / 0 / negative = ignored row) -> out_losses [2] =
+// (loss_rpn_cls, loss_rpn_loc), both / normalizer.  Rows with labels[i] < 0 contribute to neither.  S == 0 gives (0, 0).
 extern "C" int lvc_rpn_losses(const float* logits, const float* deltas, const float* anchors, const float* gt_boxes,
                               const signed char* labels, int S, float smooth_l1_beta, float normalizer, float* out_losses,
                               void* stream) {
@@ -248,7 +261,8 @@ extern "C" int lvc_rpn_losses(const float* logits, const float* deltas, const fl
   return LVC_OK;
 }
 
-// same losses plus d(loss_cls)/d(logits) [S] and d(loss_loc)/d(deltas) [S,4] (zero rows for non-positive anchors)
+// same losses plus d(loss_cls)/d(logits) [S] (zero for ignored rows) and d(loss_loc)/d(deltas) [S,4] (zero rows for non-positive
+// anchors)
 extern "C" int lvc_rpn_losses_grad(const float* logits, const float* deltas, const float* anchors, const float* gt_boxes,
                                    const signed char* labels, int S, float smooth_l1_beta, float normalizer,
                                    float* out_losses, float* dlogits, float* ddeltas, void* stream) {

@@ -2211,7 +2211,8 @@ def subsample_batched(labels, keys, cap_pos, bs, seed=0):
 def rpn_gather_sampled(fused, A, cell_anchors, strides, sel, counts, matches, gt, gt_off):
     """Rows of the sampled anchors straight from the head's per-level outputs fused[l] [B,H,W,ld] (channel a = objectness, A + 4 a + c =
     delta c).  -> (logits [S], deltas [S,4], anchors [S,4], matched gt boxes [S,4], labels int8 [S]) with S = B * bs; padding rows carry
-    label -1."""
+    label -1 (logit 0, deltas 0, anchor and gt (0,0,1,1)), which `rpn_losses` ignores.  Contract: sel[b, j] for j < counts[b].sum()
+    is -1 or an anchor index below sum_l H_l W_l A, and matches[b, sel] lies inside image b's ground truth; neither is checked."""
     L = len(fused)
     B, bs = sel.shape
     dev = sel.device
@@ -2249,8 +2250,10 @@ def roi_build_table(pboxes, plogits, pcount, gt, gt_off, gt_logit, Wt):
 
 
 def roi_gather_sampled(boxes, logits, matches, sel, counts, gt_classes, gt_off, num_classes):
-    """Sampled rows of the table -> (boxes [B,bs,4], logits [B,bs], classes int64 [B,bs] (K = background, -1 padding), matched gt index
-    int64 [B,bs])."""
+    """Sampled rows of the table -> (boxes [B,bs,4], logits [B,bs], classes int64 [B,bs] (K = background AND padding: the rows behind
+    an image's counts are zero boxes of class K with match 0; callers cut them off or check the counts), matched gt index int64
+    [B,bs]).  Contract: sel[b, j] for j < counts[b].sum() lies in [0, Wt) and matches[b, sel] in [0, number of gt of image b); the
+    kernel does not check either."""
     B, Wt = logits.shape
     bs = sel.shape[1]
     dev = boxes.device
@@ -2266,7 +2269,10 @@ def roi_gather_sampled(boxes, logits, matches, sel, counts, gt_classes, gt_off, 
 
 
 def fast_rcnn_losses(logits, deltas, proposals, gt_boxes, gt_classes, num_classes, box_weights, smooth_l1_beta):
-    """Returns (losses [2] = (loss_cls, loss_box_reg), dlogits [R,K+1], ddeltas [R,4K|4])."""
+    """Returns (losses [2] = (loss_cls, loss_box_reg), dlogits [R,K+1], ddeltas [R,4K|4]).
+    logits [R, >=K+1] and deltas [R, 4K | 4] may be column slices of a wider tensor (unit column stride).
+    Contract: every gt_classes[r] lies in [0, K] (K = background).  The kernel indexes the row's logits with it unchecked: a
+    negative or larger class reads outside the row."""
     _req_cuda(logits, deltas, proposals, gt_boxes, gt_classes)
     R = logits.shape[0]
     K = num_classes
@@ -2739,8 +2745,9 @@ def linear_backward(x, weight, dz, need_dx=True, need_dw=True):
 
 
 def rpn_losses(logits, deltas, anchors, gt_boxes, labels, smooth_l1_beta, normalizer, with_grad=False):
-    """Sampled-anchor RPN losses.  All inputs are rows gathered at the sampled anchors.  with_grad: also returns
-    d(loss_cls)/d(logits) [S] and d(loss_loc)/d(deltas) [S,4]."""
+    """Sampled-anchor RPN losses.  All inputs are rows gathered at the sampled anchors; labels int8: 1 positive, 0 negative,
+    negative = ignored (the padding rows of `rpn_gather_sampled`): such a row adds nothing to either loss and has a zero gradient.
+    with_grad: also returns d(loss_cls)/d(logits) [S] and d(loss_loc)/d(deltas) [S,4]."""
     _req_cuda(logits, deltas, anchors, gt_boxes, labels)
     S = logits.shape[0]
     out = torch.zeros(2, device=logits.device, dtype=torch.float32)

@@ -706,3 +706,80 @@ def test_deferred_read_training_forward_falls_back_when_an_image_misses_its_quot
     for k_ in res[False][0]:
         assert abs(res[True][0][k_] - res[False][0][k_]) <= 2e-6 * max(1.0, abs(res[False][0][k_])), k_
     assert float(res[True][1]["roi_head/num_bg_samples"]) == float(res[False][1]["roi_head/num_bg_samples"]) < 512
+
+
+@pytest.mark.parametrize("which", ["frozen_head", "trainable_head"])
+def test_rpn_losses_batched_when_an_image_cannot_fill_its_anchor_quota(which):
+    """`RPN._losses_batched` on one 4x4 level (48 anchors) with BATCH_SIZE_PER_IMAGE = 64: every labelled anchor is sampled, whatever
+    the permutation, and the rest of each image's 64 rows is padding (label -1).  Against the reference's formula per image (rpn.py:
+    269-400 in float64: BCE "sum" over the anchors with label >= 0, smooth-L1 "sum" over the positives, both / (64 * B)), with the
+    Matcher restated here.  Padding rows must add nothing; in the trainable branch they are read at anchor 0 (`sel.clamp(min=0)`), so a
+    gradient they carried would land on anchor 0 of the head's output."""
+    import torch.nn.functional as F
+
+    from lvc_amd.config.presets import base_rcnn_fpn
+    from lvc_amd.layers import ShapeSpec
+    from lvc_amd.modeling.proposal_generator.rpn import RPN
+    from lvc_amd.structures import Boxes, Instances
+
+    cfg = base_rcnn_fpn()
+    cfg.MODEL.RPN.IN_FEATURES = ["p4"]
+    cfg.MODEL.ANCHOR_GENERATOR.SIZES = [[32]]
+    cfg.MODEL.RPN.BATCH_SIZE_PER_IMAGE = 64
+    d = torch.device("cuda:0")
+    rpn = RPN(cfg, {"p4": ShapeSpec(channels=16, stride=8)}).to(d).train()
+    A, B, bs, beta = 3, 2, 64, rpn.smooth_l1_beta
+    g = torch.Generator().manual_seed(21)
+    fused_cpu = torch.randn(B, 4, 4, 16, generator=g)            # objectness | deltas | one zero-weight channel, as the head lays them out
+    gts = [torch.tensor([[2.0, 1.0, 30.0, 29.0], [10.0, 12.0, 40.0, 26.0]]), torch.tensor([[0.0, 4.0, 22.0, 31.0]])]
+    inst = []
+    for t in gts:
+        x = Instances((32, 40))
+        x.gt_boxes = Boxes(t.to(d))
+        inst.append(x)
+    flist = [torch.zeros(B, 4, 4, 16, device=d)]
+    fused = fused_cpu.to(d).requires_grad_(which == "trainable_head")
+    with torch.set_grad_enabled(which == "trainable_head"):
+        losses, counts, _ = rpn._losses_batched([fused], flist, inst)
+    counts = counts.cpu()
+
+    # the reference, per image
+    anchors = torch.cat(rpn.anchor_generator._grid_anchors([(4, 4)]), 0).cpu()
+    ref = fused_cpu.double().requires_grad_(True)
+    lc, ll, nsel = 0.0, 0.0, []
+    for b, gt in enumerate(gts):
+        a1 = (gt[:, 2] - gt[:, 0]) * (gt[:, 3] - gt[:, 1])
+        a2 = (anchors[:, 2] - anchors[:, 0]) * (anchors[:, 3] - anchors[:, 1])
+        wh = (torch.min(gt[:, None, 2:], anchors[None, :, 2:]) - torch.max(gt[:, None, :2], anchors[None, :, :2])).clamp(min=0)
+        inter = wh[..., 0] * wh[..., 1]
+        iou = torch.where(inter > 0, inter / (a1[:, None] + a2[None, :] - inter), torch.zeros_like(inter))
+        vals, midx = iou.max(dim=0)
+        lab = torch.where(vals < 0.3, 0, torch.where(vals < 0.7, -1, 1))
+        lab[(iou == iou.max(dim=1).values[:, None]).any(dim=0)] = 1
+        pos, valid = (lab == 1).nonzero().view(-1), (lab >= 0).nonzero().view(-1)
+        assert 0 < len(pos) <= 32 and len(valid) < 48, "the case needs positives, ignored anchors and an unfilled quota"
+        nsel.append([len(pos), len(valid) - len(pos)])
+        logit = ref[b, :, :, :A].reshape(-1)
+        delta = ref[b, :, :, A:5 * A].reshape(-1, 4)
+        lc = lc + F.binary_cross_entropy_with_logits(logit[valid], (lab[valid] == 1).double(), reduction="sum")
+        an, gb = anchors[pos].double(), gt[midx[pos]].double()
+        sw, sh, tw, th = an[:, 2] - an[:, 0], an[:, 3] - an[:, 1], gb[:, 2] - gb[:, 0], gb[:, 3] - gb[:, 1]
+        t = torch.stack([((gb[:, 0] + 0.5 * tw) - (an[:, 0] + 0.5 * sw)) / sw, ((gb[:, 1] + 0.5 * th) - (an[:, 1] + 0.5 * sh)) / sh,
+                         torch.log(tw / sw), torch.log(th / sh)], 1)
+        n = (delta[pos] - t).abs()
+        ll = ll + (n.sum() if beta < 1e-5 else torch.where(n < beta, 0.5 * n * n / beta, n - 0.5 * beta).sum())
+    lc, ll = lc / (bs * B), ll / (bs * B)
+    assert counts.tolist() == nsel and int(counts.sum(1).max()) < bs
+    got_c, got_l = float(losses["loss_rpn_cls"].detach()), float(losses["loss_rpn_loc"].detach())
+    print(which, "sampled", counts.tolist(), "loss_rpn_cls %.7f ref %.7f loss_rpn_loc %.7f ref %.7f" % (got_c, float(lc), got_l, float(ll)))
+    assert abs(got_c - float(lc)) <= 1e-5 * max(1.0, abs(float(lc)))
+    assert abs(got_l - float(ll)) <= 1e-5 * max(1.0, abs(float(ll)))
+    if which == "trainable_head":
+        (lc + ll).backward()
+        (losses["loss_rpn_cls"] + losses["loss_rpn_loc"]).backward()
+        want, got = ref.grad, fused.grad.cpu().double()
+        err = (got - want).abs()
+        print("head output gradient: max |err| %.3e of max |ref| %.3e; at anchor 0: %s ref %s" % (float(err.max()), float(want.abs().max()),
+              got[:, 0, 0, 0].tolist(), want[:, 0, 0, 0].tolist()))
+        assert float(err.max()) <= 1e-5 * float(want.abs().max())
+        assert float(err[:, 0, 0, [0, 3, 4, 5, 6]].max()) <= 1e-5 * float(want.abs().max()), "anchor 0: its logit and its four deltas"
