@@ -309,6 +309,24 @@ int lvc_train_input_u8(const void* h_blob, const void* d_blob, long long blob_by
 int lvc_train_input_tiles_u8(const void* h_blob, const void* d_blob, long long blob_bytes, int B, unsigned char* tmp,
                              long long tmp_bytes, float* out, int n_slots, int Hp, int Wp, const float* mean3, const float* std3,
                              int* launches, void* stream);
+/* INPUT.LSJ (reference ResizeScale -> FixedSizeCrop -> RandomFlip, detectron2/data/transforms/augmentation_impl.py:123-161, 391-431)
+ * of a whole batch in two launches (lvc_amd/csrc/train_input.hip): the crop window of a tiled job (tiles and painting rule of
+ * lvc_train_input_tiles_u8; a plain image or a jittered crop is one tile) is resized WHOLE to sh x sw with Pillow's tables for the
+ * full resize, of which only the output window (ox, oy, ow, oh) is computed -- the scaled image is never written -- and placed at
+ * the top left of a th x tw canvas whose right and bottom are `fill`; a flipped job mirrors the canvas (fill on the left).
+ *   Arguments as lvc_train_input_tiles_u8, with int64 jobs [B][140] first in the blob.  Job words: 0 X0, 1 Y0, 2 crop w, 3 crop h,
+ *   4 sh, 5 sw (the whole scaled image), 6 xb offset (-1: width unchanged), 7 xk offset, 8 kxs, 9 yb offset (-1: height unchanged),
+ *   10 yk offset, 11 kys (tables of the full crop -> scaled resize), 12 flip, 13 slot, 14 optional uint8 output pointer [th,tw,3]
+ *   (0: none), 15 byte offset of the job's [bh,ow,3] intermediate in tmp, 16 number of tiles (1..9), 17 ox, 18 oy, 19 ow, 20 oh,
+ *   21 th, 22 tw, 23 fill byte, 24 by0, 25 bh (the band of crop-window rows the vertical taps of rows [oy, oy + oh) touch; the rows
+ *   themselves where the height stays), 26-31 reserved; tile t at words 32 + 12 t as in lvc_train_input_tiles_u8.
+ *   out [n_slots,Hp,Wp,4] fp32 = (v - mean) / std on the canvas, zero outside it.  Refused before anything is launched: what
+ *   lvc_train_input_tiles_u8 refuses of a window and its tiles, an output window outside the scaled image or larger than the canvas,
+ *   a canvas outside the padded batch, a fill that is no byte, a band outside the crop window, column taps outside the crop window,
+ *   row taps outside the band, two jobs on one slot, an intermediate outside tmp or over another job's. */
+int lvc_train_input_lsj_u8(const void* h_blob, const void* d_blob, long long blob_bytes, int B, unsigned char* tmp,
+                           long long tmp_bytes, float* out, int n_slots, int Hp, int Wp, const float* mean3, const float* std3,
+                           int* launches, void* stream);
 /* INPUT.COLOR_JITTER (reference ColorJitterPIL: torchvision's ColorJitter on a PIL image, i.e. Pillow's ImageEnhance blends,
  * convert("L") and RGB <-> HSV conversion) of a whole batch (csrc/color_jitter.hip): per job the crop window of a canvas painted
  * from 1 to 9 tiles (tiles and painting rule of lvc_train_input_tiles_u8) goes through up to four steps in the job's own order and

@@ -19,6 +19,9 @@
 //
 // lvc_train_input_tiles_u8 (below, with kernels and a job table of its own): the same for images that are MOSAICS of 1 to 9 tiles
 // (reference lvc/data/mosaic.py get_mosaic / get_mosaic9), read in place -- neither the canvas nor the composite exists in memory.
+//
+// lvc_train_input_lsj_u8 (at the end, with kernels and a job table of its own): INPUT.LSJ -- the window of the scaled image that
+// FixedSizeCrop keeps, on its padded canvas, without the scaled image ever being written.
 #include "common.h"
 
 #define TI_PREC 22
@@ -358,6 +361,220 @@ extern "C" int lvc_train_input_tiles_u8(const void* h_blob, const void* d_blob, 
   LVC_CHECK_LAUNCH();
   if (launches) ++*launches;
   hipLaunchKernelGGL(train_input_tiles_v_kernel, dim3(lvc_cdiv(Wp, 256), Hp, B), dim3(256), 0, st, db, tmp, out, Hp, Wp, mean3[0],
+                     mean3[1], mean3[2], std3[0], std3[1], std3[2]);
+  LVC_CHECK_LAUNCH();
+  if (launches) ++*launches;
+  return LVC_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ large-scale jitter (INPUT.LSJ)
+// ResizeScale -> FixedSizeCrop -> RandomFlip (reference detectron2/data/transforms/augmentation_impl.py:123-161, 391-431): the crop
+// window of a tiled job is resized WHOLE to sh x sw (Pillow's tables for the full cw -> sw / ch -> sh resize: support and weights
+// depend on the full sizes), the window (ox, oy, ow, oh) of that scaled image lands at the top left of a th x tw canvas filled with
+// `fill` at its right and bottom, and the canvas is mirrored where the job says so.  The scaled image never exists: the window only
+// selects columns and rows of the tables.  Two launches whatever B and the mix:
+//   1. horizontal pass, grid (x tiles, rows of the largest band, B), always run (a copy where the width stays): output columns
+//      [ox, ox + ow) of the source rows [by0, by0 + bh) of the crop window -- the band the vertical taps of rows [oy, oy + oh) touch
+//      (those rows themselves where the height stays) -- through the tile list, as train_input_tiles_h_kernel -> tmp [bh][ow][3];
+//   2. vertical pass, grid (x tiles, Hp, B): thread (yo, xo) owns OUTPUT pixel (yo, xo) of its slot; its canvas column before the
+//      flip is xc = flip ? tw-1-xo : xo; inside oh x ow it resamples column xc of tmp with the taps of scaled row oy + yo, elsewhere
+//      inside the canvas it is the fill; both are normalised as above; outside the canvas it is the batch's zero padding.
+#define LJ_HEAD 32        // int64 words in front of a job's tiles
+#define LJ_FIELDS (LJ_HEAD + TT_MAX_TILES * TT_TILE)   // 140 words per job (lvc_amd.h)
+
+enum {
+  LJ_X0 = 0, LJ_Y0, LJ_CW, LJ_CH, LJ_SH, LJ_SW, LJ_XB, LJ_XK, LJ_KXS, LJ_YB, LJ_YK, LJ_KYS, LJ_FLIP, LJ_SLOT, LJ_U8, LJ_TMP, LJ_NT,
+  LJ_OX, LJ_OY, LJ_OW, LJ_OH, LJ_TH, LJ_TW, LJ_FILL, LJ_BY0, LJ_BH
+};
+
+// rows [by0, by0 + bh) of the crop window (through the tile list), scaled columns [ox, ox + ow) -> tmp [bh][ow][3]
+__global__ __launch_bounds__(256) void train_input_lsj_h_kernel(const char* __restrict__ blob, unsigned char* __restrict__ tmp) {
+  const long long* jb = reinterpret_cast<const long long*>(blob) + (size_t)blockIdx.z * LJ_FIELDS;
+  const int y = blockIdx.y, ow = (int)jb[LJ_OW], cw = (int)jb[LJ_CW];
+  if (y >= (int)jb[LJ_BH] || (int)(blockIdx.x * 256) >= ow) return;   // the whole workgroup leaves: nobody waits below
+  __shared__ int seg_lo[TT_MAX_TILES], seg_hi[TT_MAX_TILES], n_seg;
+  __shared__ long long seg_sx[TT_MAX_TILES], seg_sc[TT_MAX_TILES];
+  __shared__ const unsigned char* seg_row[TT_MAX_TILES];      // the tile's pixel under window column 0 of this row
+  if (threadIdx.x < 64) {      // the first wavefront: lane t tests tile t; the crossing tiles are compacted in paint order
+    const long long X0 = jb[LJ_X0], Y = jb[LJ_Y0] + jb[LJ_BY0] + y;
+    const long long* tl = jb + LJ_HEAD + (size_t)(threadIdx.x < TT_MAX_TILES ? threadIdx.x : 0) * TT_TILE;
+    long long lo = 0, hi = 0;
+    bool cross = false;
+    if ((long long)threadIdx.x < jb[LJ_NT] && Y >= tl[TL_Y1A] && Y < tl[TL_Y2A]) {
+      lo = tl[TL_X1A] > X0 ? tl[TL_X1A] - X0 : 0;
+      hi = tl[TL_X2A] < X0 + cw ? tl[TL_X2A] - X0 : cw;
+      cross = lo < hi;
+    }
+    const unsigned long long m = __ballot(cross);
+    if (cross) {
+      const int p = __popcll(m & ((1ull << threadIdx.x) - 1ull));
+      seg_lo[p] = (int)lo; seg_hi[p] = (int)hi; seg_sx[p] = tl[TL_SX]; seg_sc[p] = tl[TL_SC];
+      seg_row[p] = reinterpret_cast<const unsigned char*>(tl[TL_SRC]) + (Y - tl[TL_Y1A] + tl[TL_Y1B]) * tl[TL_SY] +
+                   (X0 - tl[TL_X1A] + tl[TL_X1B]) * tl[TL_SX];
+    }
+    if (threadIdx.x == 0) n_seg = __popcll(m);
+  }
+  __syncthreads();
+  const int xo = blockIdx.x * 256 + threadIdx.x;
+  if (xo >= ow) return;
+  const int xs = (int)jb[LJ_OX] + xo;      // the column of the scaled image
+  int xmin = xs, cnt = 1;
+  const int* k = nullptr;      // width unchanged: one tap of weight 1
+  if (jb[LJ_XB] >= 0) {
+    const int* xb = reinterpret_cast<const int*>(blob + jb[LJ_XB]);
+    k = reinterpret_cast<const int*>(blob + jb[LJ_XK]) + (size_t)xs * (int)jb[LJ_KXS];
+    xmin = xb[2 * xs]; cnt = xb[2 * xs + 1];
+  }
+  const int ns = n_seg;
+  int run_hi = -1;                       // taps below run_hi have the owner found last
+  const unsigned char* row = nullptr;    // its row (nullptr: no tile, the mosaic's fill colour)
+  long long sx = 0, sc = 0;
+  int s0 = 1 << (TI_PREC - 1), s1 = s0, s2 = s0;
+  for (int t = 0; t < cnt; ++t) {
+    const int x = xmin + t;
+    if (x >= run_hi) {      // the last tile that covers x owns it; the run ends where that tile ends or a later one begins
+      row = nullptr; run_hi = cw;
+      for (int i = 0; i < ns; ++i) {
+        const int lo = seg_lo[i], hi = seg_hi[i];
+        if (lo <= x && x < hi) { row = seg_row[i]; sx = seg_sx[i]; sc = seg_sc[i]; run_hi = hi; }
+        else if (lo > x && lo < run_hi) run_hi = lo;
+      }
+    }
+    int p0 = TT_FILL, p1 = TT_FILL, p2 = TT_FILL;
+    if (row) {
+      const unsigned char* p = row + x * sx;
+      p0 = p[0]; p1 = p[sc]; p2 = p[2 * sc];
+    }
+    const int c = k ? k[t] : 1 << TI_PREC;
+    s0 += p0 * c; s1 += p1 * c; s2 += p2 * c;
+  }
+  unsigned char* o = tmp + jb[LJ_TMP] + ((size_t)y * ow + xo) * 3;
+  o[0] = ti_clip8(s0); o[1] = ti_clip8(s1); o[2] = ti_clip8(s2);
+}
+
+// tmp [bh][ow][3] -> the job's slot (and its optional uint8 canvas [th][tw][3])
+__global__ __launch_bounds__(256) void train_input_lsj_v_kernel(const char* __restrict__ blob, const unsigned char* __restrict__ tmp,
+                                                                float* __restrict__ out, int Hp, int Wp, float m0, float m1, float m2,
+                                                                float d0, float d1, float d2) {
+  const long long* jb = reinterpret_cast<const long long*>(blob) + (size_t)blockIdx.z * LJ_FIELDS;
+  const int xo = blockIdx.x * 256 + threadIdx.x, yo = blockIdx.y;
+  if (xo >= Wp) return;
+  const int th = (int)jb[LJ_TH], tw = (int)jb[LJ_TW];
+  float4 v = {0.f, 0.f, 0.f, 0.f};
+  if (yo < th && xo < tw) {
+    const int xc = jb[LJ_FLIP] ? tw - 1 - xo : xo;   // HFlipTransform(tw) on the padded canvas: the fill moves to the left
+    const int ow = (int)jb[LJ_OW];
+    unsigned char r0, r1, r2;
+    r0 = r1 = r2 = (unsigned char)jb[LJ_FILL];
+    if (yo < (int)jb[LJ_OH] && xc < ow) {
+      const unsigned char* col = tmp + jb[LJ_TMP] + (size_t)xc * 3;
+      const long long sy = (long long)ow * 3;
+      const int ys = (int)jb[LJ_OY] + yo, by0 = (int)jb[LJ_BY0];      // the row of the scaled image; the band's first source row
+      if (jb[LJ_YB] >= 0) {
+        const int* yb = reinterpret_cast<const int*>(blob + jb[LJ_YB]);
+        const int* k = reinterpret_cast<const int*>(blob + jb[LJ_YK]) + (size_t)ys * (int)jb[LJ_KYS];
+        const int ymin = yb[2 * ys] - by0, cnt = yb[2 * ys + 1];
+        int s0 = 1 << (TI_PREC - 1), s1 = s0, s2 = s0;
+        for (int y = 0; y < cnt; ++y) {
+          const unsigned char* p = col + (ymin + y) * sy;
+          const int c = k[y];
+          s0 += p[0] * c; s1 += p[1] * c; s2 += p[2] * c;
+        }
+        r0 = ti_clip8(s0); r1 = ti_clip8(s1); r2 = ti_clip8(s2);
+      } else {   // height unchanged: Pillow skips the vertical pass
+        const unsigned char* p = col + (ys - by0) * sy;
+        r0 = p[0]; r1 = p[1]; r2 = p[2];
+      }
+    }
+    if (jb[LJ_U8]) {
+      unsigned char* o = reinterpret_cast<unsigned char*>(jb[LJ_U8]) + ((size_t)yo * tw + xo) * 3;
+      o[0] = r0; o[1] = r1; o[2] = r2;
+    }
+    v.x = ((float)r0 - m0) / d0;
+    v.y = ((float)r1 - m1) / d1;
+    v.z = ((float)r2 - m2) / d2;
+  }
+  *reinterpret_cast<float4*>(out + (((size_t)jb[LJ_SLOT] * Hp + yo) * Wp + xo) * 4) = v;
+}
+
+// h_blob / d_blob / blob_bytes as lvc_train_input_tiles_u8, with int64 jobs [B][140] first.  Job words: 0 X0, 1 Y0, 2 cw, 3 ch (the
+// crop window in canvas coordinates: what is resized), 4 sh, 5 sw (the size of the WHOLE scaled image), 6 xb offset (-1: sw == cw),
+// 7 xk offset, 8 kxs, 9 yb offset (-1: sh == ch), 10 yk offset, 11 kys (the tables of the full cw -> sw / ch -> sh resize), 12 flip,
+// 13 slot, 14 optional uint8 output pointer [th][tw][3] (0: none), 15 byte offset of the job's [bh][ow][3] intermediate in tmp,
+// 16 number of tiles (1..9), 17 ox, 18 oy, 19 ow, 20 oh (the output window inside the scaled image), 21 th, 22 tw (the canvas),
+// 23 fill byte, 24 by0, 25 bh (the band of crop-window rows the horizontal pass produces), 26-31 reserved; tile t at words
+// 32 + 12 t as in lvc_train_input_tiles_u8.  Checked on the host copy before anything is launched: what lvc_train_input_tiles_u8
+// checks of a window and its tiles, the output window inside the scaled image and not larger than the canvas, the canvas inside the
+// padded batch, the band inside the crop window, every tap of the window's columns inside the crop window and of its rows inside the
+// band, the intermediate inside tmp and apart from every other job's, no slot written twice.  launches: optional, the number of kernel launches issued (two).
+extern "C" int lvc_train_input_lsj_u8(const void* h_blob, const void* d_blob, long long blob_bytes, int B, unsigned char* tmp,
+                                      long long tmp_bytes, float* out, int n_slots, int Hp, int Wp, const float* mean3,
+                                      const float* std3, int* launches, void* stream) {
+  if (launches) *launches = 0;
+  LVC_CHECK_ARG(B >= 0 && n_slots >= B && Hp > 0 && Wp > 0, "bad batch size");
+  if (B == 0) return LVC_OK;
+  LVC_CHECK_ARG(h_blob && d_blob && out && tmp && mean3 && std3, "null argument");
+  LVC_CHECK_ARG(((uintptr_t)h_blob & 7) == 0 && ((uintptr_t)d_blob & 7) == 0, "the blob must be 8-byte aligned");
+  LVC_CHECK_ARG(blob_bytes >= (long long)B * LJ_FIELDS * 8, "blob smaller than its job table");
+  const long long* jobs = reinterpret_cast<const long long*>(h_blob);
+  const char* hb = reinterpret_cast<const char*>(h_blob);
+  int gw = 0, gh = 0;
+  unsigned long long slots_seen = 0;
+  for (int i = 0; i < B; ++i) {
+    const long long* j = jobs + (size_t)i * LJ_FIELDS;
+    const long long X0 = j[LJ_X0], Y0 = j[LJ_Y0], cw = j[LJ_CW], ch = j[LJ_CH], sh = j[LJ_SH], sw = j[LJ_SW];
+    const long long ox = j[LJ_OX], oy = j[LJ_OY], ow = j[LJ_OW], oh = j[LJ_OH], th = j[LJ_TH], tw = j[LJ_TW];
+    const long long by0 = j[LJ_BY0], bh = j[LJ_BH];
+    LVC_CHECK_ARG(j[LJ_NT] >= 1 && j[LJ_NT] <= TT_MAX_TILES, "a job has 1 to 9 tiles");
+    LVC_CHECK_ARG(X0 >= 0 && Y0 >= 0 && cw > 0 && ch > 0 && X0 < TT_COORD_MAX && Y0 < TT_COORD_MAX && cw < TT_COORD_MAX &&
+                  ch < TT_COORD_MAX, "bad crop window");
+    for (int t = 0; t < (int)j[LJ_NT]; ++t) {
+      const long long* tl = j + LJ_HEAD + (size_t)t * TT_TILE;
+      LVC_CHECK_ARG(tl[TL_SRC] && tl[TL_H] > 0 && tl[TL_W] > 0 && tl[TL_H] < TT_COORD_MAX && tl[TL_W] < TT_COORD_MAX, "bad tile image");
+      LVC_CHECK_ARG(tl[TL_SY] > 0 && tl[TL_SX] > 0 && tl[TL_SC] > 0, "strides must be positive");
+      for (int f = TL_X1A; f <= TL_Y1B; ++f) LVC_CHECK_ARG(tl[f] > -TT_COORD_MAX && tl[f] < TT_COORD_MAX, "tile coordinate out of range");
+      LVC_CHECK_ARG(tl[TL_X2A] >= tl[TL_X1A] && tl[TL_Y2A] >= tl[TL_Y1A], "canvas rectangle with negative extent");
+      const long long lx = tl[TL_X1A] > X0 ? tl[TL_X1A] : X0, hx = tl[TL_X2A] < X0 + cw ? tl[TL_X2A] : X0 + cw;
+      const long long ly = tl[TL_Y1A] > Y0 ? tl[TL_Y1A] : Y0, hy = tl[TL_Y2A] < Y0 + ch ? tl[TL_Y2A] : Y0 + ch;
+      if (lx < hx && ly < hy)      // the part of the tile's rectangle the crop window sees: read from inside the tile
+        LVC_CHECK_ARG(lx - tl[TL_X1A] + tl[TL_X1B] >= 0 && hx - tl[TL_X1A] + tl[TL_X1B] <= tl[TL_W] &&
+                      ly - tl[TL_Y1A] + tl[TL_Y1B] >= 0 && hy - tl[TL_Y1A] + tl[TL_Y1B] <= tl[TL_H], "a tile is read outside its image");
+    }
+    LVC_CHECK_ARG(sh > 0 && sw > 0 && sh < TT_COORD_MAX && sw < TT_COORD_MAX, "bad scaled size");
+    LVC_CHECK_ARG(ox >= 0 && oy >= 0 && ow > 0 && oh > 0 && ox <= sw - ow && oy <= sh - oh, "output window outside the scaled image");
+    LVC_CHECK_ARG(th > 0 && tw > 0 && ow <= tw && oh <= th && th <= Hp && tw <= Wp, "canvas outside the padded batch or smaller than its window");
+    LVC_CHECK_ARG(j[LJ_FILL] >= 0 && j[LJ_FILL] <= 255, "the fill is a byte");
+    LVC_CHECK_ARG(j[LJ_SLOT] >= 0 && j[LJ_SLOT] < n_slots, "bad slot");
+    if (j[LJ_SLOT] < 64) {
+      LVC_CHECK_ARG(!(slots_seen >> j[LJ_SLOT] & 1ull), "two jobs write one slot");
+      slots_seen |= 1ull << j[LJ_SLOT];
+    }
+    LVC_CHECK_ARG((j[LJ_XB] >= 0) == (sw != cw) && (j[LJ_YB] >= 0) == (sh != ch), "coefficients must match the size change");
+    LVC_CHECK_ARG(by0 >= 0 && bh > 0 && by0 <= ch - bh, "band outside the crop window");
+    if (j[LJ_XB] >= 0) LVC_CHECK_ARG(ti_check_axis(hb, blob_bytes, j[LJ_XB], j[LJ_XK], j[LJ_KXS], cw, sw), "bad column tables");
+    if (j[LJ_YB] >= 0) {
+      LVC_CHECK_ARG(ti_check_axis(hb, blob_bytes, j[LJ_YB], j[LJ_YK], j[LJ_KYS], ch, sh), "bad row tables");
+      const int* b = reinterpret_cast<const int*>(hb + j[LJ_YB]);
+      for (long long r = oy; r < oy + oh; ++r)
+        LVC_CHECK_ARG(b[2 * r] >= by0 && (long long)b[2 * r] + b[2 * r + 1] <= by0 + bh, "row taps outside the band");
+    } else {
+      LVC_CHECK_ARG(by0 <= oy && oy + oh <= by0 + bh, "output rows outside the band");
+    }
+    LVC_CHECK_ARG(j[LJ_TMP] >= 0 && j[LJ_TMP] <= tmp_bytes && bh * ow * 3 <= tmp_bytes - j[LJ_TMP], "intermediate outside the scratch buffer");
+    for (int k = 0; k < i; ++k) {      // both passes of all jobs run side by side: no two intermediates may share a byte
+      const long long* o = jobs + (size_t)k * LJ_FIELDS;
+      LVC_CHECK_ARG(j[LJ_TMP] + bh * ow * 3 <= o[LJ_TMP] || o[LJ_TMP] + o[LJ_BH] * o[LJ_OW] * 3 <= j[LJ_TMP],
+                    "two jobs share bytes of the intermediate");
+    }
+    gw = ow > gw ? (int)ow : gw;
+    gh = bh > gh ? (int)bh : gh;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const char* db = reinterpret_cast<const char*>(d_blob);
+  hipLaunchKernelGGL(train_input_lsj_h_kernel, dim3(lvc_cdiv(gw, 256), gh, B), dim3(256), 0, st, db, tmp);
+  LVC_CHECK_LAUNCH();
+  if (launches) ++*launches;
+  hipLaunchKernelGGL(train_input_lsj_v_kernel, dim3(lvc_cdiv(Wp, 256), Hp, B), dim3(256), 0, st, db, tmp, out, Hp, Wp, mean3[0],
                      mean3[1], mean3[2], std3[0], std3[1], std3[2]);
   LVC_CHECK_LAUNCH();
   if (launches) ++*launches;

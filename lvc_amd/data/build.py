@@ -22,6 +22,10 @@ refused, as it always was): the items whose draw carries a jitter go through one
 (lvc_color_jitter_tiles_u8, csrc/color_jitter.hip: two launches for the batch), which writes their jittered crop windows into a
 scratch of the rotating buffer; lvc_train_input_u8 then resizes those as plain images.  A batch without a jitter item takes the
 calls it always took.
+
+Large-scale jitter (INPUT.LSJ; both builders take `lsj=True` to follow the key, or a transforms.LargeScaleJitter): the batch -- plain
+items, mosaics and jittered crops alike -- is one call of lvc_train_input_lsj_u8 on the same side stream, buffers and events, which
+computes only the window of each scaled image that FixedSizeCrop keeps.  Without it every call made before is made unchanged.
 """
 import itertools
 import os
@@ -84,6 +88,14 @@ def _plain_batches(dataset, batch_size):
     it = iter(dataset)
     while True:
         yield [next(it) for _ in range(batch_size)]
+
+
+def _lsj_batch(drawn):
+    """Whether the batch goes through the large-scale jitter: all of its items or none (one mapper setting draws them all)."""
+    n = sum(1 for _, _, p in drawn if p.lsj is not None)
+    if n not in (0, len(drawn)):
+        raise ValueError("a batch mixes items with and without the large-scale jitter: give both mappers the same `lsj`")
+    return n > 0
 
 
 class PreparedBatch:
@@ -152,6 +164,10 @@ class TrainInputLoader:
                                             workspace=slot.jitter)
             for i, crop in zip(jit, crops):
                 images[i], jobs[i] = crop, drawn[i][2].crop_job()
+        if _lsj_batch(drawn):      # every item through the large-scale jitter: the window of its scaled image on its canvas
+            items = [p.lsj_item(plain_tiles(img), job[0:4]) for img, job, (_, _, p) in zip(images, jobs, drawn)]
+            K.train_input_lsj_u8(items, buf, self.mapper.pixel_mean, self.mapper.pixel_std, resample_coeffs, workspace=slot.workspace)
+            return
         K.train_input_u8(images, jobs, buf, self.mapper.pixel_mean, self.mapper.pixel_std, resample_coeffs, workspace=slot.workspace)
 
     def _items(self, drawn, indices, batch):
@@ -239,6 +255,14 @@ class MosaicTrainInputLoader(TrainInputLoader):
         slot.images = [[r.to(self.device, non_blocking=True) for r in raws] for _, raws, _ in drawn]
         items = [p.tiles_item(tiles) if len(tiles) > 1 else plain_tiles_item(tiles[0], p) for tiles, (_, _, p) in zip(slot.images, drawn)]
         jit = [i for i, (_, _, p) in enumerate(drawn) if p.jitter is not None]
+        if _lsj_batch(drawn):      # plain and mosaic items, jittered or not, in one call of the large-scale jitter's entry
+            lsj = [p.lsj_item(it[0], it[1]) for it, (_, _, p) in zip(items, drawn)]
+            if jit:
+                crops = K.color_jitter_tiles_u8([jitter_item(items[i][0], items[i][1], drawn[i][2]) for i in jit], workspace=slot.jitter)
+                for i, crop in zip(jit, crops):
+                    lsj[i] = drawn[i][2].lsj_item(plain_tiles(crop), drawn[i][2].crop_job()[0:4])
+            K.train_input_lsj_u8(lsj, buf, self.mapper.pixel_mean, self.mapper.pixel_std, resample_coeffs, workspace=slot.workspace)
+            return
         if jit:      # their jittered crop windows (of the painted canvas, 114 fill included) become plain one-tile items
             crops = K.color_jitter_tiles_u8([jitter_item(items[i][0], items[i][1], drawn[i][2]) for i in jit], workspace=slot.jitter)
             if len(jit) == len(items):      # every item is a plain image now: the plain entry
@@ -268,20 +292,20 @@ def _loader_args(cfg, size_divisibility):
 
 
 def build_detection_train_mosaic_loader(cfg, dataset_dicts, mapper=None, seed=None, size_divisibility=None, sync=False, *,
-                                        color_jitter=None):
+                                        color_jitter=None, lsj=None):
     """build_detection_train_loader for INPUT.MOSAIC > 0 (reference lvc/data/build.py build_detection_train_mosaic_loader): each
     sampled item is, by MapDatasetMosaic's draws from Python's `random` module (seed it with `random.seed`), a plain item or a
     mosaic of 4 / 9 dataset items.  mapper: the plain branch's (default: a DatasetMapper of this cfg); the mosaic branch is
     DatasetMapperMosaic.from_config(cfg).  With INPUT.MOSAIC == 0 this is the plain loader.  Everything else as
-    build_detection_train_loader (color_jitter goes to both mappers)."""
+    build_detection_train_loader (color_jitter and lsj go to both mappers)."""
     from .dataset_mapper import MOSAIC_KEYS
     from .mosaic import DatasetMapperMosaic, MapDatasetMosaic
 
-    check_supported(cfg, allow=jitter_allow(MOSAIC_KEYS, color_jitter))
+    check_supported(cfg, allow=jitter_allow(MOSAIC_KEYS, color_jitter, lsj))
     batch_size, size_divisibility = _loader_args(cfg, size_divisibility)
     if mapper is None:
-        mapper = DatasetMapper._from_config(cfg, True, allow=MOSAIC_KEYS, color_jitter=color_jitter)
-    mosaic_mapper = DatasetMapperMosaic.from_config(cfg, True, color_jitter=color_jitter)
+        mapper = DatasetMapper._from_config(cfg, True, allow=MOSAIC_KEYS, color_jitter=color_jitter, lsj=lsj)
+    mosaic_mapper = DatasetMapperMosaic.from_config(cfg, True, color_jitter=color_jitter, lsj=lsj)
     sampler = TrainingSampler(len(dataset_dicts), seed=seed)
     loader = MosaicTrainInputLoader(dataset_dicts, mapper, mosaic_mapper, MapDatasetMosaic(dataset_dicts, mosaic_mapper, mapper, cfg),
                                     batch_size, sampler, size_divisibility, aspect_ratio_grouping=cfg.DATALOADER.ASPECT_RATIO_GROUPING,
@@ -289,17 +313,19 @@ def build_detection_train_mosaic_loader(cfg, dataset_dicts, mapper=None, seed=No
     return iter(loader)
 
 
-def build_detection_train_loader(cfg, dataset_dicts, mapper=None, seed=None, size_divisibility=None, sync=False, *, color_jitter=None):
+def build_detection_train_loader(cfg, dataset_dicts, mapper=None, seed=None, size_divisibility=None, sync=False, *, color_jitter=None,
+                                 lsj=None):
     """An infinite iterator of batches of SOLVER.IMS_PER_BATCH // world_size items for `model(batched_inputs)` in training mode.
     dataset_dicts: the reference's dataset format with the decoded image under "raw" (uint8 [H,W,3], pinned host memory makes the
     upload asynchronous).  seed: the sampler's (the same on every rank); the augmentations draw from numpy's global generator.
     size_divisibility: the backbone's (default: 32 for the FPN backbones, else 0).  color_jitter: None -- a cfg that sets
     INPUT.COLOR_JITTER is refused; True -- follow the key; a transforms.ColorJitter -- use it (its draws come from torch's default
-    generator: `torch.manual_seed`)."""
-    check_supported(cfg, jitter_allow((), color_jitter))
+    generator: `torch.manual_seed`).  lsj: None -- a cfg that sets INPUT.LSJ is refused; True -- follow the key (the reference's
+    ResizeScale(0.5, 1.6, 800, 800) + FixedSizeCrop((800, 800)): every batch is 800 x 800); a transforms.LargeScaleJitter -- use it."""
+    check_supported(cfg, jitter_allow((), color_jitter, lsj))
     batch_size, size_divisibility = _loader_args(cfg, size_divisibility)
     if mapper is None:
-        mapper = DatasetMapper.from_config(cfg, True, color_jitter=color_jitter)
+        mapper = DatasetMapper.from_config(cfg, True, color_jitter=color_jitter, lsj=lsj)
     sampler = TrainingSampler(len(dataset_dicts), seed=seed)
     loader = TrainInputLoader(dataset_dicts, mapper, batch_size, sampler, size_divisibility,
                               aspect_ratio_grouping=cfg.DATALOADER.ASPECT_RATIO_GROUPING, device=cfg.MODEL.DEVICE, sync=sync)

@@ -15,10 +15,12 @@ files is the caller's business, as in `eval_loop_host_inputs`.
 Built: INPUT.CROP (all four types), MIN_SIZE_TRAIN / MAX_SIZE_TRAIN / MIN_SIZE_TRAIN_SAMPLING, the horizontal flip, boxes, classes,
 ignore flags, ids; INPUT.COLOR_JITTER (transforms.ColorJitter; pixels: `kernels.color_jitter_tiles_u8`, csrc/color_jitter.hip, on the
 crop window in front of the resize) for callers that opt in with `color_jitter=True` -- without it the key still raises, as it
-always has; INPUT.MOSAIC / INPUT.MOSAIC49SPLIT through entry points of their own, as in the reference (mosaic.py:
+always has; INPUT.LSJ (transforms.LargeScaleJitter: ResizeScale -> FixedSizeCrop in ResizeShortestEdge's place; pixels:
+`kernels.train_input_lsj_u8`, which computes only the window of the scaled image that survives) for callers that opt in with
+`lsj=True`, the same way; INPUT.MOSAIC / INPUT.MOSAIC49SPLIT through entry points of their own, as in the reference (mosaic.py:
 `DatasetMapperMosaic`, `MapDatasetMosaic`, build.py `build_detection_train_mosaic_loader`) -- `DatasetMapper.from_config` and
 `build_detection_train_loader` never do mosaic and refuse a cfg that asks for it, pointing there.  Not built (NotImplementedError
-naming the key): INPUT.BLUR, INPUT.LSJ, MODEL.MASK_ON, MODEL.KEYPOINT_ON, MODEL.LOAD_PROPOSALS,
+naming the key): INPUT.BLUR (torchvision's GaussianBlur: an fp32 convolution whose summation order cannot be pinned), MODEL.MASK_ON, MODEL.KEYPOINT_ON, MODEL.LOAD_PROPOSALS,
 QUERY_EXPAND.GET_CROPS; "sem_seg_file_name" in an input dict.
 """
 import numpy as np
@@ -26,7 +28,8 @@ import torch
 
 from .. import kernels as K
 from ..structures import Boxes, BoxMode, Instances
-from .transforms import AugmentationList, ColorJitter, RandomCrop, RandomFlip, ResizeShortestEdge, resample_coeffs
+from .transforms import (AugmentationList, ColorJitter, LargeScaleJitter, RandomCrop, RandomFlip, ResizeShortestEdge,
+                         resample_coeffs)
 
 
 def _unsupported(cfg):
@@ -40,6 +43,7 @@ def _unsupported(cfg):
 
 MOSAIC_KEYS = ("INPUT.MOSAIC", "INPUT.MOSAIC49SPLIT")     # built, but only by the mosaic entry points (mosaic.py)
 JITTER_KEY = "INPUT.COLOR_JITTER"                          # built, but only for callers that pass color_jitter
+LSJ_KEY = "INPUT.LSJ"                                      # built, but only for callers that pass lsj
 
 
 def check_supported(cfg, allow=()):
@@ -52,22 +56,38 @@ def check_supported(cfg, allow=()):
             if key == JITTER_KEY:
                 raise NotImplementedError("{} is not applied by default: pass `color_jitter=True` to the loader builder or to the "
                                           "mapper's from_config to get the device colour jitter".format(key))
-            raise NotImplementedError("{} is not implemented by the device training input (crop, colour jitter, resize, flip, mosaic only)".format(key))
+            if key == LSJ_KEY:
+                raise NotImplementedError("{} is not applied by default: pass `lsj=True` to the loader builder or to the mapper's "
+                                          "from_config to get the device large-scale jitter".format(key))
+            raise NotImplementedError("{} is not implemented by the device training input (crop, colour jitter, resize, large-scale "
+                                      "jitter, flip, mosaic only)".format(key))
 
 
-def jitter_allow(allow, color_jitter):
-    """The keys a caller handles, with INPUT.COLOR_JITTER among them once it has opted in."""
-    return tuple(allow) + ((JITTER_KEY,) if color_jitter is not None and color_jitter is not False else ())
+def jitter_allow(allow, color_jitter, lsj=None):
+    """The keys a caller handles, with INPUT.COLOR_JITTER / INPUT.LSJ among them once it has opted in."""
+    return (tuple(allow) + ((JITTER_KEY,) if color_jitter is not None and color_jitter is not False else ()) +
+            ((LSJ_KEY,) if lsj is not None and lsj is not False else ()))
 
 
-def build_augmentation(cfg, is_train=True, allow=(), color_jitter=None):
+def build_augmentation(cfg, is_train=True, allow=(), color_jitter=None, lsj=None):
     """detection_utils.build_augmentation (:563-598) with the crop of DatasetMapperIgnore.from_config (:92-99) in front.
     color_jitter: None -- a cfg that sets INPUT.COLOR_JITTER raises; True -- follow the key (ColorJitter() in front of the resize if
-    it is set, as the reference's list has it, none if not); a transforms.ColorJitter -- use it whatever the key says."""
-    check_supported(cfg, jitter_allow(allow, color_jitter))
+    it is set, as the reference's list has it, none if not); a transforms.ColorJitter -- use it whatever the key says.
+    lsj: None -- a cfg that sets INPUT.LSJ raises; True -- follow the key (ResizeScale(0.5, 1.6, 800, 800) and FixedSizeCrop((800,
+    800)) in ResizeShortestEdge's place if it is set, as the reference's list has it); a transforms.LargeScaleJitter -- use its two
+    policies whatever the key says.  INPUT.BLUR raises whatever is passed: it is torchvision's GaussianBlur, an fp32 convolution
+    whose summation order cannot be pinned to bytes."""
+    check_supported(cfg, jitter_allow(allow, color_jitter, lsj))
     if not (color_jitter is None or color_jitter is True or color_jitter is False or isinstance(color_jitter, ColorJitter)):
         raise TypeError("color_jitter is None, True or a ColorJitter, got {!r}".format(color_jitter))
-    augs = [ResizeShortestEdge.from_config(cfg, is_train)]
+    if not (lsj is None or lsj is True or lsj is False or isinstance(lsj, LargeScaleJitter)):
+        raise TypeError("lsj is None, True or a LargeScaleJitter, got {!r}".format(lsj))
+    if is_train and lsj is True and cfg.INPUT.LSJ:
+        lsj = LargeScaleJitter()
+    if is_train and isinstance(lsj, LargeScaleJitter):
+        augs = lsj.augmentations()
+    else:
+        augs = [ResizeShortestEdge.from_config(cfg, is_train)]
     if is_train and color_jitter is True and cfg.INPUT.COLOR_JITTER:
         color_jitter = ColorJitter()
     if is_train and isinstance(color_jitter, ColorJitter):
@@ -166,12 +186,12 @@ class DatasetMapper:
         self.device = torch.device(device)
 
     @classmethod
-    def from_config(cls, cfg, is_train=True, *, color_jitter=None):
-        return cls._from_config(cfg, is_train, color_jitter=color_jitter)
+    def from_config(cls, cfg, is_train=True, *, color_jitter=None, lsj=None):
+        return cls._from_config(cfg, is_train, color_jitter=color_jitter, lsj=lsj)
 
     @classmethod
-    def _from_config(cls, cfg, is_train=True, allow=(), color_jitter=None):
-        return cls(is_train, augmentations=build_augmentation(cfg, is_train, allow, color_jitter), image_format=cfg.INPUT.FORMAT,
+    def _from_config(cls, cfg, is_train=True, allow=(), color_jitter=None, lsj=None):
+        return cls(is_train, augmentations=build_augmentation(cfg, is_train, allow, color_jitter, lsj), image_format=cfg.INPUT.FORMAT,
                    pixel_mean=cfg.MODEL.PIXEL_MEAN, pixel_std=cfg.MODEL.PIXEL_STD, device=cfg.MODEL.DEVICE)
 
     def draw(self, dataset_dict):
@@ -199,7 +219,11 @@ class DatasetMapper:
         job = params.job()
         if params.jitter is not None:      # the jittered crop window is the image the resize reads
             raw, job = K.color_jitter_tiles_u8([jitter_item(plain_tiles(raw), params.crop, params)])[0], params.crop_job()
-        u8 = K.train_input_u8([raw], [job], slot, self.pixel_mean, self.pixel_std, resample_coeffs, want_u8=True)[0]
+        if params.lsj is not None:
+            item = params.lsj_item(plain_tiles(raw), job[0:4])
+            u8 = K.train_input_lsj_u8([item], slot, self.pixel_mean, self.pixel_std, resample_coeffs, want_u8=True)[0]
+        else:
+            u8 = K.train_input_u8([raw], [job], slot, self.pixel_mean, self.pixel_std, resample_coeffs, want_u8=True)[0]
         d["image"] = u8.permute(2, 0, 1).contiguous()
         d["normalized"] = slot[0]       # [new_h,new_w,4] fp32: (image - mean) / std as the model's batch slot holds it
         return d

@@ -28,7 +28,7 @@ import random
 import torch
 
 from .. import kernels as K
-from .dataset_mapper import MOSAIC_KEYS, DatasetMapper, _raw_of, jitter_item, mapped_instances
+from .dataset_mapper import MOSAIC_KEYS, DatasetMapper, _raw_of, jitter_item, mapped_instances, plain_tiles
 from .transforms import TrainInputParams, resample_coeffs
 
 FILL = 114      # the canvas colour, all three channels
@@ -216,8 +216,8 @@ class DatasetMapperMosaic(DatasetMapper):
     "normalized" as DatasetMapper.__call__).  `draw(list)` is the host half: (dict, tile images, MosaicInputParams)."""
 
     @classmethod
-    def from_config(cls, cfg, is_train=True, *, color_jitter=None):
-        return cls._from_config(cfg, is_train, allow=MOSAIC_KEYS, color_jitter=color_jitter)
+    def from_config(cls, cfg, is_train=True, *, color_jitter=None, lsj=None):
+        return cls._from_config(cfg, is_train, allow=MOSAIC_KEYS, color_jitter=color_jitter, lsj=lsj)
 
     def draw(self, dataset_dicts):
         raws = [_raw_of(d) for d in dataset_dicts]
@@ -237,6 +237,7 @@ class DatasetMapperMosaic(DatasetMapper):
         transforms, drawn = self.augmentations.draw(h, w)
         params = MosaicInputParams(h, w, layout)
         params.crop, params.new_size, params.flip, params.jitter = drawn.crop, drawn.new_size, drawn.flip, drawn.jitter
+        params.scaled, params.lsj = drawn.scaled, drawn.lsj
         out.pop("annotations", None)
         out["instances"] = mapped_instances(annos, transforms, params.new_size)
         return out, raws, params
@@ -247,7 +248,13 @@ class DatasetMapperMosaic(DatasetMapper):
         nh, nw = params.new_size
         slot = torch.empty(1, nh, nw, 4, dtype=torch.float32, device=self.device)
         item = params.tiles_item(tiles)
-        if params.jitter is not None:      # the jittered window of the painted canvas (114 fill included) is the image the resize reads
+        if params.lsj is not None:      # the window of the painted canvas (or its jittered copy) through the large-scale jitter
+            lsj_item = params.lsj_item(item[0], item[1])
+            if params.jitter is not None:
+                crop = K.color_jitter_tiles_u8([jitter_item(item[0], item[1], params)])[0]
+                lsj_item = params.lsj_item(plain_tiles(crop), params.crop_job()[0:4])
+            u8 = K.train_input_lsj_u8([lsj_item], slot, self.pixel_mean, self.pixel_std, resample_coeffs, want_u8=True)[0]
+        elif params.jitter is not None:      # the jittered window of the painted canvas (114 fill included) is the image the resize reads
             crop = K.color_jitter_tiles_u8([jitter_item(item[0], item[1], params)])[0]
             u8 = K.train_input_u8([crop], [params.crop_job()], slot, self.pixel_mean, self.pixel_std, resample_coeffs, want_u8=True)[0]
         else:

@@ -265,8 +265,9 @@ class ResizeShortestEdge:
 class CropTransform:
     """fvcore CropTransform(x0, y0, w, h): the window img[y0:y0+h, x0:x0+w]; coordinates shift by (-x0, -y0)."""
 
-    def __init__(self, x0, y0, w, h):
+    def __init__(self, x0, y0, w, h, orig_w=None, orig_h=None):
         self.x0, self.y0, self.w, self.h = int(x0), int(y0), int(w), int(h)
+        self.orig_w, self.orig_h = orig_w, orig_h      # fvcore keeps them for `inverse` only
 
     def apply_image(self, img):
         """HWC array / tensor: a view of the window, as fvcore's slicing."""
@@ -341,6 +342,105 @@ class RandomFlip:
         return HFlipTransform(w) if do else NoOpTransform()
 
 
+class PadTransform:
+    """fvcore PadTransform(x0, y0, x1, y1, orig_w, orig_h, pad_value): `np.pad` of the image with the constant on its four sides
+    (left, top, right, bottom); coordinates shift by (x0, y0)."""
+
+    def __init__(self, x0, y0, x1, y1, orig_w=None, orig_h=None, pad_value=0):
+        self.x0, self.y0, self.x1, self.y1 = int(x0), int(y0), int(x1), int(y1)
+        self.orig_w, self.orig_h, self.pad_value = orig_w, orig_h, pad_value
+
+    def apply_image(self, img):
+        """HWC numpy array, as fvcore (the device path pads inside csrc/train_input.hip)."""
+        padding = ((self.y0, self.y1), (self.x0, self.x1)) + (((0, 0),) if img.ndim == 3 else ())
+        return np.pad(img, padding, mode="constant", constant_values=self.pad_value)
+
+    def apply_coords(self, coords):
+        coords[:, 0] += self.x0
+        coords[:, 1] += self.y0
+        return coords
+
+    def apply_box(self, box):
+        return _corners_to_box(self.apply_coords(_box_corners(box)))
+
+
+class ResizeScale:
+    """reference augmentation_impl.py:391-431: one `np.random.uniform(min_scale, max_scale)` draw s; the image is resized WHOLE by
+    k = min(s * target_height / h, s * target_width / w) to round(h * k) x round(w * k), halves to even (`np.round`).  Float64
+    scalars in that order of operations: the sizes are the reference's, bit for bit."""
+
+    def __init__(self, min_scale, max_scale, target_height, target_width, interp=None):
+        self.min_scale, self.max_scale = min_scale, max_scale
+        self.target_height, self.target_width, self.interp = int(target_height), int(target_width), interp
+
+    def get_transform(self, img):
+        h, w = int(img.shape[0]), int(img.shape[1])
+        s = float(np.random.uniform(self.min_scale, self.max_scale))
+        k = min(self.target_height * s / h, self.target_width * s / w)
+        return ResizeTransform(h, w, _round_half_even(h * k), _round_half_even(w * k), self.interp)
+
+    def __repr__(self):
+        return "ResizeScale(min_scale={}, max_scale={}, target_height={}, target_width={})".format(
+            self.min_scale, self.max_scale, self.target_height, self.target_width)
+
+
+def _round_half_even(x):
+    """np.round of a float64 scalar as an int: Python's round is the same IEEE round-half-to-even."""
+    return int(round(float(x)))
+
+
+class FixedSizeCropTransform(TransformList):
+    """What one draw of FixedSizeCrop decided: [CropTransform, PadTransform], with the numbers the batch kernel needs -- `window`
+    (ox, oy, ow, oh) inside the image it was drawn for, `target` (th, tw) and the `fill` byte."""
+
+    def __init__(self, crop, pad, window, target, fill):
+        super().__init__([crop, pad])
+        self.window, self.target, self.fill = tuple(int(v) for v in window), (int(target[0]), int(target[1])), int(fill)
+
+
+class FixedSizeCrop:
+    """reference augmentation_impl.py:123-161: ONE scalar `np.random.uniform(0, 1)` draw u for both axes; where the image is larger
+    than crop_size (th, tw) the window starts at round(excess * u), halves to even, and where it is smaller the right and bottom
+    are padded with pad_value up to crop_size."""
+
+    def __init__(self, crop_size, pad_value=128.0):
+        self.crop_size, self.pad_value = (int(crop_size[0]), int(crop_size[1])), pad_value
+        if not (0 <= float(pad_value) <= 255 and float(pad_value) == int(pad_value)):      # np.pad writes it into a uint8 image
+            raise ValueError("FixedSizeCrop: pad_value {} is not a uint8 value".format(pad_value))
+        self.fill = int(pad_value)
+
+    def get_transform(self, img):
+        h, w = int(img.shape[0]), int(img.shape[1])
+        th, tw = self.crop_size
+        u = float(np.random.uniform(0.0, 1.0))
+        oy, ox = _round_half_even(max(h - th, 0) * u), _round_half_even(max(w - tw, 0) * u)
+        kept_h, kept_w = min(h, th), min(w, tw)      # what slicing leaves of a th x tw window at that offset
+        crop = CropTransform(ox, oy, tw, th, w, h)
+        pad = PadTransform(0, 0, tw - kept_w, th - kept_h, kept_w, kept_h, self.pad_value)
+        return FixedSizeCropTransform(crop, pad, (ox, oy, kept_w, kept_h), (th, tw), self.fill)
+
+    def __repr__(self):
+        return "FixedSizeCrop(crop_size={}, pad_value={})".format(self.crop_size, self.pad_value)
+
+
+class LargeScaleJitter:
+    """INPUT.LSJ: the pair build_augmentation puts in ResizeShortestEdge's place (detection_utils.py:589-593) -- ResizeScale then
+    FixedSizeCrop; the defaults are the reference's.  `augmentations()` -> the two policies, in order."""
+
+    def __init__(self, min_scale=0.5, max_scale=1.6, target_height=800, target_width=800, pad_value=128.0):
+        self.min_scale, self.max_scale, self.pad_value = min_scale, max_scale, pad_value
+        self.target_height, self.target_width = int(target_height), int(target_width)
+        self.resize = ResizeScale(min_scale, max_scale, target_height, target_width)
+        self.crop = FixedSizeCrop((target_height, target_width), pad_value)
+
+    def augmentations(self):
+        return [self.resize, self.crop]
+
+    def __repr__(self):
+        return "LargeScaleJitter(min_scale={}, max_scale={}, target_height={}, target_width={}, pad_value={})".format(
+            self.min_scale, self.max_scale, self.target_height, self.target_width, self.pad_value)
+
+
 class ColorJitterTransform(NoOpTransform):
     """What one draw of ColorJitter decided: `ops`, the step ids in the order they are applied (0 brightness, 1 contrast, 2
     saturation, 3 hue), and `factors`, their fp32 factors as Python floats.  Coordinates and boxes pass unchanged; the pixels are
@@ -404,6 +504,12 @@ class TrainInputParams:
         self.new_size = (int(h), int(w))
         self.flip = False
         self.jitter = None
+        self.scaled = None      # with INPUT.LSJ: the (h, w) the crop window is resized to, WHOLE
+        self.lsj = None         # and ((ox, oy, ow, oh), (th, tw), fill): the window of it that is kept, the canvas, the fill byte
+
+    def lsj_item(self, tiles, window=None):
+        """The job of kernels.train_input_lsj_u8 on `tiles` (default window: the crop; a jittered crop is its own whole window)."""
+        return (tiles, tuple(self.crop if window is None else window), self.scaled) + self.lsj + (self.flip,)
 
     def crop_job(self):
         """The job of kernels.train_input_u8 on the jittered crop, a plain image of the window's size."""
@@ -413,17 +519,21 @@ class TrainInputParams:
         return self.crop + self.new_size + (self.flip,)
 
     def __repr__(self):
-        return "TrainInputParams(crop={}, new_size={}, flip={})".format(self.crop, self.new_size, self.flip)
+        lsj = "" if self.lsj is None else ", scaled={}, lsj={}".format(self.scaled, self.lsj)
+        return "TrainInputParams(crop={}, new_size={}, flip={}{})".format(self.crop, self.new_size, self.flip, lsj)
 
 
 class AugmentationList:
     """AugInput.apply_augmentations (reference augmentation.py:212-245) for images known by their size alone: asks each policy in
     turn for its transform, handing the next one the size the previous transform leaves.  `draw(h, w)` -> (TransformList,
     TrainInputParams).  A crop is only understood in front of the resize and a flip behind it, a colour jitter between the crop and
-    the resize (the order from_config builds)."""
+    the resize (the order from_config builds); a LargeScaleJitter stands for its two policies, and its fixed-size crop is only
+    understood between the resize and the flip."""
 
     def __init__(self, augmentations):
-        self.augmentations = list(augmentations)
+        self.augmentations = []
+        for a in augmentations:
+            self.augmentations.extend(a.augmentations() if isinstance(a, LargeScaleJitter) else [a])
 
     def draw(self, h, w):
         p = TrainInputParams(h, w)
@@ -432,13 +542,17 @@ class AugmentationList:
             t = aug.get_transform(_Shape(h, w))
             if t is None:
                 t = NoOpTransform()
-            if isinstance(t, CropTransform):
+            if isinstance(t, FixedSizeCropTransform):
+                assert p.lsj is None and not p.flip, "the fixed-size crop comes once, behind the resize and in front of the flip"
+                p.scaled, p.lsj, p.new_size = p.new_size, (t.window, t.target, t.fill), t.target
+                h, w = t.target
+            elif isinstance(t, CropTransform):
                 assert (not tfms or all(isinstance(u, NoOpTransform) for u in tfms)) and p.jitter is None, "a crop must come first"
                 p.crop = (t.x0, t.y0, t.w, t.h)
                 p.new_size = (t.h, t.w)
                 h, w = t.h, t.w
             elif isinstance(t, ResizeTransform):
-                assert not p.flip, "a resize must come before the flip"
+                assert not p.flip and p.lsj is None, "a resize must come before the flip"
                 p.new_size = (t.new_h, t.new_w)
                 h, w = t.new_h, t.new_w
             elif isinstance(t, HFlipTransform):

@@ -1806,6 +1806,104 @@ def train_input_tiles_u8(items, out, mean, std, coeffs_fn, want_u8=False, worksp
     return u8 if want_u8 else None
 
 
+TRAIN_INPUT_LSJ_LAUNCHES = []   # kernel launches of the last (up to 64) lvc_train_input_lsj_u8 calls, as the library counted them
+TRAIN_INPUT_LSJ_HEAD = 32       # int64 words in front of the tiles of a job of lvc_train_input_lsj_u8 (include/lvc_amd.h)
+TRAIN_INPUT_LSJ_FIELDS = TRAIN_INPUT_LSJ_HEAD + TRAIN_INPUT_TILES_MAX * TRAIN_INPUT_TILES_TILE
+
+
+def lsj_band(size_in, size_out, o0, on, coeffs_fn):
+    """The source rows [b0, b0 + bn) that the taps of output rows [o0, o0 + on) of the full size_in -> size_out resize touch (the
+    rows themselves when the size stays: Pillow skips the pass)."""
+    if size_in == size_out:
+        return int(o0), int(on)
+    b = coeffs_fn(size_in, size_out)[0][o0:o0 + on]
+    lo = int(b[:, 0].min())
+    return lo, int((b[:, 0] + b[:, 1]).max()) - lo
+
+
+def train_input_lsj_blob(items, coeffs_fn, u8_ptrs=None):
+    """The host half of train_input_lsj_u8, numpy only: (job table int64 [B,140], the int32 tables behind it, blob bytes, bytes of
+    the intermediate).  items: per output slot (tiles, (X0, Y0, crop_w, crop_h), (sh, sw), (ox, oy, ow, oh), (th, tw), fill, flip);
+    a tile is (image, rectangle, origin) as train_input_tiles_u8, or (pointer, H, W, sy, sx, sc) in place of the image."""
+    import numpy as np
+
+    B = len(items)
+    F, HEAD, TILE = TRAIN_INPUT_LSJ_FIELDS, TRAIN_INPUT_LSJ_HEAD, TRAIN_INPUT_TILES_TILE
+    tab = np.zeros((B, F), np.int64)
+    tables, off, tmp_off = [], B * F * 8, 0
+    for i, (tiles, (X0, Y0, cw, ch), (sh, sw), (ox, oy, ow, oh), (th, tw), fill, flip) in enumerate(items):
+        assert 1 <= len(tiles) <= TRAIN_INPUT_TILES_MAX, "an item has 1 to 9 tiles"
+        row = tab[i]
+        row[0:6] = (X0, Y0, cw, ch, sh, sw)
+        row[6] = row[9] = -1
+        for size_in, size_out, at in ((cw, sw, 6), (ch, sh, 9)):      # Pillow's tables of the FULL resize; the window selects rows of them
+            if size_in != size_out:
+                b, k, ks = coeffs_fn(size_in, size_out)
+                row[at], row[at + 1], row[at + 2] = off, off + b.nbytes, ks
+                tables += [b, k]
+                off += b.nbytes + k.nbytes
+        row[12], row[13] = int(bool(flip)), i
+        if u8_ptrs is not None:
+            row[14] = u8_ptrs[i]
+        row[16] = len(tiles)
+        row[17:24] = (ox, oy, ow, oh, th, tw, fill)
+        row[24:26] = lsj_band(ch, sh, oy, oh, coeffs_fn) if 0 <= oy and 0 < oh and oy + oh <= sh else (oy, oh)
+        row[15] = tmp_off
+        tmp_off += (int(row[25]) * int(ow) * 3 + 255) & ~255
+        for t, (img, rect, origin) in enumerate(tiles):
+            at = HEAD + t * TILE
+            row[at:at + 6] = img if isinstance(img, tuple) else (img.data_ptr(), img.shape[0], img.shape[1], img.stride(0),
+                                                                  img.stride(1), img.stride(2))
+            row[at + 6:at + 10] = rect
+            row[at + 10:at + 12] = origin
+    return tab, tables, off, tmp_off
+
+
+def train_input_lsj_u8(items, out, mean, std, coeffs_fn, want_u8=False, workspace=None, table_hook=None):
+    """INPUT.LSJ of a whole batch in two launches (csrc/train_input.hip lvc_train_input_lsj_u8), on the current stream: the crop
+    window of each item is resized whole to (sh, sw) -- Pillow's bilinear, bit for bit -- of which only the window (ox, oy, ow, oh)
+    is computed; it lands at the top left of a (th, tw) canvas filled with `fill`, mirrored when `flip`.  items: see
+    train_input_lsj_blob (tiles: uint8 device tensors of any strides; a plain image is one tile).  out [n_slots,Hp,Wp,4] fp32: item
+    i fills slot i completely ((canvas - mean) / std, zero outside the canvas).  Returns the uint8 [th,tw,3] canvases when want_u8.
+    coeffs_fn, workspace, table_hook(tab): as train_input_tiles_u8.  One host->device copy carries every table."""
+    import numpy as np
+
+    B = len(items)
+    assert B > 0
+    _req_cuda(out)
+    assert out.dim() == 4 and out.shape[3] == 4 and out.is_contiguous() and out.dtype == torch.float32 and out.shape[0] >= B
+    for it in items:
+        for img, _, _ in it[0]:
+            _req_cuda(img)
+            assert img.dtype == torch.uint8 and img.dim() == 3 and img.shape[2] == 3 and img.device == out.device
+    ws = workspace if workspace is not None else TrainInputWorkspace(out.device)
+    u8 = [torch.empty(it[4][0], it[4][1], 3, dtype=torch.uint8, device=out.device) for it in items] if want_u8 else []
+    tab, tables, off, tmp_off = train_input_lsj_blob(items, coeffs_fn, [t.data_ptr() for t in u8] if want_u8 else None)
+    if table_hook is not None:
+        table_hook(tab)
+    ws.wait_host()
+    ws.reserve(off, tmp_off)
+    hb = ws.host.numpy()
+    hb[:tab.nbytes] = tab.reshape(-1).view(np.uint8)
+    at = tab.nbytes
+    for t in tables:
+        hb[at:at + t.nbytes] = np.ascontiguousarray(t, np.int32).reshape(-1).view(np.uint8)
+        at += t.nbytes
+    ws.dev[:off].copy_(ws.host[:off], non_blocking=True)
+    ws.uploaded = torch.cuda.Event()
+    ws.uploaded.record(torch.cuda.current_stream(out.device))
+    m = (c_float * 3)(*[float(v) for v in mean])
+    s = (c_float * 3)(*[float(v) for v in std])
+    n = c_int(0)
+    rc = _lib.lib().lvc_train_input_lsj_u8(ptr(ws.host), ptr(ws.dev), c_longlong(off), c_int(B), ptr(ws.tmp),
+                                           c_longlong(ws.tmp.numel()), ptr(out), c_int(out.shape[0]), c_int(out.shape[1]),
+                                           c_int(out.shape[2]), m, s, ctypes.byref(n), _stream(out))
+    check(rc, "lvc_train_input_lsj_u8")
+    TRAIN_INPUT_LSJ_LAUNCHES.append(n.value)
+    del TRAIN_INPUT_LSJ_LAUNCHES[:-64]
+    return u8 if want_u8 else None
+
+
 COLOR_JITTER_LAUNCHES = []   # kernel launches of the last (up to 64) lvc_color_jitter_tiles_u8 calls, as the library counted them
 COLOR_JITTER_FIELDS = TRAIN_INPUT_TILES_FIELDS      # int64 words per job of lvc_color_jitter_tiles_u8 (include/lvc_amd.h)
 COLOR_JITTER_OPS = ("brightness", "contrast", "saturation", "hue")      # step ids 0..3, torchvision's
