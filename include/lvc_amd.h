@@ -622,6 +622,15 @@ int lvc_conv3x3_grouped_wgrad_nhwc(const float* x, const float* dy, const float*
  * block input of res3.0 / res4.0 / res5.0 next to conv2's output: conv3 + projection shortcut as one GEMM, resnet.py:117-160). */
 int lvc_subsample2_nhwc(const float* x, float* y, int N, int H, int W, int C, int ldy, void* stream);
 int lvc_downsum2x2_nhwc(const float* x, float* y, int N, int Hs, int Ws, int C, void* stream);
+/* nn.AvgPool2d(2) of the ResNet-D trunk (RESNETS.D: the pools of a BottleneckBlockCLIP, reference resnet.py:359, :399), csrc/avgpool.hip,
+ * NHWC fp32, C % 4 == 0, H >= 2, W >= 2, 16-byte aligned pointers; anything else returns LVC_ERR_INVALID.
+ * lvc_avgpool2_nhwc: y[n, i, j, 0..C) = (((x[2i,2j] + x[2i,2j+1]) + x[2i+1,2j]) + x[2i+1,2j+1]) * 0.25f in exactly that order, no
+ *   contraction; [N, H/2, W/2] outputs (floor: an odd last row / column is dropped); rows of ldo floats in y (0 = C; ldo % 4 == 0):
+ *   y may point at a channel slice of a wider buffer, whose other channels are not touched.
+ * lvc_avgpool2_bwd_nhwc: dx [N,H,W,C] = 0.25f * dy[n, h/2, w/2, :], zeros in a dropped odd row / column; dy [N,H/2,W/2,*] with rows of
+ *   ldi floats (0 = C). */
+int lvc_avgpool2_nhwc(const float* x, float* y, int N, int H, int W, int C, int ldo, void* stream);
+int lvc_avgpool2_bwd_nhwc(const float* dy, float* dx, int N, int H, int W, int C, int ldi, void* stream);
 int lvc_colsum_atomic(const float* x, int M, int N, int ldx, float* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------

@@ -51,3 +51,11 @@ def resnext_rcnn_fpn(depth=101, num_groups=32, width_per_group=8, num_classes=80
     cfg.merge_from_list(["MODEL.RESNETS.NUM_GROUPS", num_groups, "MODEL.RESNETS.WIDTH_PER_GROUP", width_per_group,
                          "MODEL.RESNETS.STRIDE_IN_1X1", False])
     return cfg
+
+
+def resnet_d_rcnn_fpn(depth=50, num_classes=80, device="cuda"):
+    """`base_rcnn_fpn` on the ResNet-D trunk (`MODEL.RESNETS.D: True`, the reference fork's CLIP-style RN50: DeepStem, and bottlenecks
+    whose stride is a 2x2 average pool).  STRIDE_IN_1X1 has no effect on such a trunk.  Depths 50 / 101 / 152."""
+    cfg = base_rcnn_fpn(depth=depth, num_classes=num_classes, device=device)
+    cfg.merge_from_list(["MODEL.RESNETS.D", True])
+    return cfg

@@ -30,7 +30,7 @@ class PackedConv:
     """Weights of one conv/linear layer in the kernel's layout + folded per-channel affine.
 
     w_packed: [Kpad, Kg] fp32, rows = out channel (zero rows up to a multiple of 128),
-              k = (c//32, r, s, c%32) (mode 0) or (r, 8 pixels x 4 ch) (mode 1, the 7x7 stem).
+              k = (c//32, r, s, c%32) (mode 0) or (r, 8 pixels x 4 ch) (mode 1, the stem: BasicStem's 7x7, DeepStem's 3x3).
     scale/shift: y = conv * scale + shift  (FrozenBN fold and/or bias), or None.
     """
 
@@ -227,7 +227,7 @@ def pack_conv(weight, bias=None, bn=None, stride=1, pad=0, eps=1e-5, stem=False,
     """weight: [K, C, R, S] (OIHW, the reference's state_dict layout) on the target device.
     bn: None or (weight, bias, running_mean, running_var) of a FrozenBatchNorm2d; affine: a precomputed
     `conv_affine(bias, bn, eps)` (the fold only changes when those tensors do, the weights change every step).
-    stem=True packs the 3-channel 7x7 stem for the NHWC4 "row mode" of the kernel.
+    stem=True packs a 3-channel stem layer (BasicStem's 7x7, DeepStem's 3x3 conv1) for the NHWC4 "row mode" of the kernel.
     groups > 1: weight is [K, C/groups, 3, 3], packed for the grouped kernel (`grouped_conv_check`).
     """
     _req_cuda(weight)
@@ -2763,6 +2763,92 @@ def downsum2x2(x):
     check(_lib.lib().lvc_downsum2x2_nhwc(ptr(x), ptr(y), c_int(N), c_int(H // 2), c_int(W // 2), c_int(C), _stream(x)),
           "lvc_downsum2x2_nhwc")
     return y
+
+
+def _avgpool2_pitch(t):
+    """Floats between consecutive pixels of the [N,H,W,C] tensor t (a dimension of size 1 has no say)."""
+    N, H, W, C = t.shape
+    return t.stride(2) if W > 1 else t.stride(1) if H > 1 else t.stride(0) if N > 1 else C
+
+
+def _avgpool2_is_slice(t):
+    """t [N,H,W,C] is laid out as an NHWC tensor or a channel slice of one: unit channel stride, one pitch for all three outer dimensions."""
+    N, H, W, C = t.shape
+    ld = _avgpool2_pitch(t)
+    return not t.numel() or (t.stride(3) == 1 and ld >= C and (H == 1 or t.stride(1) == W * ld) and (N == 1 or t.stride(0) == H * W * ld))
+
+
+def _avgpool2_dims(t, what):
+    """[N,H,W,C] and the row pitch of `t`, a unit-channel-stride NHWC tensor or channel slice of one; ValueError for what
+    csrc/avgpool.hip does not take (raised before any device is touched: it answers on a machine without a GPU)."""
+    if t.dim() != 4 or t.dtype != torch.float32:
+        raise ValueError("avgpool2: {} must be a float32 [N,H,W,C] tensor (got {} {})".format(what, t.dtype, tuple(t.shape)))
+    N, H, W, C = t.shape
+    ld = _avgpool2_pitch(t)
+    if C < 1 or C % 4 or ld % 4 or t.storage_offset() % 4:
+        raise ValueError("avgpool2: channels, row pitch and channel offset of {} must be multiples of 4 (16-byte loads and stores); got "
+                         "C={}, pitch {}, offset {}".format(what, C, ld, t.storage_offset()))
+    if not _avgpool2_is_slice(t):
+        raise ValueError("avgpool2: {} must be an NHWC tensor or a channel slice of one (strides {})".format(what, t.stride()))
+    return N, H, W, C, ld
+
+
+def avgpool2_into(x, out=None):
+    """nn.AvgPool2d(2) on NHWC: x [N,H,W,C] contiguous -> [N,H//2,W//2,C] (an odd last row / column is dropped), each value
+    (((x00 + x01) + x10) + x11) * 0.25f.  out: a [N,H//2,W//2,C] view with unit channel stride that receives it -- rows may be wider
+    (a channel slice of a concat buffer: the other channels are not touched).  ValueError for H < 2, W < 2, or a channel count /
+    row pitch that is no multiple of 4."""
+    N, H, W, C, ldx = _avgpool2_dims(x, "the input")
+    if H < 2 or W < 2:
+        raise ValueError("avgpool2: the map must be at least 2 x 2 (got {} x {})".format(H, W))
+    if ldx != C:
+        raise ValueError("avgpool2: the input must be contiguous")
+    if out is not None:
+        No, Ho, Wo, Co, ldo = _avgpool2_dims(out, "the output")
+        if (No, Ho, Wo, Co) != (N, H // 2, W // 2, C):
+            raise ValueError("avgpool2: output {} for input {}".format(tuple(out.shape), tuple(x.shape)))
+    _req_cuda(x, out)
+    if out is None:
+        out, ldo = torch.empty(N, H // 2, W // 2, C, device=x.device, dtype=torch.float32), C
+    if N:
+        check(_lib.lib().lvc_avgpool2_nhwc(ptr(x), ptr(out), c_int(N), c_int(H), c_int(W), c_int(C), c_int(ldo), _stream(x)),
+              "lvc_avgpool2_nhwc")
+    return out
+
+
+def avgpool2_backward(dy, H, W):
+    """dx [N,H,W,C] = 0.25 * dy[n, h // 2, w // 2, :], zeros in a dropped odd row / column.  dy: [N,H//2,W//2,C], contiguous or a
+    channel slice of a wider buffer."""
+    N, Ho, Wo, C, ldi = _avgpool2_dims(dy, "the gradient")
+    if H < 2 or W < 2 or (Ho, Wo) != (H // 2, W // 2):
+        raise ValueError("avgpool2: gradient {} for a {} x {} map".format(tuple(dy.shape), H, W))
+    _req_cuda(dy)
+    dx = torch.empty(N, H, W, C, device=dy.device, dtype=torch.float32)
+    if N:
+        check(_lib.lib().lvc_avgpool2_bwd_nhwc(ptr(dy), ptr(dx), c_int(N), c_int(H), c_int(W), c_int(C), c_int(ldi), _stream(dy)),
+              "lvc_avgpool2_bwd_nhwc")
+    return dx
+
+
+class _AvgPool2Fn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        ctx.hw = (x.shape[1], x.shape[2])
+        return avgpool2_into(x)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        if not _avgpool2_is_slice(dy) or _avgpool2_pitch(dy) % 4 or dy.storage_offset() % 4:
+            dy = dy.contiguous()      # any other view autograd hands over (permuted, expanded, odd outer strides, unaligned)
+        return avgpool2_backward(dy, *ctx.hw)
+
+
+def avgpool2_nhwc(x):
+    """`avgpool2_into` as a differentiable function of x (both pools of a BottleneckBlockCLIP under autograd)."""
+    if torch.is_grad_enabled() and x.requires_grad:
+        return _AvgPool2Fn.apply(x)
+    return avgpool2_into(x)
 
 
 def pack_conv_dgrad(weight, scale, pad, groups=1):

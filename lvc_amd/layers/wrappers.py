@@ -206,7 +206,7 @@ class _ConvFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, residual, conv, res_mode, relu):
         if conv.in_channels == 3:
-            raise NotImplementedError("training the 7x7 stem is not implemented (every shipped config has FREEZE_AT >= 1)")
+            raise NotImplementedError("training the stem's first convolution (BasicStem's 7x7, DeepStem's 3x3) is not implemented (every shipped config has FREEZE_AT >= 1)")
         if K._WGRAD_ARMED[0] and not K.in_backward():
             # a backward() that raised left queued weight gradients behind.  (A forward INSIDE a live backward -- checkpoint
             # recomputation, a hook -- keeps the queue: those gradients are still to be delivered.)

@@ -5,8 +5,10 @@ detectron2/modeling/backbone/resnet.py:101-211 (BottleneckBlock), :564-592 (Basi
 :648-763 (ResNet), :845-941 (builder), so reference checkpoints load unchanged.  Every conv+FrozenBN
 (+ReLU, +residual add) is one launch of an implicit-GEMM MFMA kernel (fp32 operands split into fp16/bf16
 planes with fp32 accumulation, fp32-accurate: DESIGN.md section 3; `LVC_CONV_ENGINE=f32` selects the exact fp32
-MFMA form); activations stay NHWC fp32 in HBM between layers.  BasicBlock / DeepStem / Dropout / CLIP / Deform variants are not selected by any
-shipped config and are not provided (the builder raises for them).  ResNeXt (`RESNETS.NUM_GROUPS` > 1, `WIDTH_PER_GROUP`): conv2 is a
+MFMA form); activations stay NHWC fp32 in HBM between layers.  BasicBlock / Dropout / Deform variants are not selected by any
+shipped config and are not provided (the builder raises for them).  ResNet-D (`RESNETS.D`, the reference's CLIP-style trunk, resnet.py:326-444,
+:595-645): `DeepStem` and `BottleneckBlockCLIP`, whose stride is a 2x2 average pool (csrc/avgpool.hip) in front of conv3 and of the
+projection shortcut; such a block runs layer by layer and takes no part in the fused block, the chains or the pre-split pair.  ResNeXt (`RESNETS.NUM_GROUPS` > 1, `WIDTH_PER_GROUP`): conv2 is a
 grouped 3x3 on csrc/conv_grouped.hip; such a block declines the paths that bake in a dense conv2 (the fused block, Winograd, the
 pre-split pair -- `fused_eligible`, `kernels.conv_route`) and keeps the pointwise ones.
 """
@@ -202,6 +204,82 @@ class BottleneckBlock(CNNBlockBase):
         return to_nchw_view(self.forward_nhwc(to_nhwc(x)))
 
 
+FUSE_POOLED_PROJECTION = True       # conv3 + the pooled projection shortcut of a stride-2 BottleneckBlockCLIP as one GEMM (`can_fuse_projection`)
+
+
+class BottleneckBlockCLIP(CNNBlockBase):
+    """The ResNet-D / CLIP bottleneck (reference resnet.py:326-444): all three convs have stride 1 -- `stride_in_1x1` is accepted and
+    ignored, as there -- and the block's stride is nn.AvgPool2d(stride) in front of conv3 and of the shortcut conv, which exists when
+    in != out or stride > 1.  conv1 -> ReLU -> conv2 -> ReLU -> pool -> conv3 -> + shortcut(pool(x)) -> ReLU.  Parameters: conv1, conv2,
+    conv3, shortcut and their norms (the pools have none), so reference checkpoints load strictly."""
+
+    def __init__(self, in_channels, out_channels, *, bottleneck_channels, stride=1, num_groups=1, norm="BN",
+                 stride_in_1x1=False, dilation=1):
+        super().__init__(in_channels, out_channels, stride)
+        if dilation != 1:
+            raise NotImplementedError("dilated bottlenecks (MODEL.RESNETS.RES5_DILATION != 1) are not built")
+        if num_groups != 1:
+            raise NotImplementedError("MODEL.RESNETS.D with MODEL.RESNETS.NUM_GROUPS > 1 is not built")
+        if stride not in (1, 2):
+            raise NotImplementedError("BottleneckBlockCLIP: the average pool is built for stride 1 and 2 (got {})".format(stride))
+        if in_channels != out_channels or stride > 1:
+            self.shortcut = Conv2d(in_channels, out_channels, kernel_size=1, stride=1, bias=False, norm=get_norm(norm, out_channels))
+        else:
+            self.shortcut = None
+        self.conv1 = Conv2d(in_channels, bottleneck_channels, kernel_size=1, bias=False,
+                            norm=get_norm(norm, bottleneck_channels), activation=F.relu_)
+        self.conv2 = Conv2d(bottleneck_channels, bottleneck_channels, kernel_size=3, padding=1, bias=False,
+                            norm=get_norm(norm, bottleneck_channels), activation=F.relu_)
+        self.conv3 = Conv2d(bottleneck_channels, out_channels, kernel_size=1, bias=False, norm=get_norm(norm, out_channels))
+        for layer in [self.conv1, self.conv2, self.conv3, self.shortcut]:
+            if layer is not None:
+                weight_init.c2_msra_fill(layer)
+
+    _grad_free = BottleneckBlock._grad_free
+    _fused_projection = BottleneckBlock._fused_projection      # [s3 W3 | s_s W_s] and b3 + b_s: the packing of FUSE_STRIDED_PROJECTION
+
+    def _pool(self, x):
+        """avgpool / avgpool_sc of the reference: AvgPool2d(1) is the identity and launches nothing."""
+        return K.avgpool2_nhwc(x) if self.stride == 2 else x
+
+    def can_fuse_projection(self, x=None):
+        """Stride-2 blocks in gradient-free passes (the condition of `BottleneckBlock.can_fuse_projection`): pool(conv2 output) and
+        pool(x) are written into the two channel slices of one buffer, and conv3 + shortcut + ReLU is one pointwise GEMM over it.
+        Gradient-free covers the block's own parameters (`_grad_free`) and, given the input x, x itself: a frozen block fed an input
+        that requires grad must still take the autograd path."""
+        if x is not None and torch.is_grad_enabled() and x.requires_grad:
+            return False
+        return (FUSE_POOLED_PROJECTION and K.FUSE_PROJECTION and K.CONV_ENGINE == "bf16x3" and self._grad_free() and self.stride == 2
+                and (self.conv2.out_channels + self.in_channels) % 32 == 0 and self.conv2.out_channels % 4 == 0 and self.in_channels % 4 == 0)
+
+    def fused_eligible(self):
+        """Never the one-launch res2 block (csrc/conv_bneck.hip has no pool between conv2 and conv3)."""
+        return False
+
+    def fused(self):
+        return None
+
+    def chain_to(self, nxt, fused_projection):
+        """Never a conv3 -> next conv1 chain: `ResNet.forward_nhwc` walks these blocks one `forward_nhwc` at a time."""
+        return None
+
+    def forward_nhwc(self, x):
+        t = self.conv2.forward_nhwc(self.conv1.forward_nhwc(x))
+        if self.can_fuse_projection(x):
+            N, H, W, _ = x.shape
+            cb = self.conv2.out_channels
+            concat = torch.empty(N, H // 2, W // 2, cb + self.in_channels, device=x.device, dtype=torch.float32)
+            K.avgpool2_into(t, concat[..., :cb])
+            K.avgpool2_into(x, concat[..., cb:])
+            return K.conv2d_nhwc(concat, self._fused_projection(), relu=True)
+        shortcut = self.shortcut.forward_nhwc(self._pool(x)) if self.shortcut is not None else x
+        # conv3 + FrozenBN + residual add + ReLU in one epilogue (reference resnet.py:434-444)
+        return self.conv3.forward_nhwc(self._pool(t), residual=shortcut, res_mode=1, relu=True)
+
+    def forward(self, x):
+        return to_nchw_view(self.forward_nhwc(to_nhwc(x)))
+
+
 class BasicStem(CNNBlockBase):
     def __init__(self, in_channels=3, out_channels=64, norm="BN"):
         super().__init__(in_channels, out_channels, 4)
@@ -221,6 +299,34 @@ class BasicStem(CNNBlockBase):
         if second is not None:
             second(y.shape).copy_(y)
         return y
+
+    def forward(self, x):
+        return to_nchw_view(self.forward_nhwc(_as_nhwc4(x)))
+
+
+class DeepStem(CNNBlockBase):
+    """The ResNet-D stem (reference resnet.py:595-645): 3x3 stride 2 to C/2, 3x3 to C/2, 3x3 to C, each with its norm and ReLU, then the
+    3x3 stride-2 max-pool; stride 4, parameters conv1 / conv2 / conv3.  conv1 reads the NHWC4 image (the stem packing, `C <= 4, S <= 8`);
+    conv2 / conv3 are ordinary layers on whatever `kernels.conv_route` gives them.  As with `BasicStem`, a trainable conv1 raises
+    (MODEL.BACKBONE.FREEZE_AT >= 1)."""
+
+    def __init__(self, in_channels=3, out_channels=64, norm="BN"):
+        super().__init__(in_channels, out_channels, 4)
+        self.in_channels = in_channels
+        mid = out_channels // 2
+        if in_channels != 3 or mid % 32:
+            raise NotImplementedError("DeepStem: 3 input channels and MODEL.RESNETS.STEM_OUT_CHANNELS a multiple of 64 (got {} -> {})".format(
+                in_channels, out_channels))
+        self.conv1 = Conv2d(in_channels, mid, kernel_size=3, stride=2, padding=1, bias=False, norm=get_norm(norm, mid), activation=F.relu_)
+        self.conv2 = Conv2d(mid, mid, kernel_size=3, stride=1, padding=1, bias=False, norm=get_norm(norm, mid), activation=F.relu_)
+        self.conv3 = Conv2d(mid, out_channels, kernel_size=3, stride=1, padding=1, bias=False, norm=get_norm(norm, out_channels),
+                            activation=F.relu_)
+        weight_init.c2_msra_fill(self.conv1)      # (the reference fills conv1 only)
+
+    def forward_nhwc(self, x4):
+        """x4: [N,H,W,4] (RGB + zero slot)."""
+        y = self.conv3.forward_nhwc(self.conv2.forward_nhwc(self.conv1.forward_nhwc(x4)))
+        return K.maxpool2d_nhwc(y, 3, 2, 1)
 
     def forward(self, x):
         return to_nchw_view(self.forward_nhwc(_as_nhwc4(x)))
@@ -345,8 +451,13 @@ def build_resnet_backbone(cfg, input_shape):
     R = cfg.MODEL.RESNETS
     norm = R.NORM
     unsupported = []
-    if R.get("D", False):
-        unsupported.append("RESNETS.D (DeepStem/CLIP blocks)")
+    resnet_d = bool(R.get("D", False))
+    if resnet_d and R.NUM_GROUPS > 1:
+        unsupported.append("RESNETS.D with RESNETS.NUM_GROUPS = {} (grouped CLIP blocks)".format(R.NUM_GROUPS))
+    if resnet_d and R.DEPTH in (18, 34):
+        unsupported.append("RESNETS.D with RESNETS.DEPTH = {}".format(R.DEPTH))
+    if resnet_d and R.RES5_DILATION != 1:
+        unsupported.append("RESNETS.D with RESNETS.RES5_DILATION = {}".format(R.RES5_DILATION))
     if R.get("DROPOUT", 0):
         unsupported.append("RESNETS.DROPOUT")
     if any(R.DEFORM_ON_PER_STAGE):
@@ -360,7 +471,7 @@ def build_resnet_backbone(cfg, input_shape):
         unsupported.append("RESNETS.NORM = '{}' (the trunk implements 'FrozenBN'; GN is built for FPN.NORM and ROI_BOX_HEAD.NORM)".format(norm))
     if unsupported:
         raise NotImplementedError("not on the path of any shipped config: " + ", ".join(unsupported))
-    stem = BasicStem(in_channels=input_shape.channels, out_channels=R.STEM_OUT_CHANNELS, norm=norm)
+    stem = (DeepStem if resnet_d else BasicStem)(in_channels=input_shape.channels, out_channels=R.STEM_OUT_CHANNELS, norm=norm)
     freeze_at = cfg.MODEL.BACKBONE.FREEZE_AT
     out_features = R.OUT_FEATURES
     bottleneck_channels = R.NUM_GROUPS * R.WIDTH_PER_GROUP
@@ -371,7 +482,7 @@ def build_resnet_backbone(cfg, input_shape):
     for idx, stage_idx in enumerate(range(2, max_stage_idx + 1)):
         first_stride = 1 if idx == 0 else 2
         blocks = ResNet.make_stage(
-            block_class=BottleneckBlock, num_blocks=num_blocks_per_stage[idx],
+            block_class=BottleneckBlockCLIP if resnet_d else BottleneckBlock, num_blocks=num_blocks_per_stage[idx],
             stride_per_block=[first_stride] + [1] * (num_blocks_per_stage[idx] - 1),
             in_channels=in_channels, out_channels=out_channels, norm=norm,
             bottleneck_channels=bottleneck_channels, stride_in_1x1=R.STRIDE_IN_1X1, dilation=1, num_groups=R.NUM_GROUPS)
