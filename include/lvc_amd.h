@@ -440,6 +440,42 @@ int lvc_rpn_proposals(const float* const* logits, const int* ld_logit, const flo
                       float* out_boxes, float* out_logits, int* d_out_count, void* workspace,
                       long long workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * RetinaNet.inference_single_image, the loop over the levels (detectron2/modeling/meta_arch/retinanet.py:327-353,
+ * anchor_generator.py:157-178, box_regression.py:73-110), for all images and levels in one call (csrc/retinanet.hip).
+ *   per level l (arrays of L [host] entries):
+ *     logits[l]  device ptr: logit of class k of anchor a at pixel p of image b = logits[l][(b*H*W + p)*ld_logit[l] + a*K + k]
+ *     deltas[l]  device ptr: delta c of anchor a                                = deltas[l][(b*H*W + p)*ld_delta[l] + a*4 + c]
+ *       (ld_logit[l] >= A*K, ld_delta[l] >= 4*A: rows may carry padding channels, which are never read as entries)
+ *     cell_anchors[l] device ptr [A,4]; Hs, Ws, strides; anchor_offset = MODEL.ANCHOR_GENERATOR.OFFSET
+ *   Per (image, level), with flat index i = (p*A + a)*K + k: the min(topk, H*W*A) entries with the largest logit (equal logits:
+ *   lower i first), of those the ones with sigmoid(logit) > score_thresh in fp32; class = i % K, anchor = i / K,
+ *   box = apply_deltas(deltas[anchor], grid anchor; weights wx..wh, scale_clamp), not clipped.
+ *   Outputs (rows = L*topk per image): out_boxes [B,rows,4], out_scores [B,rows], out_classes [B,rows] int32, out_index [B,rows]
+ *   int32 (= i) -- an image's candidates level after level, densely, inside a level in selection order; d_count[b] = their
+ *   number; rows past it are zero.  Bit-identical between runs.  topk <= 2048; H*W*A*K < 2^31 per level.
+ *   max_survivors: capacity of the per-(image, level) list of entries above the threshold (H*W*A*K cannot overflow); an overflow
+ *   ORs 4 into *d_status [1] int32 (never cleared here) and leaves the outputs of the call unspecified.
+ *   One pass over the logits; no host read.
+ */
+long long lvc_retinanet_select_workspace_bytes(int B, int L, int A, int K, const int* Hs, const int* Ws, int topk,
+                                               int max_survivors);
+int lvc_retinanet_select(const float* const* logits, const int* ld_logit, const float* const* deltas, const int* ld_delta,
+                         const float* const* cell_anchors, const int* Hs, const int* Ws, const int* strides,
+                         float anchor_offset, int L, int A, int K, int B, int topk, float score_thresh, float wx, float wy,
+                         float ww, float wh, float scale_clamp, int max_survivors, float* out_boxes, float* out_scores,
+                         int* out_classes, int* out_index, int* d_count, int* d_status, void* workspace,
+                         long long workspace_bytes, void* stream);
+
+/* Gather of the rows an NMS kept, with detector_postprocess (detectron2/modeling/postprocessing.py:10-79, box fields):
+ *   boxes [B,Nmax,4], scores / classes / rows [B,Nmax] (rows: any int32 carried along, e.g. out_index of lvc_retinanet_select),
+ *   keep [B,Nmax] int32 + d_num_keep [B] as lvc_batched_nms writes them; the first min(d_num_keep[b], topk) kept rows, in order.
+ *   d_post NULL or [B,4] fp32 = (scale_x, scale_y, out_h, out_w): scale, clip to the output size, drop empty boxes.
+ *   Outputs [B,topk,...], zero past d_out_count[b]. */
+int lvc_gather_detections(const float* boxes, const float* scores, const int* classes, const int* rows, const int* keep,
+                          const int* d_num_keep, int B, int Nmax, int topk, const float* d_post, float* out_boxes,
+                          float* out_scores, int* out_classes, int* out_rows, int* d_out_count, void* stream);
+
 /* assign_boxes_to_levels + convert_boxes_to_pooler_format (detectron2/modeling/poolers.py:23-59, 69-96).
  * boxes [B,R,4] -> levels [B*R] int32 (offset from min_level), rois [B*R,5] (may be NULL). */
 int lvc_assign_levels_rois(const float* boxes, int B, int R, int min_level, int max_level, int canonical_box_size,

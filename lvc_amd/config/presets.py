@@ -59,3 +59,21 @@ def resnet_d_rcnn_fpn(depth=50, num_classes=80, device="cuda"):
     cfg = base_rcnn_fpn(depth=depth, num_classes=num_classes, device=device)
     cfg.merge_from_list(["MODEL.RESNETS.D", True])
     return cfg
+
+
+def retinanet_r_fpn(depth=50, num_classes=80, device="cuda"):
+    """RetinaNet on a ResNet-FPN trunk: what detectron2's `Base-RetinaNet.yaml` sets on top of the defaults (the pyramid over
+    res3..res5 with P6 / P7 from res5, three anchor scales per octave and level).  Inference only."""
+    cfg = get_cfg()
+    M = cfg.MODEL
+    M.META_ARCHITECTURE = "RetinaNet"
+    M.DEVICE = device
+    M.MASK_ON = False
+    M.BACKBONE.NAME = "build_retinanet_resnet_fpn_backbone"
+    M.RESNETS.OUT_FEATURES = ["res3", "res4", "res5"]
+    M.RESNETS.DEPTH = depth
+    M.FPN.IN_FEATURES = ["res3", "res4", "res5"]
+    M.ANCHOR_GENERATOR.SIZES = [[x, x * 2 ** (1.0 / 3), x * 2 ** (2.0 / 3)] for x in [32, 64, 128, 256, 512]]
+    M.ANCHOR_GENERATOR.ASPECT_RATIOS = [[0.5, 1.0, 2.0]]
+    M.RETINANET.NUM_CLASSES = num_classes
+    return cfg

@@ -15,9 +15,9 @@
 // (level-major candidate order, row-major (roi, class) order, score-sorted keep) are reproduced by
 // ORDERED compaction (block scan), never by atomics.
 #include "common.h"
+#include "select_common.h"
 #include <stdlib.h>
 
-typedef unsigned long long u64;
 
 extern "C" int lvc_batched_nms(const float*, const float*, const int*, const int*, int, int, double, int,
                                int*, int*, void*, long long, void*);
@@ -25,12 +25,6 @@ extern "C" long long lvc_batched_nms_workspace_bytes(int, int);
 
 #define MAXL 8
 
-__device__ __forceinline__ unsigned int desc_key(float f) {
-  if (f == 0.f) f = 0.f;
-  unsigned int u = __float_as_uint(f);
-  u ^= (u >> 31) ? 0xFFFFFFFFu : 0x80000000u;
-  return ~u;
-}
 
 // block-wide exclusive scan of one int per thread (1024 threads = 16 waves); returns exclusive prefix,
 // *total gets the block sum.  `sh` must hold >= 17 ints.
@@ -55,21 +49,6 @@ __device__ __forceinline__ int block_excl_scan_1024(int v, int* sh, int* total) 
   return sh[wave] + x - v;
 }
 
-template <typename T>
-__device__ __forceinline__ void bitonic_sort_lds(T* keys, int npad) {
-  for (int k = 2; k <= npad; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int t = threadIdx.x; t < npad / 2; t += blockDim.x) {
-        int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-        int hi = lo | j;
-        bool up = (lo & k) == 0;
-        T a = keys[lo], b = keys[hi];
-        if ((a > b) == up) { keys[lo] = b; keys[hi] = a; }
-      }
-      __syncthreads();
-    }
-  }
-}
 
 // =====================================================================================
 // RPN step 1: per (image, level) top-k of the objectness logits, sorted descending (ties: lower index).
@@ -86,29 +65,6 @@ struct RpnLevels {
   int L, A;
 };
 
-// first 256 threads: digit d with  sum(h[0..d-1]) < krem <= sum(h[0..d]);  returns through sh[8] = d, sh[9] = sum(h[0..d-1])
-__device__ __forceinline__ void find_digit(const int* __restrict__ h, int krem, int* sh) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int x = 0, incl = 0;
-  if (tid < 256) {
-    x = h[tid];
-    incl = x;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int t = __shfl_up(incl, o);
-      if (lane >= o) incl += t;
-    }
-    if (lane == 63) sh[wave] = incl;
-  }
-  __syncthreads();
-  if (tid < 256) {
-    int off = 0;
-    for (int w = 0; w < wave; ++w) off += sh[w];
-    incl += off;
-    if (incl - x < krem && krem <= incl) { sh[8] = tid; sh[9] = incl - x; }
-  }
-  __syncthreads();
-}
 
 #define TOPK_PAD 2048
 __global__ __launch_bounds__(1024) void rpn_topk_kernel(RpnLevels lv, int topk, unsigned int* __restrict__ wkeys,
@@ -342,22 +298,6 @@ __global__ __launch_bounds__(1024) void rpn_topk_final_kernel(RpnLevels lv, int 
   }
 }
 
-// =====================================================================================
-// shared decode (Box2BoxTransform.apply_deltas, box_regression.py:73-110)
-// =====================================================================================
-__device__ __forceinline__ void apply_deltas(float bx1, float by1, float bx2, float by2, float d0, float d1,
-                                             float d2, float d3, float wx, float wy, float ww, float wh,
-                                             float scale_clamp, float* o) {
-  const float widths = bx2 - bx1, heights = by2 - by1;
-  const float ctr_x = bx1 + 0.5f * widths, ctr_y = by1 + 0.5f * heights;
-  const float dx = d0 / wx, dy = d1 / wy;
-  float dw = d2 / ww, dh = d3 / wh;
-  dw = dw > scale_clamp ? scale_clamp : dw;  // torch.clamp(max=): NaN stays NaN
-  dh = dh > scale_clamp ? scale_clamp : dh;
-  const float pcx = dx * widths + ctr_x, pcy = dy * heights + ctr_y;
-  const float pw = expf(dw) * widths, ph = expf(dh) * heights;
-  o[0] = pcx - 0.5f * pw; o[1] = pcy - 0.5f * ph; o[2] = pcx + 0.5f * pw; o[3] = pcy + 0.5f * ph;
-}
 __device__ __forceinline__ float clampf(float v, float lo, float hi) {  // torch clamp_(min,max)
   v = v < lo ? lo : v;
   return v > hi ? hi : v;
@@ -862,6 +802,23 @@ extern "C" int lvc_fast_rcnn_inference(const float* cls_logits, int ld_cls, cons
   if (rc) return rc;
   hipLaunchKernelGGL(det_gather_kernel, dim3(B), dim3(256), 0, st, cboxes, cscores, cclass, crow, keep, nk,
                      max_candidates, topk, d_post, out_boxes, out_scores, out_classes, out_rows, d_out_count);
+  LVC_CHECK_LAUNCH();
+  return LVC_OK;
+}
+
+// The gather above as an entry of its own (RetinaNet: candidates from lvc_retinanet_select, keep lists from lvc_batched_nms):
+// rows keep[b][0 .. min(num_keep[b], topk)) of an image's [Nmax] candidate rows, in that order, through detector_postprocess when
+// d_post [B,4] = (scale_x, scale_y, out_h, out_w) is given (scale, clip, drop empty boxes); rows past the count are zero.
+extern "C" int lvc_gather_detections(const float* boxes, const float* scores, const int* classes, const int* rows,
+                                     const int* keep, const int* d_num_keep, int B, int Nmax, int topk, const float* d_post,
+                                     float* out_boxes, float* out_scores, int* out_classes, int* out_rows, int* d_out_count,
+                                     void* stream) {
+  LVC_CHECK_ARG(B > 0 && Nmax > 0 && topk > 0, "bad B / Nmax / topk");
+  LVC_CHECK_ARG(boxes && scores && classes && rows && keep && d_num_keep && out_boxes && out_scores && out_classes && out_rows &&
+                    d_out_count, "null pointer");
+  LVC_CHECK_ARG(((uintptr_t)boxes & 15) == 0 && ((uintptr_t)out_boxes & 15) == 0, "box pointers must be 16-byte aligned");
+  hipLaunchKernelGGL(det_gather_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, boxes, scores, classes, rows, keep,
+                     d_num_keep, Nmax, topk, d_post, out_boxes, out_scores, out_classes, out_rows, d_out_count);
   LVC_CHECK_LAUNCH();
   return LVC_OK;
 }

@@ -1537,6 +1537,111 @@ def fast_rcnn_inference(cls_logits, deltas, proposals, prop_count, image_sizes, 
     return ob, osc, ocl, orow, cnt
 
 
+RETINANET_MAX_SURVIVORS = 1 << 16     # default capacity of the per-(image, level) list of entries above the score threshold
+RETINANET_OVERFLOW = 4                # the status bit lvc_retinanet_select raises when such a list overflows
+
+
+def retinanet_select(logits, deltas, cell_anchors, strides, anchor_offset, num_classes, topk, score_thresh,
+                     box_weights=(1.0, 1.0, 1.0, 1.0), max_survivors=RETINANET_MAX_SURVIVORS, status=None):
+    """The per-level candidate selection of RetinaNet's inference (reference retinanet.py:327-353) for all images and levels in one
+    call (csrc/retinanet.hip): one pass over the logits, no host read.
+
+    logits[l]: [B,H,W,>=A*K] view whose channel a*K + k holds the logit of class k of anchor a; deltas[l]: [B,H,W,>=4A] view whose
+    channel a*4 + c holds delta c of anchor a.  Both may be channel slices of wider NHWC tensors (padded rows).
+    cell_anchors[l]: [A,4] device tensors.  max_survivors: capacity of the per-(image, level) list of entries above the threshold;
+    None = H*W*A*K (cannot overflow).  An overflow sets `RETINANET_OVERFLOW` in the status word and leaves this call's outputs
+    unspecified: the caller that reads the status repeats the call with None (`retinanet_select_checked`, or the model's
+    `run_with_fallbacks`).
+    Returns (boxes [B,L*topk,4], scores [B,L*topk], classes [B,L*topk] int32, index [B,L*topk] int32 -- the flat index
+    (p*A + a)*K + k inside the level --, count [B] int32, status [1] int32); rows past count are zero."""
+    L = len(logits)
+    if not (L == len(deltas) == len(cell_anchors) == len(strides) and 1 <= L <= 8):
+        raise ValueError("retinanet_select: 1..8 levels with logits, deltas, cell anchors and a stride each")
+    _req_cuda(*logits, *deltas, *cell_anchors, status)
+    B, A, K = logits[0].shape[0], cell_anchors[0].shape[0], int(num_classes)
+    dev = logits[0].device
+    if not (0 < topk <= 2048):
+        raise ValueError("retinanet_select: topk must be in 1..2048 (got {})".format(topk))
+    if any(c.shape != (A, 4) for c in cell_anchors):
+        raise NotImplementedError("retinanet_select: a different number of anchors per level is not built")
+    Hs = [t.shape[1] for t in logits]
+    Ws = [t.shape[2] for t in logits]
+    for t, d, h, w in zip(logits, deltas, Hs, Ws):
+        for u, need in ((t, A * K), (d, 4 * A)):
+            if not (u.dtype == torch.float32 and u.dim() == 4 and u.shape[:3] == (B, h, w) and u.shape[3] >= need and u.stride(3) == 1
+                    and u.stride(1) == w * u.stride(2) and u.stride(0) == h * w * u.stride(2)):
+                raise ValueError("retinanet_select: need fp32 NHWC channel slices [B,H,W,>=A*K] / [B,H,W,>=4A] of dense pixel rows")
+        if h * w * A * K >= (1 << 31) or h * w * t.stride(2) >= (1 << 31):
+            raise ValueError("retinanet_select: a level with 2^31 entries per image")
+    full = max(h * w * A * K for h, w in zip(Hs, Ws))
+    max_survivors = full if max_survivors is None else max(1, min(int(max_survivors), full))
+    if status is None:
+        status = new_status(dev)
+    VP, IP = c_void_p * L, c_int * L
+    lp = VP(*[t.data_ptr() for t in logits])
+    dp = VP(*[t.data_ptr() for t in deltas])
+    anchors = [t.contiguous().float() for t in cell_anchors]
+    ap = VP(*[t.data_ptr() for t in anchors])
+    ldl = IP(*[t.stride(2) for t in logits])
+    ldd = IP(*[t.stride(2) for t in deltas])
+    hs, ws_, st = IP(*Hs), IP(*Ws), IP(*[int(s) for s in strides])
+    lib = _lib.lib()
+    lib.lvc_retinanet_select_workspace_bytes.restype = c_longlong
+    nbytes = lib.lvc_retinanet_select_workspace_bytes(c_int(B), c_int(L), c_int(A), c_int(K), hs, ws_, c_int(topk), c_int(max_survivors))
+    if nbytes < 0:
+        raise ValueError("retinanet_select: shapes outside the kernel's range")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    rows = L * topk
+    boxes = torch.empty(B, rows, 4, device=dev, dtype=torch.float32)
+    scores = torch.empty(B, rows, device=dev, dtype=torch.float32)
+    classes = torch.empty(B, rows, device=dev, dtype=torch.int32)
+    index = torch.empty(B, rows, device=dev, dtype=torch.int32)
+    count = torch.empty(B, device=dev, dtype=torch.int32)
+    wx, wy, ww, wh = [float(v) for v in box_weights]
+    rc = lib.lvc_retinanet_select(lp, ldl, dp, ldd, ap, hs, ws_, st, c_float(anchor_offset), c_int(L), c_int(A), c_int(K), c_int(B),
+                                  c_int(topk), c_float(score_thresh), c_float(wx), c_float(wy), c_float(ww), c_float(wh),
+                                  c_float(SCALE_CLAMP), c_int(max_survivors), ptr(boxes), ptr(scores), ptr(classes), ptr(index),
+                                  ptr(count), ptr(status), ptr(ws), c_longlong(nbytes), _stream(boxes))
+    check(rc, "lvc_retinanet_select")
+    return boxes, scores, classes, index, count, status
+
+
+def retinanet_select_checked(*args, max_survivors=RETINANET_MAX_SURVIVORS, **kw):
+    """`retinanet_select` for callers outside a model pass: reads the status word (ONE device->host read) and, where a list
+    overflowed, repeats the call with the full capacity.  Same return values; the status word comes back clear of the bit."""
+    out = retinanet_select(*args, max_survivors=max_survivors, **kw)
+    if max_survivors is not None and int(out[5].item()) & RETINANET_OVERFLOW:
+        _log_once("retinanet_overflow", "more than %d entries above the score threshold on one (image, level): the selection is "
+                  "repeated with the list sized for H*W*A*K", max_survivors)
+        kw.pop("status", None)
+        out = retinanet_select(*args, max_survivors=None, **kw)
+    return out
+
+
+def gather_detections(boxes, scores, classes, rows, keep, num_keep, topk, post=None):
+    """The rows an NMS kept (`batched_nms_batch`), in its order, at most topk per image, through detector_postprocess when
+    post [B,4] fp32 = (scale_x, scale_y, out_h, out_w) is given.  boxes [B,Nmax,4], scores / classes / rows [B,Nmax].
+    Returns (boxes [B,topk,4], scores, classes int32, rows int32 [B,topk], count [B] int32); rows past count are zero; no sync."""
+    _req_cuda(boxes, scores, classes, rows, keep, num_keep, post)
+    B, Nmax = scores.shape
+    dev = boxes.device
+    for t in (classes, rows, keep):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.shape == (B, Nmax)
+    assert boxes.is_contiguous() and scores.is_contiguous() and boxes.dtype == scores.dtype == torch.float32 and boxes.shape == (B, Nmax, 4)
+    assert num_keep.dtype == torch.int32 and num_keep.numel() == B
+    if post is not None:
+        assert post.dtype == torch.float32 and post.is_contiguous() and post.shape == (B, 4)
+    ob = torch.empty(B, topk, 4, device=dev, dtype=torch.float32)
+    osc = torch.empty(B, topk, device=dev, dtype=torch.float32)
+    ocl = torch.empty(B, topk, device=dev, dtype=torch.int32)
+    orow = torch.empty(B, topk, device=dev, dtype=torch.int32)
+    cnt = torch.empty(B, device=dev, dtype=torch.int32)
+    check(_lib.lib().lvc_gather_detections(ptr(boxes), ptr(scores), ptr(classes), ptr(rows), ptr(keep), ptr(num_keep), c_int(B), c_int(Nmax),
+                                           c_int(topk), ptr(post), ptr(ob), ptr(osc), ptr(ocl), ptr(orow), ptr(cnt), _stream(boxes)),
+          "lvc_gather_detections")
+    return ob, osc, ocl, orow, cnt
+
+
 # --------------------------------------------------------------------------- trunk elementwise
 def preprocess_into(image, out_slot, mean, std):
     """image: CHW (3,h,w) float32 or uint8 device tensor; out_slot: [Hp,Wp,4] view of the batch tensor.
@@ -2415,6 +2520,12 @@ def relu_backward(dy, y):
     out = torch.empty_like(dy)
     check(_lib.lib().lvc_relu_backward(ptr(dy), ptr(y), c_longlong(dy.numel()), ptr(out), _stream(dy)), "lvc_relu_backward")
     return out
+
+
+def relu(x):
+    """max(x, 0) as a pass of its own (where no producer's epilogue can take it: LastLevelP6P7 outputs p6 un-rectified and feeds
+    relu(p6) to p7).  One launch of lvc_relu_backward with dy = y = x, which writes x where x > 0 and 0 elsewhere."""
+    return relu_backward(x, x)
 
 
 def colsum(x):

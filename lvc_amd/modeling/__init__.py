@@ -1,8 +1,9 @@
 """`lvc_amd.modeling`: the reference's registry surface (lvc/modeling/__init__.py) on gfx950 kernels."""
 from .anchor_generator import ANCHOR_GENERATOR_REGISTRY, DefaultAnchorGenerator, build_anchor_generator
-from .backbone import BACKBONE_REGISTRY, FPN, Backbone, ResNet, build_backbone, build_resnet_backbone, build_resnet_fpn_backbone
+from .backbone import (BACKBONE_REGISTRY, FPN, Backbone, LastLevelP6P7, ResNet, build_backbone, build_resnet_backbone, build_resnet_fpn_backbone,
+                       build_retinanet_resnet_fpn_backbone)
 from .box_regression import Box2BoxTransform
-from .meta_arch import META_ARCH_REGISTRY, GeneralizedRCNN, GeneralizedRCNNRegOnly, ProposalNetwork, build_model
+from .meta_arch import META_ARCH_REGISTRY, GeneralizedRCNN, GeneralizedRCNNRegOnly, ProposalNetwork, RetinaNet, RetinaNetHead, build_model
 from .poolers import ROIPooler
 from .postprocessing import detector_postprocess
 from .proposal_generator import PROPOSAL_GENERATOR_REGISTRY, RPN, RPN_HEAD_REGISTRY, StandardRPNHead, build_proposal_generator

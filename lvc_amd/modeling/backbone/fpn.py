@@ -51,6 +51,30 @@ class LastLevelMaxPool(nn.Module):
         return [to_nchw_view(t) for t in self.forward_nhwc(to_nhwc(x))]
 
 
+class LastLevelP6P7(nn.Module):
+    """p6 = conv3x3 stride 2 on `in_feature`, p7 = the same conv on relu(p6) (reference fpn.py:180-198; RetinaNet's two extra
+    levels).  Both are ordinary `Conv2d` layers: whatever entry `kernels.conv_route` gives a 3x3 / stride 2 / pad 1 layer."""
+
+    def __init__(self, in_channels, out_channels, in_feature="res5"):
+        super().__init__()
+        self.num_levels = 2
+        self.in_feature = in_feature
+        self.p6 = Conv2d(in_channels, out_channels, 3, 2, 1)
+        self.p7 = Conv2d(out_channels, out_channels, 3, 2, 1)
+        for module in [self.p6, self.p7]:
+            weight_init.c2_xavier_fill(module)
+
+    def forward_nhwc(self, x):
+        p6 = self.p6.forward_nhwc(x)
+        # p6 itself is an output, un-rectified: relu(p6) is its own pass over that small map
+        return [p6, self.p7.forward_nhwc(K.relu(p6))]
+
+    def forward(self, x):
+        from ...layers.layout import to_nhwc
+
+        return [to_nchw_view(t) for t in self.forward_nhwc(to_nhwc(x))]
+
+
 MERGE_OUTPUT_CONVS = True      # the 3x3 output convs of all levels as one launch (FPN.forward_nhwc)
 
 
@@ -138,3 +162,14 @@ def build_resnet_fpn_backbone(cfg, input_shape: ShapeSpec):
     bottom_up = build_resnet_backbone(cfg, input_shape)
     return FPN(bottom_up=bottom_up, in_features=cfg.MODEL.FPN.IN_FEATURES, out_channels=cfg.MODEL.FPN.OUT_CHANNELS,
                norm=cfg.MODEL.FPN.NORM, top_block=LastLevelMaxPool(), fuse_type=cfg.MODEL.FPN.FUSE_TYPE)
+
+
+@BACKBONE_REGISTRY.register()
+def build_retinanet_resnet_fpn_backbone(cfg, input_shape: ShapeSpec):
+    """reference fpn.py:224-245: the pyramid over res3..res5 with P6 / P7 computed from res5."""
+    bottom_up = build_resnet_backbone(cfg, input_shape)
+    in_features = cfg.MODEL.FPN.IN_FEATURES
+    out_channels = cfg.MODEL.FPN.OUT_CHANNELS
+    in_channels_p6p7 = bottom_up.output_shape()["res5"].channels
+    return FPN(bottom_up=bottom_up, in_features=in_features, out_channels=out_channels, norm=cfg.MODEL.FPN.NORM,
+               top_block=LastLevelP6P7(in_channels_p6p7, out_channels), fuse_type=cfg.MODEL.FPN.FUSE_TYPE)

@@ -50,6 +50,11 @@ class _RCNNBase(nn.Module):
         assert len(self.pixel_mean) == 3, "the stem kernel is built for 3-channel images"
         self._input_cfg = cfg
 
+    def _mean_std(self):
+        """(PIXEL_MEAN, PIXEL_STD) as host floats.  A model that keeps them as state_dict buffers (RetinaNet, as its reference) holds
+        the host copies in `_norm`."""
+        return self.__dict__.get("_norm") or (self.pixel_mean, self.pixel_std)
+
     def preprocess_image(self, batched_inputs):
         """Normalize, pad and batch (reference rcnn.py:324-333).  Storage is NHWC with 4 channel slots;
         `.tensor` is the NCHW-shaped [N,3,Hp,Wp] view of it."""
@@ -63,10 +68,10 @@ class _RCNNBase(nn.Module):
         Hp, Wp = ImageList.padded_size(sizes, self.backbone.size_divisibility)
         buf = torch.empty(len(images), Hp, Wp, 4, device=self.device, dtype=torch.float32)
         if len({im.dtype for im in images}) == 1 and images[0].dtype in (torch.float32, torch.uint8):
-            K.preprocess_batch_into(images, buf, self.pixel_mean, self.pixel_std)     # the whole batch in one launch
+            K.preprocess_batch_into(images, buf, *self._mean_std())     # the whole batch in one launch
         else:
             for i, im in enumerate(images):
-                K.preprocess_into(im, buf[i], self.pixel_mean, self.pixel_std)
+                K.preprocess_into(im, buf[i], *self._mean_std())
         return ImageList(buf.permute(0, 3, 1, 2)[:, :3], sizes)
 
     def _preprocess_raw(self, batched_inputs):
@@ -86,9 +91,9 @@ class _RCNNBase(nn.Module):
         buf = torch.empty(len(raws), Hp, Wp, 4, device=self.device, dtype=torch.float32)
         for i, (r, t) in enumerate(zip(raws, tfms)):
             if t is None:
-                K.preprocess_into(r.permute(2, 0, 1), buf[i], self.pixel_mean, self.pixel_std)
+                K.preprocess_into(r.permute(2, 0, 1), buf[i], *self._mean_std())
             else:
-                t.apply_image(r, out_slot=buf[i], mean=self.pixel_mean, std=self.pixel_std)
+                t.apply_image(r, out_slot=buf[i], mean=self._mean_std()[0], std=self._mean_std()[1])
         return ImageList(buf.permute(0, 3, 1, 2)[:, :3], sizes)
 
 

@@ -1,0 +1,225 @@
+"""RetinaNet, inference only (reference detectron2/modeling/meta_arch/retinanet.py:37-449): `RetinaNetHead` + `RetinaNet`.
+
+`forward(batched_inputs: list[dict]) -> list[{"instances": Instances}]` in eval mode, with the reference's state_dict (names,
+order, shapes: `backbone.*`, `head.{cls_subnet,bbox_subnet}.{0,2,4,6}.*`, `head.cls_score.*`, `head.bbox_pred.*`,
+`anchor_generator.cell_anchors.*`, `pixel_mean`, `pixel_std`).
+
+Launch plan, one stream, fixed shapes, ONE device->host read at the end (per-image counts + the status words):
+  preprocess  ->  ResNet / FPN with P6, P7 from res5 (`LastLevelP6P7`)
+  ->  the head: every layer of the two towers and the two predictors as ONE launch over the five levels (`kernels.conv3x3_levels`,
+      the shared-layer form the RPN head runs on); outputs stay NHWC, so channel a*K + k of a pixel is already the reference's
+      `permute_to_N_HWA_K` order
+  ->  `kernels.retinanet_select` (csrc/retinanet.hip): threshold + per-level top-k + decode, one pass over the logits
+  ->  `kernels.batched_nms_batch` over the L * topk candidate rows of an image  ->  `kernels.gather_detections` (keep order, at most
+      DETECTIONS_PER_IMAGE, detector_postprocess).
+Training (focal loss, label_anchors, the normaliser EMA) is not built.
+"""
+import math
+
+import torch
+from torch import nn
+
+from ... import kernels as K
+from ...layers import Conv2d
+from ...layers.layout import to_nchw_view, to_nhwc
+from ...layers.wrappers import _PackedCache
+from ..anchor_generator import build_anchor_generator
+from ..backbone import build_backbone
+from ..box_regression import Box2BoxTransform
+from ..roi_heads.roi_heads import instances_from_batched, run_with_fallbacks
+from .build import META_ARCH_REGISTRY
+from .rcnn import _RCNNBase
+
+MERGE_LEVELS = True      # every head layer over all pyramid levels as one launch (RetinaNetHead.forward_nhwc)
+_DELTA_PAD = 64          # bbox_pred's 4A = 36 outputs are packed with zero channels up to the direct 3x3 kernel's narrowest tile
+
+
+class RetinaNetHead(nn.Module):
+    """Two towers of NUM_CONVS x (3x3 conv + ReLU) and a 3x3 predictor each, shared by the levels (reference retinanet.py:377-448)."""
+
+    def __init__(self, cfg, input_shape):
+        super().__init__()
+        in_channels = input_shape[0].channels
+        num_classes = cfg.MODEL.RETINANET.NUM_CLASSES
+        num_convs = cfg.MODEL.RETINANET.NUM_CONVS
+        prior_prob = cfg.MODEL.RETINANET.PRIOR_PROB
+        if cfg.MODEL.RETINANET.get("NORM", ""):
+            raise NotImplementedError("MODEL.RETINANET.NORM: a normalised RetinaNet head is not built")
+        num_anchors = build_anchor_generator(cfg, input_shape).num_cell_anchors
+        if len(set(num_anchors)) != 1:
+            raise NotImplementedError("MODEL.ANCHOR_GENERATOR: a different number of anchors per level is not built (nor in the reference)")
+        num_anchors = num_anchors[0]
+        self.num_anchors, self.num_classes = num_anchors, num_classes
+        cls_subnet, bbox_subnet = [], []
+        for _ in range(num_convs):
+            cls_subnet += [Conv2d(in_channels, in_channels, kernel_size=3, stride=1, padding=1), nn.ReLU()]
+            bbox_subnet += [Conv2d(in_channels, in_channels, kernel_size=3, stride=1, padding=1), nn.ReLU()]
+        self.cls_subnet = nn.Sequential(*cls_subnet)
+        self.bbox_subnet = nn.Sequential(*bbox_subnet)
+        self.cls_score = Conv2d(in_channels, num_anchors * num_classes, kernel_size=3, stride=1, padding=1)
+        self.bbox_pred = Conv2d(in_channels, num_anchors * 4, kernel_size=3, stride=1, padding=1)
+        for modules in [self.cls_subnet, self.bbox_subnet, self.cls_score, self.bbox_pred]:
+            for layer in modules.modules():
+                if isinstance(layer, Conv2d):
+                    # logits / deltas decide a top-k and an NMS: the two-accumulator form of the direct 3x3 kernel, as the RPN head
+                    layer.two_acc = True
+                    torch.nn.init.normal_(layer.weight, mean=0, std=0.01)
+                    torch.nn.init.constant_(layer.bias, 0)
+        torch.nn.init.constant_(self.cls_score.bias, -(math.log((1 - prior_prob) / prior_prob)))
+        self._bbox_packed = _PackedCache()
+
+    def towers(self):
+        """[(Conv2d, relu)] of the classification and of the box branch, predictor last."""
+        cls = [(m, True) for m in self.cls_subnet if isinstance(m, Conv2d)] + [(self.cls_score, False)]
+        box = [(m, True) for m in self.bbox_subnet if isinstance(m, Conv2d)] + [(self.bbox_pred, False)]
+        return cls, box
+
+    def packed_bbox_pred(self):
+        """bbox_pred with zero output channels up to `_DELTA_PAD`: 4A = 36 is below the 64 channels the direct 3x3 kernel's narrowest
+        tile writes, and the generic fp32 kernel it would fall to is several times slower on the large levels."""
+        conv = self.bbox_pred
+
+        def build():
+            w, b = conv.weight.detach(), conv.bias.detach()
+            pad = max(0, _DELTA_PAD - w.shape[0])
+            if pad:
+                w = torch.cat([w, w.new_zeros((pad,) + tuple(w.shape[1:]))], 0)
+                b = torch.cat([b, b.new_zeros(pad)], 0)
+            pc = K.pack_conv(w, bias=b, stride=1, pad=1)
+            return pc
+
+        pc = self._bbox_packed.get([conv.weight, conv.bias], build)
+        pc.two_acc = True
+        pc.state = conv._range_state
+        return pc
+
+    def packed_layer(self, conv):
+        return self.packed_bbox_pred() if conv is self.bbox_pred else conv.packed()
+
+    def forward_nhwc(self, feats):
+        """feats: list of [B,H_l,W_l,C] -> (logits: list of [B,H_l,W_l,A*K], deltas: list of [B,H_l,W_l,>=4A]; channels past 4A of the
+        deltas are the packed operand's zero padding).  Gradient-free."""
+        cls, box = self.towers()
+        outs = []
+        for tower in (cls, box):
+            xs = list(feats)
+            for conv, relu in tower:
+                pc = self.packed_layer(conv)
+                if MERGE_LEVELS and len(xs) > 1:
+                    xs = K.conv3x3_levels(xs, pc, relu=relu)
+                else:
+                    xs = [K.conv2d_nhwc(x, pc, relu=relu) for x in xs]
+            outs.append(xs)
+        return outs[0], outs[1]
+
+    def forward(self, features):
+        """Reference signature: list of NCHW maps -> (list of [N,A*K,H,W], list of [N,4A,H,W])."""
+        with torch.no_grad():
+            logits, deltas = self.forward_nhwc([to_nhwc(f) for f in features])
+        A = self.num_anchors
+        return [to_nchw_view(t) for t in logits], [to_nchw_view(t[..., :4 * A]) for t in deltas]
+
+
+@META_ARCH_REGISTRY.register()
+class RetinaNet(_RCNNBase):
+    def __init__(self, cfg):
+        super().__init__()
+        self._init_common(cfg)
+        R = cfg.MODEL.RETINANET
+        self.num_classes = R.NUM_CLASSES
+        self.in_features = R.IN_FEATURES
+        self.score_threshold = R.SCORE_THRESH_TEST
+        self.topk_candidates = R.TOPK_CANDIDATES_TEST
+        self.nms_threshold = R.NMS_THRESH_TEST
+        self.max_detections_per_image = cfg.TEST.DETECTIONS_PER_IMAGE
+        self.backbone = build_backbone(cfg)
+        backbone_shape = self.backbone.output_shape()
+        feature_shapes = [backbone_shape[f] for f in self.in_features]
+        self.head = RetinaNetHead(cfg, feature_shapes)
+        self.anchor_generator = build_anchor_generator(cfg, feature_shapes)
+        self.box2box_transform = Box2BoxTransform(weights=tuple(R.BBOX_REG_WEIGHTS))
+        # the reference keeps the normalisation constants as buffers (part of its state_dict); the preprocess kernels take them as
+        # host floats, kept next to the buffers and refreshed when a checkpoint brings its own (`_load_from_state_dict`)
+        mean, std = self.pixel_mean, self.pixel_std
+        del self.pixel_mean, self.pixel_std
+        self.__dict__["_norm"] = (mean, std)
+        self.register_buffer("pixel_mean", torch.Tensor(mean).view(-1, 1, 1))
+        self.register_buffer("pixel_std", torch.Tensor(std).view(-1, 1, 1))
+        self.max_survivors = K.RETINANET_MAX_SURVIVORS     # x 4 after every overflow, at last None = H*W*A*K (`widen_limits`)
+        self.to(self.device)
+        # (MODEL.BACKBONE.FREEZE_AT is the trunk's own; nothing here trains)
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        mean, std = state_dict.get(prefix + "pixel_mean"), state_dict.get(prefix + "pixel_std")
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+        if mean is not None and std is not None and mean.numel() == 3 and std.numel() == 3:
+            self.__dict__["_norm"] = ([float(v) for v in mean.flatten().tolist()], [float(v) for v in std.flatten().tolist()])
+
+    def forward(self, batched_inputs):
+        if self.training:
+            raise NotImplementedError("RetinaNet training (focal loss, label_anchors) is not built")
+        return run_with_fallbacks(self, lambda: self._inference(batched_inputs))
+
+    def inference(self, batched_inputs, detected_instances=None, do_postprocess=True):
+        """The eval-mode forward under the R-CNN's name (what lvc_amd.evaluation's pipelines call to repeat a batch)."""
+        assert not self.training
+        if detected_instances is not None or not do_postprocess:
+            raise NotImplementedError("RetinaNet.inference: detected_instances / do_postprocess=False are not built")
+        return self.forward(batched_inputs)
+
+    def head_outputs(self, feats):
+        return self.head.forward_nhwc([feats[f] for f in self.in_features])
+
+    def select_nms_post(self, logits, deltas, post, status=None, return_rows=False):
+        """The head's per-level outputs -> (boxes [B,D,4], scores [B,D], classes [B,D] int32, count [B] int32, status): selection,
+        class-wise NMS, the first D = DETECTIONS_PER_IMAGE kept rows through detector_postprocess (post [B,4] or None).  No sync.
+        return_rows: two more values -- for every detection its row in the image's candidate list [B,D] int32, and the candidates' flat
+        indices inside their level [B,L*topk] int32 (rows of a level follow those of the levels below it)."""
+        A, Kc = self.head.num_anchors, self.num_classes
+        ag = self.anchor_generator
+        boxes, scores, classes, index, count, status = K.retinanet_select(
+            [t[..., :A * Kc] for t in logits], [t[..., :4 * A] for t in deltas], list(ag.cell_anchors), ag.strides, ag.offset, Kc,
+            self.topk_candidates, self.score_threshold, self.box2box_transform.weights, max_survivors=self.max_survivors, status=status)
+        D = self.max_detections_per_image
+        keep, num_keep = K.batched_nms_batch(boxes, scores, classes, count, self.nms_threshold, max_keep=D)
+        if return_rows:
+            pos = torch.arange(scores.shape[1], device=scores.device, dtype=torch.int32).repeat(scores.shape[0], 1)
+            ob, osc, ocl, rows, cnt = K.gather_detections(boxes, scores, classes, pos, keep, num_keep, D, post=post)
+            return ob, osc, ocl, cnt, status, rows, index
+        ob, osc, ocl, _rows, cnt = K.gather_detections(boxes, scores, classes, index, keep, num_keep, D, post=post)
+        return ob, osc, ocl, cnt, status
+
+    def _out_sizes(self, batched_inputs, sizes, do_postprocess=True):
+        out = []
+        for inp, (h, w) in zip(batched_inputs, sizes):
+            dh, dw = (int(inp["raw"].shape[0]), int(inp["raw"].shape[1])) if ("image" not in inp and "raw" in inp) else (h, w)
+            out.append((inp.get("height", dh), inp.get("width", dw)) if do_postprocess else (h, w))
+        return out
+
+    def inference_batched(self, batched_inputs, do_postprocess=True, status=None):
+        """Whole forward with device-resident, fixed-shape outputs and no host sync, in the form of GeneralizedRCNN.inference_batched:
+        (boxes [B,D,4], scores [B,D], classes [B,D] int32, count [B] int32, status [1] int32), D = TEST.DETECTIONS_PER_IMAGE."""
+        with torch.no_grad():
+            images = self.preprocess_image(batched_inputs)
+            sizes = images.image_sizes
+            N, _, Hp, Wp = images.tensor.shape
+            x4 = images.tensor.as_strided((N, Hp, Wp, 4), (Hp * Wp * 4, Wp * 4, 4, 1), images.tensor.storage_offset())
+            post = None
+            if do_postprocess:
+                outs = self._out_sizes(batched_inputs, sizes)
+                post = self._dev_const([[ow / w, oh / h, float(oh), float(ow)] for (oh, ow), (h, w) in zip(outs, sizes)], torch.float32)
+            feats = self.backbone.forward_nhwc(x4)
+            logits, deltas = self.head_outputs(feats)
+            return self.select_nms_post(logits, deltas, post, status)
+
+    def _inference(self, batched_inputs):
+        ob, osc, ocl, cnt, status = self.inference_batched(batched_inputs)
+        sizes = []
+        for inp in batched_inputs:
+            if "image" in inp:
+                sizes.append((int(inp["image"].shape[-2]), int(inp["image"].shape[-1])))
+            else:      # raw file pixels: the network saw the ResizeShortestEdge size
+                t = self._test_resize.get_transform(inp["raw"])
+                sizes.append((t.new_h, t.new_w) if t is not None else (int(inp["raw"].shape[0]), int(inp["raw"].shape[1])))
+        insts = instances_from_batched(ob, osc, ocl, cnt, self._out_sizes(batched_inputs, sizes), status)      # the ONE read: counts, status, range words
+        return [{"instances": r} for r in insts]

@@ -403,6 +403,16 @@ def widen_limits(model, exc):
     import logging
 
     if isinstance(exc, CandidateOverflow):
+        if hasattr(model, "max_survivors"):      # RetinaNet: the per-(image, level) list of entries above SCORE_THRESH_TEST
+            if model.max_survivors is None:
+                return False
+            # four times the capacity per step (the workspace is 8 bytes per slot, image and level), H*W*A*K only as the last resort
+            wider = None if model.max_survivors >= (1 << 28) else model.max_survivors * 4
+            logging.getLogger("lvc_amd").warning(
+                "more than %d entries above SCORE_THRESH_TEST on one (image, level): re-running with lists of %s and keeping that size",
+                model.max_survivors, "H*W*A*K" if wider is None else wider)
+            model.max_survivors = wider
+            return True
         heads = getattr(model, "roi_heads", None)
         if heads is None or heads.det_max_candidates is None:
             return False
@@ -486,3 +496,6 @@ def check_status(st):
     if st & 2:
         raise CandidateOverflow("lvc_fast_rcnn_inference: more (roi, class) candidates above SCORE_THRESH_TEST in one "
                                 "image than the candidate list holds; re-run with max_candidates=None (= R*K)")
+    if st & 4:
+        raise CandidateOverflow("lvc_retinanet_select: more entries above SCORE_THRESH_TEST on one (image, level) than the survivor "
+                                "list holds; re-run with max_survivors=None (= H*W*A*K)")
