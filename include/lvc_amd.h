@@ -144,6 +144,14 @@ void lvc_set_wino_streamk(int mode);
 /* Process-wide A/B and test switches (no environment lookups inside the library): the NMS ordered reduce of short lists from global
  * memory instead of LDS (same keep lists); the bf16x3 3x3 halo kernel with a fixed patch shape / without its small-map fallback. */
 void lvc_set_nms_reduce_global(int on);
+/* The selections after the convs, or (0) as they were before their short forms: the parity witness and A/B arm.  Bit 0: lvc_rpn_proposals
+ * runs the per-level top-k as one wide launch (keys + histogram of their top 12 bits) and ONE workgroup per (image, level) for every
+ * other radix pass, the take and the sort, instead of five phase launches and two finishing kernels; with bit 2 also set that workgroup
+ * does the key pass too (the whole selection in one launch; measured slower on the detector's p2).  Bit 1: lvc_batched_nms's head-block
+ * form puts only its head rows in order (radix select + sort of the head; the rest is sorted on the device only for an image whose head
+ * block did not yield max_keep boxes).  Default 3; same outputs for every value. */
+void lvc_set_select_onelaunch(int mode);
+int lvc_select_onelaunch(void);
 void lvc_set_halo_test_hooks(int ph, int pw, int force);
 /* 3x3 / stride 1 / pad 1 as Winograd F(2,3) along x (round 5, csrc/conv3x3_wino.hip; the 256-channel layers of
  * detectron2/modeling/backbone/fpn.py:141-144 and proposal_generator/rpn.py:92-94 on the large maps): two thirds of the MFMAs of

@@ -46,6 +46,9 @@ def lib():
         L.lvc_set_halo_test_hooks.restype = None
         if os.environ.get("LVC_NMS_REDUCE_GLOBAL", "0") != "0":      # read once, here: the library itself never looks at the environment
             L.lvc_set_nms_reduce_global(c_int(1))
+        L.lvc_set_select_onelaunch.restype = None
+        if os.environ.get("LVC_SELECT_ONELAUNCH", "3") != "3":
+            L.lvc_set_select_onelaunch(c_int(int(os.environ["LVC_SELECT_ONELAUNCH"])))
         _lib = L
     return _lib
 

@@ -22,6 +22,7 @@
 extern "C" int lvc_batched_nms(const float*, const float*, const int*, const int*, int, int, double, int,
                                int*, int*, void*, long long, void*);
 extern "C" long long lvc_batched_nms_workspace_bytes(int, int);
+extern "C" int lvc_select_onelaunch(void);
 
 #define MAXL 8
 
@@ -298,6 +299,230 @@ __global__ __launch_bounds__(1024) void rpn_topk_final_kernel(RpnLevels lv, int 
   }
 }
 
+// Keys and the 4096-bin histogram of their top 12 bits for EVERY level, spread over slices of TK_SLICE anchors (one trip of eight loads
+// per thread): p2's logits are 4.3 MB per image of a [.., 16]-channel tensor that other workgroups wrote -- one workgroup pulls them at
+// ~46 GB/s (95 us, measured), a thousand slices take what phase 0 above takes.  ghist [B, L, 4096] is zeroed by the caller.
+__global__ __launch_bounds__(1024) void rpn_topk_keys_kernel(RpnLevels lv, unsigned int* __restrict__ wkeys,
+                                                             int* __restrict__ ghist) {
+  __shared__ int hist[2 * 4096];
+  const int slice = blockIdx.x, l = blockIdx.y, b = blockIdx.z, tid = threadIdx.x;
+  const int A = lv.A, HW = lv.H[l] * lv.W[l], n = HW * A;
+  const int i0 = slice * TK_SLICE;
+  if (i0 >= n) return;
+  const int ld = lv.ld_logit[l];
+  const float* lg = lv.logits[l] + (size_t)b * HW * ld;
+  unsigned int* keys = wkeys + (size_t)b * lv.key_off[lv.L] + lv.key_off[l];
+  for (int t = tid; t < 2 * 4096; t += 1024) hist[t] = 0;
+  __syncthreads();
+  int* myhist = hist + (tid & 1) * 4096;     // two copies by lane parity: the logits cluster in a few bins
+  float v[TK_SLICE / 1024];
+#pragma unroll
+  for (int u = 0; u < TK_SLICE / 1024; ++u) {
+    const int i = i0 + u * 1024 + tid;
+    const int p = i / A, a = i - p * A;
+    v[u] = i < n ? lg[(size_t)p * ld + a] : 0.f;
+  }
+#pragma unroll
+  for (int u = 0; u < TK_SLICE / 1024; ++u) {
+    const int i = i0 + u * 1024 + tid;
+    if (i < n) {
+      const unsigned int key = desc_key(v[u]);
+      keys[i] = key;
+      atomicAdd(&myhist[key >> 20], 1);
+    }
+  }
+  __syncthreads();
+  int* G = ghist + ((size_t)b * lv.L + l) * 4096;
+  for (int t = tid; t < 4096; t += 1024) {
+    const int c = hist[t] + hist[4096 + t];
+    if (c) atomicAdd(&G[t], c);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The rest of the selection, every level, in ONE workgroup per (image, level): the phases above are seven dependent launches
+// (plus a memset) of 7 - 44 us each that mostly wait for one another.  Digits of 12 + 12 + 8 bits.  With the top digit's
+// histogram known, the keys that can still be selected -- those whose top 12 bits are at most the k-th key's; 2 000 of p2's
+// 201 600 on the detector's batch -- are moved into LDS in one sweep (16-byte loads, eight in flight per thread), and the
+// remaining digit passes, the take of the keys < T and the tie list run there.  More than TK1_CAND such keys (a constant
+// level): the digit passes sweep the global keys instead.  The selected set and its order are defined by (key, index)
+// alone, so the output equals the multi-launch form's.  LDS histograms and workgroup barriers only: nothing crosses
+// workgroups.  ghist == NULL: the workgroup also builds the keys and the first histogram itself (the whole selection in one
+// launch; p2's logits through one compute unit make that 156 us against 75 for the two launches).
+#define TK1_CAND 8192            // candidates (keys that share the top 12 bits of the k-th, or lie before them) held in LDS
+__global__ __launch_bounds__(1024) void rpn_topk_one_kernel(RpnLevels lv, int topk, unsigned int* __restrict__ wkeys,
+                                                            float* __restrict__ cand_score, int* __restrict__ cand_idx,
+                                                            int Ntot, const int* __restrict__ ghist) {
+  __shared__ u64 sortbuf[TOPK_PAD];
+  __shared__ unsigned int tiebuf[TOPK_PAD];
+  __shared__ int hist[2 * 4096];
+  __shared__ unsigned int ckey[TK1_CAND], cidx[TK1_CAND];
+  __shared__ int sh[20];
+  __shared__ int s_cnt[2];
+  const int l = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+  const int A = lv.A, HW = lv.H[l] * lv.W[l], n = HW * A;
+  if (n == 0) return;
+  const int k = topk < n ? topk : n;
+  const int ld = lv.ld_logit[l];
+  const float* lg = lv.logits[l] + (size_t)b * HW * ld;
+  unsigned int* keys = wkeys + (size_t)b * lv.key_off[lv.L] + lv.key_off[l];
+  const int npad = k <= 1024 ? 1024 : TOPK_PAD;
+
+  if (ghist) {
+    // keys and the histogram of their top digit come from rpn_topk_keys_kernel
+    const int* G = ghist + ((size_t)b * lv.L + l) * 4096;
+    for (int t = tid; t < 4096; t += 1024) hist[t] = G[t];
+  } else {
+    for (int t = tid; t < 2 * 4096; t += 1024) hist[t] = 0;
+    __syncthreads();
+    int* myhist = hist + (tid & 1) * 4096;
+    for (int i0 = tid; i0 < n; i0 += 8 * 1024) {
+      float v[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int i = i0 + u * 1024;
+        const int p = i / A, a = i - p * A;
+        v[u] = i < n ? lg[(size_t)p * ld + a] : 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int i = i0 + u * 1024;
+        if (i < n) {
+          const unsigned int key = desc_key(v[u]);
+          keys[i] = key;
+          atomicAdd(&myhist[key >> 20], 1);
+        }
+      }
+    }
+    __syncthreads();
+    for (int t = tid; t < 4096; t += 1024) hist[t] += hist[4096 + t];
+  }
+  // the keys that can still be selected: those whose top digit is at most the k-th smallest key's
+  find_bin_1024(hist, 4096, k, sh);
+  const unsigned int d0 = (unsigned int)sh[18];
+  const int ncand = sh[19] + hist[d0];
+  if (tid < 2) s_cnt[tid] = 0;
+  __syncthreads();
+  unsigned int T;
+  int need_eq;
+  const unsigned int* skeys = keys;       // where the last sweep finds its keys, and (LDS list) their indices
+  const unsigned int* sidx = nullptr;
+  int m = n;
+  if (ncand <= TK1_CAND) {
+    // ONE more sweep over the keys (16-byte loads, four in flight per thread) moves those candidates -- a few thousand of 201 600 on
+    // p2 -- into LDS, where the rest of the select and the take run; order in the list does not matter (wave-aggregated append)
+    int a0 = (int)((4 - (((uintptr_t)keys >> 2) & 3)) & 3);      // keys before the first 16-byte aligned one
+    if (a0 > n) a0 = n;
+    const int nv = (n - a0) >> 2, tail0 = a0 + 4 * nv;           // whole vectors; first key behind them
+    {
+      // the (fewer than 8) keys outside the vectors
+      int i = -1;
+      if (tid < a0) i = tid; else if (tid - a0 < n - tail0) i = tail0 + (tid - a0);
+      if (i >= 0) {
+        const unsigned int key = keys[i];
+        if ((key >> 20) <= d0) {
+          const int slot = atomicAdd(&s_cnt[0], 1);
+          if (slot < TK1_CAND) { ckey[slot] = key; cidx[slot] = (unsigned int)i; }
+        }
+      }
+    }
+    const uint4* kv4 = reinterpret_cast<const uint4*>(keys + a0);
+    for (int v0 = tid; v0 < nv; v0 += 8 * 1024) {
+      uint4 q[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int v = v0 + u * 1024;
+        q[u] = uint4{0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+        if (v < nv) q[u] = kv4[v];
+      }
+      // about one key in a hundred is a candidate: count this thread's, reserve their slots with one atomic
+      int cnt = 0;
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const bool in = v0 + u * 1024 < nv;
+        cnt += (in && (q[u].x >> 20) <= d0) + (in && (q[u].y >> 20) <= d0) + (in && (q[u].z >> 20) <= d0) +
+               (in && (q[u].w >> 20) <= d0);
+      }
+      if (cnt == 0) continue;
+      int slot = atomicAdd(&s_cnt[0], cnt);
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int v = v0 + u * 1024;
+        if (v >= nv) continue;
+        const unsigned int kk[4] = {q[u].x, q[u].y, q[u].z, q[u].w};
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          if ((kk[c] >> 20) <= d0) {
+            if (slot < TK1_CAND) { ckey[slot] = kk[c]; cidx[slot] = (unsigned int)(a0 + 4 * v + c); }
+            ++slot;
+          }
+        }
+      }
+    }
+    __syncthreads();
+    m = s_cnt[0] < TK1_CAND ? s_cnt[0] : TK1_CAND;
+    __syncthreads();
+    if (tid == 0) s_cnt[0] = 0;
+    skeys = ckey;
+    sidx = cidx;
+    radix_select_1024(ckey, m, k, false, hist, sh, &T, &need_eq);
+  } else {
+    radix_select_1024(keys, n, k, true, hist, sh, &T, &need_eq);
+  }
+  const int n_lt = k - need_eq;
+
+  for (int i = tid; i < npad; i += 1024) sortbuf[i] = ~0ull;
+  __syncthreads();
+  for (int j0 = tid; j0 < m; j0 += 8 * 1024) {
+    unsigned int kv[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) { const int j = j0 + u * 1024; kv[u] = j < m ? skeys[j] : 0xFFFFFFFFu; }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int j = j0 + u * 1024;
+      if (j >= m) continue;
+      const unsigned int i = sidx ? sidx[j] : (unsigned int)j;
+      if (kv[u] < T) {                      // n_lt < k of them: order irrelevant, they are sorted below
+        const int slot = atomicAdd(&s_cnt[0], 1);
+        if (slot < TOPK_PAD) sortbuf[slot] = ((u64)kv[u] << 32) | i;
+      } else if (kv[u] == T) {
+        const int slot = atomicAdd(&s_cnt[1], 1);
+        if (slot < TOPK_PAD) tiebuf[slot] = i;
+      }
+    }
+  }
+  __syncthreads();
+  const int tie_total = s_cnt[1];
+  if (tie_total <= TOPK_PAD) {
+    // ties at the threshold: the `need_eq` lowest indices
+    int tp = 64;
+    while (tp < tie_total) tp <<= 1;
+    for (int i = tie_total + tid; i < tp; i += 1024) tiebuf[i] = 0xFFFFFFFFu;
+    __syncthreads();
+    bitonic_sort_lds(tiebuf, tp);
+    for (int r = tid; r < need_eq; r += 1024) sortbuf[n_lt + r] = ((u64)T << 32) | tiebuf[r];
+  } else {
+    // more equal keys than the tie list holds (e.g. constant logits): ordered scan, stops once need_eq are found
+    int eq_base = 0;
+    for (int i0 = 0; i0 < n && eq_base < need_eq; i0 += 1024) {
+      const int i = i0 + tid;
+      const bool is_eq = i < n && keys[i] == T;
+      int tot;
+      const int rank = eq_base + block_excl_scan_1024(is_eq ? 1 : 0, sh, &tot);
+      if (is_eq && rank < need_eq) sortbuf[n_lt + rank] = ((u64)T << 32) | (unsigned)i;
+      eq_base += tot;
+    }
+  }
+  __syncthreads();
+  bitonic_sort_lds(sortbuf, npad);
+  for (int r = tid; r < k; r += 1024) {
+    const int i = (int)(sortbuf[r] & 0xFFFFFFFFu);
+    const int pp = i / A, a = i - pp * A;
+    cand_idx[(size_t)b * Ntot + lv.cand_off[l] + r] = i;
+    cand_score[(size_t)b * Ntot + lv.cand_off[l] + r] = lg[(size_t)pp * ld + a];
+  }
+}
+
 __device__ __forceinline__ float clampf(float v, float lo, float hi) {  // torch clamp_(min,max)
   v = v < lo ? lo : v;
   return v > hi ? hi : v;
@@ -419,18 +644,19 @@ static long long align16(long long x) { return (x + 15) & ~15ll; }
 struct RpnPlan {
   int Ntot;
   long long nkeys;  // per image
-  long long off_keys, off_cscore, off_cidx, off_cboxes, off_cscores2, off_clevels, off_ccount, off_keep, off_hist, off_ckeys, off_ties, off_nms, total;
+  long long off_keys, off_cscore, off_cidx, off_cboxes, off_cscores2, off_clevels, off_ccount, off_keep, off_hist, off_hist12, off_ckeys, off_ties, off_nms, total;
   long long off_sboxes, off_sscores, off_scount, off_skeep, off_snk, off_snms, snms_bytes;   // per-(image, level) segments
-  int max_slices, SN;
+  int max_slices, all_slices, SN;
 };
 static RpnPlan rpn_plan(int B, int L, int A, const int* Hs, const int* Ws, int pre_topk) {
   RpnPlan p;
-  p.Ntot = 0; p.nkeys = 0; p.max_slices = 0;
+  p.Ntot = 0; p.nkeys = 0; p.max_slices = 0; p.all_slices = 0;
   for (int l = 0; l < L; ++l) {
     long long n = (long long)Hs[l] * Ws[l] * A;
     p.nkeys += n;
     p.Ntot += (int)(n < pre_topk ? n : pre_topk);
     if (n > TK_SLICE) { int sl = (int)((n + TK_SLICE - 1) / TK_SLICE); if (sl > p.max_slices) p.max_slices = sl; }
+    { int sl = (int)((n + TK_SLICE - 1) / TK_SLICE); if (sl > p.all_slices) p.all_slices = sl; }
   }
   long long o = 0;
   p.off_keys = o; o = align16(o + (long long)B * p.nkeys * 4);
@@ -442,6 +668,7 @@ static RpnPlan rpn_plan(int B, int L, int A, const int* Hs, const int* Ws, int p
   p.off_ccount = o; o = align16(o + (long long)B * 4);
   p.off_keep = o; o = align16(o + (long long)B * p.Ntot * 4);
   p.off_hist = o; o = align16(o + (long long)B * L * TK_HSTRIDE * 4);
+  p.off_hist12 = o; o = align16(o + (long long)B * L * 4096 * 4);
   p.off_ckeys = o; o = align16(o + (long long)B * p.Ntot * 8);
   p.off_ties = o; o = align16(o + (long long)B * L * TOPK_PAD * 4);
   p.off_nms = o; o = align16(o + lvc_batched_nms_workspace_bytes(B, p.Ntot));
@@ -502,6 +729,23 @@ extern "C" int lvc_rpn_proposals(const float* const* logits, const int* ld_logit
   float* cand_score = (float*)(ws + p.off_cscore);
   int* cand_idx = (int*)(ws + p.off_cidx);
   const bool multi = p.max_slices > 0;
+  const int sel = lvc_select_onelaunch();
+  if ((sel & 1) && (sel & 4)) {
+    // everything in one launch: correct, and slower than the phases (one workgroup pulls a large level's logits alone)
+    hipLaunchKernelGGL(rpn_topk_one_kernel, dim3(L, B), dim3(1024), 0, st, lv, pre_nms_topk, keys, cand_score, cand_idx,
+                       p.Ntot, (const int*)nullptr);
+  } else if (sel & 1) {
+    // keys + top-digit histogram on the whole chip, then one workgroup per (image, level) for the rest
+    int* hist12 = (int*)(ws + p.off_hist12);
+    if (hipMemsetAsync(hist12, 0, (size_t)B * L * 4096 * 4, st) != hipSuccess) {
+      lvc_set_error("%s: hipMemsetAsync failed", __func__);
+      return LVC_ERR_HIP;
+    }
+    if (p.all_slices > 0)
+      hipLaunchKernelGGL(rpn_topk_keys_kernel, dim3(p.all_slices, L, B), dim3(1024), 0, st, lv, keys, hist12);
+    hipLaunchKernelGGL(rpn_topk_one_kernel, dim3(L, B), dim3(1024), 0, st, lv, pre_nms_topk, keys, cand_score, cand_idx,
+                       p.Ntot, (const int*)hist12);
+  } else {
   if (multi) {
     int* hist = (int*)(ws + p.off_hist);
     u64* ckeys = (u64*)(ws + p.off_ckeys);
@@ -518,6 +762,7 @@ extern "C" int lvc_rpn_proposals(const float* const* logits, const int* ld_logit
   }
   hipLaunchKernelGGL(rpn_topk_kernel, dim3(L, B), dim3(1024), 0, st, lv, pre_nms_topk, keys, cand_score,
                      cand_idx, p.Ntot, multi ? TK_SLICE : 0x7FFFFFFF);
+  }
   LVC_CHECK_LAUNCH();
   // NMS per (image, level) segment -- levels never interact under `batched_nms` -- and a rank merge of the kept lists in the
   // order the concatenated form keeps them (136 instead of 2 926 mask blocks per image; the concatenated form lost the A/B in

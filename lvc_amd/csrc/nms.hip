@@ -25,8 +25,7 @@
 //                 registers (ffs over the alive word + readlane of the row's diagonal word), then ORs
 //                 the mask rows of the kept boxes into the removed-words (lane = word, coalesced rows).
 #include "common.h"
-
-typedef unsigned long long u64;
+#include "select_common.h"
 
 __device__ __forceinline__ unsigned int ordered_desc_key(float f) {
   if (f == 0.f) f = 0.f;  // -0.0 and +0.0 compare equal in the reference sort
@@ -113,6 +112,172 @@ __global__ __launch_bounds__(1024) void nms_prep_kernel(const float* __restrict_
     sb[r * 4 + 3] = bx[i * 4 + 3] + off;
     si[r] = id;
   }
+}
+
+// ---------------------------------------------------------------- 1b. prep, head form: only the head rows in order
+// The head-block form below runs the greedy pass on the first `head` sorted rows and ends there for every image that has
+// its max_keep boxes by then: sorting all 16 384 candidates was 78 us for rows nobody reads.  Here the workgroup finds the
+// `head` best rows with a radix select on the 32-bit score keys in LDS (ties at the cut: lower index first, as the 64-bit
+// sort key orders them), sorts those alone, and writes the other rows behind them in index order, UNSORTED, with
+// tail_flag[img] = 1.  nms_tail_sort_kernel orders rows [head, n) for the images that need them.  maxp1 is kept for it.
+#define NMS_HEADSORT_MAX 2048    // head rows of the head form (one LDS sort buffer); larger heads keep the full sort
+__global__ __launch_bounds__(1024) void nms_prep_head_kernel(const float* __restrict__ boxes, const float* __restrict__ scores,
+                                                             const int* __restrict__ idxs, const int* __restrict__ counts,
+                                                             int Nmax, int head, int* __restrict__ order,
+                                                             float* __restrict__ sboxes, int* __restrict__ sidx,
+                                                             float* __restrict__ maxp1_out, int* __restrict__ tail_flag) {
+  __shared__ unsigned int k32[16384];       // score key of row i (Nmax <= 16 384 on this path)
+  __shared__ u64 hbuf[NMS_HEADSORT_MAX];
+  __shared__ int hist[4096];
+  __shared__ float red[16];
+  __shared__ int sh[20];
+  const int img = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int n = counts ? counts[img] : Nmax;
+  if (n > Nmax) n = Nmax;
+  if (n < 0) n = 0;
+  const float* bx = boxes + (size_t)img * Nmax * 4;
+  const float* sc = scores + (size_t)img * Nmax;
+  const int* ix = idxs ? idxs + (size_t)img * Nmax : nullptr;
+
+  float m = -INFINITY;
+  for (int i = tid; i < n * 4; i += 1024) {
+    float v = bx[i];
+    m = v > m ? v : m;
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    float t = __shfl_xor(m, o);
+    m = t > m ? t : m;
+  }
+  if (lane == 0) red[wave] = m;
+  __syncthreads();
+  if (tid < 64) {
+    float v = tid < 16 ? red[tid] : -INFINITY;
+    for (int o = 8; o > 0; o >>= 1) {
+      float t = __shfl_xor(v, o);
+      v = t > v ? t : v;
+    }
+    if (tid == 0) red[0] = v;
+  }
+  __syncthreads();
+  const float maxp1 = red[0] + 1.0f;
+  const int h = n < head ? n : head;        // rows that come out sorted
+  if (tid == 0) { maxp1_out[img] = maxp1; tail_flag[img] = n > h ? 1 : 0; }
+
+  int* ord = order + (size_t)img * Nmax;
+  float* sb = sboxes + (size_t)img * Nmax * 4;
+  int* si = sidx + (size_t)img * Nmax;
+  for (int i = tid; i < n; i += 1024) k32[i] = ordered_desc_key(sc[i]);
+  __syncthreads();
+  if (n > h) {
+    unsigned int T;
+    int need_eq;
+    radix_select_1024(k32, n, h, false, hist, sh, &T, &need_eq);
+    const int n_lt = h - need_eq;
+    // ordered partition, one scan per 1024 rows on (count of keys < T) | (count of keys == T) << 16
+    int base_lt = 0, base_eq = 0;
+    for (int i0 = 0; i0 < n; i0 += 1024) {
+      const int i = i0 + tid;
+      const unsigned int key = i < n ? k32[i] : 0xFFFFFFFFu;
+      const bool is_lt = i < n && key < T, is_eq = i < n && key == T;
+      const int v = (is_lt ? 1 : 0) | (is_eq ? 1 << 16 : 0);
+      int x = v;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const int t = __shfl_up(x, o);
+        if (lane >= o) x += t;
+      }
+      __syncthreads();   // sh from the previous trip
+      if (lane == 63) sh[wave] = x;
+      __syncthreads();
+      int excl = x - v, tot = 0;
+      for (int w = 0; w < 16; ++w) { const int t = sh[w]; if (w < wave) excl += t; tot += t; }
+      const int lt_before = base_lt + (excl & 0xFFFF), eq_before = base_eq + (excl >> 16);
+      if (is_lt) {
+        hbuf[lt_before] = ((u64)key << 32) | (unsigned)i;
+      } else if (is_eq && eq_before < need_eq) {
+        hbuf[n_lt + eq_before] = ((u64)key << 32) | (unsigned)i;
+      } else if (i < n) {
+        const int r = h + i - lt_before - (eq_before < need_eq ? eq_before : need_eq);
+        ord[r] = i;
+        const int id = ix ? ix[i] : 0;
+        const float off = (float)id * maxp1;
+        sb[r * 4 + 0] = bx[i * 4 + 0] + off;
+        sb[r * 4 + 1] = bx[i * 4 + 1] + off;
+        sb[r * 4 + 2] = bx[i * 4 + 2] + off;
+        sb[r * 4 + 3] = bx[i * 4 + 3] + off;
+        si[r] = id;
+      }
+      base_lt += tot & 0xFFFF;
+      base_eq += tot >> 16;
+    }
+  } else {
+    for (int i = tid; i < n; i += 1024) hbuf[i] = ((u64)k32[i] << 32) | (unsigned)i;
+  }
+  const int npad = h <= 1024 ? 1024 : NMS_HEADSORT_MAX;
+  for (int i = h + tid; i < npad; i += 1024) hbuf[i] = ~0ull;
+  __syncthreads();
+  bitonic_sort_lds(hbuf, npad);
+  for (int r = tid; r < h; r += 1024) {
+    const int i = (int)(hbuf[r] & 0xFFFFFFFFu);
+    ord[r] = i;
+    const int id = ix ? ix[i] : 0;
+    const float off = (float)id * maxp1;
+    sb[r * 4 + 0] = bx[i * 4 + 0] + off;
+    sb[r * 4 + 1] = bx[i * 4 + 1] + off;
+    sb[r * 4 + 2] = bx[i * 4 + 2] + off;
+    sb[r * 4 + 3] = bx[i * 4 + 3] + off;
+    si[r] = id;
+  }
+}
+
+// Rows [head, n) of an image whose head block did not yield max_keep boxes: the 64-bit key sort of nms_prep_kernel on those
+// rows alone, and the same gather.  Launched for every image; returns at once where the image is done or its tail is in order.
+__global__ __launch_bounds__(1024) void nms_tail_sort_kernel(const float* __restrict__ boxes, const float* __restrict__ scores,
+                                                             const int* __restrict__ idxs, const int* __restrict__ counts,
+                                                             int Nmax, int head, int max_keep,
+                                                             const int* __restrict__ num_keep,
+                                                             const float* __restrict__ maxp1_in, int* __restrict__ tail_flag,
+                                                             int* __restrict__ order, float* __restrict__ sboxes,
+                                                             int* __restrict__ sidx) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char dsm[];
+  u64* keys = reinterpret_cast<u64*>(dsm);
+  const int img = blockIdx.x, tid = threadIdx.x;
+  if (num_keep[img] >= max_keep || !tail_flag[img]) return;
+  int n = counts ? counts[img] : Nmax;
+  if (n > Nmax) n = Nmax;
+  const int mt = n - head;                  // > 0: the flag is set
+  const float* bx = boxes + (size_t)img * Nmax * 4;
+  const float* sc = scores + (size_t)img * Nmax;
+  const int* ix = idxs ? idxs + (size_t)img * Nmax : nullptr;
+  int* ord = order + (size_t)img * Nmax + head;
+  float* sb = sboxes + ((size_t)img * Nmax + head) * 4;
+  int* si = sidx + (size_t)img * Nmax + head;
+  const float maxp1 = maxp1_in[img];
+  int npad = 1024;
+  while (npad < mt) npad <<= 1;
+  for (int r = tid; r < npad; r += 1024) {
+    u64 key = ~0ull;
+    if (r < mt) {
+      const int i = ord[r];
+      key = ((u64)ordered_desc_key(sc[i]) << 32) | (unsigned)i;
+    }
+    keys[r] = key;
+  }
+  __syncthreads();
+  bitonic_sort_lds(keys, npad);
+  for (int r = tid; r < mt; r += 1024) {
+    const int i = (int)(keys[r] & 0xFFFFFFFFu);
+    ord[r] = i;
+    const int id = ix ? ix[i] : 0;
+    const float off = (float)id * maxp1;
+    sb[r * 4 + 0] = bx[i * 4 + 0] + off;
+    sb[r * 4 + 1] = bx[i * 4 + 1] + off;
+    sb[r * 4 + 2] = bx[i * 4 + 2] + off;
+    sb[r * 4 + 3] = bx[i * 4 + 3] + off;
+    si[r] = id;
+  }
+  if (tid == 0) tail_flag[img] = 0;
 }
 
 // ---------------------------------------------------------------- 2. suppression mask via ballot
@@ -534,7 +699,7 @@ extern "C" long long lvc_batched_nms_workspace_bytes(int B, int Nmax) {
   if (Nmax > NMS_TILE)   // blocked form: kept positions, initial removed words, global sort keys, max key
     per += (long long)Nmax * 4 + NMS_MAX_WORDS * 8 + pad_pow2_ll(Nmax) * 8 + 16;
   else if (Nmax > NMS_HEAD_MIN)   // head-block form (max_keep << Nmax): kept positions, initial removed words
-    per += (long long)Nmax * 4 + NMS_MAX_WORDS * 8 + 16;
+    per += (long long)Nmax * 4 + NMS_MAX_WORDS * 8 + 16 + 16 /*head form of the sort: maxp1, tail flag*/;
   return (long long)B * per + 512;
 }
 
@@ -549,6 +714,13 @@ extern "C" long long lvc_batched_nms_workspace_bytes(int B, int Nmax) {
 // form of tests/test_gpu_kernels.py::test_nms_reduce_from_lds_equals_the_global_form_and_the_oracle (no environment lookup per launch)
 static int g_nms_reduce_global = 0;
 extern "C" void lvc_set_nms_reduce_global(int on) { g_nms_reduce_global = on; }
+// The selections in their one-launch / head-only forms (default) or as before them -- the parity witness and A/B arm of
+// tests/test_gpu_select_onelaunch.py and tests/test_gpu_nms_headsort.py.  bit 0: lvc_rpn_proposals' per-level top-k as a wide key pass
+// + one workgroup per (image, level) (boxes.hip), with bit 2 that workgroup alone (one launch, slower); bit 1: the head-block form
+// sorts only its head rows (nms_prep_head_kernel).
+static int g_select_onelaunch = 3;
+extern "C" void lvc_set_select_onelaunch(int mode) { g_select_onelaunch = mode; }
+extern "C" int lvc_select_onelaunch(void) { return g_select_onelaunch; }
 
 extern "C" int lvc_batched_nms(const float* boxes, const float* scores, const int* idxs,
                                const int* d_counts, int B, int Nmax, double iou_threshold,
@@ -577,6 +749,10 @@ extern "C" int lvc_batched_nms(const float* boxes, const float* scores, const in
   const dim3 mask_grid(nwords < NMS_MASK_STRIDE ? nwords : NMS_MASK_STRIDE, nwords, B);
 
   if (Nmax <= NMS_TILE) {
+    int head = ((8 * max_keep + 63) / 64) * 64;
+    if (head < 1024) head = 1024;
+    const bool head_form = Nmax > NMS_HEAD_MIN && head * 2 <= Nmax;
+    const bool head_sort = head_form && head <= NMS_HEADSORT_MAX && (g_select_onelaunch & 2);
     const int npad = pad_pow2(Nmax);
     const size_t lds = (size_t)npad * 8;
 #define LAUNCH_PREP(NP)                                                                              \
@@ -586,7 +762,7 @@ extern "C" int lvc_batched_nms(const float* boxes, const float* scores, const in
     hipLaunchKernelGGL(nms_prep_kernel<NP>, dim3(B), dim3(1024), lds, st, boxes, scores, idxs,       \
                        d_counts, Nmax, order, sboxes, sidx);                                         \
   }
-    switch (npad) {
+    if (!head_sort) switch (npad) {
       case 1024: LAUNCH_PREP(1024); break;
       case 2048: LAUNCH_PREP(2048); break;
       case 4096: LAUNCH_PREP(4096); break;
@@ -601,12 +777,19 @@ extern "C" int lvc_batched_nms(const float* boxes, const float* scores, const in
     // (mask + reduce over a 1024-row block); the rest of the list follows as a second block of the blocked form below --
     // suppression by the boxes kept so far (nms_cross_kernel), mask, reduce -- whose kernels return at once for every image
     // that already has its max_keep boxes.  Same kernels, same decisions as the one-pass form.
-    int head = ((8 * max_keep + 63) / 64) * 64;
-    if (head < 1024) head = 1024;
-    if (Nmax > NMS_HEAD_MIN && head * 2 <= Nmax) {
+    // The sort above covers the whole list only where the head is too long for nms_prep_head_kernel (or on request): otherwise the
+    // head rows alone are in order, and nms_tail_sort_kernel orders the rest for the images that get to the second block.
+    if (head_form) {
       int* kept_pos = (int*)ws; ws += (size_t)B * Nmax * 4;
       ws = (char*)(((uintptr_t)ws + 15) & ~(uintptr_t)15);
-      u64* removed_init = (u64*)ws;
+      u64* removed_init = (u64*)ws; ws += (size_t)B * NMS_MAX_WORDS * 8;
+      float* maxp1 = (float*)ws; ws += (size_t)B * 4;
+      int* tail_flag = (int*)ws;
+      if (head_sort) {
+        hipLaunchKernelGGL(nms_prep_head_kernel, dim3(B), dim3(1024), 0, st, boxes, scores, idxs, d_counts, Nmax, head, order,
+                           sboxes, sidx, maxp1, tail_flag);
+        LVC_CHECK_LAUNCH();
+      }
       if (hipMemsetAsync(d_num_keep, 0, sizeof(int) * B, st) != hipSuccess) {
         lvc_set_error("%s: hipMemsetAsync failed", __func__);
         return LVC_ERR_HIP;
@@ -618,6 +801,12 @@ extern "C" int lvc_batched_nms(const float* boxes, const float* scores, const in
       hipLaunchKernelGGL(nms_reduce_kernel, dim3(B), dim3(64), 0, st, mask, order, d_counts, Nmax, hw, max_keep, keep,
                          d_num_keep, 0, head, removed_init, kept_pos, 1);
       LVC_CHECK_LAUNCH();
+      if (head_sort) {
+        (void)hipFuncSetAttribute((const void*)nms_tail_sort_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(nms_tail_sort_kernel, dim3(B), dim3(1024), lds, st, boxes, scores, idxs, d_counts, Nmax, head,
+                           max_keep, (const int*)d_num_keep, (const float*)maxp1, tail_flag, order, sboxes, sidx);
+        LVC_CHECK_LAUNCH();
+      }
       const int rest = Nmax - head, rw = (rest + 63) / 64;
       hipLaunchKernelGGL(nms_cross_kernel, dim3(lvc_cdiv(rw, 4), B), dim3(256), 0, st, sboxes, sidx, d_counts, Nmax, rw,
                          iou_threshold, kept_pos, d_num_keep, max_keep, head, rest, removed_init);

@@ -1393,6 +1393,19 @@ def roi_align_fpn_backward_nhwc(grad, shapes, scales, rois, levels, sampling_rat
 
 
 # --------------------------------------------------------------------------- NMS
+# Proposal / detection selection (csrc/boxes.hip, csrc/nms.hip): bit 0 = the RPN's per-level top-k as a wide key pass + one workgroup per
+# (image, level) (with bit 2: that workgroup alone, one launch, slower), bit 1 = the detection NMS sorts only its head rows.  3 (default) =
+# both; 0 = the multi-launch top-k and the full sort they replace, kept as the parity witness of tests/test_gpu_select_onelaunch.py /
+# test_gpu_nms_headsort.py and as the A/B arm.  Same outputs for every value.
+SELECT_ONELAUNCH = int(_os.environ.get("LVC_SELECT_ONELAUNCH", "3"))
+
+
+def set_select_onelaunch(mode):
+    global SELECT_ONELAUNCH
+    SELECT_ONELAUNCH = int(mode)
+    _lib.lib().lvc_set_select_onelaunch(c_int(int(mode)))
+
+
 def batched_nms_batch(boxes, scores, idxs, counts, iou_threshold, max_keep=0):
     """boxes [B,Nmax,4], scores [B,Nmax], idxs [B,Nmax] int32 or None, counts [B] int32 device or None.
     Returns (keep [B,Nmax] int32, num_keep [B] int32), all on device, no sync."""
