@@ -593,7 +593,8 @@ int lvc_colsum(const float* x, int M, int N, int ldx, float* out, void* stream);
  *   FrozenBatchNorm2d scale that follows the conv, batch_norm.py:45-65), dw [K,R,S,C] zeroed by the call.  Exact fp32
  *   MFMA; partial sums over pixel ranges are combined with fp32 atomics (not run-to-run deterministic).
  *   The data gradient needs no entry point of its own: it is lvc_conv2d_nhwc_* / lvc_conv3x3_nhwc_bf16x3 on dy with the
- *   weights flipped and transposed (host: kernels.pack_conv_dgrad), followed for a stride-2 1x1 by lvc_scatter_stride2_nhwc.
+ *   weights flipped and transposed (host: kernels.pack_conv_dgrad), followed for a stride-2 1x1 by lvc_scatter_stride2_nhwc
+ *   (a stride-2 3x3 / pad 1: dy is zero-stuffed onto the input grid by lvc_scatter_stride2_nhwc first, then the stride-1 product).
  * lvc_scatter_stride2_nhwc: y[n,2i,2j,:] = x[n,i,j,:], 0 elsewhere; x [N,(H-1)/2+1,(W-1)/2+1,C] -> y [N,H,W,C]
  *   (input gradient of a stride-2 1x1 conv and of LastLevelMaxPool, fpn.py:165-177).
  * lvc_downsum2x2_nhwc: y[n,i,j,:] = sum of x[n,2i..2i+1,2j..2j+1,:]; x [N,2Hs,2Ws,C] (backward of the nearest x2
@@ -627,7 +628,8 @@ int lvc_conv_wgrad_nhwc_bf16x3(const float* x, const float* dy, const float* sca
                                int K, int R, int S, int stride, int pad, int lddy, void* stream);
 /* lvc_conv_wgrad_nhwc on the two-way fp16 split MFMA path (gfx950 LDS transpose reads for the pixel-major operands).
  * dy and x must lie inside fp16's range -- gradients scaled by a power of two (lvc_amd.solver.LossScaler); a value beyond
- * 65504 raises bit 1 (value 2) of *err_word (the conv error word of lvc_conv_workspace; may be NULL). */
+ * 65504 raises bit 1 (value 2) of *err_word (the conv error word of lvc_conv_workspace; may be NULL).  A layer with fewer than 16
+ * output pixels (less than one k-step of the fp16 MFMA) runs on lvc_conv_wgrad_nhwc instead: exact products, no range restriction. */
 int lvc_conv_wgrad_nhwc_f16x2(const float* x, const float* dy, const float* scale, float* dw, int N, int H, int W, int C,
                               int K, int R, int S, int stride, int pad, int lddy, int* err_word, void* stream);
 /* The weight gradients of `njobs` layers in one launch of the bf16x3 kernel (round 5): ATen's conv2d backward runs one wgrad per

@@ -539,6 +539,11 @@ extern "C" int lvc_conv_wgrad_nhwc_f16x2(const float* x, const float* dy, const 
   LVC_CHECK_ARG(Ho > 0 && Wo > 0, "empty output map");
   const long long M64 = (long long)N * Ho * Wo;
   LVC_CHECK_ARG(M64 < (1ll << 31) - 64, "too many output pixels");
+  // Fewer output pixels than ONE k-step of the fp16 MFMA (16): the contraction does not fill a single instruction, so the split
+  // buys no time, and the sum is too short to hide its operand precision -- two fp16 planes carry 22 bits and the a2 b2 product is
+  // left out (up to 2^-21 per product), while an fp32 sum of a few terms is exact to a rounding (measured on 6 pixels: 6.4 x the
+  // error of the fp32 form).  Such a layer runs on the exact fp32 MFMA form (no range restriction: the error word stays untouched).
+  if (M64 < 16) return lvc_conv_wgrad_nhwc(x, dy, scale, dw, N, H, W, C, K, R, S, stride, pad, lddy, stream);
   hipStream_t st = (hipStream_t)stream;
   if (hipMemsetAsync(dw, 0, (size_t)K * R * S * C * sizeof(float), st) != hipSuccess) {
     lvc_set_error("%s: hipMemsetAsync failed", __func__);

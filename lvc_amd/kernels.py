@@ -2579,6 +2579,8 @@ def conv_wgrad(x, dy, scale, R, S, stride, pad, split=None):
     """dW of y = conv(x, W) (* scale per output channel): x [N,H,W,C], dy [N,Ho,Wo,K] -> [K,R,S,C] fp32."""
     if BWD_TIMER is not None:
         eng = "f16x2" if (split or DGRAD_SPLIT) == "f16x2" else WGRAD_ENGINE
+        if eng == "f16x2" and dy.shape[0] * dy.shape[1] * dy.shape[2] < 16:
+            eng = "f32"      # fewer pixels than one k-step of the fp16 MFMA: lvc_conv_wgrad_nhwc_f16x2 runs the exact fp32 form
         fl = 2.0 * dy.shape[0] * dy.shape[1] * dy.shape[2] * dy.shape[3] * x.shape[3] * R * S
         nb = 4.0 * (x.numel() + dy.numel() + dy.shape[3] * R * S * x.shape[3])
         tag = "%dx%dx%d %d>%d %dx%d s%d" % (dy.shape[0], dy.shape[1], dy.shape[2], x.shape[3], dy.shape[3], R, S, stride)
@@ -2980,7 +2982,8 @@ def pack_conv_dgrad(weight, scale, pad, groups=1):
     gradient is zero-stuffed onto the input grid before it (`conv_dgrad`).  Otherwise:
     Packed weights of the DATA gradient of y = conv(x, weight, stride 1 after sub-sampling, pad) * scale:
     dx = conv(dy, Wt, pad = R-1-pad) with Wt[c][k][r][s] = scale[k] * weight[k][c][R-1-r][S-1-s].  A strided 1x1 is
-    the same product on the sub-sampled grid followed by `scatter_stride2`.  Output channels of the forward conv
+    the same product on the sub-sampled grid followed by `scatter_stride2`; a stride-2 3x3 / pad 1 layer's gradient is
+    zero-stuffed onto the input grid first (`conv_dgrad`), so the operand does not depend on the stride.  Output channels of the forward conv
     (the contraction here) are zero-padded to the kernels' 32-channel chunk."""
     Kout, C, R, S = weight.shape
     if groups != 1:
@@ -3006,6 +3009,15 @@ def conv_dgrad(dy, pcd, x_shape, stride):
         dxs = _bwd_timed("dgrad", "f32_grouped", fl, nb, lambda: conv2d_nhwc(g, pcd), "grouped %dx%dx%d %d g%d s%d" % (N, H, W, C, pcd.groups, stride))
         assert tuple(dxs.shape) == (N, H, W, C), (dxs.shape, x_shape)
         return dxs
+    if stride != 1:
+        one, three = (pcd.R, pcd.S, pcd.pad) == (1, 1, 0), (pcd.R, pcd.S, pcd.pad) == (3, 3, 1)
+        if stride != 2 or not (one or three):
+            raise NotImplementedError("data gradient of a {}x{} convolution with stride {} and padding {}: strided layers are built for "
+                                      "1x1 / padding 0 and 3x3 / padding 1 at stride 2".format(pcd.R, pcd.S, stride, pcd.R - 1 - pcd.pad))
+        if three:
+            # dense 3x3 / pad 1 / stride 2 (conv2 of res3.0 / res4.0 / res5.0 with STRIDE_IN_1X1: False): as the grouped branch above,
+            # the gradient is zero-stuffed onto the input grid, then the stride-1 product on the flipped operand
+            dy, stride = scatter_stride2(dy, H, W), 1
     if dy.shape[3] != pcd.C:   # contraction padded to 32 channels
         dy = torch.nn.functional.pad(dy, (0, pcd.C - dy.shape[3]))
     if BWD_TIMER is not None:
@@ -3018,8 +3030,7 @@ def conv_dgrad(dy, pcd, x_shape, stride):
     if stride == 1:
         assert tuple(dxs.shape) == (N, H, W, C), (dxs.shape, x_shape)
         return dxs
-    assert stride == 2 and pcd.R == 1, "strided 3x3 convolutions are not on the path (STRIDE_IN_1X1)"
-    return scatter_stride2(dxs, H, W)
+    return scatter_stride2(dxs, H, W)      # a strided 1x1: the product ran on the sub-sampled grid
 
 
 def linear_backward(x, weight, dz, need_dx=True, need_dw=True):

@@ -89,6 +89,7 @@ def _ref_conv(x, w, b, bn, stride, pad, relu, residual, res_mode):
     (512, 256, 1, 1, 0, False, True, False, 2, 50, 84),   # FPN lateral + up2(top)
     (256, 256, 3, 1, 1, False, True, False, 0, 26, 42),   # FPN output
     (256, 256, 3, 1, 1, False, True, True, 0, 13, 21),    # RPN conv
+    (128, 128, 3, 2, 1, True, False, True, 0, 51, 85),    # dense strided conv2 (STRIDE_IN_1X1: False; odd map)
 ])
 def test_conv2d_module_backward(C, K, R, stride, pad, bn, bias, relu, res_mode, H, W):
     from lvc_amd.layers import Conv2d, FrozenBatchNorm2d
@@ -135,6 +136,52 @@ def test_conv2d_module_backward(C, K, R, stride, pad, bn, bias, relu, res_mode, 
         assert _rel(conv.bias.grad, br.grad) < TOL
     if res is not None:
         assert _rel(rd.grad.permute(0, 3, 1, 2), rr.grad) < TOL
+
+
+def test_bottleneck_with_the_stride_in_the_3x3_trains():
+    """`MODEL.RESNETS.STRIDE_IN_1X1: False` with one group: conv2 of res3.0 / res4.0 / res5.0 is a dense 3x3 with stride 2.  Forward
+    and backward of such a block (26x42 map) against the same block evaluated by torch in fp64 on the CPU: the output, the input
+    gradient and every weight gradient, at this file's bars."""
+    from lvc_amd.modeling.backbone.resnet import BottleneckBlock
+
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(53)
+    blk = BottleneckBlock(256, 512, bottleneck_channels=128, stride=2, stride_in_1x1=False, norm="FrozenBN")
+    assert blk.conv2.stride == 2 and blk.conv2.groups == 1 and blk.conv1.stride == 1 and blk.shortcut.stride == 2
+    layers = {"conv1": (blk.conv1, 1, 0, True), "conv2": (blk.conv2, 2, 1, True), "conv3": (blk.conv3, 1, 0, False),
+              "shortcut": (blk.shortcut, 2, 0, False)}
+    with torch.no_grad():
+        for conv, _, _, _ in layers.values():
+            Kc, C, R, _ = conv.weight.shape
+            conv.weight.copy_(torch.randn(Kc, C, R, R, generator=g) * (2.0 / (C * R * R)) ** 0.5)
+            conv.norm.weight.copy_(torch.rand(Kc, generator=g) + 0.5)
+            conv.norm.bias.copy_(torch.randn(Kc, generator=g) * 0.1)
+            conv.norm.running_mean.copy_(torch.randn(Kc, generator=g) * 0.1)
+            conv.norm.running_var.copy_(torch.rand(Kc, generator=g) + 0.5)
+    N, H, W = 2, 26, 42
+    x = torch.randn(N, 256, H, W, generator=g)
+    dy = torch.randn(N, 512, 13, 21, generator=g) * 1e-3
+    # fp64 reference
+    xr = x.double().requires_grad_(True)
+    wr = {}
+
+    def ref(name, t, residual=None, relu=None):
+        conv, stride, pad, act = layers[name]
+        wr[name] = conv.weight.detach().double().requires_grad_(True)
+        bn = [b.detach() for b in (conv.norm.weight, conv.norm.bias, conv.norm.running_mean, conv.norm.running_var)]
+        return _ref_conv(t, wr[name], None, bn, stride, pad, act if relu is None else relu, residual, 1)
+
+    yr = ref("conv3", ref("conv2", ref("conv1", xr)), residual=ref("shortcut", xr), relu=True)
+    (yr * dy.double()).sum().backward()
+    # device
+    blk = blk.to(dev)
+    xd = x.permute(0, 2, 3, 1).contiguous().to(dev).requires_grad_(True)
+    yd = blk.forward_nhwc(xd)
+    assert _rel(yd.permute(0, 3, 1, 2), yr) < 1e-5
+    yd.backward(dy.permute(0, 2, 3, 1).contiguous().to(dev))
+    assert _rel(xd.grad.permute(0, 3, 1, 2), xr.grad) < TOL
+    for name, (conv, _, _, _) in layers.items():
+        assert conv.weight.grad is not None and _rel(conv.weight.grad, wr[name].grad) < TOL, name
 
 
 @pytest.mark.parametrize("N,H,W,C,K,R,stride,pad,scaled", [

@@ -125,3 +125,41 @@ def test_failed_status_names_the_called_entry_point_and_resets_the_slot(T):
             assert rec.calls[-1][0] == entry and len(rec.calls) == 1
             assert str(e.value).startswith(entry + " failed (status 3)")
             assert rec.raw[-1] == ("lvc_set_range_slot", [0]) and rec.slot == 0
+
+
+def test_data_gradient_cases_reach_their_entry_points(monkeypatch):
+    """The data-gradient cases of tests/test_gpu_conv_backward_exact.py (helpers.DGRAD_CASES) land on the entry points they are
+    there for -- `conv_route` on plain numbers, under the switches those tests run with -- and between them reach every forward
+    kernel the data gradient is built on: a change of the routing thresholds cannot quietly empty a GPU case."""
+    from helpers import DGRAD_CASES, DGRAD_ENTRIES_REQUIRED, dgrad_route
+    from lvc_amd import _lib
+    from lvc_amd import kernels as K
+
+    def no_library():
+        raise AssertionError("conv_route touched the native library")
+
+    monkeypatch.setattr(_lib, "lib", no_library)
+    for name, value in (("CONV_ENGINE", "bf16x3"), ("CONV_SPLIT", "f16x2"), ("CONV_HALO", True), ("_PW_NARROW", True)):
+        monkeypatch.setattr(K, name, value)
+    reached = set()
+    for split in ("bf16x3", "f16x2"):
+        monkeypatch.setattr(K, "DGRAD_SPLIT", split)
+        if split == "f16x2":
+            monkeypatch.setattr(K, "_HALO_H2_MIN_TILES", 0)
+        for shape, want in DGRAD_CASES:
+            got = dgrad_route(K, shape, split)
+            assert got == want[split], (shape, split, got)
+            reached.add(got)
+    assert set(DGRAD_ENTRIES_REQUIRED) <= reached
+    assert len({shape for shape, _ in DGRAD_CASES}) == len(DGRAD_CASES)
+
+
+def test_data_gradient_of_an_unbuilt_strided_layer_says_so():
+    """Strided layers have a data gradient for 1x1 / padding 0 and 3x3 / padding 1 at stride 2; anything else raises a
+    NotImplementedError that names the layer before anything is launched (no bare assert in the middle of a backward pass)."""
+    from lvc_amd import kernels as K
+
+    for R, pad, stride in ((3, 0, 2), (3, 1, 3), (1, 0, 3), (5, 2, 2), (1, 1, 2)):
+        pcd = types.SimpleNamespace(groups=1, R=R, S=R, pad=R - 1 - pad, C=32, K=32)
+        with pytest.raises(NotImplementedError, match="{0}x{0} convolution with stride {1} and padding {2}".format(R, stride, pad)):
+            K.conv_dgrad(None, pcd, (1, 8, 8, 32), stride)
