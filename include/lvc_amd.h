@@ -484,6 +484,38 @@ int lvc_gather_detections(const float* boxes, const float* scores, const int* cl
                           const int* d_num_keep, int B, int Nmax, int topk, const float* d_post, float* out_boxes,
                           float* out_scores, int* out_classes, int* out_rows, int* d_out_count, void* stream);
 
+/* RetinaNet's training loss (detectron2/modeling/meta_arch/retinanet.py:184-236 `losses`: fvcore sigmoid_focal_loss "sum" over the
+ * valid anchors' K entries, smooth_l1_loss "sum" of the deltas against Box2BoxTransform.get_deltas(anchor, matched gt) over the positive
+ * anchors, both divided by the EMA loss normaliser) on the head's per-level NHWC outputs (csrc/retinanet_loss.hip).
+ *   logits[l] / deltas[l], ld_logit / ld_delta, Hs, Ws, L (1..8), A, K, B: as for lvc_retinanet_select; padding channels are never read.
+ *   anchors [R,4] (R = sum_l H_l W_l A, level after level, p*A + a inside a level), matches int32 [B,R] and labels int8 [B,R] as
+ *   lvc_match_boxes_batched writes them (1: the class of the matched gt box is the target; 0: every target 0; -1: no loss, zero
+ *   gradient; an image without gt is background everywhere), gt [Gtot,4], gt_classes int64 [Gtot], gt_off int32 [B+1]: all DEVICE.
+ *   alpha < 0: no alpha weighting; gamma 0 or >= 1 (2, 0 and 1 do not go through powf); beta < 1e-5: pure L1.
+ * lvc_retinanet_loss (two launches: the streaming pass, and a one-workgroup finish that adds the workgroups' fp64 partial sums in index
+ *   order): *num_pos = the number of positive anchors, *normalizer_out = momentum * *normalizer_in + one_minus_momentum *
+ *   max(num_pos, 1) in fp64 with a separately rounded multiply and add (the reference's Python float, bit for bit; the two slots must
+ *   differ), out_losses [2] = (loss_cls, loss_box_reg) = the two sums / *normalizer_out, out_sums [2] (may be NULL) = the two sums
+ *   themselves in fp64.  The loss terms are evaluated in fp64 (alpha, gamma, beta and the weights are doubles: the reference's Python
+ *   floats), the gradient entries in fp32.  Bit-identical between runs; no host read.
+ * lvc_retinanet_loss_grad (one launch): dlogits[l] [B,H_l,W_l,ld_dlogit[l]] = *g_cls / *normalizer * d(focal sum)/d(logits) and
+ *   ddeltas[l] [B,H_l,W_l,ld_ddelta[l]] = *g_box / *normalizer * d(smooth-L1 sum)/d(deltas); zero on ignored anchors (dlogits), on
+ *   every anchor that is not positive (ddeltas) and on the padding channels.  normalizer, g_cls, g_box: device scalars.
+ * 16-byte accesses where a level's ld is a multiple of 4 and its base pointer is 16-byte aligned; scalar accesses otherwise. */
+long long lvc_retinanet_loss_workspace_bytes(int B, int L, int A, int K, const int* Hs, const int* Ws);
+int lvc_retinanet_loss(const float* const* logits, const int* ld_logit, const float* const* deltas, const int* ld_delta,
+                       const int* Hs, const int* Ws, int L, int A, int K, int B, const float* anchors, const int* matches,
+                       const signed char* labels, const float* gt, const long long* gt_classes, const int* gt_off, double alpha,
+                       double gamma, double beta, double wx, double wy, double ww, double wh, double momentum,
+                       double one_minus_momentum, const double* normalizer_in, double* normalizer_out, float* out_losses,
+                       double* out_sums /* [2] or NULL */, int* num_pos, void* workspace, long long workspace_bytes, void* stream);
+int lvc_retinanet_loss_grad(const float* const* logits, const int* ld_logit, const float* const* deltas, const int* ld_delta,
+                            const int* Hs, const int* Ws, int L, int A, int K, int B, const float* anchors, const int* matches,
+                            const signed char* labels, const float* gt, const long long* gt_classes, const int* gt_off, double alpha,
+                            double gamma, double beta, double wx, double wy, double ww, double wh, const double* normalizer,
+                            const float* g_cls, const float* g_box, float* const* dlogits, const int* ld_dlogit,
+                            float* const* ddeltas, const int* ld_ddelta, void* stream);
+
 /* assign_boxes_to_levels + convert_boxes_to_pooler_format (detectron2/modeling/poolers.py:23-59, 69-96).
  * boxes [B,R,4] -> levels [B*R] int32 (offset from min_level), rois [B*R,5] (may be NULL). */
 int lvc_assign_levels_rois(const float* boxes, int B, int R, int min_level, int max_level, int canonical_box_size,

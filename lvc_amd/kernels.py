@@ -1631,6 +1631,107 @@ def retinanet_select_checked(*args, max_survivors=RETINANET_MAX_SURVIVORS, **kw)
     return out
 
 
+class RetinaNetLossArgs:
+    """The arguments `retinanet_loss` and `retinanet_loss_grad` share, checked once: the head's per-level NHWC outputs
+    logits[l] [B,H,W,>=A*K] / deltas[l] [B,H,W,>=4A] (channel slices of wider rows allowed; the padding is never read), anchors [R,4]
+    in `Boxes.cat(anchors)` order, matches int32 [B,R] / labels int8 [B,R] from `match_boxes_batched`, gt [G,4], gt_classes int64 [G],
+    gt_off int32 [B+1] from `cat_ground_truth`."""
+
+    def __init__(self, logits, deltas, num_anchors, num_classes, anchors, matches, labels, gt, gt_classes, gt_off,
+                 alpha=0.25, gamma=2.0, beta=0.1, box_weights=(1.0, 1.0, 1.0, 1.0)):
+        L = len(logits)
+        if not (L == len(deltas) and 1 <= L <= 8):
+            raise ValueError("retinanet_loss: 1..8 levels with logits and deltas each")
+        if 0.0 < float(gamma) < 1.0 or float(gamma) < 0.0:
+            raise NotImplementedError("MODEL.RETINANET.FOCAL_LOSS_GAMMA = {}: an exponent in (0, 1) has an unbounded derivative at "
+                                      "saturation (and a negative one is no focal loss); 0 or >= 1 are built".format(gamma))
+        _req_cuda(*logits, *deltas, anchors, matches, labels, gt_off, gt_classes)
+        A, Kc = int(num_anchors), int(num_classes)
+        B = logits[0].shape[0]
+        self.Hs = [t.shape[1] for t in logits]
+        self.Ws = [t.shape[2] for t in logits]
+        for t, d, h, w in zip(logits, deltas, self.Hs, self.Ws):
+            for u, need in ((t, A * Kc), (d, 4 * A)):
+                if not (u.dtype == torch.float32 and u.dim() == 4 and u.shape[:3] == (B, h, w) and u.shape[3] >= need and u.stride(3) == 1
+                        and u.stride(1) == w * u.stride(2) and u.stride(0) == h * w * u.stride(2)):
+                    raise ValueError("retinanet_loss: need fp32 NHWC channel slices [B,H,W,>=A*K] / [B,H,W,>=4A] of dense pixel rows")
+        R = sum(h * w for h, w in zip(self.Hs, self.Ws)) * A
+        G = gt.shape[0]
+        if not (anchors.shape == (R, 4) and anchors.dtype == torch.float32 and anchors.is_contiguous()):
+            raise ValueError("retinanet_loss: anchors must be a contiguous fp32 [R,4], R = sum_l H_l W_l A = {}".format(R))
+        if not (matches.shape == (B, R) and matches.dtype == torch.int32 and matches.is_contiguous()
+                and labels.shape == (B, R) and labels.dtype == torch.int8 and labels.is_contiguous()):
+            raise ValueError("retinanet_loss: matches int32 [B,R] and labels int8 [B,R] (match_boxes_batched)")
+        if not (gt_off.dtype == torch.int32 and gt_off.numel() == B + 1 and gt.dtype == torch.float32 and gt.shape == (G, 4)
+                and gt.is_contiguous() and gt_classes.dtype == torch.int64 and gt_classes.numel() == G and gt_classes.is_contiguous()):
+            raise ValueError("retinanet_loss: gt fp32 [G,4], gt_classes int64 [G], gt_off int32 [B+1]")
+        self.logits, self.deltas = list(logits), list(deltas)
+        self.L, self.A, self.K, self.B, self.R = L, A, Kc, B, R
+        self.tensors = (anchors, matches, labels, gt, gt_classes, gt_off)
+        self.scalars = (float(alpha), float(gamma), float(beta)) + tuple(float(v) for v in box_weights)
+        self.dev = logits[0].device
+
+    def _levels(self, ts):
+        VP, IP = c_void_p * self.L, c_int * self.L
+        return VP(*[t.data_ptr() for t in ts]), IP(*[t.stride(2) for t in ts])
+
+    def common(self):
+        lp, ldl = self._levels(self.logits)
+        dp, ldd = self._levels(self.deltas)
+        IP = c_int * self.L
+        return ([lp, ldl, dp, ldd, IP(*self.Hs), IP(*self.Ws), c_int(self.L), c_int(self.A), c_int(self.K), c_int(self.B)]
+                + [ptr(t) for t in self.tensors] + [c_double(v) for v in self.scalars])
+
+
+def retinanet_loss(args, normalizer_in, normalizer_out, momentum=0.9, one_minus_momentum=1 - 0.9, return_sums=False):
+    """RetinaNet.losses (reference retinanet.py:184-236) in two launches (csrc/retinanet_loss.hip): one streaming pass over the logits
+    and deltas, one finish.  args: `RetinaNetLossArgs`; normalizer_in / normalizer_out: DIFFERENT device float64 [1] tensors -- the
+    EMA `momentum * in + one_minus_momentum * max(num_pos, 1)` is written to `normalizer_out` in the reference's Python float
+    arithmetic (`one_minus_momentum` is formed by the caller as `1 - momentum`: 0.09999999999999998 for 0.9, not 0.1) and divides both
+    sums.  -> (losses fp32 [2] = (loss_cls, loss_box_reg), num_pos int32 [1]); no host read.  return_sums: a third value, the two sums
+    before the division as float64 [2]."""
+    _req_cuda(normalizer_in, normalizer_out)
+    if not (normalizer_in.dtype == normalizer_out.dtype == torch.float64 and normalizer_in.numel() == normalizer_out.numel() == 1
+            and normalizer_in.data_ptr() != normalizer_out.data_ptr()):
+        raise ValueError("retinanet_loss: normalizer_in / normalizer_out must be two different float64 [1] device tensors")
+    lib = _lib.lib()
+    IP = c_int * args.L
+    lib.lvc_retinanet_loss_workspace_bytes.restype = c_longlong
+    nbytes = lib.lvc_retinanet_loss_workspace_bytes(c_int(args.B), c_int(args.L), c_int(args.A), c_int(args.K), IP(*args.Hs), IP(*args.Ws))
+    if nbytes < 0:
+        raise ValueError("retinanet_loss: shapes outside the kernel's range")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=args.dev)
+    out = torch.empty(2, dtype=torch.float32, device=args.dev)
+    num_pos = torch.empty(1, dtype=torch.int32, device=args.dev)
+    sums = torch.empty(2, dtype=torch.float64, device=args.dev) if return_sums else None
+    rc = lib.lvc_retinanet_loss(*args.common(), c_double(momentum), c_double(one_minus_momentum), ptr(normalizer_in), ptr(normalizer_out),
+                                ptr(out), ptr(sums), ptr(num_pos), ptr(ws), c_longlong(nbytes), _stream(out))
+    check(rc, "lvc_retinanet_loss")
+    return (out, num_pos, sums) if return_sums else (out, num_pos)
+
+
+def retinanet_loss_grad(args, normalizer, g_cls, g_box, dlogits=None, ddeltas=None):
+    """The gradient of `retinanet_loss` in one launch: dlogits[l] / ddeltas[l] (dense [B,H,W,A*K] / [B,H,W,4A] unless given: any
+    [B,H,W,>=A*K] / [B,H,W,>=4A] tensors with contiguous rows, whose padding channels are written as zero) = the derivative of the two
+    losses times the upstream scalars g_cls / g_box (fp32 [1] device) over `normalizer` (float64 [1] device, `retinanet_loss`'s
+    normalizer_out).  Zero on ignored anchors; ddeltas zero on every anchor that is not positive.  No host read."""
+    _req_cuda(normalizer, g_cls, g_box)
+    assert normalizer.dtype == torch.float64 and g_cls.dtype == g_box.dtype == torch.float32
+    if dlogits is None:
+        dlogits = [torch.empty(t.shape[:3] + (args.A * args.K,), dtype=torch.float32, device=args.dev) for t in args.logits]
+    if ddeltas is None:
+        ddeltas = [torch.empty(t.shape[:3] + (4 * args.A,), dtype=torch.float32, device=args.dev) for t in args.deltas]
+    for outs, ins, need in ((dlogits, args.logits, args.A * args.K), (ddeltas, args.deltas, 4 * args.A)):
+        if len(outs) != args.L or any(not (o.is_contiguous() and o.dtype == torch.float32 and o.shape[:3] == t.shape[:3] and o.shape[3] >= need)
+                                      for o, t in zip(outs, ins)):
+            raise ValueError("retinanet_loss_grad: gradient tensors must be contiguous fp32 [B,H,W,>=A*K] / [B,H,W,>=4A]")
+    glp, gldl = args._levels(dlogits)
+    gdp, gldd = args._levels(ddeltas)
+    rc = _lib.lib().lvc_retinanet_loss_grad(*args.common(), ptr(normalizer), ptr(g_cls), ptr(g_box), glp, gldl, gdp, gldd, _stream(g_cls))
+    check(rc, "lvc_retinanet_loss_grad")
+    return dlogits, ddeltas
+
+
 def gather_detections(boxes, scores, classes, rows, keep, num_keep, topk, post=None):
     """The rows an NMS kept (`batched_nms_batch`), in its order, at most topk per image, through detector_postprocess when
     post [B,4] fp32 = (scale_x, scale_y, out_h, out_w) is given.  boxes [B,Nmax,4], scores / classes / rows [B,Nmax].

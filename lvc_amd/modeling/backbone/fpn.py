@@ -51,6 +51,21 @@ class LastLevelMaxPool(nn.Module):
         return [to_nchw_view(t) for t in self.forward_nhwc(to_nhwc(x))]
 
 
+class _Relu(torch.autograd.Function):
+    """relu as a pass of its own under autograd (p7's input when p6 trains): backward masks the gradient by y > 0."""
+
+    @staticmethod
+    def forward(ctx, x):
+        y = K.relu(x)
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        return K.relu_backward(g, ctx.saved_tensors[0])
+
+
 class LastLevelP6P7(nn.Module):
     """p6 = conv3x3 stride 2 on `in_feature`, p7 = the same conv on relu(p6) (reference fpn.py:180-198; RetinaNet's two extra
     levels).  Both are ordinary `Conv2d` layers: whatever entry `kernels.conv_route` gives a 3x3 / stride 2 / pad 1 layer."""
@@ -67,6 +82,8 @@ class LastLevelP6P7(nn.Module):
     def forward_nhwc(self, x):
         p6 = self.p6.forward_nhwc(x)
         # p6 itself is an output, un-rectified: relu(p6) is its own pass over that small map
+        if torch.is_grad_enabled() and p6.requires_grad:
+            return [p6, self.p7.forward_nhwc(_Relu.apply(p6))]
         return [p6, self.p7.forward_nhwc(K.relu(p6))]
 
     def forward(self, x):

@@ -50,6 +50,22 @@ class _RCNNBase(nn.Module):
         assert len(self.pixel_mean) == 3, "the stem kernel is built for 3-channel images"
         self._input_cfg = cfg
 
+    def _prepack_trainable(self):
+        """The kernel-layout operands of every convolution whose weight trains, rebuilt after an optimizer step in a few grouped
+        launches (forward operand, and the data-gradient operand where a gradient flows further down) instead of 2-3 per layer."""
+        if not K.PREPACK or not torch.is_grad_enabled():
+            return
+        lst = self.__dict__.get("_trainable_convs")
+        if lst is None or lst[0] != sum(1 for p in self.parameters() if p.requires_grad):
+            from ...layers import Conv2d
+
+            convs = [m for m in self.modules() if isinstance(m, Conv2d) and m.weight.requires_grad]
+            lst = self.__dict__["_trainable_convs"] = (sum(1 for p in self.parameters() if p.requires_grad), convs)
+        if lst[1]:
+            from ...layers import Conv2d
+
+            Conv2d.prepack(lst[1], holder=self.__dict__.setdefault("_prepack_plan", {}))
+
     def _mean_std(self):
         """(PIXEL_MEAN, PIXEL_STD) as host floats.  A model that keeps them as state_dict buffers (RetinaNet, as its reference) holds
         the host copies in `_norm`."""
@@ -145,22 +161,6 @@ class GeneralizedRCNN(_RCNNBase):
             return losses
 
         return run_with_fallbacks(self, once)
-
-    def _prepack_trainable(self):
-        """The kernel-layout operands of every convolution whose weight trains, rebuilt after an optimizer step in a few grouped
-        launches (forward operand, and the data-gradient operand where a gradient flows further down) instead of 2-3 per layer."""
-        if not K.PREPACK or not torch.is_grad_enabled():
-            return
-        lst = self.__dict__.get("_trainable_convs")
-        if lst is None or lst[0] != sum(1 for p in self.parameters() if p.requires_grad):
-            from ...layers import Conv2d
-
-            convs = [m for m in self.modules() if isinstance(m, Conv2d) and m.weight.requires_grad]
-            lst = self.__dict__["_trainable_convs"] = (sum(1 for p in self.parameters() if p.requires_grad), convs)
-        if lst[1]:
-            from ...layers import Conv2d
-
-            Conv2d.prepack(lst[1], holder=self.__dict__.setdefault("_prepack_plan", {}))
 
     def _forward_train(self, batched_inputs):
         # training forward (reference rcnn.py:127-175): losses of the RPN (logged; frozen) and of the box predictor
