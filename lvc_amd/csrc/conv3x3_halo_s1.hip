@@ -698,8 +698,9 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_halo_s1_kernel(HaloArgsS p) {
       using T0 = std::integral_constant<int, 0>; using T1 = std::integral_constant<int, 1>; using T2 = std::integral_constant<int, 2>;
       if (p.presplit) {      // (the entry point admits it without residual, with ReLU)
         rows(T0{}, std::true_type{}, std::true_type{});
-        // not lvc_report_range: this copy compares the SCALED value, unlike every other one (the presplit range check); kept as it is
-        if (!(bigq * LVC_ACT_SCALE <= LVC_ACT_MAX)) atomicOr(p.flags + p.next_err_index, bigq < INFINITY ? 2 : 4);
+        // the consumer's limit on the UNSCALED value, as its own split would report it (|a| <= 4094): the scaled value was compared here
+        // once, which moved conv3 a tier up for any conv2 output above 255.9 (tests/test_gpu_conv_forward_exact.py, the presplit pair)
+        lvc_report_range(p.flags, p.next_err_index, bigq, LVC_ACT_MAX);
       }
       else if (p.res_mode == 0) { if (p.relu) rows(T0{}, std::true_type{}, std::false_type{}); else rows(T0{}, std::false_type{}, std::false_type{}); }
       else if (p.res_mode == 1) { if (p.relu) rows(T1{}, std::true_type{}, std::false_type{}); else rows(T1{}, std::false_type{}, std::false_type{}); }

@@ -1,5 +1,7 @@
 """Shared test helpers: golden loading, the conditioned R50-FPN state_dict, detection matching."""
+import collections
 import os
+import types
 
 import numpy as np
 import torch
@@ -132,8 +134,6 @@ DGRAD_ENTRIES_REQUIRED = (_H3, _G3, _F32, _H2, _DMA)
 def dgrad_route(K, shape, split):
     """The entry point `kernels.conv_dgrad` runs the data gradient of forward layer `shape` on, from `kernels.conv_route` alone (no
     tensor, no library): the operand geometry of `kernels.pack_conv_dgrad` and the grid `conv_dgrad` multiplies on."""
-    import types
-
     N, H, W, Cin, Kout, R, stride, pad = shape
     pcd = types.SimpleNamespace(R=R, S=R, C=(Kout + 31) // 32 * 32, K=Cin, stride=1, pad=R - 1 - pad, mode=0, two_acc=False, state={"tier": 0})
     if stride == 1 or R != 1:
@@ -141,3 +141,183 @@ def dgrad_route(K, shape, split):
     else:
         h, w = (H - 1) // stride + 1, (W - 1) // stride + 1      # a strided 1x1: the product on the sub-sampled grid
     return K.conv_route(pcd, N, h, w, split=split).entry
+
+
+# ------------------------------------------------------------------- exact / fp64 conv tests: what the backward and the forward module share
+K_NOISE = 3.0      # test C: ours <= K x the noise of torch's fp32 CPU evaluation of the same inputs (test_gpu_grouped_conv.py)
+IMPULSE_BAR = {"f32": 0.0, "bf16x3": 2.0 ** -23, "f16x2": 2.0 ** -21}
+
+
+def ids(shape):
+    return "x".join(map(str, shape))
+
+
+def gen(shape, salt):
+    return torch.Generator().manual_seed(salt + sum((i + 1) * 7919 * v for i, v in enumerate(shape)))
+
+
+def ints(g, shape, m):
+    return torch.randint(-m, m + 1, shape, generator=g).float()
+
+
+def pow2(g, n):
+    return torch.tensor([0.5, 1.0, 2.0, 4.0])[torch.randint(0, 4, (n,), generator=g)]
+
+
+def full(g, shape, mag=1.0):
+    """Values with full fp32 mantissas and 2^-6 <= |v| / mag: inside fp16's normal range for mag = 1, second plane included."""
+    r = torch.randn(shape, generator=g)
+    return (r + torch.copysign(torch.full_like(r, 2.0 ** -6), r)) * mag
+
+
+def out_hw(H, W, R, stride, pad):
+    return (H + 2 * pad - R) // stride + 1, (W + 2 * pad - R) // stride + 1
+
+
+def assert_impulse(got, ref64, engine):
+    """Every element is one operand value or exactly 0: the per-engine bar of B."""
+    assert got.shape == ref64.shape
+    if engine == "f32":
+        assert torch.equal(got, ref64.float())
+        return
+    err = (got.double() - ref64).abs()
+    bad = err > IMPULSE_BAR[engine] * ref64.abs()
+    assert not bool(bad.any()), (int(bad.sum()), float((err / ref64.abs().clamp_min(1e-300))[bad].max()), int((ref64[bad] == 0).sum()))
+
+
+def stats(got, ref64):
+    d = got.double() - ref64
+    return float(d.norm() / ref64.norm().clamp_min(1e-300)), float(d.abs().max())
+
+
+def assert_noise(worst, key, engine, got, ref32, ref64):
+    """Both statistics of C against the fp32-CPU noise (clamped from below by one fp32 rounding of the result); prints ours / noise,
+    keeps the largest per engine in `worst` and returns the two ratios (the caller asserts them against its K)."""
+    assert got.shape == ref64.shape
+    zero = ref64 == 0
+    assert float(got[zero].abs().max() if bool(zero.any()) else 0.0) == 0.0, key      # taps that lie in the padding
+    o_rel, o_max = stats(got, ref64)
+    n_rel, n_max = stats(ref32, ref64)
+    n_rel, n_max = max(n_rel, 2.0 ** -25), max(n_max, 2.0 ** -24 * float(ref64.abs().max()))
+    r_rel, r_max = o_rel / n_rel, o_max / n_max
+    print("%-58s norm-rel ours %.3e noise %.3e ratio %5.2f | max-abs ours %.3e noise %.3e ratio %5.2f" % (key, o_rel, n_rel, r_rel, o_max, n_max, r_max))
+    w = worst.setdefault(engine, [0.0, 0.0])
+    w[0], w[1] = max(w[0], r_rel), max(w[1], r_max)
+    return r_rel, r_max
+
+
+# ------------------------------------------------------------------------------------------------ conv forward: shapes and routes
+# tests/test_gpu_conv_forward_exact.py.  The switches of lvc_amd/kernels.py every row starts from (a row's own switches override them):
+# the production configuration, with the size thresholds that keep small maps off a kernel taken away and Winograd off (its rows turn
+# it on).
+FWD_SWITCHES = {"CONV_ENGINE": "bf16x3", "CONV_SPLIT": "f16x2", "CONV_HALO": True, "_PW_NARROW": True, "HALO_S1": 2, "PW_S1": 2, "PW_W2": True,
+                "CONV_WINO": False, "WINO_RPN": False, "PRESPLIT": False, "_HALO_H2_MIN_TILES": 0, "_WINO_MIN_TILES": 1, "_PW_W2_MIN_C": 256,
+                "_PW_W2_MIN_ROWS": 1}
+# shape: (N, H, W, C, K, R, stride, pad); switches: module switches of this row; entry: the entry point the launch must land on;
+# opts: two_acc (pc.two_acc), res (the route needs a residual: only the epilogues with one run), streamk (WINO_STREAMK), patch / force
+# (lvc_set_halo_test_hooks), pad_c (the tensor is launched with its channels zero-padded to pad_c: `pack_conv` takes multiples of 32),
+# stem (`pack_conv(stem=True)` on NHWC4 rows), linear (`pack_linear` + `linear`).
+FwdCase = collections.namedtuple("FwdCase", "shape switches entry opts")
+_E = "lvc_conv2d_nhwc_f32 lvc_conv2d_nhwc_bf16x3 lvc_conv2d_nhwc_f16x2 lvc_conv2d_nhwc_f16x2_dma lvc_conv3x3_nhwc_bf16x3 lvc_conv3x3_nhwc_f16x2 " \
+     "lvc_conv3x3_nhwc_f16x2_pipe lvc_conv3x3_nhwc_f16s1 lvc_conv3x3_nhwc_wino lvc_conv1x1_nhwc_f16x2_pipe lvc_conv1x1_nhwc_f16s1 lvc_conv1x1_nhwc_f16s1_w2".split()
+_F32, _G3, _REG, _DMA, _H3, _H2, _H2P, _HS1, _WINO, _PWP, _PWS1, _PWW2 = _E
+
+
+def _fwd_cases():
+    rows = []
+
+    def add(shape, entry, switches=None, **opts):
+        rows.append(FwdCase(tuple(shape), dict(switches or {}), entry, dict(opts)))
+
+    # ---- 3x3 / stride 1 / pad 1: every shape on every form
+    s3 = ((1, 1, 1, 32, 64),        # single pixel: eight taps lie in the padding
+          (1, 2, 3, 32, 64),        # tiny map
+          (2, 7, 9, 32, 128),       # one partial patch, one channel chunk, image boundary inside a tile row
+          (1, 13, 21, 64, 132),     # K tail of 4
+          (1, 17, 33, 96, 128),     # odd width (Winograd's last pair has one pixel), W crosses the 32-column patch, H the 8- / 16-row ones, 3 chunks
+          (3, 16, 32, 128, 256))    # exact patch multiples, two channel tiles
+    for N, H, W, C, Kc in s3:
+        sh = (N, H, W, C, Kc, 3, 1, 1)
+        add(sh, _H3, {"CONV_SPLIT": "bf16x3"})              # (fewer than 128 tiles: the entry point hands over to the generic kernel)
+        if H * W >= 63:
+            add(sh, _H3, {"CONV_SPLIT": "bf16x3"}, force=1)     # ... and the halo kernel itself, as test_conv3x3_halo_matches_cpu forces it
+        add(sh, _H2, {"HALO_S1": 0})
+        add(sh, _H2P, {"HALO_S1": 1})
+        add(sh, _HS1)
+        if Kc >= 128:
+            for mode in (0, 1, 2):
+                add(sh, _WINO, {"CONV_WINO": True}, streamk=mode)
+    add((1, 13, 21, 64, 132, 3, 1, 1), _H2P, two_acc=True)       # the layer flag keeps two accumulators under HALO_S1 = 2
+    for patch in ((3, 70), (10, 24)):
+        add((1, 17, 33, 96, 128, 3, 1, 1), _H3, {"CONV_SPLIT": "bf16x3"}, force=1, patch=patch)
+    # ---- 1x1 with at least 2048 rows
+    add((2, 33, 32, 64, 256, 1, 1, 0), _PWP)                     # 2112 rows (a 64-row tail); C < 256 keeps two accumulators
+    add((2, 33, 32, 64, 256, 1, 1, 0), _DMA, {"PW_S1": 0})
+    add((2, 33, 32, 64, 256, 1, 1, 0), _G3, {"CONV_SPLIT": "bf16x3"})
+    add((2, 33, 32, 256, 64, 1, 1, 0), _PWS1)                    # 64-channel narrow tile
+    add((2, 33, 32, 256, 64, 1, 1, 0), _PWP, two_acc=True)
+    add((2, 33, 32, 256, 64, 1, 1, 0), _DMA, {"PW_S1": 0})
+    add((2, 33, 32, 256, 64, 1, 1, 0), _G3, {"CONV_SPLIT": "bf16x3"})
+    add((2, 33, 32, 256, 16, 1, 1, 0), _DMA)                     # 32-channel narrow tile (fewer than 64 outputs: never the pipelined kernel)
+    add((2, 33, 32, 256, 16, 1, 1, 0), _G3, {"CONV_SPLIT": "bf16x3"})
+    add((2, 33, 32, 288, 132, 1, 1, 0), _PWS1)                   # nine chunks, K tail
+    add((2, 33, 32, 288, 132, 1, 1, 0), _PWP, two_acc=True)
+    add((2, 33, 32, 288, 132, 1, 1, 0), _DMA, {"PW_S1": 0})
+    add((2, 33, 32, 288, 132, 1, 1, 0), _REG, {"PW_S1": 0}, res=1)      # a residual with K % 32 != 0: the register-staged kernel
+    add((2, 33, 32, 288, 132, 1, 1, 0), _G3, {"CONV_SPLIT": "bf16x3"})
+    add((2, 33, 32, 256, 256, 1, 1, 0), _PWW2)                   # the 256 x 256 tile ...
+    add((2, 33, 32, 256, 256, 1, 1, 0), _PWS1, {"PW_W2": False})      # ... against the 256 x 128 tile
+    add((2, 33, 32, 256, 256, 1, 1, 0), _PWP, two_acc=True)
+    add((2, 33, 32, 256, 256, 1, 1, 0), _DMA, {"PW_S1": 0})
+    add((2, 65, 65, 256, 128, 1, 2, 0), _PWS1)                   # stride 2 on an odd map: 2178 rows
+    add((2, 65, 65, 256, 128, 1, 2, 0), _PWP, two_acc=True)
+    add((2, 65, 65, 256, 128, 1, 2, 0), _DMA, {"PW_S1": 0})
+    add((2, 65, 65, 256, 128, 1, 2, 0), _G3, {"CONV_SPLIT": "bf16x3"})
+    add((2, 34, 32, 256, 256, 1, 1, 0), _PWW2, res=2)            # upsample-add: residual [2, 17, 16, 256]
+    add((2, 34, 32, 256, 256, 1, 1, 0), _PWS1, {"PW_W2": False}, res=2)
+    add((2, 34, 32, 256, 256, 1, 1, 0), _PWP, two_acc=True, res=2)
+    add((2, 34, 32, 256, 256, 1, 1, 0), _DMA, {"PW_S1": 0}, res=2)
+    add((2, 34, 32, 256, 256, 1, 1, 0), _G3, {"CONV_SPLIT": "bf16x3"}, res=2)
+    # ---- small and generic
+    add((1, 13, 21, 128, 132, 1, 1, 0), _G3)                     # fewer than 2048 rows
+    add((1, 13, 21, 256, 15, 1, 1, 0), _F32)                     # K % 4 != 0
+    add((1, 13, 21, 16, 64, 3, 1, 1), _F32, {"CONV_HALO": False}, pad_c=32)      # C % 32 != 0: launched zero-padded to 32 channels
+    add((1, 13, 21, 32, 32, 3, 1, 1), _F32)                      # a 3x3 with fewer than 64 output channels
+    add((1, 13, 21, 32, 128, 3, 2, 1), _G3)                      # strided 3x3, odd and even maps
+    add((1, 12, 20, 32, 128, 3, 2, 1), _G3)
+    add((1, 1, 9, 128, 128, 1, 2, 0), _G3)                       # strided 1x1 on a one-row map
+    add((1, 37, 41, 3, 64, 7, 2, 3), _F32, stem=True)            # BasicStem's 7x7 / 2 on NHWC4 rows
+    add((2, 14, 18, 3, 64, 7, 2, 3), _F32, stem=True)
+    add((300, 1, 1, 1024, 81, 1, 1, 0), _F32, linear=True)       # the box predictor's class scores
+    return tuple(rows)
+
+
+FWD_CASES = _fwd_cases()
+# the fused and multi-map launches the forward module drives next to `conv2d_nhwc`: its tests take the entry point they assert from here,
+# so the host test's union over this table cannot stay whole when one of them goes
+FWD_FUSED = {"levels": "lvc_conv3x3_nhwc_f16_levels", "layers": "lvc_conv3x3_nhwc_f16_layers", "levels_pred": "lvc_conv3x3_nhwc_f16_levels_pred",
+             "wino_pred": "lvc_conv3x3_nhwc_wino_pred", "presplit_3x3": "lvc_conv3x3_nhwc_f16s1_presplit",
+             "presplit_1x1": "lvc_conv1x1_nhwc_f16s1_presplit", "chain": "lvc_conv1x1_chain_nhwc_f16s1", "bottleneck": "lvc_bottleneck_nhwc_f16s1"}
+FWD_FUSED_ENTRIES = tuple(FWD_FUSED.values())
+
+
+def fwd_case_id(case):
+    opts = "".join("-%s%s" % (k, "" if v is True else "x".join(map(str, v)) if isinstance(v, tuple) else v) for k, v in sorted(case.opts.items()))
+    return "%s-%s%s" % (ids(case.shape), case.entry[4:].replace("_nhwc", ""), opts)
+
+
+def fwd_set_switches(monkeypatch, K, case):
+    for name, value in dict(FWD_SWITCHES, **case.switches).items():
+        monkeypatch.setattr(K, name, value)
+
+
+def fwd_route(K, case, res_mode=0, ldo=None):
+    """The entry point `kernels.conv2d_nhwc` runs `case` on under the switches as they are (`fwd_set_switches`), from `kernels.conv_route`
+    on plain numbers: res_mode 0 / 1 / 2 the residual operand, ldo the last dimension of the output buffer (None: K)."""
+    N, H, W, C, Kc, R, stride, pad = case.shape
+    o = case.opts
+    C = 4 if o.get("stem") else o.get("pad_c", C)
+    pc = types.SimpleNamespace(R=R, S=R, C=C, K=Kc, stride=stride, pad=pad, mode=1 if o.get("stem") else 0, two_acc=bool(o.get("two_acc")), state={"tier": 0})
+    Ho, Wo = out_hw(H, W, R, stride, pad)
+    res_numel = 0 if not res_mode else N * Ho * Wo * Kc if res_mode == 1 else N * (Ho // 2) * (Wo // 2) * Kc
+    return K.conv_route(pc, N, H, W, ldo=ldo, out_numel=None if ldo is None else N * Ho * Wo * ldo, ldr=Kc if res_mode else None, res_numel=res_numel).entry

@@ -35,7 +35,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from helpers import DGRAD_CASES, WGRAD_SHAPES, dgrad_route
+from helpers import DGRAD_CASES, WGRAD_SHAPES, assert_noise, dgrad_route
+from helpers import assert_impulse as _assert_impulse, full as _full, gen as _gen, ids as _ids, ints as _ints, out_hw as _out_hw, pow2 as _pow2
 
 pytestmark = pytest.mark.gpu
 
@@ -45,37 +46,14 @@ _WORST = {}      # engine -> largest ours / noise of this run (norm-relative, ma
 
 ENGINES = ("bf16x3", "f32", "f16x2")
 SPLITS = ("bf16x3", "f16x2")
-IMPULSE_BAR = {"f32": 0.0, "bf16x3": 2.0 ** -23, "f16x2": 2.0 ** -21}
-
-
-def _ids(shape):
-    return "x".join(map(str, shape))
 
 
 def _dev():
     return torch.device("cuda:0")
 
 
-def _gen(shape, salt):
-    return torch.Generator().manual_seed(salt + sum((i + 1) * 7919 * v for i, v in enumerate(shape)))
-
-
-def _ints(g, shape, m):
-    return torch.randint(-m, m + 1, shape, generator=g).float()
-
-
-def _pow2(g, n):
-    return torch.tensor([0.5, 1.0, 2.0, 4.0])[torch.randint(0, 4, (n,), generator=g)]
-
-
-def _full(g, shape, mag=1.0):
-    """Values with full fp32 mantissas and 2^-6 <= |v| / mag: inside fp16's normal range for mag = 1, second plane included."""
-    r = torch.randn(shape, generator=g)
-    return (r + torch.copysign(torch.full_like(r, 2.0 ** -6), r)) * mag
-
-
-def _out_hw(H, W, R, stride, pad):
-    return (H + 2 * pad - R) // stride + 1, (W + 2 * pad - R) // stride + 1
+def _assert_noise(key, engine, got, ref32, ref64):
+    return assert_noise(_WORST, key, engine, got, ref32, ref64)
 
 
 def _wgrad_ref(x, dy, scale, R, stride, pad, dtype=torch.float64):
@@ -138,37 +116,6 @@ def _dgrad(Kn, monkeypatch, shape, want, split, dy, w, scale):
 def _dgrad_engine(want, split):
     e = want[split]
     return "f32" if e.endswith("_f32") else "f16x2" if "f16x2" in e else "bf16x3"
-
-
-def _assert_impulse(got, ref64, engine):
-    """Every element is one operand value or exactly 0: the per-engine bar of B."""
-    assert got.shape == ref64.shape
-    if engine == "f32":
-        assert torch.equal(got, ref64.float())
-        return
-    err = (got.double() - ref64).abs()
-    bad = err > IMPULSE_BAR[engine] * ref64.abs()
-    assert not bool(bad.any()), (int(bad.sum()), float((err / ref64.abs().clamp_min(1e-300))[bad].max()), int((ref64[bad] == 0).sum()))
-
-
-def _stats(got, ref64):
-    d = got.double() - ref64
-    return float(d.norm() / ref64.norm().clamp_min(1e-300)), float(d.abs().max())
-
-
-def _assert_noise(key, engine, got, ref32, ref64):
-    """Both statistics of C against K x the fp32-CPU noise (clamped from below by one fp32 rounding of the result); prints ours / noise."""
-    assert got.shape == ref64.shape
-    zero = ref64 == 0
-    assert float(got[zero].abs().max() if bool(zero.any()) else 0.0) == 0.0, key      # taps that lie in the padding
-    o_rel, o_max = _stats(got, ref64)
-    n_rel, n_max = _stats(ref32, ref64)
-    n_rel, n_max = max(n_rel, 2.0 ** -25), max(n_max, 2.0 ** -24 * float(ref64.abs().max()))
-    r_rel, r_max = o_rel / n_rel, o_max / n_max
-    print("%-58s norm-rel ours %.3e noise %.3e ratio %5.2f | max-abs ours %.3e noise %.3e ratio %5.2f" % (key, o_rel, n_rel, r_rel, o_max, n_max, r_max))
-    w = _WORST.setdefault(engine, [0.0, 0.0])
-    w[0], w[1] = max(w[0], r_rel), max(w[1], r_max)
-    return r_rel, r_max
 
 
 @pytest.fixture(scope="module", autouse=True)

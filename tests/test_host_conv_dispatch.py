@@ -154,6 +154,30 @@ def test_data_gradient_cases_reach_their_entry_points(monkeypatch):
     assert len({shape for shape, _ in DGRAD_CASES}) == len(DGRAD_CASES)
 
 
+def test_forward_exact_cases_reach_their_entry_points(monkeypatch):
+    """The rows of helpers.FWD_CASES (tests/test_gpu_conv_forward_exact.py) land on the entry points they name -- `conv_route` on plain
+    numbers under each row's switches, with the residual a row needs for its route -- and, with the fused launches that module drives,
+    name every forward entry point there is: a change of the routing cannot quietly move a GPU case onto another kernel."""
+    from helpers import FWD_CASES, FWD_FUSED_ENTRIES, fwd_case_id, fwd_route, fwd_set_switches
+    from lvc_amd import _lib
+    from lvc_amd import kernels as K
+
+    def no_library():
+        raise AssertionError("conv_route touched the native library")
+
+    monkeypatch.setattr(_lib, "lib", no_library)
+    for case in FWD_CASES:
+        fwd_set_switches(monkeypatch, K, case)
+        got = fwd_route(K, case, res_mode=case.opts.get("res", 0))
+        assert got == case.entry, (fwd_case_id(case), got)
+        if case.opts.get("pad_c"):      # the row as written (its own channel count) is the fp32 kernel's as well
+            assert fwd_route(K, case._replace(opts={}), 0) == case.entry
+    assert len({fwd_case_id(c) for c in FWD_CASES}) == len(FWD_CASES)
+    six = {"lvc_conv2d_nhwc_f32", "lvc_conv2d_nhwc_bf16x3", "lvc_conv2d_nhwc_f16x2", "lvc_conv2d_nhwc_f16x2_dma", "lvc_conv3x3_nhwc_bf16x3",
+           "lvc_conv3x3_nhwc_f16x2"}
+    assert {c.entry for c in FWD_CASES} | set(FWD_FUSED_ENTRIES) == (set(ENTRY_POINTS) - {"lvc_gelu"}) | six
+
+
 def test_data_gradient_of_an_unbuilt_strided_layer_says_so():
     """Strided layers have a data gradient for 1x1 / padding 0 and 3x3 / padding 1 at stride 2; anything else raises a
     NotImplementedError that names the layer before anything is launched (no bare assert in the middle of a backward pass)."""
