@@ -189,7 +189,10 @@ class GradientBuckets:
             return
         from . import kernels as K
 
-        if K.wgrad_queued(p):   # more of this parameter's gradient is still to come (another use's deferred job): not final yet
+        # more of this parameter's gradient is still to come (a deferred job in the queue): not final yet.  The queue alone decides: this
+        # runs after AccumulateGrad (every use of the pass has run its backward node) or from a flush that delivers only parameters whose
+        # uses are done -- `kernels._WGRAD_USES` also counts forwards whose backward never ran and must not hold a gradient back here
+        if K.wgrad_job_queued(p):
             return
         bi, off = self._where[id(p)]
         b = self.buckets[bi]
@@ -242,6 +245,9 @@ class GradientBuckets:
             b["pending"], b["launched"] = len(b["params"]), False
             b["seen"].clear()
         self._next = 0
+        from . import kernels as K
+
+        K.forget_wgrad_uses(self.params)      # uses counted by forwards of this step whose backward never ran
         n, self.bytes_reduced = self.bytes_reduced, 0
         return n
 

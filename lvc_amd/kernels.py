@@ -2813,10 +2813,20 @@ def wgrad_use_done(param):
         _WGRAD_USES[id(param)] = n - 1
 
 
-def wgrad_queued(param):
-    """True while a deferred weight gradient of `param` waits in the queue or more uses of it have yet to run their backward:
-    its gradient is not final (lvc_amd.distributed.GradientBuckets._hook)."""
-    return _WGRAD_USES.get(id(param), 0) > 0 or any(j[0] is param for j in _WGRAD_Q)
+def wgrad_job_queued(param):
+    """True while a deferred weight gradient of `param` waits in the queue: its gradient is not final
+    (lvc_amd.distributed.GradientBuckets._hook).  That is all a post-accumulate hook needs to know: the engine
+    runs a parameter's AccumulateGrad node only after every use of this pass has run its backward node, so by then whatever is still to
+    come is in the queue -- the use counts say nothing there, and a forward whose backward never ran leaves them positive."""
+    return any(j[0] is param for j in _WGRAD_Q)
+
+
+def forget_wgrad_uses(params):
+    """Drop the use counts of `params`: the step is over (`GradientBuckets.finish`).  Counts left by forwards whose backward never ran
+    -- a pass repeated after Fp16RangeError, an exception, a loss that was skipped -- would otherwise hold the parameters back in every
+    later non-final flush, and for ever where no deferred job is queued (LVC_DEFER_WGRAD=0, another weight-gradient engine)."""
+    for p in params:
+        _WGRAD_USES.pop(id(p), None)
 
 
 def can_defer_wgrad(x, g):
@@ -2846,8 +2856,8 @@ def flush_wgrad(final=False):
     if final:
         q = list(_WGRAD_Q)
         del _WGRAD_Q[:]
-        # uses counted by a forward whose backward never ran (two forwards, one backward) made `wgrad_queued` hold back parameters that
-        # got their whole gradient through AccumulateGrad: report those now, the pass is over
+        # uses counted by a forward whose backward never ran (two forwards, one backward): the pass is over, the counts go, and a sink
+        # whose parameter got its whole gradient through AccumulateGrad is told once more (a report it has seen already changes nothing)
         stale = [i for i, n in _WGRAD_USES.items() if n > 0]
         _WGRAD_USES.clear()
         queued = {id(j[0]) for j in q}

@@ -145,7 +145,10 @@ class FPN(Backbone):
         bottom_up = self.bottom_up.forward_nhwc(x4)
         x = [bottom_up[f] for f in self.in_features[::-1]]
         results = []
-        grad_free = not torch.is_grad_enabled() or not any(p.requires_grad for p in self.parameters())
+        # gradient-free: autograd off, or nothing here trains AND no trunk map requires grad -- the merged launch returns detached
+        # tensors, and a frozen pyramid over a training trunk (a stub or wrapped `bottom_up` whose parameters are not this module's)
+        # must still hand the trunk its gradient
+        grad_free = not torch.is_grad_enabled() or not (any(t.requires_grad for t in x) or any(p.requires_grad for p in self.parameters()))
         if grad_free and MERGE_OUTPUT_CONVS and all(c.norm is None and c.activation is None for c in self.output_convs):
             # the top-down path first (lateral + upsample-add, coarse to fine), then the output convs of ALL levels as one launch
             # (kernels.conv3x3_levels: a layer per map; the small levels no longer pay a launch each that cannot fill the chip)

@@ -61,11 +61,11 @@ class BottleneckBlock(CNNBlockBase):
             if layer is not None:
                 weight_init.c2_msra_fill(layer)
 
-    def can_fuse_projection(self):
+    def can_fuse_projection(self, *inputs):
         """Gradient-free passes only (inference, or a frozen block in training -- res2 under FREEZE_AT 2): conv3 and a
         stride-1 projection shortcut (res2.0: both 64 -> 256 at 1/4 resolution, both HBM streams) as ONE pointwise GEMM
-        over the concatenated input [conv2 output | block input]."""
-        grad_free = not torch.is_grad_enabled() or not any(p.requires_grad for p in self.parameters())
+        over the concatenated input [conv2 output | block input].  inputs: the tensors the pass reads (`_grad_free`)."""
+        grad_free = self._grad_free(*inputs)
         # stride 2 in the 1x1 layers (res3.0 / res4.0 / res5.0 with STRIDE_IN_1X1): the shortcut samples x[:, ::2, ::2]; that sampling is
         # a copy into the buffer's tail channels (kernels.subsample2_into) -- the strided projection launch (168 us on res3.0 for 137 MB
         # read + 275 MB written) and the residual round trip of its output go away
@@ -95,18 +95,25 @@ class BottleneckBlock(CNNBlockBase):
             self._cache_fused = _PackedCache()
         return self._cache_fused.get([self.conv3.weight, self.shortcut.weight, a3[0], a3[1], asc[0], asc[1]], build)
 
-    def _grad_free(self):
-        return not torch.is_grad_enabled() or not any(p.requires_grad for p in self.parameters())
+    def _grad_free(self, *inputs):
+        """No gradient is asked of this pass: autograd is off, or the block's parameters are frozen AND none of the tensors it reads
+        (`inputs`: x, the look-ahead t; None entries are skipped) requires grad.  The fused launches return detached tensors: a frozen
+        block fed an input that requires grad must take the autograd path, or everything below it trains on no gradient."""
+        if not torch.is_grad_enabled():
+            return True
+        if any(t is not None and t.requires_grad for t in inputs):
+            return False
+        return not any(p.requires_grad for p in self.parameters())
 
-    def chain_to(self, nxt, fused_projection):
+    def chain_to(self, nxt, fused_projection, *inputs):
         """conv3 (+ shortcut add + ReLU) of this block and conv1 (+ ReLU) of `nxt` as ONE launch (csrc/conv_pw_chain.hip): the
         4x-wide block output is written once and never read back by conv1.  Returns the packed pair, or None when the pair is
-        outside that kernel's range (gradient passes, a strided conv1, channel counts it has no instance for, a layer that must
-        keep two accumulators, the range-free split)."""
+        outside that kernel's range (gradient passes -- `inputs`: the tensors this block reads, `_grad_free` --, a strided conv1,
+        channel counts it has no instance for, a layer that must keep two accumulators, the range-free split)."""
         if nxt is not None and nxt.fused_eligible():
             return None     # the next block is one launch of its own: it reads this block's output, not a conv1 result
         if not (K.CHAIN and K.CONV_ENGINE == "bf16x3" and K.CONV_SPLIT == "f16x2" and K.PW_S1 == 2 and nxt is not None
-                and self._grad_free() and nxt._grad_free() and nxt.conv1.stride == 1 and self.conv2.stride == 1
+                and self._grad_free(*inputs) and nxt._grad_free() and nxt.conv1.stride == 1 and self.conv2.stride == 1
                 and not getattr(self.conv3, "two_acc", False) and not getattr(nxt.conv1, "two_acc", False)):
             return None
         k1 = self.conv2.out_channels + (self.in_channels if fused_projection else 0)
@@ -122,8 +129,8 @@ class BottleneckBlock(CNNBlockBase):
         pb = nxt.conv1.packed()
         return self._cache_chain.get([pa.w, pa.scale, pa.shift, pb.w, pb.scale, pb.shift], lambda: K.pack_chain(pa, pb, self._chain_state))
 
-    def fused_eligible(self):
-        """The cheap half of `fused`: everything but the packing (flags, shapes, gradient-free pass, range state).  `ResNet.forward_nhwc`
+    def fused_eligible(self, *inputs):
+        """The cheap half of `fused`: everything but the packing (flags, shapes, gradient-free pass over `inputs`, range state).  `ResNet.forward_nhwc`
         decides with it whether the stem writes a second copy of its output BEFORE the stem is launched -- at the top of a step the GPU
         queue is empty and every host microsecond in front of the first launches is exposed."""
         if not (K.BNECK and K.CONV_ENGINE == "bf16x3" and K.CONV_SPLIT == "f16x2" and self.conv1.stride == 1 and self.conv2.stride == 1
@@ -134,18 +141,18 @@ class BottleneckBlock(CNNBlockBase):
             return False
         if getattr(self, "_bneck_state", None) is not None and self._bneck_state["off"]:
             return False     # an operand left the kernel's range once (|a| > 4094): the block's layers run on their own tiers from then on
-        if not self._grad_free():
+        if not self._grad_free(*inputs):
             return False
-        if proj and (self.shortcut.stride != 1 or not self.can_fuse_projection()):
+        if proj and (self.shortcut.stride != 1 or not self.can_fuse_projection(*inputs)):
             return False
         layers = (self.conv1, self.conv2, self.conv3, self.shortcut) if proj else (self.conv1, self.conv2, self.conv3)
         return not any(not l._folds_norm() or getattr(l, "two_acc", False) or l._range_state["tier"] for l in layers)
 
-    def fused(self):
+    def fused(self, *inputs):
         """The whole block as ONE launch (csrc/conv_bneck.hip: conv1's output in LDS, conv2's in registers) -- the packed weights, or None
         when the block is outside that kernel's range: gradient passes, strides, channel counts other than res2's (64 mid / 256 out,
         256 in with the identity shortcut or 64 in with a stride-1 projection), a layer off the one-accumulator tier, `K.BNECK` off."""
-        if not self.fused_eligible():
+        if not self.fused_eligible(*inputs):
             return None
         proj = self.shortcut is not None
         if not hasattr(self, "_cache_bneck"):
@@ -162,26 +169,25 @@ class BottleneckBlock(CNNBlockBase):
         tail already produced it (else None); nxt: the following block of the stage (or None).  Returns (block output,
         conv1 output of `nxt` or None).  concat: as `forward_nhwc`."""
         if t is None and concat is None:
-            bk = self.fused()
+            bk = self.fused(x)
             if bk is not None and x.shape[0] * x.shape[1] * x.shape[2] * max(x.shape[3], 256) * 4 < 0xFFF00000:
                 return K.bottleneck_fused(x, bk), None
         if t is None:
             t = self.conv1.forward_nhwc(x)
-        if (concat is None and self.shortcut is not None and self.shortcut.stride == 2 and self.can_fuse_projection()
-                and self.chain_to(nxt, False) is None):      # res3.0 keeps its conv3 -> res3.1.conv1 chain (shortcut as the residual)
+        if (concat is None and self.shortcut is not None and self.shortcut.stride == 2 and self.can_fuse_projection(x, t)
+                and self.chain_to(nxt, False, x, t) is None):      # res3.0 keeps its conv3 -> res3.1.conv1 chain (shortcut as the residual)
             # a stage head with stride 2: [conv2 output | x sampled at the even pixels] built here (res2.0's buffer comes from the stem)
             cb = self.conv2.out_channels
             concat = torch.empty(t.shape[0], t.shape[1], t.shape[2], cb + self.in_channels, device=t.device, dtype=torch.float32)
             K.subsample2_into(x, concat[..., cb:])
         if concat is not None:
             K.conv2d_nhwc(t, self.conv2.packed(), relu=True, out=concat)      # channels [0, bottleneck), row stride = buffer
-            ch = self.chain_to(nxt, True)
+            ch = self.chain_to(nxt, True, x, t)
             if ch is not None and concat.numel() < (1 << 29):
                 return K.conv1x1_chain(concat, ch)
             return K.conv2d_nhwc(concat, self._fused_projection(), relu=True), None
-        ch = self.chain_to(nxt, False)
-        if (ch is None and self.conv2.activation is not None and self._grad_free()
-                and not (torch.is_grad_enabled() and (t.requires_grad or x.requires_grad))):
+        ch = self.chain_to(nxt, False, x, t)
+        if ch is None and self.conv2.activation is not None and self._grad_free(x, t):
             p2, p3 = self.conv2.packed(), self.conv3.packed()
             shortcut = self.shortcut.forward_nhwc(x) if self.shortcut is not None else x
             if K.presplit_pair_ok(t, p2, p3, shortcut):
@@ -376,8 +382,8 @@ class ResNet(Backbone):
         outputs = {}
         first = self.stages_and_names[0][0][0] if self.stages_and_names else None
         concat = []
-        if (isinstance(first, BottleneckBlock) and first.shortcut is not None and first.shortcut.stride == 1 and first.can_fuse_projection()
-                and not first.fused_eligible()):   # the stem writes into a concat buffer at ITS resolution: stride-1 projections only
+        if (isinstance(first, BottleneckBlock) and first.shortcut is not None and first.shortcut.stride == 1 and first.can_fuse_projection(x4)
+                and not first.fused_eligible(x4)):   # the stem writes into a concat buffer at ITS resolution: stride-1 projections only
             # the stem writes its output a second time, into the tail channels of res2.0's [conv2 output | x] buffer
             def second(shape):
                 n, h, w, c = shape

@@ -321,3 +321,13 @@ def fwd_route(K, case, res_mode=0, ldo=None):
     Ho, Wo = out_hw(H, W, R, stride, pad)
     res_numel = 0 if not res_mode else N * Ho * Wo * Kc if res_mode == 1 else N * (Ho // 2) * (Wo // 2) * Kc
     return K.conv_route(pc, N, H, W, ldo=ldo, out_numel=None if ldo is None else N * Ho * Wo * ldo, ldr=Kc if res_mode else None, res_numel=res_numel).entry
+
+
+class Recorded:
+    """`kernels._launch` wrapped (the bracket around every conv / GEMM launch): `ran` lists the entry points that ran, in order.
+    monkeypatch undoes the wrap when the test ends; `ran.clear()` starts a new list."""
+
+    def __init__(self, K, monkeypatch):
+        self.ran = []
+        launch = K._launch
+        monkeypatch.setattr(K, "_launch", lambda tag, flops, nbytes, slot, what, call: (self.ran.append(what), launch(tag, flops, nbytes, slot, what, call))[1])
