@@ -18,26 +18,20 @@
 // after the fmod matters); HSV -> RGB is in integers (Pillow rounds v * (1 - s * f) half away from zero; the exact quotient over
 // 255 * 255 is never at a half, and the integer form equals Pillow on all 2^24 triples).  Channels are taken by position.
 // EXACT flags (-ffp-contract=off -fno-fast-math).
-#include "common.h"
+#include "input_common.h"
 
-#define CJ_HEAD 20        // int64 words in front of a job's tiles
-#define CJ_TILE 12        // int64 words per tile (the tile layout of lvc_train_input_tiles_u8)
-#define CJ_MAX_TILES 9
-#define CJ_FIELDS (CJ_HEAD + CJ_MAX_TILES * CJ_TILE)   // 128 words = 1 KiB per job (lvc_amd.h)
-#define CJ_FILL 114
-#define CJ_COORD_MAX (1ll << 30)
+#define CJ_FIELDS (TL_HEAD + TL_MAX_TILES * TL_WORDS)   // 128 words = 1 KiB per job (lvc_amd.h); the tile list: input_common.h
 #define CJ_PIX 4          // pixels per thread
 #define CJ_BLOCK 256
 #define CJ_MAX_GRID (1 << 18)   // workgroups per job; larger windows are walked in strides
 
 enum { CJ_X0 = 0, CJ_Y0, CJ_CW, CJ_CH, CJ_OUT, CJ_NOPS, CJ_OP0, CJ_F0 = CJ_OP0 + 4, CJ_NT = CJ_F0 + 4, CJ_SUM = 19 };
-enum { CL_SRC = 0, CL_H, CL_W, CL_SY, CL_SX, CL_SC, CL_X1A, CL_Y1A, CL_X2A, CL_Y2A, CL_X1B, CL_Y1B };
 enum { CJ_BRIGHTNESS = 0, CJ_CONTRAST, CJ_SATURATION, CJ_HUE };
 
 // the tiles of a job in window coordinates, in paint order
 struct CjTiles {
-  int lo_x[CJ_MAX_TILES], hi_x[CJ_MAX_TILES], lo_y[CJ_MAX_TILES], hi_y[CJ_MAX_TILES];
-  long long base[CJ_MAX_TILES], sy[CJ_MAX_TILES], sx[CJ_MAX_TILES], sc[CJ_MAX_TILES];   // window pixel (y, x): base + y * sy + x * sx
+  int lo_x[TL_MAX_TILES], hi_x[TL_MAX_TILES], lo_y[TL_MAX_TILES], hi_y[TL_MAX_TILES];
+  long long base[TL_MAX_TILES], sy[TL_MAX_TILES], sx[TL_MAX_TILES], sc[TL_MAX_TILES];   // window pixel (y, x): base + y * sy + x * sx
   int n;
 };
 
@@ -50,13 +44,13 @@ struct CjOps {
 __device__ __forceinline__ void cj_load_tiles(const long long* jb, CjTiles* tl) {
   const int t = threadIdx.x, nt = (int)jb[CJ_NT];
   if (t < nt) {
-    const long long* q = jb + CJ_HEAD + (size_t)t * CJ_TILE;
+    const long long* q = jb + TL_HEAD + (size_t)t * TL_WORDS;
     const long long X0 = jb[CJ_X0], Y0 = jb[CJ_Y0], cw = jb[CJ_CW], ch = jb[CJ_CH];
-    const long long lx = q[CL_X1A] - X0, hx = q[CL_X2A] - X0, ly = q[CL_Y1A] - Y0, hy = q[CL_Y2A] - Y0;
+    const long long lx = q[TL_X1A] - X0, hx = q[TL_X2A] - X0, ly = q[TL_Y1A] - Y0, hy = q[TL_Y2A] - Y0;
     tl->lo_x[t] = (int)(lx > 0 ? lx : 0); tl->hi_x[t] = (int)(hx < cw ? hx : cw);
     tl->lo_y[t] = (int)(ly > 0 ? ly : 0); tl->hi_y[t] = (int)(hy < ch ? hy : ch);
-    tl->sy[t] = q[CL_SY]; tl->sx[t] = q[CL_SX]; tl->sc[t] = q[CL_SC];
-    tl->base[t] = q[CL_SRC] + (Y0 - q[CL_Y1A] + q[CL_Y1B]) * q[CL_SY] + (X0 - q[CL_X1A] + q[CL_X1B]) * q[CL_SX];
+    tl->sy[t] = q[TL_SY]; tl->sx[t] = q[TL_SX]; tl->sc[t] = q[TL_SC];
+    tl->base[t] = q[TL_SRC] + (Y0 - q[TL_Y1A] + q[TL_Y1B]) * q[TL_SY] + (X0 - q[TL_X1A] + q[TL_X1B]) * q[TL_SX];
   }
   if (t == 0) tl->n = nt;
 }
@@ -71,12 +65,12 @@ __device__ __forceinline__ void cj_load_ops(const long long* jb, CjOps& o, int n
   }
 }
 
-// window pixel (y, x) through the tile list: the last tile that covers it, CJ_FILL where none does
+// window pixel (y, x) through the tile list: the last tile that covers it, TL_FILL where none does
 __device__ __forceinline__ void cj_fetch(const CjTiles* tl, int y, int x, int& c0, int& c1, int& c2) {
   int own = -1;
   for (int i = 0; i < tl->n; ++i)
     if (tl->lo_x[i] <= x && x < tl->hi_x[i] && tl->lo_y[i] <= y && y < tl->hi_y[i]) own = i;
-  c0 = c1 = c2 = CJ_FILL;
+  c0 = c1 = c2 = TL_FILL;
   if (own >= 0) {
     const long long sc = tl->sc[own];
     const unsigned char* p = reinterpret_cast<const unsigned char*>(tl->base[own] + y * tl->sy[own] + x * tl->sx[own]);
@@ -229,14 +223,9 @@ __global__ __launch_bounds__(CJ_BLOCK) void color_jitter_pixels_kernel(const cha
   }
 }
 
-// h_blob: host, blob_bytes bytes: int64 jobs [B][128]; d_blob: its device copy (uploaded by the caller on `stream` or ordered before
-// it; it is WRITTEN: word 19 receives the grey-level sum).  Job words: 0 X0, 1 Y0, 2 cw, 3 ch (the crop window in canvas
-// coordinates), 4 byte offset of the job's packed [ch][cw][3] output in `out` (a multiple of 4; outputs must not overlap), 5 n_ops
-// (0..4), 6-9 op ids in the order they are applied (0 brightness, 1 contrast, 2 saturation, 3 hue; at most one contrast step),
-// 10-13 their factors (the bits of an fp32 in the low half; hue: the hue_factor in [-0.5, 0.5]), 14 number of tiles (1..9), 15-18
-// reserved, 19 must be 0; tile t at words 20 + 12 t as in lvc_train_input_tiles_u8.  Checked on the host copy before anything is
-// launched: every pixel of a rectangle that the window sees lies inside its tile, outputs inside `out`.  launches: optional, the
-// number of kernel launches issued (two).
+// Job words and arguments: include/lvc_amd.h.  d_blob is WRITTEN: word 19 receives the grey-level sum.  Checked on the host copy
+// before anything is launched: every pixel of a rectangle that the window sees lies inside its tile, outputs inside `out`.
+// launches: optional, the number of kernel launches issued (two).
 extern "C" int lvc_color_jitter_tiles_u8(const void* h_blob, void* d_blob, long long blob_bytes, int B, unsigned char* out,
                                          long long out_bytes, int* launches, void* stream) {
   if (launches) *launches = 0;
@@ -244,27 +233,13 @@ extern "C" int lvc_color_jitter_tiles_u8(const void* h_blob, void* d_blob, long 
   if (B == 0) return LVC_OK;
   LVC_CHECK_ARG(h_blob && d_blob && out, "null argument");
   LVC_CHECK_ARG(((uintptr_t)h_blob & 7) == 0 && ((uintptr_t)d_blob & 7) == 0 && ((uintptr_t)out & 3) == 0, "the blob must be 8-byte, the output 4-byte aligned");
-  LVC_CHECK_ARG(blob_bytes >= (long long)B * CJ_FIELDS * 8, "blob smaller than its job table");
+  LVC_CHECK_MSG(check_blob(h_blob, d_blob, blob_bytes, B, CJ_FIELDS));
   const long long* jobs = reinterpret_cast<const long long*>(h_blob);
   long long most = 0;
   for (int i = 0; i < B; ++i) {
     const long long* j = jobs + (size_t)i * CJ_FIELDS;
-    const long long X0 = j[CJ_X0], Y0 = j[CJ_Y0], cw = j[CJ_CW], ch = j[CJ_CH];
-    LVC_CHECK_ARG(j[CJ_NT] >= 1 && j[CJ_NT] <= CJ_MAX_TILES, "a job has 1 to 9 tiles");
-    LVC_CHECK_ARG(X0 >= 0 && Y0 >= 0 && cw > 0 && ch > 0 && X0 < CJ_COORD_MAX && Y0 < CJ_COORD_MAX && cw < CJ_COORD_MAX &&
-                  ch < CJ_COORD_MAX, "bad crop window");
-    for (int t = 0; t < (int)j[CJ_NT]; ++t) {
-      const long long* tl = j + CJ_HEAD + (size_t)t * CJ_TILE;
-      LVC_CHECK_ARG(tl[CL_SRC] && tl[CL_H] > 0 && tl[CL_W] > 0 && tl[CL_H] < CJ_COORD_MAX && tl[CL_W] < CJ_COORD_MAX, "bad tile image");
-      LVC_CHECK_ARG(tl[CL_SY] > 0 && tl[CL_SX] > 0 && tl[CL_SC] > 0, "strides must be positive");
-      for (int f = CL_X1A; f <= CL_Y1B; ++f) LVC_CHECK_ARG(tl[f] > -CJ_COORD_MAX && tl[f] < CJ_COORD_MAX, "tile coordinate out of range");
-      LVC_CHECK_ARG(tl[CL_X2A] >= tl[CL_X1A] && tl[CL_Y2A] >= tl[CL_Y1A], "canvas rectangle with negative extent");
-      const long long lx = tl[CL_X1A] > X0 ? tl[CL_X1A] : X0, hx = tl[CL_X2A] < X0 + cw ? tl[CL_X2A] : X0 + cw;
-      const long long ly = tl[CL_Y1A] > Y0 ? tl[CL_Y1A] : Y0, hy = tl[CL_Y2A] < Y0 + ch ? tl[CL_Y2A] : Y0 + ch;
-      if (lx < hx && ly < hy)      // the part of the tile's rectangle the window sees: read from inside the tile
-        LVC_CHECK_ARG(lx - tl[CL_X1A] + tl[CL_X1B] >= 0 && hx - tl[CL_X1A] + tl[CL_X1B] <= tl[CL_W] &&
-                      ly - tl[CL_Y1A] + tl[CL_Y1B] >= 0 && hy - tl[CL_Y1A] + tl[CL_Y1B] <= tl[CL_H], "a tile is read outside its image");
-    }
+    const long long cw = j[CJ_CW], ch = j[CJ_CH];
+    LVC_CHECK_MSG(check_window_tiles(j, j[CJ_NT], j + TL_HEAD));
     LVC_CHECK_ARG(j[CJ_NOPS] >= 0 && j[CJ_NOPS] <= 4, "a job has 0 to 4 steps");
     int contrasts = 0;
     for (int k = 0; k < (int)j[CJ_NOPS]; ++k) {

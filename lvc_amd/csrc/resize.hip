@@ -7,16 +7,9 @@
 // The resample is Pillow's (third-party, src/libImaging/Resample.c ImagingResampleHorizontal_8bpc / Vertical_8bpc),
 // bit for bit: 22-bit fixed-point coefficients (computed on the host in double exactly as precompute_coeffs /
 // normalize_coeffs_8bpc do, lvc_amd/data/transforms.py), a horizontal pass into a uint8 intermediate, then a vertical
-// pass; each output = clip8((2^21 + sum k * pixel) >> 22) in int32.  Integer work: bit-exact by construction.
+// pass; each output = clip8((2^21 + sum k * pixel) >> 22) in int32 (input_common.h).  Integer work: bit-exact by construction.
 // HBM-bound byte streams; lanes walk x so the source windows of neighbouring lanes overlap in cache.
-#include "common.h"
-
-#define RS_PREC 22
-
-__device__ __forceinline__ unsigned char clip8(int v) {
-  v >>= RS_PREC;
-  return (unsigned char)(v < 0 ? 0 : (v > 255 ? 255 : v));
-}
+#include "input_common.h"
 
 // src [H][W][3] u8 -> dst [H][new_w][3] u8
 __global__ __launch_bounds__(256) void resize_h_kernel(const unsigned char* __restrict__ src, int H, int W, int new_w,
@@ -24,18 +17,8 @@ __global__ __launch_bounds__(256) void resize_h_kernel(const unsigned char* __re
                                                        int ksize, unsigned char* __restrict__ dst) {
   const int xo = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
   if (xo >= new_w) return;
-  const int xmin = bounds[2 * xo], cnt = bounds[2 * xo + 1];
-  const int* k = kk + (size_t)xo * ksize;
-  const unsigned char* row = src + ((size_t)y * W + xmin) * 3;
-  int s0 = 1 << (RS_PREC - 1), s1 = s0, s2 = s0;
-  for (int x = 0; x < cnt; ++x) {
-    const int c = k[x];
-    s0 += row[3 * x] * c;
-    s1 += row[3 * x + 1] * c;
-    s2 += row[3 * x + 2] * c;
-  }
   unsigned char* o = dst + ((size_t)y * new_w + xo) * 3;
-  o[0] = clip8(s0); o[1] = clip8(s1); o[2] = clip8(s2);
+  resample_taps(src + ((size_t)y * W + bounds[2 * xo]) * 3, 0, 3, 1, kk + (size_t)xo * ksize, bounds[2 * xo + 1], o[0], o[1], o[2]);
 }
 
 // src [H][new_w][3] u8 -> optional out_u8 [new_h][new_w][3] and/or out_f [Hp][Wp][4] = (v - mean) / std, zero padded
@@ -49,27 +32,12 @@ __global__ __launch_bounds__(256) void resize_v_kernel(const unsigned char* __re
   float4 v = {0.f, 0.f, 0.f, 0.f};
   if (yo < new_h && xo < new_w) {
     unsigned char r0, r1, r2;
-    if (kk) {
-      const int ymin = bounds[2 * yo], cnt = bounds[2 * yo + 1];
-      const int* k = kk + (size_t)yo * ksize;
-      int s0 = 1 << (RS_PREC - 1), s1 = s0, s2 = s0;
-      for (int y = 0; y < cnt; ++y) {
-        const unsigned char* p = src + ((size_t)(ymin + y) * new_w + xo) * 3;
-        const int c = k[y];
-        s0 += p[0] * c; s1 += p[1] * c; s2 += p[2] * c;
-      }
-      r0 = clip8(s0); r1 = clip8(s1); r2 = clip8(s2);
-    } else {   // height unchanged: Pillow skips the vertical pass
-      const unsigned char* p = src + ((size_t)yo * new_w + xo) * 3;
-      r0 = p[0]; r1 = p[1]; r2 = p[2];
-    }
+    resample_v_pixel(src + (size_t)xo * 3, (size_t)new_w * 3, 1, bounds, kk, ksize, yo, 0, r0, r1, r2);
     if (out_u8) {
       unsigned char* o = out_u8 + ((size_t)yo * new_w + xo) * 3;
       o[0] = r0; o[1] = r1; o[2] = r2;
     }
-    v.x = ((float)r0 - m0) / d0;
-    v.y = ((float)r1 - m1) / d1;
-    v.z = ((float)r2 - m2) / d2;
+    v = normalise4(r0, r1, r2, m0, m1, m2, d0, d1, d2);
   }
   if (out_f && yo < Hp) *reinterpret_cast<float4*>(out_f + ((size_t)yo * Wp + xo) * 4) = v;
 }

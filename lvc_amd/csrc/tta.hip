@@ -5,8 +5,9 @@
 //    sizes.  The vertical pass writes each resized pixel into up to two NHWC4 fp32 batch slots -- the plain one and the horizontally
 //    mirrored one (RandomFlip(prob=1) -> HFlipTransform(new_w) after the resize: column x -> new_w - 1 - x) -- as (v - mean) / std,
 //    zero-padded to each slot's own padded size with the 4th channel zero, and optionally the uint8 [new_h,new_w,3] images.
-//    The resample is resize.hip's, bit for bit: Pillow's 22-bit coefficients (lvc_amd/data/transforms.py resample_coeffs), a uint8
-//    intermediate, an unchanged axis skipped.  The source is read through strides (CHW `image` or HWC `raw` without a copy).
+//    The resample is resize.hip's (input_common.h), bit for bit: Pillow's 22-bit coefficients (lvc_amd/data/transforms.py
+//    resample_coeffs), a uint8 intermediate, an unchanged axis skipped.  The source is read through strides (CHW `image` or HWC
+//    `raw` without a copy).
 // 2. lvc_tta_merge: _get_augmented_boxes (:228-244) + _merge_detections (:246-264) -> fast_rcnn_inference_single_image
 //    (detectron2/modeling/roi_heads/fast_rcnn.py:111-158) for B images at once from the device-resident per-augmentation outputs.
 //    One workgroup per image walks its augmentations in order and gathers the union in the reference's order (augmentation, then
@@ -17,22 +18,16 @@
 //
 // Byte streams and latency-bound bookkeeping: built with the EXACT flags (-ffp-contract=off -fno-fast-math): the fp32 steps of the
 // inverse transforms and the normaliser must round exactly as numpy / preprocess_image do.
-#include "common.h"
+#include "input_common.h"
 
 extern "C" long long lvc_batched_nms_workspace_bytes(int B, int Nmax);   // nms.hip
 extern "C" int lvc_batched_nms(const float* boxes, const float* scores, const int* idxs, const int* d_counts, int B, int Nmax,
                                double iou_threshold, int max_keep, int* keep, int* d_num_keep, void* workspace,
                                long long workspace_bytes, void* stream);
 
-#define TTA_PREC 22
 #define TTA_MAX_JOBS 16
 #define TTA_MAX_STEPS 4
 #define TTA_PARAM_STRIDE 16
-
-__device__ __forceinline__ unsigned char tta_clip8(int v) {
-  v >>= TTA_PREC;
-  return (unsigned char)(v < 0 ? 0 : (v > 255 ? 255 : v));
-}
 
 struct TtaHJob {
   const int* xb;
@@ -67,19 +62,8 @@ __global__ __launch_bounds__(256) void tta_resize_h_kernel(const unsigned char* 
   const TtaHJob& jb = tab.j[blockIdx.z];
   const int xo = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
   if (xo >= jb.new_w) return;
-  const int xmin = jb.xb[2 * xo], cnt = jb.xb[2 * xo + 1];
-  const int* k = jb.xk + (size_t)xo * jb.kxs;
-  const unsigned char* row = src + (size_t)y * sy + (size_t)xmin * sx;
-  int s0 = 1 << (TTA_PREC - 1), s1 = s0, s2 = s0;
-  for (int x = 0; x < cnt; ++x) {
-    const int c = k[x];
-    const unsigned char* p = row + (size_t)x * sx;
-    s0 += p[0] * c;
-    s1 += p[sc] * c;
-    s2 += p[2 * sc] * c;
-  }
   unsigned char* o = jb.tmp + ((size_t)y * jb.new_w + xo) * 3;
-  o[0] = tta_clip8(s0); o[1] = tta_clip8(s1); o[2] = tta_clip8(s2);
+  resample_taps(src + (size_t)y * sy + (size_t)jb.xb[2 * xo] * sx, 0, sx, sc, jb.xk + (size_t)xo * jb.kxs, jb.xb[2 * xo + 1], o[0], o[1], o[2]);
 }
 
 // one launch for every output size: grid (x tiles, rows, jobs).  Thread (yo, xo) resamples pixel (yo, xo) of its job (when inside
@@ -93,21 +77,7 @@ __global__ __launch_bounds__(256) void tta_resize_v_kernel(TtaVTable tab, float 
   float4 v = {0.f, 0.f, 0.f, 0.f};
   if (inside) {
     unsigned char r0, r1, r2;
-    const unsigned char* col = jb.src + (size_t)xo * jb.sx;
-    if (jb.yk) {
-      const int ymin = jb.yb[2 * yo], cnt = jb.yb[2 * yo + 1];
-      const int* k = jb.yk + (size_t)yo * jb.kys;
-      int s0 = 1 << (TTA_PREC - 1), s1 = s0, s2 = s0;
-      for (int y = 0; y < cnt; ++y) {
-        const unsigned char* p = col + (size_t)(ymin + y) * jb.sy;
-        const int c = k[y];
-        s0 += p[0] * c; s1 += p[jb.sc] * c; s2 += p[2 * jb.sc] * c;
-      }
-      r0 = tta_clip8(s0); r1 = tta_clip8(s1); r2 = tta_clip8(s2);
-    } else {   // height unchanged: Pillow skips the vertical pass
-      const unsigned char* p = col + (size_t)yo * jb.sy;
-      r0 = p[0]; r1 = p[jb.sc]; r2 = p[2 * jb.sc];
-    }
+    resample_v_pixel(jb.src + (size_t)xo * jb.sx, jb.sy, jb.sc, jb.yb, jb.yk, jb.kys, yo, 0, r0, r1, r2);
     const int xm = jb.new_w - 1 - xo;
     if (jb.u8) {
       unsigned char* o = jb.u8 + ((size_t)yo * jb.new_w + xo) * 3;
@@ -117,9 +87,7 @@ __global__ __launch_bounds__(256) void tta_resize_v_kernel(TtaVTable tab, float 
       unsigned char* o = jb.u8m + ((size_t)yo * jb.new_w + xm) * 3;
       o[0] = r0; o[1] = r1; o[2] = r2;
     }
-    v.x = ((float)r0 - m0) / d0;
-    v.y = ((float)r1 - m1) / d1;
-    v.z = ((float)r2 - m2) / d2;
+    v = normalise4(r0, r1, r2, m0, m1, m2, d0, d1, d2);
     if (jb.fm) *reinterpret_cast<float4*>(jb.fm + ((size_t)yo * jb.Wpm + xm) * 4) = v;
   } else if (jb.fm && yo < jb.Hpm && xo < jb.Wpm) {
     *reinterpret_cast<float4*>(jb.fm + ((size_t)yo * jb.Wpm + xo) * 4) = v;

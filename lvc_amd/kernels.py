@@ -25,6 +25,10 @@ def _req_cuda(*ts):
             raise RuntimeError("lvc_amd kernels need device tensors (got a CPU tensor); there is no CPU path")
 
 
+def _float3(v):
+    return (c_float * 3)(*[float(x) for x in v])
+
+
 # --------------------------------------------------------------------------- convolution / GEMM
 class PackedConv:
     """Weights of one conv/linear layer in the kernel's layout + folded per-channel affine.
@@ -1770,8 +1774,8 @@ def preprocess_into(image, out_slot, mean, std):
     image = image.contiguous()
     Hp, Wp, four = out_slot.shape
     assert four == 4 and out_slot.is_contiguous()
-    m = (c_float * 3)(*[float(v) for v in mean])
-    s = (c_float * 3)(*[float(v) for v in std])
+    m = _float3(mean)
+    s = _float3(std)
     rc = _lib.lib().lvc_preprocess_nhwc4(ptr(image), c_int(dt), c_int(image.shape[1]), c_int(image.shape[2]), m, s,
                                          ptr(out_slot), c_int(Hp), c_int(Wp), _stream(image))
     check(rc, "lvc_preprocess_nhwc4")
@@ -1795,8 +1799,8 @@ def preprocess_batch_into(images, out, mean, std):
     P = (c_void_p * B)(*[im.data_ptr() for im in imgs])
     hs = (c_int * B)(*[int(im.shape[1]) for im in imgs])
     ws = (c_int * B)(*[int(im.shape[2]) for im in imgs])
-    m = (c_float * 3)(*[float(v) for v in mean])
-    s_ = (c_float * 3)(*[float(v) for v in std])
+    m = _float3(mean)
+    s_ = _float3(std)
     rc = _lib.lib().lvc_preprocess_batch_nhwc4(P, c_int(1 if u8 else 0), hs, ws, c_int(B), m, s_, ptr(out), c_int(out.shape[1]),
                                                c_int(out.shape[2]), _stream(out))
     check(rc, "lvc_preprocess_batch_nhwc4")
@@ -1825,8 +1829,8 @@ def resize_bilinear_u8(img, new_h, new_w, coeffs_fn, out_slot=None, mean=None, s
     if out_slot is not None:
         Hp, Wp, four = out_slot.shape
         assert four == 4 and out_slot.is_contiguous() and out_slot.dtype == torch.float32
-        m = (c_float * 3)(*[float(v) for v in mean])
-        s = (c_float * 3)(*[float(v) for v in std])
+        m = _float3(mean)
+        s = _float3(std)
     rc = _lib.lib().lvc_resize_bilinear_u8(ptr(img), c_int(H), c_int(W), c_int(new_h), c_int(new_w), ptr(xb), ptr(xk),
                                            c_int(kxs), ptr(yb), ptr(yk), c_int(kys), ptr(tmp), ptr(out), ptr(out_slot),
                                            c_int(Hp), c_int(Wp), m, s, _stream(img))
@@ -1861,38 +1865,132 @@ def tta_resize_u8(img, H, W, strides, hjobs, vjobs, mean, std):
                   fm.data_ptr() if fm is not None else 0, fm.shape[0] if fm is not None else 0, fm.shape[1] if fm is not None else 0]
     hj = (c_longlong * max(1, len(hrows)))(*hrows)
     vj = (c_longlong * len(vrows))(*vrows)
-    m = (c_float * 3)(*[float(v) for v in mean])
-    s = (c_float * 3)(*[float(v) for v in std])
+    m = _float3(mean)
+    s = _float3(std)
     sy, sx, sc = strides
     rc = _lib.lib().lvc_tta_resize_u8(ptr(img), c_int(H), c_int(W), c_longlong(sy), c_longlong(sx), c_longlong(sc), hj,
                                       c_int(len(hjobs)), vj, c_int(len(vjobs)), m, s, _stream(img))
     check(rc, "lvc_tta_resize_u8")
 
 
+# --------------------------------------------------------------------------- training input: job blobs
+# Every entry below takes ONE pinned blob -- an int64 job table with the int32 resample tables behind it (layouts: include/lvc_amd.h)
+# -- that is uploaded once per call.
 TRAIN_INPUT_LAUNCHES = []  # kernel launches of the last (up to 64) lvc_train_input_u8 calls, as the library counted them
 TRAIN_INPUT_FIELDS = 24   # int64 words per job of lvc_train_input_u8 (include/lvc_amd.h)
+TRAIN_INPUT_TILES_LAUNCHES = []   # ... of the last (up to 64) lvc_train_input_tiles_u8 calls
+TRAIN_INPUT_TILES_HEAD, TRAIN_INPUT_TILES_TILE, TRAIN_INPUT_TILES_MAX = 20, 12, 9   # job layout of lvc_train_input_tiles_u8
+TRAIN_INPUT_TILES_FIELDS = TRAIN_INPUT_TILES_HEAD + TRAIN_INPUT_TILES_MAX * TRAIN_INPUT_TILES_TILE      # (include/lvc_amd.h)
+TRAIN_INPUT_LSJ_LAUNCHES = []   # ... of the last (up to 64) lvc_train_input_lsj_u8 calls
+TRAIN_INPUT_LSJ_HEAD = 32       # int64 words in front of the tiles of a job of lvc_train_input_lsj_u8 (include/lvc_amd.h)
+TRAIN_INPUT_LSJ_FIELDS = TRAIN_INPUT_LSJ_HEAD + TRAIN_INPUT_TILES_MAX * TRAIN_INPUT_TILES_TILE
+COLOR_JITTER_LAUNCHES = []   # ... of the last (up to 64) lvc_color_jitter_tiles_u8 calls
+COLOR_JITTER_FIELDS = TRAIN_INPUT_TILES_FIELDS      # int64 words per job of lvc_color_jitter_tiles_u8 (include/lvc_amd.h)
+COLOR_JITTER_OPS = ("brightness", "contrast", "saturation", "hue")      # step ids 0..3, torchvision's
 
 
 class TrainInputWorkspace:
-    """Buffers of one lvc_train_input_u8 call, reused from batch to batch (grown, never shrunk): the pinned host blob (job table +
-    coefficient tables), its device copy and the horizontal pass's uint8 intermediate.  `uploaded` is recorded after the blob's
-    copy is queued: the host blob must not be rewritten before it has passed (`wait_host`)."""
+    """Buffers of one job-blob call, reused from batch to batch (grown, never shrunk): the pinned host blob (job table +
+    coefficient tables), its device copy and a device scratch buffer (`tmp`: the horizontal pass's uint8 intermediate).  `uploaded`
+    is recorded after the blob's copy is queued: the host blob must not be rewritten before it has passed (`wait_host`)."""
+    MIN_BLOB = 1 << 16
 
     def __init__(self, device):
         self.device = torch.device(device)
-        self.host = self.dev = self.tmp = self.uploaded = None
+        self.host = self.dev = self.scratch = self.uploaded = None
+
+    tmp = property(lambda self: self.scratch)
 
     def wait_host(self):
         if self.uploaded is not None:
             self.uploaded.synchronize()      # this event only: the copy out of the pinned blob, queued two batches ago
 
-    def reserve(self, blob_bytes, tmp_bytes):
+    def reserve(self, blob_bytes, scratch_bytes):
         if self.host is None or self.host.numel() < blob_bytes:
-            n = max(blob_bytes * 3 // 2, 1 << 16)
+            n = max(blob_bytes * 3 // 2, self.MIN_BLOB)
             self.host = torch.empty(n, dtype=torch.uint8).pin_memory()
             self.dev = torch.empty(n, dtype=torch.uint8, device=self.device)
-        if self.tmp is None or self.tmp.numel() < tmp_bytes:
-            self.tmp = torch.empty(max(tmp_bytes * 3 // 2, 1 << 16), dtype=torch.uint8, device=self.device)
+        if self.scratch is None or self.scratch.numel() < scratch_bytes:
+            self.scratch = torch.empty(max(scratch_bytes * 3 // 2, 1 << 16), dtype=torch.uint8, device=self.device)
+
+    def upload(self, tab, tables, scratch_bytes, device):
+        """The job table and the int32 tables behind it into the pinned blob and, on `device`'s current stream, into its device
+        copy; -> the bytes of the blob."""
+        import numpy as np
+
+        nbytes = tab.nbytes + sum(t.nbytes for t in tables)
+        self.wait_host()
+        self.reserve(nbytes, scratch_bytes)
+        hb, at = self.host.numpy(), tab.nbytes
+        hb[:at] = tab.reshape(-1).view(np.uint8)
+        for t in tables:
+            hb[at:at + t.nbytes] = np.ascontiguousarray(t, np.int32).reshape(-1).view(np.uint8)
+            at += t.nbytes
+        self.dev[:nbytes].copy_(self.host[:nbytes], non_blocking=True)
+        self.uploaded = torch.cuda.Event()
+        self.uploaded.record(torch.cuda.current_stream(device))
+        return nbytes
+
+
+class ColorJitterWorkspace(TrainInputWorkspace):
+    """The workspace of one lvc_color_jitter_tiles_u8 call: its blob is the job table alone, and `scratch` receives the jittered
+    crops (the results are views of it: they live until the next call on this workspace)."""
+    MIN_BLOB = 1 << 14
+
+
+def _log_launches(log, n):
+    log.append(n)
+    del log[:-64]
+
+
+def _image_words(img):
+    """Words 0-5 of a tile or of a plain job: (pointer, H, W, sy, sx, sc) of a uint8 [H,W,3] tensor of any strides, or that tuple."""
+    return img if isinstance(img, tuple) else (img.data_ptr(), img.shape[0], img.shape[1], img.stride(0), img.stride(1), img.stride(2))
+
+
+def _req_image(img, device):
+    _req_cuda(img)
+    assert img.dtype == torch.uint8 and img.dim() == 3 and img.shape[2] == 3 and img.device == device
+
+
+def _write_tiles(row, head, tiles, device=None):
+    """The 12 words of every tile (image, canvas rectangle, tile pixel at its first corner) from word `head` of a job on.  device:
+    where the images must lie (None: not checked -- train_input_lsj_blob, whose images may be the tuples of _image_words)."""
+    assert 1 <= len(tiles) <= TRAIN_INPUT_TILES_MAX, "an item has 1 to 9 tiles"
+    for t, (img, rect, origin) in enumerate(tiles):
+        if device is not None:
+            _req_image(img, device)
+        at = head + t * TRAIN_INPUT_TILES_TILE
+        row[at:at + TRAIN_INPUT_TILES_TILE] = (*_image_words(img), *rect, *origin)
+
+
+def _axis_tables(row, at, x_sizes, y_sizes, coeffs_fn, tables, off):
+    """The two resample axes of a job, (size in, size out) each: words at.. = (bounds offset, coefficient offset, ksize) of the
+    columns, then of the rows, the offset -1 where the size stays.  Appends the tables; -> the blob offset behind them."""
+    for (size_in, size_out), w in ((x_sizes, at), (y_sizes, at + 3)):
+        row[w] = -1
+        if size_in != size_out:
+            b, k, ks = coeffs_fn(size_in, size_out)
+            row[w], row[w + 1], row[w + 2] = off, off + b.nbytes, ks
+            tables += [b, k]
+            off += b.nbytes + k.nbytes
+    return off
+
+
+def _train_input_call(entry, log, ws, tab, tables, tmp_bytes, out, mean, std):
+    """Upload the blob and call one of the three lvc_train_input*_u8 entries (one signature) on out's current stream."""
+    nbytes = ws.upload(tab, tables, tmp_bytes, out.device)
+    n = c_int(0)
+    rc = getattr(_lib.lib(), entry)(ptr(ws.host), ptr(ws.dev), c_longlong(nbytes), c_int(len(tab)), ptr(ws.scratch), c_longlong(ws.scratch.numel()),
+                                    ptr(out), c_int(out.shape[0]), c_int(out.shape[1]), c_int(out.shape[2]), _float3(mean), _float3(std),
+                                    ctypes.byref(n), _stream(out))
+    check(rc, entry)
+    _log_launches(log, n.value)
+
+
+def _req_batch(out, B):
+    _req_cuda(out)
+    assert B > 0 and out.dim() == 4 and out.shape[3] == 4 and out.is_contiguous() and out.dtype == torch.float32 and out.shape[0] >= B
 
 
 def train_input_u8(images, jobs, out, mean, std, coeffs_fn, want_u8=False, workspace=None):
@@ -1904,25 +2002,18 @@ def train_input_u8(images, jobs, out, mean, std, coeffs_fn, want_u8=False, works
     import numpy as np
 
     B = len(images)
-    assert B == len(jobs) and B > 0
-    _req_cuda(out, *images)
-    assert out.dim() == 4 and out.shape[3] == 4 and out.is_contiguous() and out.dtype == torch.float32 and out.shape[0] >= B
+    assert B == len(jobs)
+    _req_batch(out, B)
     ws = workspace if workspace is not None else TrainInputWorkspace(out.device)
     tab = np.zeros((B, TRAIN_INPUT_FIELDS), np.int64)
-    tables, off, tmp_off = [], B * TRAIN_INPUT_FIELDS * 8, 0
+    tables, off, tmp_off = [], tab.nbytes, 0
     u8 = []
     for i, (img, (x0, y0, cw, ch, nh, nw, flip)) in enumerate(zip(images, jobs)):
-        assert img.dtype == torch.uint8 and img.dim() == 3 and img.shape[2] == 3 and img.device == out.device
+        _req_image(img, out.device)
         row = tab[i]
-        row[0:6] = (img.data_ptr(), img.shape[0], img.shape[1], img.stride(0), img.stride(1), img.stride(2))
+        row[0:6] = _image_words(img)
         row[6:12] = (x0, y0, cw, ch, nh, nw)
-        row[12] = row[15] = -1
-        for size_in, size_out, at in ((cw, nw, 12), (ch, nh, 15)):
-            if size_in != size_out:
-                b, k, ks = coeffs_fn(size_in, size_out)
-                row[at], row[at + 1], row[at + 2] = off, off + b.nbytes, ks
-                tables += [b, k]
-                off += b.nbytes + k.nbytes
+        off = _axis_tables(row, 12, (cw, nw), (ch, nh), coeffs_fn, tables, off)
         row[18], row[19] = int(bool(flip)), i
         if want_u8:
             u8.append(torch.empty(nh, nw, 3, dtype=torch.uint8, device=out.device))
@@ -1930,32 +2021,8 @@ def train_input_u8(images, jobs, out, mean, std, coeffs_fn, want_u8=False, works
         if nw != cw:
             row[21] = tmp_off
             tmp_off += (ch * nw * 3 + 255) & ~255
-    ws.wait_host()
-    ws.reserve(off, tmp_off)
-    hb = ws.host.numpy()
-    hb[:tab.nbytes] = tab.reshape(-1).view(np.uint8)
-    at = tab.nbytes
-    for t in tables:
-        hb[at:at + t.nbytes] = np.ascontiguousarray(t, np.int32).reshape(-1).view(np.uint8)
-        at += t.nbytes
-    ws.dev[:off].copy_(ws.host[:off], non_blocking=True)
-    ws.uploaded = torch.cuda.Event()
-    ws.uploaded.record(torch.cuda.current_stream(out.device))
-    m = (c_float * 3)(*[float(v) for v in mean])
-    s = (c_float * 3)(*[float(v) for v in std])
-    n = c_int(0)
-    rc = _lib.lib().lvc_train_input_u8(ptr(ws.host), ptr(ws.dev), c_longlong(off), c_int(B), ptr(ws.tmp), c_longlong(ws.tmp.numel()),
-                                       ptr(out), c_int(out.shape[0]), c_int(out.shape[1]), c_int(out.shape[2]), m, s, ctypes.byref(n),
-                                       _stream(out))
-    check(rc, "lvc_train_input_u8")
-    TRAIN_INPUT_LAUNCHES.append(n.value)
-    del TRAIN_INPUT_LAUNCHES[:-64]
+    _train_input_call("lvc_train_input_u8", TRAIN_INPUT_LAUNCHES, ws, tab, tables, tmp_off, out, mean, std)
     return u8 if want_u8 else None
-
-
-TRAIN_INPUT_TILES_LAUNCHES = []   # kernel launches of the last (up to 64) lvc_train_input_tiles_u8 calls, as the library counted them
-TRAIN_INPUT_TILES_HEAD, TRAIN_INPUT_TILES_TILE, TRAIN_INPUT_TILES_MAX = 20, 12, 9   # job layout of lvc_train_input_tiles_u8
-TRAIN_INPUT_TILES_FIELDS = TRAIN_INPUT_TILES_HEAD + TRAIN_INPUT_TILES_MAX * TRAIN_INPUT_TILES_TILE      # (include/lvc_amd.h)
 
 
 def train_input_tiles_u8(items, out, mean, std, coeffs_fn, want_u8=False, workspace=None, table_hook=None):
@@ -1968,25 +2035,15 @@ def train_input_tiles_u8(items, out, mean, std, coeffs_fn, want_u8=False, worksp
     import numpy as np
 
     B = len(items)
-    assert B > 0
-    _req_cuda(out)
-    assert out.dim() == 4 and out.shape[3] == 4 and out.is_contiguous() and out.dtype == torch.float32 and out.shape[0] >= B
+    _req_batch(out, B)
     ws = workspace if workspace is not None else TrainInputWorkspace(out.device)
-    F, HEAD, TILE = TRAIN_INPUT_TILES_FIELDS, TRAIN_INPUT_TILES_HEAD, TRAIN_INPUT_TILES_TILE
-    tab = np.zeros((B, F), np.int64)
-    tables, off, tmp_off = [], B * F * 8, 0
+    tab = np.zeros((B, TRAIN_INPUT_TILES_FIELDS), np.int64)
+    tables, off, tmp_off = [], tab.nbytes, 0
     u8 = []
     for i, (tiles, (X0, Y0, cw, ch), nh, nw, flip) in enumerate(items):
-        assert 1 <= len(tiles) <= TRAIN_INPUT_TILES_MAX, "an item has 1 to 9 tiles"
         row = tab[i]
         row[0:6] = (X0, Y0, cw, ch, nh, nw)
-        row[6] = row[9] = -1
-        for size_in, size_out, at in ((cw, nw, 6), (ch, nh, 9)):
-            if size_in != size_out:
-                b, k, ks = coeffs_fn(size_in, size_out)
-                row[at], row[at + 1], row[at + 2] = off, off + b.nbytes, ks
-                tables += [b, k]
-                off += b.nbytes + k.nbytes
+        off = _axis_tables(row, 6, (cw, nw), (ch, nh), coeffs_fn, tables, off)
         row[12], row[13] = int(bool(flip)), i
         if want_u8:
             u8.append(torch.empty(nh, nw, 3, dtype=torch.uint8, device=out.device))
@@ -1994,40 +2051,11 @@ def train_input_tiles_u8(items, out, mean, std, coeffs_fn, want_u8=False, worksp
         row[15] = tmp_off
         tmp_off += (ch * nw * 3 + 255) & ~255
         row[16] = len(tiles)
-        for t, (img, rect, origin) in enumerate(tiles):
-            assert img.dtype == torch.uint8 and img.dim() == 3 and img.shape[2] == 3 and img.device == out.device
-            at = HEAD + t * TILE
-            row[at:at + 6] = (img.data_ptr(), img.shape[0], img.shape[1], img.stride(0), img.stride(1), img.stride(2))
-            row[at + 6:at + 10] = rect
-            row[at + 10:at + 12] = origin
+        _write_tiles(row, TRAIN_INPUT_TILES_HEAD, tiles, out.device)
     if table_hook is not None:
         table_hook(tab)
-    ws.wait_host()
-    ws.reserve(off, tmp_off)
-    hb = ws.host.numpy()
-    hb[:tab.nbytes] = tab.reshape(-1).view(np.uint8)
-    at = tab.nbytes
-    for t in tables:
-        hb[at:at + t.nbytes] = np.ascontiguousarray(t, np.int32).reshape(-1).view(np.uint8)
-        at += t.nbytes
-    ws.dev[:off].copy_(ws.host[:off], non_blocking=True)
-    ws.uploaded = torch.cuda.Event()
-    ws.uploaded.record(torch.cuda.current_stream(out.device))
-    m = (c_float * 3)(*[float(v) for v in mean])
-    s = (c_float * 3)(*[float(v) for v in std])
-    n = c_int(0)
-    rc = _lib.lib().lvc_train_input_tiles_u8(ptr(ws.host), ptr(ws.dev), c_longlong(off), c_int(B), ptr(ws.tmp),
-                                             c_longlong(ws.tmp.numel()), ptr(out), c_int(out.shape[0]), c_int(out.shape[1]),
-                                             c_int(out.shape[2]), m, s, ctypes.byref(n), _stream(out))
-    check(rc, "lvc_train_input_tiles_u8")
-    TRAIN_INPUT_TILES_LAUNCHES.append(n.value)
-    del TRAIN_INPUT_TILES_LAUNCHES[:-64]
+    _train_input_call("lvc_train_input_tiles_u8", TRAIN_INPUT_TILES_LAUNCHES, ws, tab, tables, tmp_off, out, mean, std)
     return u8 if want_u8 else None
-
-
-TRAIN_INPUT_LSJ_LAUNCHES = []   # kernel launches of the last (up to 64) lvc_train_input_lsj_u8 calls, as the library counted them
-TRAIN_INPUT_LSJ_HEAD = 32       # int64 words in front of the tiles of a job of lvc_train_input_lsj_u8 (include/lvc_amd.h)
-TRAIN_INPUT_LSJ_FIELDS = TRAIN_INPUT_LSJ_HEAD + TRAIN_INPUT_TILES_MAX * TRAIN_INPUT_TILES_TILE
 
 
 def lsj_band(size_in, size_out, o0, on, coeffs_fn):
@@ -2046,21 +2074,12 @@ def train_input_lsj_blob(items, coeffs_fn, u8_ptrs=None):
     a tile is (image, rectangle, origin) as train_input_tiles_u8, or (pointer, H, W, sy, sx, sc) in place of the image."""
     import numpy as np
 
-    B = len(items)
-    F, HEAD, TILE = TRAIN_INPUT_LSJ_FIELDS, TRAIN_INPUT_LSJ_HEAD, TRAIN_INPUT_TILES_TILE
-    tab = np.zeros((B, F), np.int64)
-    tables, off, tmp_off = [], B * F * 8, 0
+    tab = np.zeros((len(items), TRAIN_INPUT_LSJ_FIELDS), np.int64)
+    tables, off, tmp_off = [], tab.nbytes, 0
     for i, (tiles, (X0, Y0, cw, ch), (sh, sw), (ox, oy, ow, oh), (th, tw), fill, flip) in enumerate(items):
-        assert 1 <= len(tiles) <= TRAIN_INPUT_TILES_MAX, "an item has 1 to 9 tiles"
         row = tab[i]
         row[0:6] = (X0, Y0, cw, ch, sh, sw)
-        row[6] = row[9] = -1
-        for size_in, size_out, at in ((cw, sw, 6), (ch, sh, 9)):      # Pillow's tables of the FULL resize; the window selects rows of them
-            if size_in != size_out:
-                b, k, ks = coeffs_fn(size_in, size_out)
-                row[at], row[at + 1], row[at + 2] = off, off + b.nbytes, ks
-                tables += [b, k]
-                off += b.nbytes + k.nbytes
+        off = _axis_tables(row, 6, (cw, sw), (ch, sh), coeffs_fn, tables, off)      # Pillow's tables of the FULL resize; the window selects rows of them
         row[12], row[13] = int(bool(flip)), i
         if u8_ptrs is not None:
             row[14] = u8_ptrs[i]
@@ -2069,12 +2088,7 @@ def train_input_lsj_blob(items, coeffs_fn, u8_ptrs=None):
         row[24:26] = lsj_band(ch, sh, oy, oh, coeffs_fn) if 0 <= oy and 0 < oh and oy + oh <= sh else (oy, oh)
         row[15] = tmp_off
         tmp_off += (int(row[25]) * int(ow) * 3 + 255) & ~255
-        for t, (img, rect, origin) in enumerate(tiles):
-            at = HEAD + t * TILE
-            row[at:at + 6] = img if isinstance(img, tuple) else (img.data_ptr(), img.shape[0], img.shape[1], img.stride(0),
-                                                                  img.stride(1), img.stride(2))
-            row[at + 6:at + 10] = rect
-            row[at + 10:at + 12] = origin
+        _write_tiles(row, TRAIN_INPUT_LSJ_HEAD, tiles)
     return tab, tables, off, tmp_off
 
 
@@ -2085,69 +2099,17 @@ def train_input_lsj_u8(items, out, mean, std, coeffs_fn, want_u8=False, workspac
     train_input_lsj_blob (tiles: uint8 device tensors of any strides; a plain image is one tile).  out [n_slots,Hp,Wp,4] fp32: item
     i fills slot i completely ((canvas - mean) / std, zero outside the canvas).  Returns the uint8 [th,tw,3] canvases when want_u8.
     coeffs_fn, workspace, table_hook(tab): as train_input_tiles_u8.  One host->device copy carries every table."""
-    import numpy as np
-
-    B = len(items)
-    assert B > 0
-    _req_cuda(out)
-    assert out.dim() == 4 and out.shape[3] == 4 and out.is_contiguous() and out.dtype == torch.float32 and out.shape[0] >= B
+    _req_batch(out, len(items))
     for it in items:
         for img, _, _ in it[0]:
-            _req_cuda(img)
-            assert img.dtype == torch.uint8 and img.dim() == 3 and img.shape[2] == 3 and img.device == out.device
+            _req_image(img, out.device)
     ws = workspace if workspace is not None else TrainInputWorkspace(out.device)
     u8 = [torch.empty(it[4][0], it[4][1], 3, dtype=torch.uint8, device=out.device) for it in items] if want_u8 else []
-    tab, tables, off, tmp_off = train_input_lsj_blob(items, coeffs_fn, [t.data_ptr() for t in u8] if want_u8 else None)
+    tab, tables, _, tmp_off = train_input_lsj_blob(items, coeffs_fn, [t.data_ptr() for t in u8] if want_u8 else None)
     if table_hook is not None:
         table_hook(tab)
-    ws.wait_host()
-    ws.reserve(off, tmp_off)
-    hb = ws.host.numpy()
-    hb[:tab.nbytes] = tab.reshape(-1).view(np.uint8)
-    at = tab.nbytes
-    for t in tables:
-        hb[at:at + t.nbytes] = np.ascontiguousarray(t, np.int32).reshape(-1).view(np.uint8)
-        at += t.nbytes
-    ws.dev[:off].copy_(ws.host[:off], non_blocking=True)
-    ws.uploaded = torch.cuda.Event()
-    ws.uploaded.record(torch.cuda.current_stream(out.device))
-    m = (c_float * 3)(*[float(v) for v in mean])
-    s = (c_float * 3)(*[float(v) for v in std])
-    n = c_int(0)
-    rc = _lib.lib().lvc_train_input_lsj_u8(ptr(ws.host), ptr(ws.dev), c_longlong(off), c_int(B), ptr(ws.tmp),
-                                           c_longlong(ws.tmp.numel()), ptr(out), c_int(out.shape[0]), c_int(out.shape[1]),
-                                           c_int(out.shape[2]), m, s, ctypes.byref(n), _stream(out))
-    check(rc, "lvc_train_input_lsj_u8")
-    TRAIN_INPUT_LSJ_LAUNCHES.append(n.value)
-    del TRAIN_INPUT_LSJ_LAUNCHES[:-64]
+    _train_input_call("lvc_train_input_lsj_u8", TRAIN_INPUT_LSJ_LAUNCHES, ws, tab, tables, tmp_off, out, mean, std)
     return u8 if want_u8 else None
-
-
-COLOR_JITTER_LAUNCHES = []   # kernel launches of the last (up to 64) lvc_color_jitter_tiles_u8 calls, as the library counted them
-COLOR_JITTER_FIELDS = TRAIN_INPUT_TILES_FIELDS      # int64 words per job of lvc_color_jitter_tiles_u8 (include/lvc_amd.h)
-COLOR_JITTER_OPS = ("brightness", "contrast", "saturation", "hue")      # step ids 0..3, torchvision's
-
-
-class ColorJitterWorkspace:
-    """Buffers of one lvc_color_jitter_tiles_u8 call, reused from batch to batch (grown, never shrunk): the pinned host job table,
-    its device copy and the scratch that receives the jittered crops (the results are views of it: they live until the next call
-    on this workspace).  `uploaded` as in TrainInputWorkspace."""
-
-    def __init__(self, device):
-        self.device = torch.device(device)
-        self.host = self.dev = self.scratch = self.uploaded = None
-
-    def wait_host(self):
-        if self.uploaded is not None:
-            self.uploaded.synchronize()
-
-    def reserve(self, blob_bytes, scratch_bytes):
-        if self.host is None or self.host.numel() < blob_bytes:
-            n = max(blob_bytes * 3 // 2, 1 << 14)
-            self.host = torch.empty(n, dtype=torch.uint8).pin_memory()
-            self.dev = torch.empty(n, dtype=torch.uint8, device=self.device)
-        if self.scratch is None or self.scratch.numel() < scratch_bytes:
-            self.scratch = torch.empty(max(scratch_bytes * 3 // 2, 1 << 16), dtype=torch.uint8, device=self.device)
 
 
 def color_jitter_tiles_u8(items, workspace=None, table_hook=None, device=None):
@@ -2164,11 +2126,9 @@ def color_jitter_tiles_u8(items, workspace=None, table_hook=None, device=None):
     if device is None:
         device = workspace.device if workspace is not None else items[0][0][0][0].device
     ws = workspace if workspace is not None else ColorJitterWorkspace(device)
-    F, HEAD, TILE = COLOR_JITTER_FIELDS, TRAIN_INPUT_TILES_HEAD, TRAIN_INPUT_TILES_TILE
-    tab = np.zeros((B, F), np.int64)
+    tab = np.zeros((B, COLOR_JITTER_FIELDS), np.int64)
     out_off, shapes = 0, []
     for i, (tiles, (X0, Y0, cw, ch), ops, factors) in enumerate(items):
-        assert 1 <= len(tiles) <= TRAIN_INPUT_TILES_MAX, "an item has 1 to 9 tiles"
         assert len(ops) == len(factors) <= 4, "an item has at most 4 steps"
         row = tab[i]
         row[0:4] = (X0, Y0, cw, ch)
@@ -2178,27 +2138,15 @@ def color_jitter_tiles_u8(items, workspace=None, table_hook=None, device=None):
         row[14] = len(tiles)
         shapes.append((out_off, int(ch), int(cw)))
         out_off += (int(ch) * int(cw) * 3 + 255) & ~255
-        for t, (img, rect, origin) in enumerate(tiles):
-            _req_cuda(img)
-            assert img.dtype == torch.uint8 and img.dim() == 3 and img.shape[2] == 3 and img.device == ws.device
-            at = HEAD + t * TILE
-            row[at:at + 6] = (img.data_ptr(), img.shape[0], img.shape[1], img.stride(0), img.stride(1), img.stride(2))
-            row[at + 6:at + 10] = rect
-            row[at + 10:at + 12] = origin
+        _write_tiles(row, TRAIN_INPUT_TILES_HEAD, tiles, ws.device)
     if table_hook is not None:
         table_hook(tab)
-    ws.wait_host()
-    ws.reserve(tab.nbytes, out_off)
-    ws.host.numpy()[:tab.nbytes] = tab.reshape(-1).view(np.uint8)
-    ws.dev[:tab.nbytes].copy_(ws.host[:tab.nbytes], non_blocking=True)
-    ws.uploaded = torch.cuda.Event()
-    ws.uploaded.record(torch.cuda.current_stream(ws.device))
+    nbytes = ws.upload(tab, [], out_off, ws.device)
     n = c_int(0)
-    rc = _lib.lib().lvc_color_jitter_tiles_u8(ptr(ws.host), ptr(ws.dev), c_longlong(tab.nbytes), c_int(B), ptr(ws.scratch),
+    rc = _lib.lib().lvc_color_jitter_tiles_u8(ptr(ws.host), ptr(ws.dev), c_longlong(nbytes), c_int(B), ptr(ws.scratch),
                                               c_longlong(ws.scratch.numel()), ctypes.byref(n), _stream(ws.scratch))
     check(rc, "lvc_color_jitter_tiles_u8")
-    COLOR_JITTER_LAUNCHES.append(n.value)
-    del COLOR_JITTER_LAUNCHES[:-64]
+    _log_launches(COLOR_JITTER_LAUNCHES, n.value)
     return [ws.scratch[off:off + h * w * 3].view(h, w, 3) for off, h, w in shapes]
 
 

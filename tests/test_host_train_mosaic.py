@@ -1,6 +1,7 @@
 """Mosaic training input, host side (lvc_amd/data/mosaic.py, build.py) against the reference's get_mosaic / get_mosaic9,
 DatasetMapperMosaic and MapDatasetMosaic + AspectRatioGroupedDataset (tests/golden/train_mosaic.npz, scripts/
 make_golden_train_mosaic.py).  No GPU needed."""
+import ctypes
 import itertools
 import os
 import random
@@ -252,3 +253,62 @@ def test_header_declares_the_new_symbol():
 
     assert K.TRAIN_INPUT_TILES_FIELDS == 128 and K.TRAIN_INPUT_FIELDS == 24
     assert "[B][128]" in text
+
+
+def test_the_three_tiled_entries_refuse_the_same_tile_lists_under_their_own_names():
+    """lvc_train_input_tiles_u8, lvc_train_input_lsj_u8 and lvc_color_jitter_tiles_u8 check a crop window and its tiles alike: one
+    40 x 50 tile under the window (10, 10, 50, 40), the same word of the tile list corrupted for each entry, comes back as
+    LVC_ERR_INVALID (1) with no launch counted and the same message under the entry's own name.  The pointers are fake: a launch
+    would not survive them, and none is made (the good table is NOT sent)."""
+    from lvc_amd import _lib
+    from lvc_amd import kernels as K
+
+    FAKE = 0x10000
+    window, tile = (10, 10, 50, 40), (FAKE, 40, 50, 150, 3, 1, 10, 10, 60, 50, 0, 0)
+    lib = _lib.lib()
+    v, ll, ci = ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int
+    m, s = (ctypes.c_float * 3)(0, 0, 0), (ctypes.c_float * 3)(1, 1, 1)
+
+    def resample_entry(fn):
+        return lambda blob, n: fn(v(blob.ctypes.data), v(FAKE), ll(blob.nbytes), ci(1), v(FAKE), ll(40 * 50 * 3), v(FAKE), ci(1), ci(40),
+                                  ci(50), m, s, ctypes.byref(n), v(0))
+
+    tiles = np.zeros((1, K.TRAIN_INPUT_TILES_FIELDS), np.int64)
+    tiles[0, 0:6], tiles[0, 6], tiles[0, 9], tiles[0, 16] = window + (40, 50), -1, -1, 1
+    lsj = K.train_input_lsj_blob([([(tile[:6], tile[6:10], tile[10:12])], window, (40, 50), (0, 0, 50, 40), (40, 50), 128, False)],
+                                 None)[0]
+    jitter = np.zeros((1, K.COLOR_JITTER_FIELDS), np.int64)
+    jitter[0, 0:4], jitter[0, 14] = window, 1
+    entries = [
+        ("lvc_train_input_tiles_u8", tiles, K.TRAIN_INPUT_TILES_HEAD, 16, resample_entry(lib.lvc_train_input_tiles_u8)),
+        ("lvc_train_input_lsj_u8", lsj, K.TRAIN_INPUT_LSJ_HEAD, 16, resample_entry(lib.lvc_train_input_lsj_u8)),
+        ("lvc_color_jitter_tiles_u8", jitter, K.TRAIN_INPUT_TILES_HEAD, 14,
+         lambda blob, n: lib.lvc_color_jitter_tiles_u8(v(blob.ctypes.data), v(FAKE), ll(blob.nbytes), ci(1), v(FAKE), ll(40 * 50 * 3),
+                                                       ctypes.byref(n), v(0))),
+    ]
+    bad = [      # (what, word of the tile (None: the tile count), value, message)
+        ("null source", 0, 0, "bad tile image"),
+        ("zero row stride", 3, 0, "strides must be positive"),
+        ("negative channel stride", 5, -1, "strides must be positive"),
+        ("rectangle of negative extent", 8, 9, "negative extent"),
+        ("a coordinate at 2^30", 6, 1 << 30, "coordinate out of range"),
+        ("the window reads above the tile", 11, -1, "a tile is read outside its image"),
+        ("no tile", None, 0, "1 to 9 tiles"),
+        ("ten tiles", None, 10, "1 to 9 tiles"),
+    ]
+    for what, word, value, msg in bad:
+        said = set()
+        for name, tab, head, nt_word, call in entries:
+            tab[0, head:head + 12] = tile
+            good = tab.copy()
+            at = nt_word if word is None else head + word
+            tab[0, at] = value
+            n = ctypes.c_int(-1)
+            rc = call(tab, n)
+            err = lib.lvc_last_error().decode()
+            tab[0, at] = good[0, at]
+            assert rc == 1 and n.value == 0, (what, name, rc, n.value)
+            assert err.startswith(name + ": ") and msg in err, (what, name, err)
+            assert tab.tolist() == good.tolist()      # the edit was undone: what was refused differs from the good table by one word
+            said.add(err[len(name):])
+        assert len(said) == 1, (what, said)      # one checker: the same words from all three
