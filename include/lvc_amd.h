@@ -141,6 +141,14 @@ int lvc_conv3x3_nhwc_f16_layers(int oneacc, const float* const* xs, float* const
  * equal share of the (tile, 16-channel chunk) list; split tiles are completed through `workspace` as in the other conv kernels, in worker
  * order: deterministic); 2 = persistent workgroups on whole tiles.  Measured: neither beats 0 on the detector's layers (conv3x3_wino.hip). */
 void lvc_set_wino_streamk(int mode);
+/* Patch decomposition of the 3x3 / stride 1 kernels.  0 = one patch shape per map (per launch for the grouped entries).  1 (default) =
+ * lvc_conv3x3_nhwc_wino* cut every map into at most two regions, each with the patch shape that wastes the fewest 256-pixel tiles on it
+ * (csrc/patch_plan.h); their outputs are bit-identical to 0.  2 = the direct kernel (lvc_conv3x3_nhwc_f16s1*, _f16x2_pipe, _f16_levels*,
+ * _f16_layers) does the same; its outputs then differ in the last bits where the stream-K worker boundaries fall, which move with the
+ * tile count -- not the default.  The library reads LVC_PATCH_PLAN (0 / 1 / 2) from the environment once, at the first launch or
+ * question; the setter overrides it. */
+void lvc_set_patch_plan(int mode);
+int lvc_patch_plan(void);
 /* Process-wide A/B and test switches (no environment lookups inside the library): the NMS ordered reduce of short lists from global
  * memory instead of LDS (same keep lists); the bf16x3 3x3 halo kernel with a fixed patch shape / without its small-map fallback. */
 void lvc_set_nms_reduce_global(int on);

@@ -4,6 +4,7 @@
 // the Python host re-raises RuntimeError with this text).
 #include "conv_common.h"
 #include <stdarg.h>
+#include <stdlib.h>
 
 static thread_local char g_err[512] = "";
 
@@ -36,4 +37,21 @@ extern "C" int lvc_cu_count(void) {
     g_cus = cus;
   }
   return g_cus;
+}
+
+// Patch decomposition of the 3x3 kernels (patch_plan.h): 0 = one patch shape per map, as before the planner -- the A/B arm and the
+// tests' witness; 1 (default) = up to two regions per map in the Winograd kernel, whose outputs do not depend on the patches (bit for
+// bit); 2 = in the direct kernel as well, where fewer tiles move the stream-K worker boundaries and with them the last bits of the
+// tiles split there -- enough to swap two detections of nearly equal score, so it is not the default.  The environment is looked at
+// ONCE, at the first question or setting (LVC_PATCH_PLAN=0/1/2), never on a later launch; the setter overrides it.
+static int g_patch_plan = -1;
+static void patch_plan_init() {
+  if (g_patch_plan >= 0) return;
+  const char* e = getenv("LVC_PATCH_PLAN");
+  g_patch_plan = (e && (e[0] == '0' || e[0] == '2') && e[1] == 0) ? e[0] - '0' : 1;
+}
+extern "C" void lvc_set_patch_plan(int mode) { g_patch_plan = mode <= 0 ? 0 : mode >= 2 ? 2 : 1; }
+extern "C" int lvc_patch_plan(void) {
+  patch_plan_init();
+  return g_patch_plan;
 }

@@ -25,6 +25,7 @@
 // Tiling (<= 256-pixel patches x 64 NI channels, 8 waves as 4 x 2), stream-K workers with grouped channel tiles, partial-tile
 // hand-off and the epilogue through LDS are conv3x3_halo_h2.hip's.
 #include "conv_common.h"
+#include "patch_plan.h"
 #include <type_traits>
 #include <stdlib.h>
 
@@ -34,6 +35,7 @@
 #define NJ 6              // halo pixels per thread (6 x 64 pixel slots x 8 float4 slots)
 #define NT 512
 #define HALO_MAX_LEVELS 6
+#define HALO_MAX_SEGS (2 * HALO_MAX_LEVELS)      // a map is cut into at most two regions (patch_plan.h)
 
 struct HaloArgsS {
   const float* x;
@@ -47,19 +49,25 @@ struct HaloArgsS {
   int N, H, W, C, K, relu, res_mode, ldy, ldr;
   int next_err_index;        // presplit: the consumer's range word (a value beyond its |a| <= 4094 is raised THERE, as its own split would)
   int presplit;              // 1: y is written as the fp16 planes its ONE consumer multiplies (see lvc_conv3x3_nhwc_f16s1_presplit)
-  int PH, PW, HW, HP, MP;
-  int inv_pw;                // ceil(2^16 / PW): (r * inv_pw) >> 16 == r / PW for the tile rows r < 256
-  int tiles_x, tiles_y, tiles_n, nk, total_units, units_per_worker, nworkers, err_index;
+  int tiles_n, nk, total_units, units_per_worker, nworkers, err_index;
+  // Patches: segment s = one region of one map with its own patch shape PH x PW (patch_plan.h) owns the row tiles
+  // [sg_tile0[s], sg_tile0[s + 1]) -- image slowest, then patch row, then patch column; a map's segments follow each other, the maps in
+  // the order given.  sg_y0 / sg_x0: the region's corner in its map; sg_inv_pw = ceil(2^16 / PW): (r * inv_pw) >> 16 == r / PW for the
+  // tile rows r < 256.  The halo is read from the whole map, and the region before a split is exact along the split axis: the
+  // "pixel inside the map" masks are all the clipping there is.
+  int nseg;
+  int sg_tile0[HALO_MAX_SEGS + 1];
+  int sg_lv[HALO_MAX_SEGS], sg_y0[HALO_MAX_SEGS], sg_x0[HALO_MAX_SEGS], sg_PH[HALO_MAX_SEGS], sg_PW[HALO_MAX_SEGS], sg_inv_pw[HALO_MAX_SEGS];
+  int sg_tx[HALO_MAX_SEGS], sg_ty[HALO_MAX_SEGS];
   int ngroup;
   int x_bytes;
   long long w_plane_elems;
-  // several maps in one launch (same weights, same channel counts, no residual: the RPN head over the pyramid levels): map l owns
-  // the row tiles [lv_tile0[l], lv_tile0[l + 1]); nlev = 0: the one map above
+  // several maps in one launch (same weights, same channel counts, no residual: the RPN head over the pyramid levels): map l = sg_lv[s]
+  // of segment s; nlev = 0: the one map above
   int nlev;
   const float* lv_x[HALO_MAX_LEVELS];
   float* lv_y[HALO_MAX_LEVELS];
-  int lv_H[HALO_MAX_LEVELS], lv_W[HALO_MAX_LEVELS], lv_tx[HALO_MAX_LEVELS], lv_ty[HALO_MAX_LEVELS], lv_xbytes[HALO_MAX_LEVELS];
-  int lv_tile0[HALO_MAX_LEVELS + 1];
+  int lv_H[HALO_MAX_LEVELS], lv_W[HALO_MAX_LEVELS], lv_xbytes[HALO_MAX_LEVELS];
   // ... or L layers of one shape, a map each (the FPN output convs): per-map weight planes, scale and shift (lv_w[0] == nullptr: p.w, p.scale, p.shift)
   const unsigned short* lv_w[HALO_MAX_LEVELS];
   const float* lv_scale[HALO_MAX_LEVELS];
@@ -189,22 +197,16 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_halo_s1_kernel(HaloArgsS p) {
 
   // fragment offsets.  A (halves): halo pixel of output pixel m at tap (0,0); rows past the patch read pixel 0.
   // B (bytes within a plane): row * 64 + swizzled granule of k16 step s2: ((s2 * 2 + fh) ^ ((row >> 2) & 3)) * 16
-  int a_frag[2];
-#pragma unroll
-  for (int mi = 0; mi < 2; ++mi) {
-    const int m = wm * 64 + mi * 32 + fi;
-    const int mm = m < p.MP ? m : 0;
-    const int py = mm / p.PW, px = mm - py * p.PW;
-    a_frag[mi] = (py * p.HW + px) * LROW + fh * 8;
-  }
+  // What depends on the patch shape (a_frag, row_off, a_lds) is formed when a tile lies in another segment than the worker's last.
+  int a_frag[2] = {0, 0};
   const int fx3 = (fi >> 2) & 3;
   const int b_row = (wn * 32 * NI + fi) * 64;
   const int b_g[2] = {((0 + fh) ^ fx3) * 16, ((2 + fh) ^ fx3) * 16};
-  const int row_off = p.HW * LROW;   // halves per halo row
-
-  int a_lds[NJ];    // LDS offset (halves) of this thread's halo slots
+  int row_off = 0;   // halves per halo row
+  int a_lds[NJ];     // LDS offset (halves) of this thread's halo slots
 #pragma unroll
-  for (int j = 0; j < NJ; ++j) a_lds[j] = min(hrow + 64 * j, p.HP - 1) * LROW + q * 4;
+  for (int j = 0; j < NJ; ++j) a_lds[j] = 0;
+  int cur_sg = -1;
   float big = 0.f;   // largest |activation| staged: beyond the scaled fp16 range -> workspace error word
 #ifdef HALO_TIMELINE
   // diagnostics build only (scripts/probe_halo_timeline.py): cycles of this wave between barriers, in the vmcnt wait, in the barrier
@@ -217,28 +219,45 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_halo_s1_kernel(HaloArgsS p) {
     const int cc1 = min(p.nk, cc0 + (u_end - u));
     const int tile_n = p.ngroup > 1 ? wsel : tile % p.tiles_n;
     const int tile_m = p.ngroup > 1 ? tile : tile / p.tiles_n;
-    // the map this row tile belongs to (one map: the launch's own fields)
-    int Hl = p.H, Wl = p.W, txl = p.tiles_x, tyl = p.tiles_y, xbl = p.x_bytes, tml = tile_m;
+    // the segment this row tile belongs to (workgroup-uniform: scalar compares), its patch shape ...
+    int sg = 0;
+#pragma unroll
+    for (int l = 1; l < HALO_MAX_SEGS; ++l) sg += (l < p.nseg && tile_m >= p.sg_tile0[l]) ? 1 : 0;
+    const int PH = p.sg_PH[sg], PW = p.sg_PW[sg], inv_pw = p.sg_inv_pw[sg];
+    const int HW = PW + 2, HP = (PH + 2) * HW, MP = PH * PW;
+    if (sg != cur_sg) {
+      cur_sg = sg;
+#pragma unroll
+      for (int mi = 0; mi < 2; ++mi) {
+        const int m = wm * 64 + mi * 32 + fi;
+        const int mm = m < MP ? m : 0;
+        const int py = (mm * inv_pw) >> 16, px = mm - py * PW;
+        a_frag[mi] = (py * HW + px) * LROW + fh * 8;
+      }
+      row_off = HW * LROW;
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) a_lds[j] = min(hrow + 64 * j, HP - 1) * LROW + q * 4;
+    }
+    // ... and its map (one map: the launch's own fields)
+    const int txl = p.sg_tx[sg], tyl = p.sg_ty[sg], tml = tile_m - p.sg_tile0[sg];
+    int Hl = p.H, Wl = p.W, xbl = p.x_bytes;
     const float* xl = p.x;
     float* yl = p.y;
     const unsigned short* wl = p.w;
     const float* scl = p.scale;
     const float* shl = p.shift;
     if (p.nlev > 0) {
-      int lv = 0;
-#pragma unroll
-      for (int l = 1; l < HALO_MAX_LEVELS; ++l) lv += (l < p.nlev && tile_m >= p.lv_tile0[l]) ? 1 : 0;
-      Hl = p.lv_H[lv]; Wl = p.lv_W[lv]; txl = p.lv_tx[lv]; tyl = p.lv_ty[lv]; xbl = p.lv_xbytes[lv];
+      const int lv = p.sg_lv[sg];
+      Hl = p.lv_H[lv]; Wl = p.lv_W[lv]; xbl = p.lv_xbytes[lv];
       xl = p.lv_x[lv]; yl = p.lv_y[lv];
       if (p.lv_w[0]) { wl = p.lv_w[lv]; scl = p.lv_scale[lv]; shl = p.lv_shift[lv]; }
-      tml = tile_m - p.lv_tile0[lv];
     }
     const __amdgpu_buffer_rsrc_t xres = __builtin_amdgcn_make_buffer_rsrc((void*)xl, 0, xbl, 0x00020000);
     const int tx = tml % txl;
     const int t2 = tml / txl;
     const int ty = t2 % tyl;
     const int img = t2 / tyl;
-    const int y0 = ty * p.PH, x0 = tx * p.PW;
+    const int y0 = p.sg_y0[sg] + ty * PH, x0 = p.sg_x0[sg] + tx * PW;
     const int n0 = tile_n * HN;
 
     unsigned a_off[NJ];
@@ -246,8 +265,8 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_halo_s1_kernel(HaloArgsS p) {
     for (int j = 0; j < NJ; ++j) {
       // slots past the halo re-stage its last pixel (same source, same destination, same data): every lane stays active and the
       // staging code has no branch to split the MFMA schedule around
-      const int h = min(hrow + 64 * j, p.HP - 1);
-      const int hy = h / p.HW, hx = h - hy * p.HW;
+      const int h = min(hrow + 64 * j, HP - 1);
+      const int hy = h / HW, hx = h - hy * HW;
       const int yy = y0 - 1 + hy, xx = x0 - 1 + hx;
       const bool ok = yy >= 0 && yy < Hl && xx >= 0 && xx < Wl;
       a_off[j] = ok ? (unsigned)(((img * Hl + yy) * Wl + xx) * p.C + q * 4) * 4u : 0x80000000u;
@@ -536,7 +555,11 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_halo_s1_kernel(HaloArgsS p) {
     const unsigned long long tl_e1 = __builtin_readcyclecounter();
     tl_hand += tl_e1 - tl_e0;
 #endif
-    // ---- epilogue through LDS: tile row r is patch pixel (r / PW, r % PW)
+    // ---- epilogue through LDS: tile row r is patch pixel (r / PW, r % PW).  The patch's row geometry is read again here, from an
+    // opaque copy of the segment index: carried through the tap loop, the three values cost scalar registers there (spills)
+    int sge = sg;
+    asm volatile("" : "+s"(sge));
+    const int ePW = p.sg_PW[sge], einv_pw = p.sg_inv_pw[sge], eMP = p.sg_PH[sge] * ePW;
     float* Cs = reinterpret_cast<float*>(smem_raw);
     if constexpr (PRED) {
       // A pointwise layer on top (HaloArgsS::pred_w): this workgroup holds act(conv) for HN of the K hidden channels of its pixels --
@@ -605,9 +628,9 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_halo_s1_kernel(HaloArgsS p) {
 #pragma unroll 2
         for (int rr = 0; rr < 32; rr += 2) {
           const int r = wave * 32 + rr + fh;
-          const int py = (r * p.inv_pw) >> 16, px = r - py * p.PW;
+          const int py = (r * einv_pw) >> 16, px = r - py * ePW;
           const float v = rblk[(rr + fh) * 32 + fi];
-          if (r < p.MP && py < ylim && px < xlim) unsafeAtomicAdd(ybase + (size_t)(unsigned)(py * Wl + px) * p.ldy, v * psc + psh);
+          if (r < eMP && py < ylim && px < xlim) unsafeAtomicAdd(ybase + (size_t)(unsigned)(py * Wl + px) * p.ldy, v * psc + psh);
         }
       }
       // the pointwise layer's own range word: a hidden value beyond fp16
@@ -656,8 +679,8 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_halo_s1_kernel(HaloArgsS p) {
 #pragma unroll 4
         for (int it = 0; it < HM / RPI; ++it) {
           const int r = it * RPI + rsub;
-          const int py = (r * p.inv_pw) >> 16, px = r - py * p.PW;
-          if (r < p.MP && py < ylim && px < xlim) {
+          const int py = (r * einv_pw) >> 16, px = r - py * ePW;
+          if (r < eMP && py < ylim && px < xlim) {
             const unsigned pix = (unsigned)(py * Wl + px);
             f32x4 v = *reinterpret_cast<const f32x4*>(cs + it * RPI * CS_STRIDE);
             v = v * sc + sh;
@@ -721,21 +744,40 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_halo_s1_kernel(HaloArgsS p) {
   lvc_report_range(p.flags, p.err_index, big, ONEACC ? LVC_ACT_MAX : LVC_F16_MAX);
 }
 
-// Patch shape for an H x W output: PH * PW <= 256 pixels, (PH + 2) * (PW + 2) <= HALO_S1 halo pixels, fewest patches
-// (every patch costs a full 256-row MFMA tile whatever its fill); ties go to the smaller halo.
-static void pick_patch_s(int H, int W, int* PH, int* PW) {
-  long long best_tiles = -1;
-  int best_halo = 0, bh = 1, bw = 8;
-  for (int pw = 4; pw <= 128; ++pw)
-    for (int ph = 1; ph * pw <= HM; ++ph) {
-      const int halo = (ph + 2) * (pw + 2);
-      if (halo > HALO_S1) break;
-      const long long tiles = (long long)lvc_cdiv(H, ph) * lvc_cdiv(W, pw);
-      if (best_tiles < 0 || tiles < best_tiles || (tiles == best_tiles && halo < best_halo)) {
-        best_tiles = tiles; best_halo = halo; bh = ph; bw = pw;
-      }
-    }
-  *PH = bh; *PW = bw;
+// Patch shapes for an H x W output: PH * PW <= 256 pixels, (PH + 2) * (PW + 2) <= HALO_S1 halo pixels, PW >= 4, fewest patches
+// (every patch costs a full 256-row MFMA tile whatever its fill); ties go to the smaller halo.  patch_plan.h: one shape per map (the
+// default: the decomposition this kernel always had, so its stream-K boundaries and every output bit stay where they were), or, under
+// lvc_set_patch_plan(2), up to two regions with a shape each; answers are memoised per map size.
+static LvcPatchPlanner& halo_s1_planner() {
+  static thread_local LvcPatchPlanner planner = LvcPatchPlanner::direct(HM, HALO_S1, 4);
+  return planner;
+}
+
+// Appends the segments of map `lv` (N images of H x W) to the launch and their row tiles to `tiles`.  forced: one given shape for the
+// whole map (the single-shape arm of the grouped launches: the largest map's; the experiment hook), else the map's own plan.
+static int halo_s1_add_map(HaloArgsS& a, int lv, int N, int H, int W, const LvcPatchShape* forced, long long* tiles) {
+  LvcPatchPlan one;
+  const LvcPatchPlan* plan;
+  if (forced) {
+    one.nreg = 1;
+    one.reg[0] = LvcPatchRegion{0, 0, H, W, forced->PH, forced->PW, lvc_cdiv(H, forced->PH), lvc_cdiv(W, forced->PW)};
+    plan = &one;
+  } else {
+    plan = &halo_s1_planner().plan(H, W, lvc_patch_plan() >= 2);
+  }
+  for (int r = 0; r < plan->nreg; ++r) {
+    const LvcPatchRegion& g = plan->reg[r];
+    LVC_CHECK_ARG(a.nseg < HALO_MAX_SEGS, "too many map regions");
+    const int s = a.nseg++;
+    a.sg_lv[s] = lv; a.sg_y0[s] = g.y0; a.sg_x0[s] = g.x0; a.sg_PH[s] = g.PH; a.sg_PW[s] = g.PW;
+    a.sg_inv_pw[s] = (65536 + g.PW - 1) / g.PW;
+    a.sg_tx[s] = g.tiles_x; a.sg_ty[s] = g.tiles_y;
+    a.sg_tile0[s] = (int)*tiles;
+    *tiles += (long long)N * g.tiles_x * g.tiles_y;
+    LVC_CHECK_ARG(*tiles < (1ll << 30), "too many tiles");
+    a.sg_tile0[s + 1] = (int)*tiles;
+  }
+  return LVC_OK;
 }
 
 // tiles_m_total row tiles (all maps); fills the stream-K split and launches
@@ -785,16 +827,18 @@ struct HaloPred {
   int K, rows, ld, slot;
 };
 
-static void halo_s1_patch(HaloArgsS& a, int H, int W) {
-  pick_patch_s(H, W, &a.PH, &a.PW);
+// the one shape forced on every map of a launch, if any: *forced is filled and returned, else nullptr (every map gets its own plan).
+// H x W: the launch's largest map, whose single shape the grouped launches use unless lvc_set_patch_plan(2) is set
+static const LvcPatchShape* halo_s1_forced_shape(int H, int W, bool grouped, LvcPatchShape* forced) {
+  const LvcPatchShape* f = nullptr;
+  if (grouped && lvc_patch_plan() < 2) { *forced = halo_s1_planner().single(H, W); f = forced; }
 #ifdef LVC_HALO_PATCH_HOOK   // experiment build only (scripts/sweep_halo_patch.sh: make HOOKS=-DLVC_HALO_PATCH_HOOK): no getenv on the launch path otherwise
   if (const char* e = getenv("LVC_HALO_PATCH")) {   // experiments: "PH,PW"
     int ph = 0, pw = 0;
-    if (sscanf(e, "%d,%d", &ph, &pw) == 2 && ph > 0 && pw > 0 && ph * pw <= HM && (ph + 2) * (pw + 2) <= HALO_S1) { a.PH = ph; a.PW = pw; }
+    if (sscanf(e, "%d,%d", &ph, &pw) == 2 && ph > 0 && pw > 0 && ph * pw <= HM && (ph + 2) * (pw + 2) <= HALO_S1) { *forced = LvcPatchShape{ph, pw, 0}; f = forced; }
   }
 #endif
-  a.HW = a.PW + 2; a.HP = (a.PH + 2) * a.HW; a.MP = a.PH * a.PW;
-  a.inv_pw = (65536 + a.PW - 1) / a.PW;
+  return f;
 }
 
 static int halo_s1_launch(bool oneacc, const float* x, const unsigned short* w_split, const float* scale, const float* shift,
@@ -817,18 +861,19 @@ static int halo_s1_launch(bool oneacc, const float* x, const unsigned short* w_s
   if (presplit) LVC_CHECK_ARG(oneacc && relu == 1 && res_mode == 0 && K % 32 == 0 && a.ldy == K, "pre-split output: single accumulator, ReLU, no residual, K % 32 == 0, dense rows");
   if (presplit) LVC_CHECK_ARG(next_slot > 0 && next_slot < lvc_range_slots(), "pre-split output: the consumer's range slot");
   a.presplit = presplit; a.next_err_index = lvc_ws_range_index(next_slot);
-  halo_s1_patch(a, H, W);
-  a.tiles_x = lvc_cdiv(W, a.PW); a.tiles_y = lvc_cdiv(H, a.PH);
   const long long xb = (long long)N * H * W * C * 4;
   LVC_CHECK_ARG(xb < (1ll << 31), "input tensor must be smaller than 2 GiB");
   a.x_bytes = (int)xb;
-  return halo_s1_finish(a, oneacc, (long long)N * a.tiles_x * a.tiles_y, Kg, workspace, stream);
+  LvcPatchShape forced;
+  long long tiles = 0;
+  if (int st = halo_s1_add_map(a, 0, N, H, W, halo_s1_forced_shape(H, W, false, &forced), &tiles)) return st;
+  return halo_s1_finish(a, oneacc, tiles, Kg, workspace, stream);
 }
 
 // L maps [N, Hs[l], Ws[l], C] through the SAME 3x3 layer in one launch (outputs ys[l] [N, Hs[l], Ws[l], K], rows of K floats): the
-// RPN head over the pyramid levels.  One stream-K split over the row tiles of all maps (in the order given), one patch shape
-// (chosen for the largest map): the small maps no longer pay a launch each that cannot fill the chip.  Per output pixel the arithmetic is
-// the single-map launch's.  oneacc as above; no residual.
+// RPN head over the pyramid levels.  One stream-K split over the row tiles of all maps (in the order given), one patch shape, chosen
+// for the largest map (under lvc_set_patch_plan(2): every map with its own patch plan): the small maps no longer pay a launch each
+// that cannot fill the chip.  Per output pixel the arithmetic is the single-map launch's.  oneacc as above; no residual.
 static int halo_s1_levels(int oneacc, const float* const* xs, float* const* ys, const int* Hs, const int* Ws, int L,
                           const unsigned short* w_split, const float* scale, const float* shift, const unsigned short* const* ws,
                           const float* const* scales, const float* const* shifts, int N, int C, int K, int Kg, int relu, void* workspace,
@@ -856,10 +901,12 @@ static int halo_s1_levels(int oneacc, const float* const* xs, float* const* ys, 
     a.pred_err_index = lvc_ws_range_index(pred->slot);
     a.ldy = pred->ld;
   }
-  int big = 0;      // the patch shape is chosen for the largest map, wherever it stands in the list
+  int big = 0;      // the largest map, wherever it stands in the list: the single-shape form takes ITS patch shape for every map
   for (int l = 1; l < L; ++l)
     if ((long long)Hs[l] * Ws[l] > (long long)Hs[big] * Ws[big]) big = l;
-  halo_s1_patch(a, Hs[big], Ws[big]);
+  LVC_CHECK_ARG(Hs[big] > 0 && Ws[big] > 0, "bad map");
+  LvcPatchShape forced_shape;
+  const LvcPatchShape* forced = halo_s1_forced_shape(Hs[big], Ws[big], true, &forced_shape);
   long long tiles = 0;
   a.nlev = L;
   for (int l = 0; l < L; ++l) {
@@ -874,13 +921,9 @@ static int halo_s1_levels(int oneacc, const float* const* xs, float* const* ys, 
                     "per-map weights: null or misaligned pointer");
       a.lv_w[l] = ws[l]; a.lv_scale[l] = scales[l]; a.lv_shift[l] = shifts[l];
     }
-    a.lv_tx[l] = lvc_cdiv(Ws[l], a.PW); a.lv_ty[l] = lvc_cdiv(Hs[l], a.PH);
-    a.lv_tile0[l] = (int)tiles;
-    tiles += (long long)N * a.lv_tx[l] * a.lv_ty[l];
-    LVC_CHECK_ARG(tiles < (1ll << 30), "too many tiles");
+    if (int st = halo_s1_add_map(a, l, N, Hs[l], Ws[l], forced, &tiles)) return st;
   }
-  a.lv_tile0[L] = (int)tiles;
-  a.x = xs[0]; a.y = ys[0]; a.H = Hs[0]; a.W = Ws[0]; a.tiles_x = a.lv_tx[0]; a.tiles_y = a.lv_ty[0]; a.x_bytes = a.lv_xbytes[0];
+  a.x = xs[0]; a.y = ys[0]; a.H = Hs[0]; a.W = Ws[0]; a.x_bytes = a.lv_xbytes[0];
   return halo_s1_finish(a, oneacc != 0, tiles, Kg, workspace, stream);
 }
 

@@ -21,6 +21,7 @@
 // in exactly that order by lvc_amd.kernels.pack_wino -- arrive by LDS-DMA one stage ahead into a ring of two.  A stage = (chunk, filter
 // row): 24 MFMAs per wave, one barrier.
 #include "conv_common.h"
+#include "patch_plan.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -42,7 +43,11 @@ struct WinoArgs {
   int* flags;
   float* partials;             // stream-K: 256 KB per worker (the conv workspace of the other kernels)
   int N, H, W, C, K, Kpad, ldy, relu;
-  int PH, PWP, lg_pwp, tiles_x, tiles_y, tiles_n, ntiles, nk, err_index;
+  // patches: at most two regions per map (patch_plan.h), each with its own patch shape; an image's tiles are region 0's, then region
+  // 1's from tile rg_first1 on (one region: rg_first1 = tiles_img, never reached)
+  int rg_y0[2], rg_x0[2], rg_PH[2], rg_PWP[2], rg_lg_pwp[2], rg_tiles_x[2];
+  int rg_first1, tiles_img;
+  int tiles_n, ntiles, nk, err_index;
   int units_per_worker, nworkers;   // stream-K: a unit = one 16-channel chunk of one tile
   unsigned x_bytes, y_bytes;
   // PRED: a pointwise layer on top of act(conv) (the RPN predictor): y = ITS output rows (ldy floats, zeroed by the caller)
@@ -57,7 +62,9 @@ struct WinoArgs {
 // whose segment does not hold the tile's first chunk hands its partial sums (still in the transformed domain: the output transform is
 // linear) to the worker that does -- the hand-off of conv_common.h: partials [worker][128 values][512 threads], a flag per
 // worker, the owner adds the later workers' parts in worker order (deterministic) and runs the epilogue.  lw = this worker.
-template <bool PRED, bool SK>
+// REGIONS: the map may be cut into two regions with a patch shape each (the one-workgroup-per-tile kernel); the stream-K / persistent
+// kernels are launched on the single-shape plan and read region 0 only.
+template <bool PRED, bool SK, bool REGIONS = false>
 __device__ __forceinline__ void wino_tile(const WinoArgs& p, const int t, const int cc0, const int cc1, const int lw, unsigned char* const smem) {
   unsigned char* const sV = smem;
   unsigned char* const sU = smem + 2 * WN_VBUF;
@@ -71,14 +78,18 @@ __device__ __forceinline__ void wino_tile(const WinoArgs& p, const int t, const 
   const int fi = lane & 31, fh = lane >> 5;
 
   // ---- tile: (image, patch row, patch column, channel tile); consecutive ids share the patch (channel tile fastest) and land on one XCD
+  // (t is the same for the whole workgroup: the region is picked by scalar compares and selects)
   const int tn = t % p.tiles_n;
-  int r0 = t / p.tiles_n;
-  const int tx = r0 % p.tiles_x;
-  r0 /= p.tiles_x;
-  const int ty = r0 % p.tiles_y;
-  const int img = r0 / p.tiles_y;
-  const int y0 = ty * p.PH, x0 = tx * 2 * p.PWP, n0 = tn * WN_CH;
-  const int VR = (p.PH + 2) * p.PWP;                  // V rows of this patch shape
+  const int r0 = t / p.tiles_n;
+  const int img = r0 / p.tiles_img;
+  int rt = r0 - img * p.tiles_img;
+  const bool reg1 = REGIONS && rt >= p.rg_first1;
+  rt -= reg1 ? p.rg_first1 : 0;
+  const int PH = reg1 ? p.rg_PH[1] : p.rg_PH[0], PWP = reg1 ? p.rg_PWP[1] : p.rg_PWP[0], lg_pwp = reg1 ? p.rg_lg_pwp[1] : p.rg_lg_pwp[0];
+  const int rtx = reg1 ? p.rg_tiles_x[1] : p.rg_tiles_x[0];
+  const int ty = rt / rtx, tx = rt - ty * rtx;
+  const int y0 = (reg1 ? p.rg_y0[1] : p.rg_y0[0]) + ty * PH, x0 = (reg1 ? p.rg_x0[1] : p.rg_x0[0]) + tx * 2 * PWP, n0 = tn * WN_CH;
+  const int VR = (PH + 2) * PWP;                      // V rows of this patch shape
 
   const __amdgpu_buffer_rsrc_t xres = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.x_bytes, 0x00020000);
 
@@ -95,7 +106,7 @@ __device__ __forceinline__ void wino_tile(const WinoArgs& p, const int t, const 
   float sgn1;
   {
     const int vrow = tid >> 2;
-    const int vy = vrow >> p.lg_pwp, vx = vrow & (p.PWP - 1);
+    const int vy = vrow >> lg_pwp, vx = vrow & (PWP - 1);
     const int iy = y0 - 1 + vy, ix = x0 + 2 * vx - 1;
     unsigned m = 0;
 #pragma unroll
@@ -107,7 +118,7 @@ __device__ __forceinline__ void wino_tile(const WinoArgs& p, const int t, const 
   {
     const int vrow = 128 + (tid >> 4), pz = (tid >> 2) & 3;
     on1 = vrow < VR;
-    const int vy = vrow >> p.lg_pwp, vx = vrow & (p.PWP - 1);
+    const int vy = vrow >> lg_pwp, vx = vrow & (PWP - 1);
     const int iy = y0 - 1 + vy, ix = x0 + 2 * vx - 1;
     // position -> (first pixel, second pixel, sign):  V0 = d0 - d2, V1 = d1 + d2, V2 = d2 - d1, V3 = d1 - d3
     const int ja = pz == 0 ? 0 : pz == 2 ? 2 : 1, jb = pz == 3 ? 3 : pz == 2 ? 1 : 2;
@@ -201,7 +212,7 @@ __device__ __forceinline__ void wino_tile(const WinoArgs& p, const int t, const 
     int arow[2];
 #pragma unroll
     for (int mi = 0; mi < 2; ++mi) {
-      const int vrow = m_lo + 32 * mi + r * p.PWP;
+      const int vrow = m_lo + 32 * mi + r * PWP;
       arow[mi] = vrow * 32 + ((fh ^ ((vrow >> 3) & 1)) << 4);
     }
 #pragma unroll
@@ -384,7 +395,7 @@ __device__ __forceinline__ void wino_tile(const WinoArgs& p, const int t, const 
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
         const int m = wm * 64 + mi * 32 + (e & 3) + 8 * (e >> 2) + 4 * fh;       // pair of the tile
-        const int py = m >> p.lg_pwp, px = m & (p.PWP - 1);
+        const int py = m >> lg_pwp, px = m & (PWP - 1);
         const int oy = y0 + py, ox = x0 + 2 * px + ph;
         const bool ok = oy < p.H && ox < p.W;
 #pragma unroll
@@ -470,7 +481,7 @@ __device__ __forceinline__ void wino_tile(const WinoArgs& p, const int t, const 
       for (int rr = 0; rr < 32; rr += 2) {
         const int r = wave * 32 + rr + fh;                                      // tile pixel row: pair r / 2, parity r & 1
         const int m = r >> 1;
-        const int oy = y0 + (m >> p.lg_pwp), ox = x0 + 2 * (m & (p.PWP - 1)) + (r & 1);
+        const int oy = y0 + (m >> lg_pwp), ox = x0 + 2 * (m & (PWP - 1)) + (r & 1);
         const float v = rblk[(rr + fh) * 32 + fi];
         if (oy < p.H && ox < p.W) unsafeAtomicAdd(p.y + ((size_t)((long long)img * p.H + oy) * p.W + ox) * p.ldy + fi, v * psc + psh);
       }
@@ -482,7 +493,7 @@ __device__ __forceinline__ void wino_tile(const WinoArgs& p, const int t, const 
 template <bool PRED>
 __global__ __launch_bounds__(WN_NT, 2) void conv3x3_wino_kernel(WinoArgs p) {
   __shared__ __attribute__((aligned(1024))) unsigned char smem[WN_SMEM];
-  wino_tile<PRED, false>(p, lvc_xcd_remap(blockIdx.x, p.ntiles), 0, p.nk, 0, smem);
+  wino_tile<PRED, false, true>(p, lvc_xcd_remap(blockIdx.x, p.ntiles), 0, p.nk, 0, smem);
 }
 
 // Stream-K form: one resident workgroup per CU, worker w takes the units [w upw, (w + 1) upw) of the (tile, chunk) list -- consecutive
@@ -534,11 +545,18 @@ static int wino_launch(const float* x, const unsigned short* u, const float* sca
   const long long xb = (long long)N * H * W * C * 4, yb = (long long)N * H * W * a.ldy * 4;
   LVC_CHECK_ARG(xb < (1ll << 31) && yb < (1ll << 31), "tensors must be smaller than 2 GiB");
   a.x_bytes = (unsigned)xb; a.y_bytes = (unsigned)yb;
-  // patch shape: 8 rows x 16 pairs (32 pixels), or 16 rows x 8 pairs for maps that waste less on it
-  auto waste = [&](int phh, int pwp) { return (long long)lvc_cdiv(H, phh) * phh * lvc_cdiv(W, 2 * pwp) * 2 * pwp; };
-  if (waste(16, 8) < waste(8, 16)) { a.PH = 16; a.PWP = 8; a.lg_pwp = 3; } else { a.PH = 8; a.PWP = 16; a.lg_pwp = 4; }
-  a.tiles_x = lvc_cdiv(W, 2 * a.PWP); a.tiles_y = lvc_cdiv(H, a.PH); a.tiles_n = lvc_cdiv(K, WN_CH);
-  const long long nt = (long long)N * a.tiles_x * a.tiles_y * a.tiles_n;
+  // patch shape: 8 rows x 16 pairs (32 pixels), or 16 rows x 8 pairs for maps that waste less on it -- per region of the map
+  // (patch_plan.h; one region under lvc_set_patch_plan(0) and for the stream-K / persistent forms)
+  static thread_local LvcPatchPlanner planner = LvcPatchPlanner::winograd();
+  const LvcPatchPlan& plan = planner.plan(H, W, lvc_patch_plan() != 0 && g_wino_streamk == 0);
+  for (int r = 0; r < 2; ++r) {
+    const LvcPatchRegion& g = plan.reg[r];
+    a.rg_y0[r] = g.y0; a.rg_x0[r] = g.x0; a.rg_PH[r] = g.PH; a.rg_PWP[r] = g.PW / 2; a.rg_lg_pwp[r] = g.PW == 32 ? 4 : 3; a.rg_tiles_x[r] = g.tiles_x;
+  }
+  a.tiles_img = (int)plan.tiles;
+  a.rg_first1 = plan.nreg == 2 ? plan.reg[0].tiles_y * plan.reg[0].tiles_x : a.tiles_img;
+  a.tiles_n = lvc_cdiv(K, WN_CH);
+  const long long nt = (long long)N * plan.tiles * a.tiles_n;
   LVC_CHECK_ARG(nt < (1ll << 31), "too many tiles");
   a.ntiles = (int)nt;
   a.nk = C / 16;
