@@ -847,6 +847,29 @@ int lvc_group_norm_bwd_nhwc(const float* dy, const float* x, const float* mean, 
                             long long x_sn, long long x_sh, long long x_sw, long long x_sc, int relu, int tile_rows,
                             void* workspace, long long workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Mask R-CNN inference: the mask head's tail and the paste of the predicted masks into the image.
+ * lvc_mask_deconv_predict (csrc/mask_deconv.hip): ConvTranspose2d(Cin, Cmid, 2, stride 2) + bias -> ReLU -> Conv2d(Cmid, K, 1) + bias ->
+ *   the plane of ONE class per RoI -> sigmoid, one launch (detectron2/modeling/roi_heads/mask_head.py `layers` + mask_rcnn_inference):
+ *     prob[m, 2y+dy, 2x+dx] = sigmoid(b_pred[c] + sum_co relu(b_deconv[co] + sum_ci x[m,y,x,ci] * Wd[ci,co,dy,dx]) * w_pred[c,co])
+ *   x [M,S,S,Cin] NHWC fp32; w_deconv [4*Cmid, Cin], row (dy*2+dx)*Cmid + co (from the parameter [Cin,Cmid,2,2]); w_pred [K,Cmid];
+ *   b_deconv [Cmid], b_pred [K] (NULL = zeros); classes [M] int32, c = classes[m] (NULL: class 0 for every row, CLS_AGNOSTIC_MASK);
+ *   d_num_valid (device int, may be NULL): rows >= *d_num_valid are neither read nor written; prob [M,2S,2S].
+ *   Cin, Cmid multiples of 64 up to 256, K >= 1, S >= 1, any M; anything else returns LVC_ERR_INVALID.  Exact fp32 MFMA (range-free).
+ *   A class outside [0, K) sets bit 3 (value 8) of *d_status and is computed as class 0.  No float atomics: two runs are bit-identical.
+ * lvc_paste_masks (csrc/mask_paste.hip): detectron2/layers/mask_ops.py paste_masks_in_image for a batch in one launch.  A job = 8 int64
+ *   words: row of prob [num_rows, mask_size, mask_size]; x0, y0, x1, y1 (fp32 bit patterns, output coordinates); out_h; out_w; byte
+ *   offset of the job's [out_h, out_w] uint8 plane in `out`.  h_jobs [host] is checked (row and plane inside their buffers, finite
+ *   boxes of positive width and height: the non-empty filter runs before the paste), d_jobs is its device copy, read by the kernel.
+ *   out: 16-byte aligned, out_bytes a multiple of 16; every byte of every job's plane is written (value >= threshold ? 1 : 0), bytes
+ *   outside the planes are not touched.  threshold >= 0 (0 sets every pixel, as in the reference; its threshold < 0 visualisation
+ *   branch is not built). */
+int lvc_mask_deconv_predict(const float* x, const float* w_deconv, const float* b_deconv, const float* w_pred, const float* b_pred,
+                            const int* classes, const int* d_num_valid, float* prob, int M, int S, int Cin, int Cmid, int K,
+                            int* d_status, void* stream);
+int lvc_paste_masks(const float* prob, int num_rows, int mask_size, const long long* h_jobs, const long long* d_jobs, int num_jobs,
+                    unsigned char* out, long long out_bytes, float threshold, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

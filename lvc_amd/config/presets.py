@@ -43,6 +43,15 @@ def gn_rcnn_fpn(depth=50, num_classes=80, device="cuda"):
     return cfg
 
 
+def mask_rcnn_fpn(depth=50, num_classes=80, device="cuda"):
+    """Mask R-CNN on the ResNet-FPN trunk: what detectron2's `COCO-InstanceSegmentation/mask_rcnn_R_50_FPN_*.yaml` and the mask keys of
+    `Base-RCNN-FPN.yaml` set on top of `base_rcnn_fpn` (four 3x3 convs, a 14x14 mask pooler).  Inference only."""
+    cfg = base_rcnn_fpn(depth=depth, num_classes=num_classes, device=device)
+    cfg.merge_from_list(["MODEL.MASK_ON", True, "MODEL.ROI_MASK_HEAD.NAME", "MaskRCNNConvUpsampleHead", "MODEL.ROI_MASK_HEAD.NUM_CONV", 4,
+                         "MODEL.ROI_MASK_HEAD.POOLER_RESOLUTION", 14])
+    return cfg
+
+
 def resnext_rcnn_fpn(depth=101, num_groups=32, width_per_group=8, num_classes=80, device="cuda"):
     """`base_rcnn_fpn` on a ResNeXt trunk: detectron2's `COCO-Detection/faster_rcnn_X_101_32x8d_FPN_3x.yaml` sets exactly these four
     keys (`STRIDE_IN_1X1: False` is the published X-101 setting; `True` builds too -- the grouped 3x3 is then always stride 1).

@@ -27,9 +27,15 @@ def _limits(model):
     return (getattr(heads, "det_max_candidates", None), K.CONV_SPLIT, K.RANGE_EPOCH)
 
 
+def _refuse_masks(model, what):
+    if getattr(getattr(model, "roi_heads", None), "mask_on", False):
+        raise NotImplementedError("MODEL.MASK_ON: {} carries the box branch only; run a mask model through its own forward()".format(what))
+
+
 class PipelinedInference:
     def __init__(self, model, depth=2):
         assert depth >= 1
+        _refuse_masks(model, "PipelinedInference (the two-stream pipeline)")
         self.model = model
         self.streams = [torch.cuda.Stream(device=model.device) for _ in range(depth)]
         self._busy = [False] * depth   # one uncollected ticket per stream: the conv error word lives in the stream's workspace
@@ -114,6 +120,7 @@ class GraphedInference:
 
     def __init__(self, model, batched_inputs, do_postprocess=True):
         assert all("image" in b for b in batched_inputs), "graphed inference takes preprocessed {'image': CHW} inputs"
+        _refuse_masks(model, "GraphedInference (hipGraph capture)")
         self.model = model
         dev = model.device
         self.static = []

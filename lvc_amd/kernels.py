@@ -3393,3 +3393,92 @@ def upsample2_residual_grad(g, res_shape):
               "lvc_upsample2_add_grad_nhwc")
     assert tuple(out.shape) == tuple(res_shape)
     return out
+
+
+# --------------------------------------------------------------------------- Mask R-CNN inference
+MASK_BAD_CLASS = 8        # the status bit lvc_mask_deconv_predict raises for a class index outside [0, K)
+MASK_DECONV_CHANNELS = (64, 128, 192, 256)
+PASTE_FIELDS = 8          # int64 words per job of lvc_paste_masks (include/lvc_amd.h)
+
+
+def mask_deconv_check(cin, cmid):
+    if cin not in MASK_DECONV_CHANNELS or cmid not in MASK_DECONV_CHANNELS:
+        raise NotImplementedError("the mask head's deconvolution kernel takes channel counts of 64, 128, 192 or 256, got {} -> {} "
+                                  "(MODEL.ROI_MASK_HEAD.CONV_DIM)".format(cin, cmid))
+
+
+def pack_mask_deconv(weight):
+    """ConvTranspose2d weight [Cin, Cmid, 2, 2] -> [4 * Cmid, Cin], row (dy*2+dx)*Cmid + co."""
+    cin, cmid = weight.shape[0], weight.shape[1]
+    mask_deconv_check(cin, cmid)
+    return weight.detach().permute(2, 3, 1, 0).reshape(4 * cmid, cin).contiguous().float()
+
+
+def mask_deconv_predict(x, w_deconv, b_deconv, w_pred, b_pred, classes=None, num_valid=None, status=None, out=None):
+    """Deconv 2x2 s2 + bias + ReLU + 1x1 predictor of one class per row + bias + sigmoid (csrc/mask_deconv.hip).
+    x [M,S,S,Cin] NHWC; w_deconv [4*Cmid,Cin] (`pack_mask_deconv`); w_pred [K,Cmid]; classes [M] int32 or None (class 0);
+    num_valid: device int32, rows past it are neither read nor written.  Returns prob [M,2S,2S] (`out` when given)."""
+    _req_cuda(x, w_deconv, b_deconv, w_pred, b_pred, classes, num_valid, status)
+    M, S, S_, cin = x.shape
+    assert S == S_ and x.is_contiguous() and x.dtype == torch.float32
+    cmid = w_deconv.shape[0] // 4
+    mask_deconv_check(cin, cmid)
+    Kc = w_pred.shape[0]
+    assert w_deconv.shape == (4 * cmid, cin) and w_deconv.is_contiguous() and w_deconv.dtype == torch.float32
+    w_pred = w_pred.reshape(Kc, -1)
+    assert w_pred.shape == (Kc, cmid) and w_pred.is_contiguous() and w_pred.dtype == torch.float32
+    for b, n in ((b_deconv, cmid), (b_pred, Kc)):
+        assert b is None or (b.numel() == n and b.is_contiguous() and b.dtype == torch.float32)
+    if classes is not None:
+        assert classes.dtype == torch.int32 and classes.is_contiguous() and classes.numel() == M
+    if num_valid is not None:
+        assert num_valid.dtype == torch.int32 and num_valid.numel() == 1
+    if out is None:
+        out = torch.empty(M, 2 * S, 2 * S, device=x.device, dtype=torch.float32)
+    assert out.shape == (M, 2 * S, 2 * S) and out.is_contiguous() and out.dtype == torch.float32
+    check(_lib.lib().lvc_mask_deconv_predict(ptr(x), ptr(w_deconv), ptr(b_deconv), ptr(w_pred), ptr(b_pred), ptr(classes), ptr(num_valid),
+                                             ptr(out), c_int(M), c_int(S), c_int(cin), c_int(cmid), c_int(Kc), ptr(status), _stream(x)),
+          "lvc_mask_deconv_predict")
+    return out
+
+
+def paste_jobs(rows, boxes, sizes, offsets):
+    """The host job table of `paste_masks`: rows [n] (row of prob), boxes [n,4] fp32 in output coordinates, sizes [n,2] = (out_h, out_w),
+    offsets [n] = byte offset of each [out_h, out_w] plane.  -> int64 numpy [n, PASTE_FIELDS]."""
+    import numpy as np
+
+    n = len(rows)
+    jobs = np.zeros((n, PASTE_FIELDS), dtype=np.int64)
+    if n:
+        jobs[:, 0] = np.asarray(rows, dtype=np.int64)
+        jobs[:, 1:5] = np.ascontiguousarray(np.asarray(boxes, dtype=np.float32).reshape(n, 4)).view(np.uint32).astype(np.int64)
+        jobs[:, 5:7] = np.asarray(sizes, dtype=np.int64).reshape(n, 2)
+        jobs[:, 7] = np.asarray(offsets, dtype=np.int64)
+    return jobs
+
+
+def paste_masks(prob, jobs, out_bytes, threshold=0.5, out=None):
+    """paste_masks_in_image for every job in one launch (csrc/mask_paste.hip).  prob [R, Sm, Sm] fp32; jobs: `paste_jobs`' table;
+    out_bytes: the size of the uint8 output buffer the offsets refer to.  Returns the buffer (uint8 [out_bytes rounded up to 16]);
+    bytes outside the jobs' planes are not written (the padding at the end of a fresh buffer stays as allocated)."""
+    import numpy as np
+
+    if not threshold >= 0:
+        raise NotImplementedError("paste_masks: the threshold < 0 visualisation branch of the reference's paste_masks_in_image "
+                                  "is not built")
+    _req_cuda(prob)
+    assert prob.dim() == 3 and prob.shape[1] == prob.shape[2] and prob.is_contiguous() and prob.dtype == torch.float32
+    jobs = np.ascontiguousarray(jobs, dtype=np.int64).reshape(-1, PASTE_FIELDS)
+    padded = (int(out_bytes) + 15) // 16 * 16
+    if out is None:
+        out = torch.empty(padded, dtype=torch.uint8, device=prob.device)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == padded
+    n = jobs.shape[0]
+    if n == 0:
+        return out
+    # pinned and asynchronous: the upload is ordered on the stream, the host does not wait for the device
+    d_jobs = torch.from_numpy(jobs).pin_memory().to(prob.device, non_blocking=True)
+    check(_lib.lib().lvc_paste_masks(ptr(prob), c_int(prob.shape[0]), c_int(prob.shape[1]), c_void_p(jobs.ctypes.data), ptr(d_jobs),
+                                     c_int(n), ptr(out), c_longlong(padded), c_float(threshold), _stream(prob)),
+          "lvc_paste_masks")
+    return out

@@ -9,6 +9,7 @@ from .postprocessing import detector_postprocess
 from .proposal_generator import PROPOSAL_GENERATOR_REGISTRY, RPN, RPN_HEAD_REGISTRY, StandardRPNHead, build_proposal_generator
 from .roi_heads import (ROI_BOX_HEAD_REGISTRY, ROI_HEADS_OUTPUT_REGISTRY, ROI_HEADS_REGISTRY, CascadeROIHeads, ROIHeads, StandardROIHeads,
                         build_box_head, build_roi_heads)
-from .test_time_augmentation import DatasetMapperTTA, GeneralizedRCNNWithTTA
+from .test_time_augmentation import DatasetMapperTTA
+from .tta_masks import GeneralizedRCNNWithTTA
 
 __all__ = [k for k in globals().keys() if not k.startswith("_")]

@@ -151,6 +151,8 @@ class GeneralizedRCNN(_RCNNBase):
     def forward(self, batched_inputs):
         if not self.training:
             return self.inference(batched_inputs)
+        if self._mask_on():
+            raise NotImplementedError("training the mask branch (MODEL.MASK_ON: mask_rcnn_loss, gt_masks) is not built")
 
         def once():
             self.__dict__["_range_checked"] = False
@@ -282,11 +284,15 @@ class GeneralizedRCNN(_RCNNBase):
         """Reference rcnn.py:177-322 (the GeneralizedRCNN + RPN + StandardROIHeads branch)."""
         assert not self.training
         if detected_instances is not None:
-            raise NotImplementedError("forward_with_given_boxes (mask/keypoint heads) is not on the box-only path")
+            if not self._mask_on():
+                raise NotImplementedError("forward_with_given_boxes (mask/keypoint heads) is not on the box-only path")
+            return self._inference_given_boxes(batched_inputs, detected_instances, do_postprocess)
         if getattr(self, "output_layer", None) == "BoxOnlyLayersCascade":
             return self._inference_box_corrector(batched_inputs)
         if not (isinstance(self.proposal_generator, RPN) and isinstance(self.roi_heads, StandardROIHeads)):
             return self._inference_modular(batched_inputs, do_postprocess)
+        if self._mask_on():
+            return run_with_fallbacks(self, lambda: self._inference_masks(batched_inputs, do_postprocess))
         return run_with_fallbacks(self, lambda: self._inference_fast(batched_inputs, do_postprocess))
 
     def _inference_fast(self, batched_inputs, do_postprocess):
@@ -303,6 +309,109 @@ class GeneralizedRCNN(_RCNNBase):
             out_sizes.append((inp.get("height", dh), inp.get("width", dw)) if do_postprocess else (h, w))
         insts = instances_from_batched(ob, osc, ocl, cnt, out_sizes, status)
         return [{"instances": r} for r in insts] if do_postprocess else insts
+
+    def _mask_on(self):
+        return bool(getattr(self.roi_heads, "mask_on", False))
+
+    def _inference_given_boxes(self, batched_inputs, detected_instances, do_postprocess):
+        """reference detectron2 rcnn.py `inference(detected_instances=...)`: the given boxes and classes (network coordinates) get the
+        other heads' outputs -- here the masks -- through `forward_with_given_boxes`; with `do_postprocess` they are pasted into the
+        output image (`detector_postprocess`)."""
+        images = self.preprocess_image(batched_inputs)
+        features = self.backbone(images.tensor)
+        detected = [x.to(self.device) for x in detected_instances]
+        results = run_with_fallbacks(self, lambda: self._given_boxes_checked(features, detected))
+        if not do_postprocess:
+            return results
+        return [{"instances": detector_postprocess(r, inp.get("height", size[0]), inp.get("width", size[1]))}
+                for r, inp, size in zip(results, batched_inputs, images.image_sizes)]
+
+    def _given_boxes_checked(self, features, detected):
+        results = self.roi_heads.forward_with_given_boxes(features, detected)
+        K.check_conv_error_word(self.device)
+        return results
+
+    mask_threshold = 0.5      # detector_postprocess's default, the reference's only value on this path
+
+    def _masks_device(self, batched_inputs, do_postprocess):
+        """The device part of a mask model's forward, nothing read back: trunk -> proposals -> box branch with post=None (raw boxes)
+        -> mask branch on the raw boxes -> (with do_postprocess) the detection gather with an identity keep list and `post`: scaled,
+        clipped, non-empty boxes, and in `rows` the row of `prob` each survivor owns.
+        -> (boxes [B,T,4], scores, classes int32, rows int32 [B,T], count [B], prob [B*T,2S,2S], status, out_sizes)."""
+        images = self.preprocess_image(batched_inputs)
+        sizes = images.image_sizes
+        N, _, Hp, Wp = images.tensor.shape
+        x4 = images.tensor.as_strided((N, Hp, Wp, 4), (Hp * Wp * 4, Wp * 4, 4, 1), images.tensor.storage_offset())
+        dev = self.device
+        sizes_dev = self._dev_const(sizes, torch.int32)
+        feats = self.backbone.forward_nhwc(x4)
+        pboxes, _plogits, pcount = self.proposal_generator.predict_proposals_batched(feats, sizes_dev)
+        status = K.new_status(dev)
+        heads = self.roi_heads
+        ob, osc, ocl, _orow, cnt = heads.forward_batched(feats, pboxes, pcount, sizes_dev, post=None, status=status)
+        prob, rows = heads.forward_masks_batched(feats, ob, ocl, cnt, status=status)
+        out_sizes = [tuple(s) for s in sizes]
+        if do_postprocess:
+            post_rows, out_sizes = [], []
+            for inp, (h, w) in zip(batched_inputs, sizes):
+                dh, dw = (int(inp["raw"].shape[0]), int(inp["raw"].shape[1])) if "image" not in inp else (h, w)
+                oh, ow = inp.get("height", dh), inp.get("width", dw)
+                post_rows.append([ow / w, oh / h, float(oh), float(ow)])
+                out_sizes.append((int(oh), int(ow)))
+            B, T = osc.shape
+            keep = self.__dict__.get("_identity_keep")
+            if keep is None or keep.shape != (B, T) or keep.device != osc.device:
+                keep = self.__dict__["_identity_keep"] = torch.arange(T, dtype=torch.int32, device=dev).repeat(B, 1).contiguous()
+            ob, osc, ocl, rows, cnt = K.gather_detections(ob, osc, ocl, rows, keep, cnt, T, post=self._dev_const(post_rows, torch.float32))
+        return ob, osc, ocl, rows, cnt, prob, status, out_sizes
+
+    def _inference_masks(self, batched_inputs, do_postprocess):
+        """A mask model's inference: `_masks_device`, then ONE device->host read (counts, status, range summary, and the survivors'
+        rows and boxes, from which the host builds the job table), then one paste launch for the batch.  `pred_masks` of an image is
+        a torch.bool [n, out_h, out_w] view of that launch's uint8 buffer (without do_postprocess: the soft [n, 1, 2S, 2S] masks).  The buffer is ONE fresh allocation per
+        call (sum of n * out_h * out_w bytes over the batch) and every image's `pred_masks` aliases it: a caller that keeps one image's
+        masks keeps the whole batch's bytes alive; `.clone()` what is to outlive the batch."""
+        import numpy as np
+
+        ob, osc, ocl, rows, cnt, prob, status, out_sizes = self._masks_device(batched_inputs, do_postprocess)
+        B, T = osc.shape
+        ocl64 = ocl.to(torch.int64)
+        meta = torch.cat([cnt, status, K.range_summary(self.device).to(torch.int32), rows.reshape(-1),
+                          ob.reshape(-1).view(torch.int32)]).cpu().numpy()      # the one read
+        counts, st, flagged = [int(c) for c in meta[:B]], int(meta[B]), int(meta[B + 1])
+        check_status(st)
+        if flagged:
+            K.check_conv_error_word(self.device)
+        rows_h = meta[B + 2: B + 2 + B * T].reshape(B, T)
+        boxes_h = np.ascontiguousarray(meta[B + 2 + B * T:]).view(np.float32).reshape(B, T, 4)
+        buf, bases = None, []
+        if do_postprocess:
+            jr, jb, js, jo, total = [], [], [], [], 0
+            for i, (oh, ow) in enumerate(out_sizes):
+                n = counts[i]
+                bases.append(total)
+                jr.append(rows_h[i, :n])
+                jb.append(boxes_h[i, :n])
+                js += [(oh, ow)] * n
+                jo += [total + k * oh * ow for k in range(n)]
+                total += n * oh * ow
+            jobs = K.paste_jobs(np.concatenate(jr), np.concatenate(jb), js, jo)
+            buf = K.paste_masks(prob, jobs, total, threshold=self.mask_threshold)
+        out = []
+        for i, size in enumerate(out_sizes):
+            n = counts[i]
+            inst = Instances(tuple(size))
+            inst.pred_boxes = Boxes(ob[i, :n])
+            inst.scores = osc[i, :n]
+            inst.pred_classes = ocl64[i, :n]
+            if do_postprocess:
+                oh, ow = size
+                inst.pred_masks = buf[bases[i]: bases[i] + n * oh * ow].view(n, oh, ow).view(torch.bool)
+            else:
+                r0 = int(rows_h[i, 0]) if n else 0      # an image's real rows are consecutive in prob
+                inst.pred_masks = prob[r0: r0 + n][:, None]
+            out.append(inst)
+        return [{"instances": r} for r in out] if do_postprocess else out
 
     def _inference_box_corrector(self, batched_inputs):
         """reference rcnn.py:201-230: evaluation of the box corrector = IoU with the matched GT before and after the

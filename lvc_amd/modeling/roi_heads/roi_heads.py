@@ -20,6 +20,7 @@ from ..sampling import subsample_labels
 from ..poolers import ROIPooler
 from .box_head import build_box_head
 from .fast_rcnn import ROI_HEADS_OUTPUT_REGISTRY
+from .mask_head import build_mask_head, mask_rcnn_inference
 
 ROI_HEADS_REGISTRY = Registry("ROI_HEADS")
 
@@ -226,6 +227,9 @@ class StandardROIHeads(ROIHeads):
     def __init__(self, cfg, input_shape):
         super().__init__(cfg, input_shape)
         self._init_box_head(cfg)
+        self.mask_on = bool(cfg.MODEL.MASK_ON)
+        if self.mask_on:
+            self._init_mask_head(cfg)
         if cfg.DEBUG:
             raise NotImplementedError("cfg.DEBUG heads (FastRCNNOutputsDebug) are not part of the hot path")
         if cfg.MODEL.META_ARCHITECTURE == "GeneralizedRCNN_Context":
@@ -244,6 +248,79 @@ class StandardROIHeads(ROIHeads):
         self.box_head = build_box_head(cfg, ShapeSpec(channels=in_channels[0], height=res, width=res))
         self.box_predictor = ROI_HEADS_OUTPUT_REGISTRY.get(cfg.MODEL.ROI_HEADS.OUTPUT_LAYER)(cfg, self.box_head.output_size)
 
+    def _init_mask_head(self, cfg):
+        """detectron2's StandardROIHeads._init_mask_head (roi_heads.py:599-622): `mask_pooler` + `mask_head` over ROI_HEADS.IN_FEATURES."""
+        MH = cfg.MODEL.ROI_MASK_HEAD
+        res = MH.POOLER_RESOLUTION
+        scales = tuple(1.0 / self.feature_strides[k] for k in self.in_features)
+        in_channels = [self.feature_channels[f] for f in self.in_features][0]
+        self.mask_in_features = self.in_features
+        self.mask_pooler = ROIPooler(output_size=res, scales=scales, sampling_ratio=MH.POOLER_SAMPLING_RATIO, pooler_type=MH.POOLER_TYPE)
+        self.mask_head = build_mask_head(cfg, ShapeSpec(channels=in_channels, width=res, height=res))
+
+    def pool_masks_batched(self, feats_nhwc, boxes, classes, count, status=None):
+        """The mask branch's input on padded batch tensors, nothing read back: the real rows of the [B, topk] table are moved to the
+        front, image after image, the others become zero boxes, and all B*topk rows go through ROIAlign over the pyramid (the
+        vectorised NHWC kernel `roi_align_fwd_nhwc4_kernel`, which takes no row count: a zero box costs it a store of zeros).
+        -> (pooled [B*topk, S, S, C], classes [B*topk] int32 in that order, rows [B, topk] int32: the row box i of image b owns,
+        total [1] int32: the number of real rows)."""
+        B, T, _ = boxes.shape
+        dev = boxes.device
+        pl = self.mask_pooler
+        feats = [feats_nhwc[f] for f in self.mask_in_features]
+        ar = torch.arange(T, device=dev, dtype=torch.int32)
+        cnt = count.clamp(min=0, max=T)
+        valid = ar[None, :] < cnt[:, None]
+        start = torch.cumsum(cnt, 0, dtype=torch.int32) - cnt
+        rows = (start[:, None] + ar[None, :]).contiguous()
+        total = cnt.sum(dtype=torch.int32).view(1)
+        # stable: the real rows first, in (image, index) order -- row start_b + i is box i of image b
+        order = torch.argsort((~valid).view(-1).to(torch.uint8), stable=True)
+        # rows past an image's count hold whatever the box branch left there: zero boxes instead (empty sampling grids)
+        boxes = torch.where(valid[:, :, None], boxes, torch.zeros_like(boxes))
+        levels, rois = K.assign_levels_rois(boxes, pl.min_level, pl.max_level, pl.canonical_box_size, pl.canonical_level)
+        rois = rois.index_select(0, order)
+        levels = None if len(feats) == 1 else levels.index_select(0, order)
+        cls = classes.reshape(-1).index_select(0, order).contiguous()
+        pooled = K.roi_align_fpn_nhwc(feats, pl.scales, rois, levels, pl.output_size[0], pl.output_size[1], pl.sampling_ratio, pl.aligned,
+                                      status=status)
+        return pooled, cls, rows, total
+
+    def forward_masks_batched(self, feats_nhwc, boxes, classes, count, status=None):
+        """The mask branch on padded batch tensors, nothing read back.  feats_nhwc: dict name -> [B,H,W,C]; boxes [B,topk,4] in network
+        coordinates; classes [B,topk] int32; count [B] int32 (rows [0, count_b) of image b are real).
+        Returns (prob [B*topk, 2S, 2S], rows [B,topk] int32): `pool_masks_batched` moves the real rows to the front, so that ONE
+        number -- their total -- is the `num_valid` of the tail kernel; `rows[b, i]` is the row of `prob` that box i of image b owns.
+        Rows of `prob` past the total are not written (ROIAlign and the convs run on all rows: zero boxes, zero maps)."""
+        if not self.mask_on:
+            raise RuntimeError("forward_masks_batched: the model was built with MODEL.MASK_ON = False")
+        pooled, cls, rows, total = self.pool_masks_batched(feats_nhwc, boxes, classes, count, status=status)
+        prob = self.mask_head.forward_nhwc(pooled, cls, num_valid=total, status=status)
+        return prob, rows
+
+    def forward_with_given_boxes(self, features, instances):
+        """Reference signature (detectron2 roi_heads.py:681-706): `instances` carry `pred_boxes` and `pred_classes` (network
+        coordinates) and get `pred_masks` [n, 1, 2S, 2S], the predicted class's mask probabilities."""
+        assert not self.training
+        assert instances[0].has("pred_boxes") and instances[0].has("pred_classes")
+        if not self.mask_on:
+            return instances
+        feats = {f: to_nhwc(features[f]) for f in self.mask_in_features}
+        dev = feats[self.mask_in_features[0]].device
+        require_device(feats[self.mask_in_features[0]], "StandardROIHeads")
+        counts = [len(p) for p in instances]
+        B, R = len(instances), max(max(counts), 1)
+        boxes = torch.zeros(B, R, 4, device=dev)
+        classes = torch.zeros(B, R, dtype=torch.int32, device=dev)
+        for i, p in enumerate(instances):
+            boxes[i, : counts[i]] = p.pred_boxes.tensor
+            classes[i, : counts[i]] = p.pred_classes.to(torch.int32)
+        status = K.new_status(dev)
+        prob, _rows = self.forward_masks_batched(feats, boxes, classes, torch.tensor(counts, dtype=torch.int32, device=dev), status=status)
+        check_status(int(status.item()))
+        mask_rcnn_inference(prob, instances)
+        return instances
+
     def forward_batched(self, feats_nhwc, prop_boxes, prop_count, image_sizes_dev, post=None, status=None):
         """feats_nhwc: dict name -> [B,H,W,C]; prop_boxes [B,R,4]; prop_count [B] int32 or None.
         Returns (boxes [B,topk,4], scores, classes int32, rows int32, count [B] int32), all on device."""
@@ -261,6 +338,8 @@ class StandardROIHeads(ROIHeads):
     def forward(self, images, features, proposals, targets=None):
         """Reference signature (roi_heads.py:554-572): -> (list[Instances], losses)."""
         if self.training:
+            if self.mask_on:
+                raise NotImplementedError("training the mask branch (MODEL.MASK_ON: mask_rcnn_loss, gt_masks) is not built")
             return self._forward_train(features, proposals, targets)
         if self.rbg:
             # reference roi_heads.py:561-562: with an RBG proposal generator the evaluation pass labels and subsamples the given
@@ -278,7 +357,13 @@ class StandardROIHeads(ROIHeads):
         status = K.new_status(dev)
         ob, osc, ocl, orow, cnt = self.forward_batched(feats, boxes, torch.tensor(counts, dtype=torch.int32, device=dev),
                                                        sizes, status=status)
-        return instances_from_batched(ob, osc, ocl, cnt, [p.image_size for p in proposals], status), {}
+        prob = rows = None
+        if self.mask_on:
+            prob, rows = self.forward_masks_batched(feats, ob, ocl, cnt, status=status)
+        insts = instances_from_batched(ob, osc, ocl, cnt, [p.image_size for p in proposals], status)
+        if prob is not None:
+            mask_rcnn_inference(prob, insts)      # the real rows lie image after image at the front of prob
+        return insts, {}
 
 
 def _sample_batched(self, pboxes, plogits, pcount, gt, gt_off, targets):
@@ -496,6 +581,8 @@ def check_status(st):
     if st & 2:
         raise CandidateOverflow("lvc_fast_rcnn_inference: more (roi, class) candidates above SCORE_THRESH_TEST in one "
                                 "image than the candidate list holds; re-run with max_candidates=None (= R*K)")
+    if st & 8:
+        raise IndexError("lvc_mask_deconv_predict: a predicted class lies outside the mask predictor's [0, K)")
     if st & 4:
         raise CandidateOverflow("lvc_retinanet_select: more entries above SCORE_THRESH_TEST on one (image, level) than the survivor "
                                 "list holds; re-run with max_survivors=None (= H*W*A*K)")

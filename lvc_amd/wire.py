@@ -13,6 +13,9 @@ from .structures import BoxMode
 
 
 def instances_to_coco_json(instances, img_id):
+    if instances.has("pred_masks"):
+        raise NotImplementedError("instances_to_coco_json: COCO RLE `segmentation` of pred_masks (MODEL.MASK_ON) is not built; "
+                                  "remove the field to write the boxes")
     n = len(instances)
     if n == 0:
         return []
