@@ -870,6 +870,44 @@ int lvc_mask_deconv_predict(const float* x, const float* w_deconv, const float* 
 int lvc_paste_masks(const float* prob, int num_rows, int mask_size, const long long* h_jobs, const long long* d_jobs, int num_jobs,
                     unsigned char* out, long long out_bytes, float threshold, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Mask R-CNN training: mask targets, the tail's logits, the mask loss and the tail's backward (detectron2 mask_head.py mask_rcnn_loss,
+ * structures/masks.py BitMasks.crop_and_resize).
+ * lvc_mask_targets (csrc/mask_targets.hip, no contraction): ROIAlign((T,T), 1.0, 0, aligned=True) of each row's matched 0/1 plane, then
+ *   >= 0.5, for the rows [0, count[b * count_stride]) of every image of boxes [B,R,4], one launch.  matched int64 [B,R]: index of the
+ *   row's plane among its image's; table: 4 int64 words per image (plane base pointer, number of planes, H, W; planes are bytes,
+ *   [n,H,W] contiguous), h_table on the host (checked), d_table its device copy.  out uint8 [B*R,T,T]; rows past the count are not
+ *   written; a row whose index is outside [0, n) gets an empty target.  fp32 in the order of ROIAlign_cpu.cpp.
+ * lvc_mask_deconv_logits (csrc/mask_deconv.hip): lvc_mask_deconv_predict without the sigmoid (classes: the GROUND-TRUTH class of each
+ *   RoI): logits [M,2S,2S]; num_valid, status bit 8 and classes = NULL as there.
+ * lvc_mask_loss (csrc/mask_train.hip, two launches): over the rows < *d_num_valid, out_loss = mean of
+ *   max(z,0) - z t + log1p(exp(-|z|)) (terms and sum in fp64; 0 when there is no row), out_sum (may be NULL) the fp64 sum, out_counts
+ *   (may be NULL) int64 [3] = pixels with (z > 0) != t, pixels with t, pixels with z > 0 and not t.  Partial sums per workgroup, added
+ *   in index order by one workgroup: bit-identical between runs.
+ * lvc_mask_deconv_grad (csrc/mask_train.hip, three launches): with dz = (sigmoid(z) - t) * *d_upstream / (*d_num_valid (2S)^2) and the
+ *   hidden tile recomputed on fp32 MFMA, writes dh [M*S*S, 4*Cmid] = dz w_pred[c,co] [h > 0] (column (dy*2+dx)*Cmid + co: the gradient of
+ *   the GEMM x [M*S*S,Cin] x w_deconv^T; the rows of x past num_valid are not read, their dh rows are zero), dw_pred [K,Cmid], db_pred [K] (rows of classes absent from the batch exactly 0) and db_deconv [Cmid].
+ *   Per-(RoI, 64-pixel tile) partials in `workspace`, added in a fixed order: no float atomics, bit-identical between runs.
+ * lvc_mask_deconv_wgrad (csrc/mask_train.hip, two launches): dw_packed [4*Cmid,Cin] = dh^T x over the rows below *d_num_valid (S*S each; the rows past it are not read) on fp32 MFMA; the rows
+ *   are cut into slices fixed by M and S, each slice's partial tile goes to `workspace`, the slices are added in index order:
+ *   bit-identical between runs (the conv weight-gradient kernels join their slices with atomics). */
+int lvc_mask_targets(const float* boxes, const long long* matched, const int* count, int count_stride, const long long* h_table,
+                     const long long* d_table, int B, int R, int T, unsigned char* out, void* stream);
+int lvc_mask_deconv_logits(const float* x, const float* w_deconv, const float* b_deconv, const float* w_pred, const float* b_pred,
+                           const int* classes, const int* d_num_valid, float* logits, int M, int S, int Cin, int Cmid, int K,
+                           int* d_status, void* stream);
+long long lvc_mask_loss_workspace_bytes(int M, int S);
+int lvc_mask_loss(const float* logits, const unsigned char* targets, const int* d_num_valid, int M, int S, float* out_loss,
+                  double* out_sum, long long* out_counts, void* workspace, long long workspace_bytes, void* stream);
+long long lvc_mask_deconv_grad_workspace_bytes(int M, int S, int Cmid);
+long long lvc_mask_deconv_wgrad_workspace_bytes(int M, int S, int Cin, int Cmid);
+int lvc_mask_deconv_wgrad(const float* dh, const float* x, const int* d_num_valid, float* dw_packed, int M, int S, int Cin, int Cmid,
+                          void* workspace, long long workspace_bytes, void* stream);
+int lvc_mask_deconv_grad(const float* x, const float* w_deconv, const float* b_deconv, const float* w_pred, const int* classes,
+                         const float* logits, const unsigned char* targets, const int* d_num_valid, const float* d_upstream, float* dh,
+                         float* dw_pred, float* db_pred, float* db_deconv, int M, int S, int Cin, int Cmid, int K,
+                         int* d_status, void* workspace, long long workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -45,7 +45,8 @@ def gn_rcnn_fpn(depth=50, num_classes=80, device="cuda"):
 
 def mask_rcnn_fpn(depth=50, num_classes=80, device="cuda"):
     """Mask R-CNN on the ResNet-FPN trunk: what detectron2's `COCO-InstanceSegmentation/mask_rcnn_R_50_FPN_*.yaml` and the mask keys of
-    `Base-RCNN-FPN.yaml` set on top of `base_rcnn_fpn` (four 3x3 convs, a 14x14 mask pooler).  Inference only."""
+    `Base-RCNN-FPN.yaml` set on top of `base_rcnn_fpn` (four 3x3 convs, a 14x14 mask pooler).  Training is opt-in:
+    `build_model(cfg).enable_mask_training()`."""
     cfg = base_rcnn_fpn(depth=depth, num_classes=num_classes, device=device)
     cfg.merge_from_list(["MODEL.MASK_ON", True, "MODEL.ROI_MASK_HEAD.NAME", "MaskRCNNConvUpsampleHead", "MODEL.ROI_MASK_HEAD.NUM_CONV", 4,
                          "MODEL.ROI_MASK_HEAD.POOLER_RESOLUTION", 14])

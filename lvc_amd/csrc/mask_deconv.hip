@@ -27,7 +27,7 @@
 #define MD_PAD 4            // floats of padding per LDS row
 #define MD_STATUS_CLASS 8   // status bit: a class index outside [0, K)
 
-template <int NBC>      // Cmid / 64: 16-channel blocks per wave and tap
+template <int NBC, bool SIGMOID>      // Cmid / 64: 16-channel blocks per wave and tap; SIGMOID false: the logits leave (training)
 __global__ __launch_bounds__(256) void mask_deconv_kernel(const float* __restrict__ x, const float* __restrict__ wd,
                                                           const float* __restrict__ bd, const float* __restrict__ wp,
                                                           const float* __restrict__ bp, const int* __restrict__ classes,
@@ -125,7 +125,7 @@ __global__ __launch_bounds__(256) void mask_deconv_kernel(const float* __restric
     if (r < R) {
       float z = (red[(0 * 4 + q) * MD_TM + p] + red[(1 * 4 + q) * MD_TM + p]) + (red[(2 * 4 + q) * MD_TM + p] + red[(3 * 4 + q) * MD_TM + p]);
       if (bp) z += bp[scls[p]];
-      const float pr = 1.f / (1.f + expf(-z));
+      const float pr = SIGMOID ? 1.f / (1.f + expf(-z)) : z;
       const int m = (int)(r / S2), rem = (int)(r - (long long)m * S2);
       const int yy = rem / S, xx = rem - yy * S;
       const int S_2 = 2 * S;
@@ -134,7 +134,7 @@ __global__ __launch_bounds__(256) void mask_deconv_kernel(const float* __restric
   }
 }
 
-template <int NBC>
+template <int NBC, bool SIGMOID>
 static int launch_mask_deconv(const float* x, const float* wd, const float* bd, const float* wp, const float* bp, const int* classes,
                               const int* d_num_valid, int* d_status, float* prob, int M, int S, int Cin, int K, hipStream_t st) {
   const size_t lds = (size_t)MD_TM * (Cin + MD_PAD) * 4 + 4 * 4 * MD_TM * 4 + MD_TM * 4;
@@ -144,23 +144,24 @@ static int launch_mask_deconv(const float* x, const float* wd, const float* bd, 
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;
   if (dev < 0 || !lds_set[dev]) {
     const size_t lds_max = (size_t)MD_TM * (256 + MD_PAD) * 4 + 4 * 4 * MD_TM * 4 + MD_TM * 4;
-    if (hipFuncSetAttribute((const void*)mask_deconv_kernel<NBC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max) != hipSuccess) {
+    if (hipFuncSetAttribute((const void*)mask_deconv_kernel<NBC, SIGMOID>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max) != hipSuccess) {
       (void)hipGetLastError();
-      lvc_set_error("lvc_mask_deconv_predict: %zu bytes of LDS refused", lds_max);
+      lvc_set_error("lvc_mask_deconv_%s: %zu bytes of LDS refused", SIGMOID ? "predict" : "logits", lds_max);
       return LVC_ERR_HIP;
     }
     if (dev >= 0) lds_set[dev] = true;
   }
   const long long rows = (long long)M * S * S;
   const unsigned blocks = (unsigned)((rows + MD_TM - 1) / MD_TM);
-  hipLaunchKernelGGL((mask_deconv_kernel<NBC>), dim3(blocks), dim3(256), lds, st, x, wd, bd, wp, bp, classes, d_num_valid, d_status, prob, M,
+  hipLaunchKernelGGL((mask_deconv_kernel<NBC, SIGMOID>), dim3(blocks), dim3(256), lds, st, x, wd, bd, wp, bp, classes, d_num_valid, d_status, prob, M,
                      S, Cin, K);
   return LVC_OK;
 }
 
-extern "C" int lvc_mask_deconv_predict(const float* x, const float* w_deconv, const float* b_deconv, const float* w_pred,
-                                       const float* b_pred, const int* classes, const int* d_num_valid, float* prob, int M, int S,
-                                       int Cin, int Cmid, int K, int* d_status, void* stream) {
+template <bool SIGMOID>
+static int mask_deconv_entry(const float* x, const float* w_deconv, const float* b_deconv, const float* w_pred, const float* b_pred,
+                             const int* classes, const int* d_num_valid, float* prob, int M, int S, int Cin, int Cmid, int K, int* d_status,
+                             void* stream) {
   LVC_CHECK_ARG(M >= 0 && S >= 1 && K >= 1, "M >= 0, S >= 1, K >= 1");
   LVC_CHECK_ARG(Cin >= 64 && Cin <= 256 && Cin % 64 == 0 && Cmid >= 64 && Cmid <= 256 && Cmid % 64 == 0,
                 "channels of the deconvolution: multiples of 64 up to 256 (MODEL.ROI_MASK_HEAD.CONV_DIM)");
@@ -171,12 +172,26 @@ extern "C" int lvc_mask_deconv_predict(const float* x, const float* w_deconv, co
   hipStream_t st = (hipStream_t)stream;
   int rc;
   switch (Cmid / 64) {
-    case 1: rc = launch_mask_deconv<1>(x, w_deconv, b_deconv, w_pred, b_pred, classes, d_num_valid, d_status, prob, M, S, Cin, K, st); break;
-    case 2: rc = launch_mask_deconv<2>(x, w_deconv, b_deconv, w_pred, b_pred, classes, d_num_valid, d_status, prob, M, S, Cin, K, st); break;
-    case 3: rc = launch_mask_deconv<3>(x, w_deconv, b_deconv, w_pred, b_pred, classes, d_num_valid, d_status, prob, M, S, Cin, K, st); break;
-    default: rc = launch_mask_deconv<4>(x, w_deconv, b_deconv, w_pred, b_pred, classes, d_num_valid, d_status, prob, M, S, Cin, K, st); break;
+    case 1: rc = launch_mask_deconv<1, SIGMOID>(x, w_deconv, b_deconv, w_pred, b_pred, classes, d_num_valid, d_status, prob, M, S, Cin, K, st); break;
+    case 2: rc = launch_mask_deconv<2, SIGMOID>(x, w_deconv, b_deconv, w_pred, b_pred, classes, d_num_valid, d_status, prob, M, S, Cin, K, st); break;
+    case 3: rc = launch_mask_deconv<3, SIGMOID>(x, w_deconv, b_deconv, w_pred, b_pred, classes, d_num_valid, d_status, prob, M, S, Cin, K, st); break;
+    default: rc = launch_mask_deconv<4, SIGMOID>(x, w_deconv, b_deconv, w_pred, b_pred, classes, d_num_valid, d_status, prob, M, S, Cin, K, st); break;
   }
   if (rc != LVC_OK) return rc;
   LVC_CHECK_LAUNCH();
   return LVC_OK;
+}
+
+extern "C" int lvc_mask_deconv_predict(const float* x, const float* w_deconv, const float* b_deconv, const float* w_pred,
+                                       const float* b_pred, const int* classes, const int* d_num_valid, float* prob, int M, int S,
+                                       int Cin, int Cmid, int K, int* d_status, void* stream) {
+  return mask_deconv_entry<true>(x, w_deconv, b_deconv, w_pred, b_pred, classes, d_num_valid, prob, M, S, Cin, Cmid, K, d_status, stream);
+}
+
+// The training tail: the same launch with the RoI's GROUND-TRUTH class and without the sigmoid -- logits [M, 2S, 2S] for lvc_mask_loss
+// and lvc_mask_deconv_grad (csrc/mask_train.hip).
+extern "C" int lvc_mask_deconv_logits(const float* x, const float* w_deconv, const float* b_deconv, const float* w_pred,
+                                      const float* b_pred, const int* classes, const int* d_num_valid, float* logits, int M, int S,
+                                      int Cin, int Cmid, int K, int* d_status, void* stream) {
+  return mask_deconv_entry<false>(x, w_deconv, b_deconv, w_pred, b_pred, classes, d_num_valid, logits, M, S, Cin, Cmid, K, d_status, stream);
 }

@@ -3482,3 +3482,132 @@ def paste_masks(prob, jobs, out_bytes, threshold=0.5, out=None):
                                      c_int(n), ptr(out), c_longlong(padded), c_float(threshold), _stream(prob)),
           "lvc_paste_masks")
     return out
+
+
+# --------------------------------------------------------------------------- Mask R-CNN training
+MASK_TABLE_FIELDS = 4     # int64 words per image of lvc_mask_targets' plane table (include/lvc_amd.h)
+
+
+def mask_targets(boxes, matched, count, planes, mask_size, out=None):
+    """BitMasks.crop_and_resize + >= 0.5 for the first count[b] rows of every image in one launch (csrc/mask_targets.hip).
+    boxes [B,R,4] fp32; matched int64 [B,R]: the row's plane among its image's; count int32 [B] (or a strided [B] view, e.g. the
+    sampler's cnt[:, 0]); planes: B tensors bool / uint8 [n_b, H_b, W_b], each contiguous on the device (sizes may differ).
+    Returns uint8 [B*R, T, T] (`out` when given); rows past an image's count are not written.  No host read."""
+    import numpy as np
+
+    _req_cuda(boxes, matched, count, *planes)
+    B, R, _ = boxes.shape
+    T = int(mask_size)
+    assert boxes.is_contiguous() and boxes.dtype == torch.float32 and boxes.shape == (B, R, 4)
+    assert matched.dtype == torch.int64 and matched.is_contiguous() and matched.shape == (B, R)
+    assert count.dtype == torch.int32 and count.dim() == 1 and count.shape[0] == B and len(planes) == B
+    table = np.zeros((max(B, 1), MASK_TABLE_FIELDS), dtype=np.int64)
+    for b, pl in enumerate(planes):
+        assert pl.dim() == 3 and pl.is_contiguous() and pl.dtype in (torch.bool, torch.uint8), "planes: contiguous bool / uint8 [n,H,W]"
+        table[b] = (pl.data_ptr() if pl.numel() else 0, pl.shape[0], pl.shape[1], pl.shape[2])
+    if out is None:
+        out = torch.empty(B * R, T, T, dtype=torch.uint8, device=boxes.device)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.shape == (B * R, T, T)
+    if B == 0 or R == 0:
+        return out
+    # pinned and asynchronous: the upload is ordered on the stream, the host does not wait for the device
+    d_table = torch.from_numpy(table).pin_memory().to(boxes.device, non_blocking=True)
+    check(_lib.lib().lvc_mask_targets(ptr(boxes), ptr(matched), ptr(count), c_int(count.stride(0)), c_void_p(table.ctypes.data), ptr(d_table),
+                                      c_int(B), c_int(R), c_int(T), ptr(out), _stream(boxes)), "lvc_mask_targets")
+    return out
+
+
+def _mask_tail_args(x, w_deconv, b_deconv, w_pred, b_pred, classes, num_valid):
+    M, S, S_, cin = x.shape
+    assert S == S_ and x.is_contiguous() and x.dtype == torch.float32
+    cmid = w_deconv.shape[0] // 4
+    mask_deconv_check(cin, cmid)
+    Kc = w_pred.shape[0]
+    assert w_deconv.shape == (4 * cmid, cin) and w_deconv.is_contiguous() and w_deconv.dtype == torch.float32
+    w_pred = w_pred.reshape(Kc, -1)
+    assert w_pred.shape == (Kc, cmid) and w_pred.is_contiguous() and w_pred.dtype == torch.float32
+    for b, n in ((b_deconv, cmid), (b_pred, Kc)):
+        assert b is None or (b.numel() == n and b.is_contiguous() and b.dtype == torch.float32)
+    if classes is not None:
+        assert classes.dtype == torch.int32 and classes.is_contiguous() and classes.numel() == M
+    if num_valid is not None:
+        assert num_valid.dtype == torch.int32 and num_valid.numel() == 1
+    return M, S, cin, cmid, Kc, w_pred
+
+
+def mask_deconv_logits(x, w_deconv, b_deconv, w_pred, b_pred, classes=None, num_valid=None, status=None, out=None):
+    """`mask_deconv_predict` without the sigmoid: the logits [M,2S,2S] of each row's class (training: the ground-truth class)."""
+    _req_cuda(x, w_deconv, b_deconv, w_pred, b_pred, classes, num_valid, status)
+    M, S, cin, cmid, Kc, w_pred = _mask_tail_args(x, w_deconv, b_deconv, w_pred, b_pred, classes, num_valid)
+    if out is None:
+        out = torch.empty(M, 2 * S, 2 * S, device=x.device, dtype=torch.float32)
+    assert out.shape == (M, 2 * S, 2 * S) and out.is_contiguous() and out.dtype == torch.float32
+    check(_lib.lib().lvc_mask_deconv_logits(ptr(x), ptr(w_deconv), ptr(b_deconv), ptr(w_pred), ptr(b_pred), ptr(classes), ptr(num_valid),
+                                            ptr(out), c_int(M), c_int(S), c_int(cin), c_int(cmid), c_int(Kc), ptr(status), _stream(x)),
+          "lvc_mask_deconv_logits")
+    return out
+
+
+def mask_loss(logits, targets, num_valid=None):
+    """Mean binary cross-entropy with logits over the rows below num_valid (csrc/mask_train.hip): logits fp32 [M,P,P], targets uint8 /
+    bool [M,P,P].  -> (loss fp32 [1], sum float64 [1], counts int64 [3] = (incorrect, positive, false positive pixels)); no host read;
+    0 when there is no row."""
+    _req_cuda(logits, targets, num_valid)
+    M, P, P_ = logits.shape
+    assert P == P_ and P % 2 == 0 and logits.is_contiguous() and logits.dtype == torch.float32
+    assert targets.shape == logits.shape and targets.is_contiguous() and targets.dtype in (torch.uint8, torch.bool)
+    if num_valid is not None:
+        assert num_valid.dtype == torch.int32 and num_valid.numel() == 1
+    lib = _lib.lib()
+    lib.lvc_mask_loss_workspace_bytes.restype = c_longlong
+    nbytes = lib.lvc_mask_loss_workspace_bytes(c_int(M), c_int(P // 2))
+    dev = logits.device
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    total = torch.empty(1, dtype=torch.float64, device=dev)
+    counts = torch.empty(3, dtype=torch.int64, device=dev)
+    check(lib.lvc_mask_loss(ptr(logits), ptr(targets), ptr(num_valid), c_int(M), c_int(P // 2), ptr(loss), ptr(total), ptr(counts), ptr(ws),
+                            c_longlong(nbytes), _stream(logits)), "lvc_mask_loss")
+    return loss, total, counts
+
+
+def mask_deconv_grad(x, w_deconv, b_deconv, w_pred, classes, logits, targets, num_valid, upstream, status=None,
+                     need_dx=True, need_dw=True):
+    """The backward of the tail + loss (csrc/mask_train.hip): lvc_mask_deconv_grad, then dx = dh @ Wd on the forward GEMM kernel and
+    dWd = dh^T @ x on lvc_mask_deconv_wgrad (neither reads a row of x past num_valid).  x [M,S,S,Cin]; w_deconv the packed operand [4*Cmid,Cin]; logits / targets [M,2S,2S];
+    upstream: fp32 [1] ON THE DEVICE (the loss's incoming gradient, not read back).  -> (dx [M,S,S,Cin], dWd [Cin,Cmid,2,2], dbd [Cmid],
+    dWp [K,Cmid], dbp [K]); dx / dWd None when not needed.  The one large intermediate is dh [M*S*S, 4*Cmid].  Bit-identical between runs."""
+    _req_cuda(x, w_deconv, b_deconv, w_pred, classes, logits, targets, num_valid, upstream, status)
+    M, S, cin, cmid, Kc, w_pred = _mask_tail_args(x, w_deconv, b_deconv, w_pred, None, classes, num_valid)
+    assert logits.shape == (M, 2 * S, 2 * S) and logits.is_contiguous() and logits.dtype == torch.float32
+    assert targets.shape == logits.shape and targets.is_contiguous() and targets.dtype in (torch.uint8, torch.bool)
+    assert upstream.dtype == torch.float32 and upstream.numel() == 1
+    dev = x.device
+    lib = _lib.lib()
+    lib.lvc_mask_deconv_grad_workspace_bytes.restype = c_longlong
+    nbytes = lib.lvc_mask_deconv_grad_workspace_bytes(c_int(M), c_int(S), c_int(cmid))
+    ws = torch.empty((nbytes + 15) // 16 * 4, dtype=torch.float32, device=dev)
+    dh = torch.empty(M * S * S, 4 * cmid, dtype=torch.float32, device=dev)
+    dwp = torch.empty(Kc, cmid, dtype=torch.float32, device=dev)
+    dbp = torch.empty(Kc, dtype=torch.float32, device=dev)
+    dbd = torch.empty(cmid, dtype=torch.float32, device=dev)
+    check(lib.lvc_mask_deconv_grad(ptr(x), ptr(w_deconv), ptr(b_deconv), ptr(w_pred), ptr(classes), ptr(logits), ptr(targets),
+                                   ptr(num_valid), ptr(upstream), ptr(dh), ptr(dwp), ptr(dbp), ptr(dbd), c_int(M), c_int(S),
+                                   c_int(cin), c_int(cmid), c_int(Kc), ptr(status), ptr(ws), c_longlong(ws.numel() * 4), _stream(x)),
+          "lvc_mask_deconv_grad")
+    dx = dwd = None
+    if M > 0 and need_dx:       # dx = dh @ Wd_packed on the forward GEMM kernel (range-free split: unscaled gradients are tiny)
+        dx = linear_backward(x.view(M * S * S, cin), w_deconv, dh, need_dx=True, need_dw=False)[0].view(M, S, S, cin)      # (x: its shape only)
+    if M > 0 and need_dw:       # dWd = dh^T @ x: conv_wgrad joins its pixel slices with atomics, this product must be bit-stable
+        lib.lvc_mask_deconv_wgrad_workspace_bytes.restype = c_longlong
+        wbytes = lib.lvc_mask_deconv_wgrad_workspace_bytes(c_int(M), c_int(S), c_int(cin), c_int(cmid))
+        wws = torch.empty(wbytes // 4, dtype=torch.float32, device=dev)
+        dw = torch.empty(4 * cmid, cin, dtype=torch.float32, device=dev)
+        check(lib.lvc_mask_deconv_wgrad(ptr(dh), ptr(x), ptr(num_valid), ptr(dw), c_int(M), c_int(S), c_int(cin), c_int(cmid), ptr(wws),
+                                        c_longlong(wbytes), _stream(x)), "lvc_mask_deconv_wgrad")
+        # packed row (dy*2+dx)*Cmid + co -> the parameter's [Cin, Cmid, 2, 2]
+        dwd = dw.view(2, 2, cmid, cin).permute(3, 2, 0, 1).contiguous()
+    if M == 0:
+        dx = torch.zeros(0, S, S, cin, device=dev) if need_dx else None
+        dwd = torch.zeros(cin, cmid, 2, 2, device=dev) if need_dw else None
+    return dx, dwd, dbd, dwp, dbp

@@ -151,7 +151,7 @@ class GeneralizedRCNN(_RCNNBase):
     def forward(self, batched_inputs):
         if not self.training:
             return self.inference(batched_inputs)
-        if self._mask_on():
+        if self._mask_on() and not self.__dict__.get("_mask_train_enabled", False):
             raise NotImplementedError("training the mask branch (MODEL.MASK_ON: mask_rcnn_loss, gt_masks) is not built")
 
         def once():
@@ -221,7 +221,7 @@ class GeneralizedRCNN(_RCNNBase):
         detector_losses, cnt, stats = heads.forward_train_batched(features, boxes, logits, count, gt, gt_off, gt_instances)
         B, bs = boxes.shape[0], heads.batch_size_per_image
         meta = torch.cat([count.long(), rpn_counts.view(-1).long(), cnt.view(-1).long(), stats.long(), K.range_summary(self.device).long()]).tolist()
-        pc, rc, cc, st, flagged = meta[:B], meta[B:3 * B], meta[3 * B:5 * B], meta[5 * B:5 * B + 4], meta[-1]
+        pc, rc, cc, st, flagged = meta[:B], meta[B:3 * B], meta[3 * B:5 * B], meta[5 * B:-1], meta[-1]      # (st: 4 counts; a mask model: 9)
         if flagged:
             K.check_conv_error_word(self.device)      # re-routes the layers concerned and raises: `run_with_fallbacks` repeats the pass
         self.__dict__["_range_checked"] = True
@@ -312,6 +312,23 @@ class GeneralizedRCNN(_RCNNBase):
 
     def _mask_on(self):
         return bool(getattr(self.roi_heads, "mask_on", False))
+
+    def enable_mask_training(self, on=True):
+        """Switch the training forward of a MODEL.MASK_ON model on (or off again); returns self.  Without the call a mask model in
+        training mode refuses, as before.  Settings the training path does not build raise here, on the host, naming their key;
+        ground-truth masks that are not BitMasks raise in the step (INPUT.MASK_FORMAT "bitmask")."""
+        heads = self.roi_heads
+        if type(heads) is not StandardROIHeads:      # (CascadeROIHeads builds no mask branch whatever MODEL.MASK_ON says)
+            raise NotImplementedError("MODEL.ROI_HEADS.NAME = {}: the mask branch and its training are built for StandardROIHeads"
+                                      .format(type(heads).__name__))
+        if not self._mask_on():
+            raise ValueError("enable_mask_training: the model was built with MODEL.MASK_ON = False")
+        if on:
+            if heads.mask_head.vis_period > 0:
+                raise NotImplementedError("VIS_PERIOD > 0: visualising the mask predictions is not built")
+        for owner in (self, heads, heads.mask_head):
+            owner.__dict__["_mask_train_enabled"] = bool(on)
+        return self
 
     def _inference_given_boxes(self, batched_inputs, detected_instances, do_postprocess):
         """reference detectron2 rcnn.py `inference(detected_instances=...)`: the given boxes and classes (network coordinates) get the

@@ -37,6 +37,27 @@ class _PoolAllLevels(torch.autograd.Function):
         return (None, None, None) + tuple(grads)
 
 
+class _PoolRois(torch.autograd.Function):
+    """`_PoolAllLevels` on rois the caller has already built and ordered ([K, 5] with their levels): the mask branch moves its real rows
+    to the front, so that ONE device number -- their total -- bounds the rows the backward scatters (`num_valid`; the forward runs on
+    all rows: a zero box costs it a store of zeros and leaves defined values for the convs that follow)."""
+
+    @staticmethod
+    def forward(ctx, pooler, rois, levels, num_valid, status, *feats):
+        ctx.pooler, ctx.rois, ctx.levels, ctx.num_valid = pooler, rois, levels, num_valid
+        ctx.shapes = [tuple(f.shape) for f in feats]
+        return K.roi_align_fpn_nhwc(list(feats), pooler.scales, rois, levels, pooler.output_size[0], pooler.output_size[1],
+                                    pooler.sampling_ratio, pooler.aligned, status=status)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        pl = ctx.pooler
+        grads = K.roi_align_fpn_backward_nhwc(grad, ctx.shapes, pl.scales, ctx.rois, ctx.levels, pl.sampling_ratio, pl.aligned,
+                                              num_valid=ctx.num_valid)
+        return (None, None, None, None, None) + tuple(grads)
+
+
 class ROIPooler(nn.Module):
     def __init__(self, output_size, scales, sampling_ratio, pooler_type, canonical_box_size=224, canonical_level=4):
         super().__init__()
@@ -72,6 +93,14 @@ class ROIPooler(nn.Module):
                                             self.canonical_level)
         if len(feats_nhwc) == 1:
             levels = None
+        return K.roi_align_fpn_nhwc(feats_nhwc, self.scales, rois, levels, self.output_size[0], self.output_size[1],
+                                    self.sampling_ratio, self.aligned, status=status)
+
+    def pool_rois_nhwc(self, feats_nhwc, rois, levels, num_valid=None, status=None):
+        """`pool_nhwc` on ready rois [K, 5] / levels [K] int32 (None with one level), recorded for autograd when a level map needs a
+        gradient; num_valid (device int32): the backward skips the rows past it."""
+        if torch.is_grad_enabled() and any(f.requires_grad for f in feats_nhwc):
+            return _PoolRois.apply(self, rois, levels, num_valid, status, *feats_nhwc)
         return K.roi_align_fpn_nhwc(feats_nhwc, self.scales, rois, levels, self.output_size[0], self.output_size[1],
                                     self.sampling_ratio, self.aligned, status=status)
 

@@ -1,4 +1,4 @@
-"""MaskRCNNConvUpsampleHead, inference side (reference detectron2/modeling/roi_heads/mask_head.py:113-285): NUM_CONV 3x3 convs with
+"""MaskRCNNConvUpsampleHead (reference detectron2/modeling/roi_heads/mask_head.py:31-285): NUM_CONV 3x3 convs with
 ReLU (`mask_fcn{k}`), a 2x2 stride-2 transposed convolution (`deconv`), ReLU, and the 1x1 `predictor`.  Parameter names and
 initialisation are the reference's.
 
@@ -6,8 +6,13 @@ The convs run on the channels-last RoI maps [M, S, S, C] through `Conv2d.forward
 deconv + ReLU + predictor + pick the predicted class + sigmoid -- is ONE launch (csrc/mask_deconv.hip): the reference's
 [M, C, 2S, 2S] and [M, K, 2S, 2S] tensors are never formed, only the selected-class probabilities [M, 2S, 2S] leave the kernel.
 
+Training (opt-in: `GeneralizedRCNN.enable_mask_training()`): the same tail with the GROUND-TRUTH class and without the sigmoid
+(lvc_mask_deconv_logits), the loss (lvc_mask_loss) and the tail's backward (lvc_mask_deconv_grad) are ONE autograd node,
+`MaskTailLoss`; the convs before it are recorded by `Conv2d.forward_nhwc`.  `mask_rcnn_loss` keeps the reference's signature, but its
+first argument is a `MaskTail` -- the tail's operands, not yet evaluated -- because the all-class logits are never formed.
+
 Not built (each raises NotImplementedError): GroupNorm in the head (MODEL.ROI_MASK_HEAD.NORM), `layers()` with all-class logits,
-the training loss (`mask_rcnn_loss`)."""
+VIS_PERIOD > 0, ground-truth masks that are not BitMasks (INPUT.MASK_FORMAT "bitmask")."""
 import torch
 import torch.nn.functional as F
 from torch import nn
@@ -16,6 +21,7 @@ from ... import kernels as K
 from ...layers import Conv2d, ConvTranspose2d, ShapeSpec
 from ...layers.layout import to_nhwc
 from ...utils import weight_init
+from ...utils.events import get_event_storage
 from ...utils.registry import Registry
 
 ROI_MASK_HEAD_REGISTRY = Registry("ROI_MASK_HEAD")
@@ -30,6 +36,103 @@ def mask_rcnn_inference(prob, pred_instances):
     parts = prob[: sum(counts)][:, None].split(counts, dim=0)
     for p, inst in zip(parts, pred_instances):
         inst.pred_masks = p
+
+
+class MaskTailLoss(torch.autograd.Function):
+    """The head's tail and the mask loss as one node: forward = lvc_mask_deconv_logits + lvc_mask_loss, backward =
+    lvc_mask_deconv_grad (+ the two GEMMs of `kernels.linear_backward`).  x [M, S, S, Cin] channels-last; classes int32 [M] (None:
+    class-agnostic); targets uint8 / bool [M, 2S, 2S]; num_valid: device int32 [1] or None.  -> (loss scalar, fp64 sum [1], counts
+    int64 [3]); gradients for x, deconv.weight, deconv.bias, predictor.weight, predictor.bias.  The upstream scalar stays on the
+    device (a LossScaler makes it 1024)."""
+
+    @staticmethod
+    def forward(ctx, x, wd, bd, wp, bp, classes, targets, num_valid, status, packed):
+        if packed is None:
+            packed = K.pack_mask_deconv(wd)
+        wp2 = wp.detach().reshape(wp.shape[0], -1)
+        z = K.mask_deconv_logits(x, packed, bd.detach(), wp2, bp.detach(), classes=classes, num_valid=num_valid, status=status)
+        loss, total, counts = K.mask_loss(z, targets, num_valid)
+        ctx.save_for_backward(x, packed, bd, wp2, z, targets)
+        ctx.misc = (classes, num_valid, status, wp.shape)
+        ctx.mark_non_differentiable(total, counts)
+        return loss.view(()), total, counts
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, _g_total, _g_counts):
+        x, packed, bd, wp2, z, targets = ctx.saved_tensors
+        classes, num_valid, status, wp_shape = ctx.misc
+        need = ctx.needs_input_grad
+        up = g.reshape(1).to(torch.float32).contiguous()
+        dx, dwd, dbd, dwp, dbp = K.mask_deconv_grad(x, packed, bd, wp2, classes, z, targets, num_valid, up, status=status,
+                                                    need_dx=need[0], need_dw=need[1])
+        return dx, dwd, dbd, dwp.view(wp_shape), dbp, None, None, None, None, None
+
+
+class MaskTail:
+    """What `MaskRCNNConvUpsampleHead.layers` would return in the reference -- the all-class logits [M, K, 2S, 2S] -- as the operands
+    they would be computed from: `x` [M, S, S, C] (channels-last, after the mask_fcn convs) and the head that owns deconv and predictor."""
+
+    def __init__(self, x, head):
+        self.x, self.head = x, head
+
+    def size(self, dim):
+        M, S = self.x.shape[0], self.x.shape[1]
+        return (M, self.head.num_classes, 2 * S, 2 * S)[dim]
+
+
+def mask_scalars(counts, numel):
+    """mask_rcnn/accuracy, false_positive, false_negative (reference mask_head.py:88-100) from the loss kernel's three counts --
+    incorrect, positive and false-positive pixels -- and the number of target pixels."""
+    incorrect, positive, false_pos = [float(c) for c in counts]
+    return {"mask_rcnn/accuracy": 1 - incorrect / max(float(numel), 1.0),
+            "mask_rcnn/false_positive": false_pos / max(float(numel) - positive, 1.0),
+            "mask_rcnn/false_negative": (incorrect - false_pos) / max(positive, 1.0)}
+
+
+def log_mask_scalars(counts, numel):
+    storage = get_event_storage()
+    for k, v in mask_scalars(counts, numel).items():
+        storage.put_scalar(k, v)
+
+
+def _require_bitmasks(masks):
+    from ...structures import BitMasks
+
+    if not isinstance(masks, BitMasks):
+        raise NotImplementedError("gt_masks of type {}: the mask targets are built from BitMasks only; set INPUT.MASK_FORMAT to "
+                                  "\"bitmask\" (polygon rasterisation is not built)".format(type(masks).__name__))
+    return masks
+
+
+def mask_rcnn_loss(pred_mask_logits, instances, vis_period=0):
+    """Reference signature (mask_head.py:31-110).  `pred_mask_logits`: a `MaskTail` (see there) whose rows correspond 1:1 to the
+    concatenated `instances`, each with `proposal_boxes`, `gt_classes` and `gt_masks` (BitMasks, one per row).  Logs the three
+    mask_rcnn/* scalars (one device->host read) and returns the scalar loss."""
+    if vis_period > 0:
+        raise NotImplementedError("VIS_PERIOD > 0: visualising the mask predictions is not built")
+    if not isinstance(pred_mask_logits, MaskTail):
+        raise TypeError("mask_rcnn_loss takes the head's MaskTail: the all-class logits [M, K, 2S, 2S] are never formed")
+    tail, head = pred_mask_logits, pred_mask_logits.head
+    side = tail.size(2)
+    gt_classes, gt_masks = [], []
+    for per_image in instances:
+        if len(per_image) == 0:
+            continue
+        gt_classes.append(per_image.gt_classes.to(torch.int32))
+        gt_masks.append(_require_bitmasks(per_image.gt_masks).crop_and_resize(per_image.proposal_boxes.tensor, side))
+    if len(gt_masks) == 0:
+        return tail.x.sum() * 0
+    targets = torch.cat(gt_masks, dim=0).to(tail.x.device).contiguous()
+    assert targets.shape[0] == tail.x.shape[0], "mask_rcnn_loss: {} rows of features, {} instances".format(tail.x.shape[0], targets.shape[0])
+    classes = None if head.cls_agnostic_mask else torch.cat(gt_classes).to(tail.x.device).contiguous()
+    status = K.new_status(tail.x.device)
+    loss, _total, counts = head.tail_loss(tail.x, classes, targets, status=status)
+    meta = torch.cat([counts, status.long()]).tolist()      # the reference reads its three scalars with .item()
+    if meta[3] & K.MASK_BAD_CLASS:
+        raise IndexError("mask head: a ground-truth class lies outside [0, {})".format(head.num_classes))
+    log_mask_scalars(meta[:3], targets.numel())
+    return loss
 
 
 @ROI_MASK_HEAD_REGISTRY.register()
@@ -80,7 +183,12 @@ class MaskRCNNConvUpsampleHead(nn.Module):
         """Reference signature (BaseMaskRCNNHead.forward, inference): x [M, C, S, S] pooled features of the concatenated instances,
         which get `pred_masks` [n, 1, 2S, 2S]."""
         if self.training:
-            raise NotImplementedError("training the mask branch (mask_rcnn_loss) is not built")
+            if not self.__dict__.get("_mask_train_enabled", False):
+                raise NotImplementedError("training the mask branch (mask_rcnn_loss) is not built")
+            h = to_nhwc(x).contiguous()
+            for layer in self.conv_norm_relus:
+                h = layer.forward_nhwc(h)
+            return {"loss_mask": mask_rcnn_loss(MaskTail(h, self), instances, self.vis_period)}
         classes = None
         if not self.cls_agnostic_mask:
             classes = torch.cat([i.pred_classes for i in instances]).to(torch.int32).contiguous()
@@ -90,6 +198,23 @@ class MaskRCNNConvUpsampleHead(nn.Module):
             raise IndexError("mask head: a predicted class lies outside [0, {})".format(self.num_classes))
         mask_rcnn_inference(prob, instances)
         return instances
+
+    def tail_loss(self, x, classes, targets, num_valid=None, status=None):
+        """x [M, S, S, C] after the mask_fcn convs -> `MaskTailLoss` with this head's deconv and predictor."""
+        if self.cls_agnostic_mask:
+            classes = None
+        packed = self.deconv.packed()      # (rebuilt when the parameter has changed)
+        return MaskTailLoss.apply(x.contiguous(), self.deconv.weight, self.deconv.bias, self.predictor.weight, self.predictor.bias,
+                                  classes, targets, num_valid, status, packed)
+
+    def loss_nhwc(self, pooled, classes, targets, num_valid=None, status=None):
+        """Training on padded rows, nothing read back: pooled [M, S, S, C]; classes int32 [M]: the ground-truth classes; targets uint8
+        [M, 2S, 2S]; num_valid: device int32 [1] (the convs run on all rows, tail and loss on the rows below it).
+        -> (loss scalar, fp64 sum [1], counts int64 [3])."""
+        x = pooled
+        for layer in self.conv_norm_relus:
+            x = layer.forward_nhwc(x)
+        return self.tail_loss(x, classes, targets, num_valid=num_valid, status=status)
 
     def layers(self, x):
         raise NotImplementedError("MaskRCNNConvUpsampleHead.layers (all-class mask logits) is not built: the kernel computes the "

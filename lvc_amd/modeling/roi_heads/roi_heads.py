@@ -67,6 +67,14 @@ class ROIHeads(nn.Module):
 
     relabel_ignored_gt = True
 
+    def _keeps_index(self, val):
+        """A mask model's sampled rows do not carry gathered full-size ground-truth planes (the reference's gt_masks[matched_idxs]:
+        512 x H x W bytes per image): the mask targets are cut from the image's planes through the matched INDEX of a row (the python
+        attribute `_lvc_matched` / the sampler's table).  A box-only model keeps exactly the fields it had."""
+        from ...structures import BitMasks
+
+        return bool(getattr(self, "mask_on", False)) and isinstance(val, BitMasks)
+
     batched_sampling = True     # class switch for A/B runs and tests (False: the per-image loop in every case)
 
     batched_targets = True      # class switch for A/B runs and tests (False: the padded table built image by image with torch ops)
@@ -113,12 +121,14 @@ class ROIHeads(nn.Module):
                 inst.gt_boxes = Boxes(s_gtb[i, :c])
                 st = None
                 for name, val in tgt.get_fields().items():
-                    if name.startswith("gt_") and not inst.has(name):
+                    if name.startswith("gt_") and not inst.has(name) and not self._keeps_index(val):
                         st = s_m[i, :c] if st is None else st
                         inst.set(name, val[st])
+                inst._lvc_matched = s_m[i, :c]
                 out.append(inst)
-            # for _forward_train: the same rows as padded batch tensors (a python attribute, not a field)
-            out[0]._lvc_sampled = (s_boxes, s_cls, s_gtb, [c[0] + c[1] for c in counts])
+            # for _forward_train: the same rows as padded batch tensors (a python attribute, not a field); the matched gt index and the
+            # device counts for the mask branch
+            out[0]._lvc_sampled = (s_boxes, s_cls, s_gtb, [c[0] + c[1] for c in counts], s_m, cnt)
             if log:
                 storage = get_event_storage()
                 storage.put_scalar("roi_head/num_fg_samples", sum(c[0] for c in counts) / B)
@@ -164,8 +174,9 @@ class ROIHeads(nn.Module):
             inst.gt_classes = s_cls[i, :c]
             st = s_m[i, :c]
             for name, val in tgt.get_fields().items():
-                if name.startswith("gt_") and not inst.has(name):
+                if name.startswith("gt_") and not inst.has(name) and not self._keeps_index(val):
                     inst.set(name, val[st])
+            inst._lvc_matched = st
             out.append(inst)
         if log:
             storage = get_event_storage()
@@ -204,8 +215,9 @@ class ROIHeads(nn.Module):
             if len(gt) > 0:
                 st = matched_idxs[sampled]
                 for name, val in tgt.get_fields().items():
-                    if name.startswith("gt_") and not inst.has(name):
+                    if name.startswith("gt_") and not inst.has(name) and not self._keeps_index(val):
                         inst.set(name, val[st])
+                inst._lvc_matched = st
             else:
                 inst.gt_boxes = Boxes(gt.new_zeros((len(sampled), 4)))
             num_bg.append(int((gt_classes == self.num_classes).sum()))
@@ -264,10 +276,19 @@ class StandardROIHeads(ROIHeads):
         vectorised NHWC kernel `roi_align_fwd_nhwc4_kernel`, which takes no row count: a zero box costs it a store of zeros).
         -> (pooled [B*topk, S, S, C], classes [B*topk] int32 in that order, rows [B, topk] int32: the row box i of image b owns,
         total [1] int32: the number of real rows)."""
+        pl = self.mask_pooler
+        feats = [feats_nhwc[f] for f in self.mask_in_features]
+        rois, levels, cls, rows, total, _order = self._mask_rows(boxes, classes, count, len(feats))
+        pooled = K.roi_align_fpn_nhwc(feats, pl.scales, rois, levels, pl.output_size[0], pl.output_size[1], pl.sampling_ratio, pl.aligned,
+                                      status=status)
+        return pooled, cls, rows, total
+
+    def _mask_rows(self, boxes, classes, count, num_levels):
+        """-> (rois [B*T, 5], levels [B*T] int32 or None, classes [B*T], rows [B, T] int32, total [1] int32, order [B*T] int64): the rows
+        of the [B, T] table with the real ones (the first count[b] of image b) moved to the front, image after image."""
         B, T, _ = boxes.shape
         dev = boxes.device
         pl = self.mask_pooler
-        feats = [feats_nhwc[f] for f in self.mask_in_features]
         ar = torch.arange(T, device=dev, dtype=torch.int32)
         cnt = count.clamp(min=0, max=T)
         valid = ar[None, :] < cnt[:, None]
@@ -280,11 +301,36 @@ class StandardROIHeads(ROIHeads):
         boxes = torch.where(valid[:, :, None], boxes, torch.zeros_like(boxes))
         levels, rois = K.assign_levels_rois(boxes, pl.min_level, pl.max_level, pl.canonical_box_size, pl.canonical_level)
         rois = rois.index_select(0, order)
-        levels = None if len(feats) == 1 else levels.index_select(0, order)
+        levels = None if num_levels == 1 else levels.index_select(0, order)
         cls = classes.reshape(-1).index_select(0, order).contiguous()
-        pooled = K.roi_align_fpn_nhwc(feats, pl.scales, rois, levels, pl.output_size[0], pl.output_size[1], pl.sampling_ratio, pl.aligned,
-                                      status=status)
-        return pooled, cls, rows, total
+        return rois, levels, cls, rows, total, order
+
+    def mask_loss_batched(self, feats_nhwc, s_boxes, s_cls, s_m, fg_count, gt_masks, status=None):
+        """The mask branch's training loss on the sampler's padded tables, with no device->host read (reference roi_heads.py
+        `_forward_mask` + `select_foreground_proposals` + mask_rcnn_loss).  s_boxes [B, R, 4], s_cls [B, R], s_m [B, R] int64 (the
+        matched gt index of every sampled row), fg_count [B] int32 on the device: foreground comes before background in the sampled
+        table, so the foreground rows of image b are its first fg_count[b], at most int(BATCH_SIZE_PER_IMAGE * POSITIVE_FRACTION);
+        gt_masks: one BitMasks per image.  The foreground rows move to the front (as `pool_masks_batched` does), the mask pooler and
+        the mask_fcn convs run under autograd on ALL padded rows (zero boxes), and the total of foreground rows is the `num_valid` of
+        tail, loss and backward.  -> (loss_mask scalar, counts int64 [3], total int32 [1])."""
+        from .mask_head import _require_bitmasks
+
+        if not self.mask_on:
+            raise RuntimeError("mask_loss_batched: the model was built with MODEL.MASK_ON = False")
+        cap = max(int(self.batch_size_per_image * self.positive_sample_fraction), 1)
+        R = min(cap, s_boxes.shape[1])
+        boxes = s_boxes[:, :R].detach().contiguous()
+        matched = s_m[:, :R].to(torch.int64).contiguous()
+        count = fg_count.to(torch.int32).clamp(min=0, max=R)
+        planes = [_require_bitmasks(m).tensor.contiguous() for m in gt_masks]
+        side = 2 * self.mask_pooler.output_size[0]
+        targets = K.mask_targets(boxes, matched, count, planes, side)
+        feats = [feats_nhwc[f] for f in self.mask_in_features]
+        rois, levels, cls, _rows, total, order = self._mask_rows(boxes, s_cls[:, :R].to(torch.int32), count, len(feats))
+        targets = targets.index_select(0, order)
+        pooled = self.mask_pooler.pool_rois_nhwc(feats, rois, levels, num_valid=total, status=status)
+        loss, _sum, counts = self.mask_head.loss_nhwc(pooled, cls, targets, num_valid=total, status=status)
+        return loss, counts, total
 
     def forward_masks_batched(self, feats_nhwc, boxes, classes, count, status=None):
         """The mask branch on padded batch tensors, nothing read back.  feats_nhwc: dict name -> [B,H,W,C]; boxes [B,topk,4] in network
@@ -338,7 +384,7 @@ class StandardROIHeads(ROIHeads):
     def forward(self, images, features, proposals, targets=None):
         """Reference signature (roi_heads.py:554-572): -> (list[Instances], losses)."""
         if self.training:
-            if self.mask_on:
+            if self.mask_on and not self.__dict__.get("_mask_train_enabled", False):
                 raise NotImplementedError("training the mask branch (MODEL.MASK_ON: mask_rcnn_loss, gt_masks) is not built")
             return self._forward_train(features, proposals, targets)
         if self.rbg:
@@ -402,8 +448,10 @@ def forward_train_batched(self, features, pboxes, plogits, pcount, gt, gt_off, t
     (`forward`) instead -- the reference's normalisation is by the true row count."""
     from .fast_rcnn import fast_rcnn_losses
 
-    s_boxes, _s_logits, s_cls, _s_m, s_gtb, cnt = _sample_batched(self, pboxes, plogits, pcount, gt, gt_off, targets)
+    s_boxes, _s_logits, s_cls, s_m, s_gtb, cnt = _sample_batched(self, pboxes, plogits, pcount, gt, gt_off, targets)
     feats = [to_nhwc(features[f]) for f in self.in_features]
+    if self.mask_on:
+        return _forward_train_batched_masks(self, features, feats, s_boxes, s_cls, s_m, s_gtb, cnt, targets)
     below = any(f.requires_grad for f in feats) or any(p.requires_grad for p in self.box_head.parameters())
     with torch.set_grad_enabled(below and torch.is_grad_enabled()):
         h = self.box_head.forward_nhwc(self.box_pooler.pool_nhwc(feats, s_boxes))
@@ -416,12 +464,45 @@ def forward_train_batched(self, features, pboxes, plogits, pcount, gt, gt_off, t
     return losses, cnt, stats
 
 
+def _box_stats(self, pred, gc):
+    fg = (gc >= 0) & (gc < self.num_classes)
+    hit = pred == gc
+    return torch.stack([fg.sum(), hit.sum(), (hit & fg).sum(), ((pred == self.num_classes) & fg).sum()])
+
+
+def _forward_train_batched_masks(self, features, feats, s_boxes, s_cls, s_m, s_gtb, cnt, targets):
+    """`forward_train_batched` of a mask model: the box branch as there, then the mask branch on the same sampled table.  The accuracy
+    counts grow to int64 [9]: the four of the box branch, the loss kernel's three (incorrect, positive, false-positive pixels), the
+    number of mask rows and the mask kernels' status word -- all read by the caller with the step's other scalars."""
+    from .fast_rcnn import fast_rcnn_losses
+
+    h = self.box_head.forward_nhwc(self.box_pooler.pool_nhwc(feats, s_boxes))
+    gc = s_cls.view(-1)
+    losses, pred = fast_rcnn_losses(self.box_predictor, h, s_boxes.view(-1, 4), s_gtb.view(-1, 4), gc)
+    mfeats = {f: to_nhwc(features[f]) for f in self.mask_in_features}
+    status = K.new_status(s_boxes.device)
+    loss_mask, mcounts, total = self.mask_loss_batched(mfeats, s_boxes, s_cls, s_m, cnt[:, 0], _gt_masks_of(targets), status=status)
+    losses = dict(losses)
+    losses["loss_mask"] = loss_mask
+    with torch.no_grad():
+        stats = torch.cat([_box_stats(self, pred, gc), mcounts, total.long(), status.long()])
+    return losses, cnt, stats
+
+
 def log_train_scalars(self, counts, stats, nrows):
-    """EventStorage scalars of label_and_sample_proposals and FastRCNNOutputs._log_accuracy from host values."""
+    """EventStorage scalars of label_and_sample_proposals and FastRCNNOutputs._log_accuracy from host values (a mask model: also the
+    three mask_rcnn/* scalars, from the counts `_forward_train_batched_masks` appended)."""
     storage = get_event_storage()
     B = len(counts)
     storage.put_scalar("roi_head/num_fg_samples", sum(c[0] for c in counts) / B)
     storage.put_scalar("roi_head/num_bg_samples", sum(c[1] for c in counts) / B)
+    if len(stats) > 4:
+        from .mask_head import log_mask_scalars
+
+        check_status(stats[8])
+        side = 2 * self.mask_pooler.output_size[0]
+        log_mask_scalars(stats[4:7], stats[7] * side * side)
+        stats = stats[:4]
     nfg, ncorrect, nfg_correct, nfg_bg = stats
     storage.put_scalar("fast_rcnn/cls_accuracy", float(ncorrect) / max(1, nrows))
     if nfg > 0:
@@ -473,7 +554,61 @@ def _forward_train(self, features, proposals, targets):
     if nfg > 0:
         storage.put_scalar("fast_rcnn/fg_cls_accuracy", float(nfg_correct) / nfg)
         storage.put_scalar("fast_rcnn/false_negative", float(nfg_bg) / nfg)
+    if self.mask_on:
+        losses = dict(losses)
+        losses["loss_mask"] = _mask_loss_from_lists(self, features, proposals, targets, sampled if full else None)
     return proposals, losses
+
+
+def _gt_masks_of(targets):
+    """The ground-truth masks of every image; an image without ground truth may come without the field: no planes."""
+    from ...structures import BitMasks
+
+    out = []
+    for t in targets:
+        if t.has("gt_masks"):
+            out.append(t.gt_masks)
+        elif len(t) == 0:
+            h, w = t.image_size
+            out.append(BitMasks(torch.zeros(0, h, w, dtype=torch.bool, device=t.gt_boxes.tensor.device)))
+        else:
+            raise ValueError("training the mask branch: an image's ground truth has no `gt_masks` field")
+    return out
+
+
+def _mask_loss_from_lists(self, features, proposals, targets, sampled):
+    """The per-image path's mask loss: the tables `mask_loss_batched` takes, built from the sampled Instances (or the sampler's own
+    tables when they are at hand), then one read for the three logged counts."""
+    from .mask_head import log_mask_scalars
+
+    dev = proposals[0].proposal_boxes.tensor.device
+    B = len(proposals)
+    if sampled is not None and len(sampled) >= 6:
+        s_boxes, s_cls, s_m, fg_count = sampled[0], sampled[1], sampled[4], sampled[5][:, 0]
+    else:
+        counts = [len(p) for p in proposals]
+        R = max(max(counts), 1)
+        s_boxes = torch.zeros(B, R, 4, device=dev)
+        s_cls = torch.full((B, R), -1, dtype=torch.int64, device=dev)
+        s_m = torch.zeros(B, R, dtype=torch.int64, device=dev)
+        for i, p in enumerate(proposals):
+            s_boxes[i, : counts[i]] = p.proposal_boxes.tensor
+            s_cls[i, : counts[i]] = p.gt_classes
+            matched = getattr(p, "_lvc_matched", None)
+            if matched is None and counts[i] and len(targets[i]) > 0:
+                raise RuntimeError("the mask branch needs the matched gt index of every sampled row (label_and_sample_proposals)")
+            if counts[i] and matched is not None:      # (an image without ground truth has background rows only)
+                s_m[i, : counts[i]] = matched
+        # foreground precedes background in a sampled table: the foreground rows are the first fg_count[b]
+        fg_count = ((s_cls >= 0) & (s_cls < self.num_classes)).sum(1).to(torch.int32)
+    mfeats = {f: to_nhwc(features[f]) for f in self.mask_in_features}
+    status = K.new_status(dev)
+    loss_mask, mcounts, total = self.mask_loss_batched(mfeats, s_boxes, s_cls, s_m, fg_count, _gt_masks_of(targets), status=status)
+    meta = torch.cat([mcounts, total.long(), status.long()]).tolist()
+    check_status(meta[4])
+    side = 2 * self.mask_pooler.output_size[0]
+    log_mask_scalars(meta[:3], meta[3] * side * side)
+    return loss_mask
 
 
 StandardROIHeads._forward_train = _forward_train
@@ -582,7 +717,8 @@ def check_status(st):
         raise CandidateOverflow("lvc_fast_rcnn_inference: more (roi, class) candidates above SCORE_THRESH_TEST in one "
                                 "image than the candidate list holds; re-run with max_candidates=None (= R*K)")
     if st & 8:
-        raise IndexError("lvc_mask_deconv_predict: a predicted class lies outside the mask predictor's [0, K)")
+        raise IndexError("lvc_mask_deconv_predict / lvc_mask_deconv_logits / lvc_mask_deconv_grad: a class index lies outside the mask "
+                         "predictor's [0, K)")
     if st & 4:
         raise CandidateOverflow("lvc_retinanet_select: more entries above SCORE_THRESH_TEST on one (image, level) than the survivor "
                                 "list holds; re-run with max_survivors=None (= H*W*A*K)")

@@ -1,5 +1,6 @@
 from .boxes import Boxes, BoxMode, pairwise_iou
 from .image_list import ImageList
 from .instances import Instances
+from .masks import BitMasks
 
-__all__ = ["Boxes", "BoxMode", "pairwise_iou", "ImageList", "Instances"]
+__all__ = ["Boxes", "BoxMode", "pairwise_iou", "ImageList", "Instances", "BitMasks"]
