@@ -138,18 +138,32 @@ extern "C" int lvc_maxpool2d_nhwc(const float* x, float* y, int N, int H, int W,
 // VEC (D % 4 == 0 and 16-byte aligned rows): lane l owns elements 256 i + 4 l .. + 3 (one dwordx4 per 256-element slice) and adds
 // their squares in that order; otherwise lane l owns elements l, l + 64, ...  The 64 partial sums meet in a butterfly.
 // rownorm_h_kernel below sums in exactly the same orders.
+// The squares are those of the exact differences x - mu and are added in fp64, and the denominator is rounded to fp32 ONCE
+// (rownorm_den): den is within half an ulp of the true one, so a whole row -- every element carries den's error -- stays within
+// one rounding of den plus one of its division, whatever the row length.  (An fp32 sum of squares put about 2 ulp on den, and with
+// it on every element of the row.)  The numerators stay the fp32 differences: y = fl(x - mu) / den, one division.
+__device__ __forceinline__ void rownorm_sq4(double& ss, const float4& v, const float4& m) {
+  const double a = (double)v.x - (double)m.x, b = (double)v.y - (double)m.y, c = (double)v.z - (double)m.z, e = (double)v.w - (double)m.w;
+  ss += a * a; ss += b * b; ss += c * c; ss += e * e;
+}
+
+__device__ __forceinline__ float rownorm_den(double ss, float eps, int mode) {
+  const double nrm = sqrt(ss);
+  return mode == 0 ? (float)(nrm + (double)eps) : (nrm > (double)eps ? (float)nrm : eps);
+}
+
 template <bool VEC>
-__device__ __forceinline__ float rownorm_sumsq(const float* __restrict__ xr, const float* __restrict__ mu, int D, int lane) {
-  float ss = 0.f;
+__device__ __forceinline__ double rownorm_sumsq(const float* __restrict__ xr, const float* __restrict__ mu, int D, int lane) {
+  double ss = 0.0;
   if constexpr (VEC) {
     for (int d = lane * 4; d < D; d += 256) {
-      float4 v = *reinterpret_cast<const float4*>(xr + d);
-      if (mu) { const float4 m = *reinterpret_cast<const float4*>(mu + d); v.x -= m.x; v.y -= m.y; v.z -= m.z; v.w -= m.w; }
-      ss += v.x * v.x; ss += v.y * v.y; ss += v.z * v.z; ss += v.w * v.w;
+      const float4 v = *reinterpret_cast<const float4*>(xr + d);
+      const float4 m = mu ? *reinterpret_cast<const float4*>(mu + d) : float4{0.f, 0.f, 0.f, 0.f};
+      rownorm_sq4(ss, v, m);
     }
   } else {
     for (int d = lane; d < D; d += 64) {
-      float v = xr[d] - (mu ? mu[d] : 0.f);
+      const double v = (double)xr[d] - (mu ? (double)mu[d] : 0.0);
       ss += v * v;
     }
   }
@@ -164,8 +178,7 @@ __global__ __launch_bounds__(256) void rownorm_kernel(const float* __restrict__ 
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= M) return;
   const float* xr = x + (size_t)row * ldx;
-  const float nrm = sqrtf(rownorm_sumsq<VEC>(xr, mu, D, lane));
-  const float den = mode == 0 ? nrm + eps : (nrm > eps ? nrm : eps);
+  const float den = rownorm_den(rownorm_sumsq<VEC>(xr, mu, D, lane), eps, mode);
   float* yr = y + (size_t)row * ldy;
   if constexpr (VEC) {
     for (int d = lane * 4; d < D; d += 256) {
@@ -184,7 +197,8 @@ __global__ __launch_bounds__(256) void rownorm_kernel(const float* __restrict__ 
 // 2-norm of each row's fp16 rounding residual resid [M] (what bounds the pre-filter's error for that row) and -- optionally --
 // the fp32 rows themselves (bit-identical to rownorm_kernel -- same summation order, same division -- for the widths this file
 // vectorises here, D <= 2048 with 16-byte aligned rows, and for unaligned rows; wider aligned rows are summed in the scalar order
-// here and in the vectorised order there: equal to fp32 rounding, not bit for bit).
+// here and in the vectorised order there: the two fp64 sums can differ in their last bits, so den is the same fp32 number unless it
+// falls on a rounding boundary -- equal to fp32 rounding, bit for bit in practice but not by construction).
 template <int NV, bool VEC>   // VEC: NV * 256 >= D, the centred row stays in registers between the two passes; else it is read twice
 __global__ __launch_bounds__(256) void rownorm_h_kernel(const float* __restrict__ x, const float* __restrict__ mu,
                                                         float* __restrict__ y, _Float16* __restrict__ yh, float* __restrict__ dens,
@@ -192,30 +206,26 @@ __global__ __launch_bounds__(256) void rownorm_h_kernel(const float* __restrict_
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= M) return;
   const float* xr = x + (size_t)row * ldx;
-  float ss = 0.f;
+  double ss = 0.0;
   float4 c[NV > 0 ? NV : 1];
   if constexpr (VEC) {
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
       const int d = i * 256 + lane * 4;
       float4 v = {0.f, 0.f, 0.f, 0.f};
-      if (d < D) {
+      if (d < D) {     // the same order as rownorm_sumsq<true>
         v = *reinterpret_cast<const float4*>(xr + d);
-        if (mu) { const float4 m = *reinterpret_cast<const float4*>(mu + d); v.x -= m.x; v.y -= m.y; v.z -= m.z; v.w -= m.w; }
+        const float4 m = mu ? *reinterpret_cast<const float4*>(mu + d) : float4{0.f, 0.f, 0.f, 0.f};
+        rownorm_sq4(ss, v, m);
+        v.x -= m.x; v.y -= m.y; v.z -= m.z; v.w -= m.w;
       }
       c[i] = v;
     }
-#pragma unroll
-    for (int i = 0; i < NV; ++i)
-      if (i * 256 + lane * 4 < D) {     // the same order as rownorm_sumsq<true>
-        ss += c[i].x * c[i].x; ss += c[i].y * c[i].y; ss += c[i].z * c[i].z; ss += c[i].w * c[i].w;
-      }
     for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
   } else {
     ss = rownorm_sumsq<false>(xr, mu, D, lane);
   }
-  const float nrm = sqrtf(ss);
-  const float den = mode == 0 ? nrm + eps : (nrm > eps ? nrm : eps);
+  const float den = rownorm_den(ss, eps, mode);
   if (dens && lane == 0) dens[row] = den;
   float* yr = y ? y + (size_t)row * D : nullptr;
   _Float16* hr = yh + (size_t)row * D;
@@ -292,6 +302,10 @@ extern "C" int lvc_rownorm(const float* x, const float* mu, float* y, int M, int
 // Backward of y = x / (|x| + eps) row-wise (mode 0 of lvc_rownorm without mu; CosineSimOutputLayers' input
 // normalisation, lvc/modeling/roi_heads/fast_rcnn.py:823-825: torch.norm's backward is x/|x|):
 //   dx = dy / (n + eps) - x * (dy . x) / ((n + eps)^2 * n),  n = |x|;  rows with n == 0 get dy / eps.
+// Evaluated with u = x / n and t = dy . u as
+//   dx = (dy - u t) / (n + eps) + u t eps / (n + eps)^2:
+// the part of dy across x and the part along it, which the first form leaves as the difference of two numbers 1 / eps times its
+// size (for D = 1 nothing else is left: u = +-1 and dy - u t = 0 exactly, the answer is the second term).  Three passes over a row.
 // dx_accum != 0: added to what dx already holds (the bbox_pred branch's gradient of the same x).
 __global__ __launch_bounds__(256) void rownorm_backward_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                                float* __restrict__ dx, int M, int D, float eps, int accum) {
@@ -299,17 +313,20 @@ __global__ __launch_bounds__(256) void rownorm_backward_kernel(const float* __re
   if (row >= M) return;
   const float* xr = x + (size_t)row * D;
   const float* gr = dy + (size_t)row * D;
-  float ss = 0.f, dot = 0.f;
-  for (int d = lane; d < D; d += 64) {
-    ss += xr[d] * xr[d];
-    dot += gr[d] * xr[d];
-  }
-  for (int o = 32; o > 0; o >>= 1) { ss += __shfl_xor(ss, o); dot += __shfl_xor(dot, o); }
+  float ss = 0.f;
+  for (int d = lane; d < D; d += 64) ss += xr[d] * xr[d];
+  for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
   const float n = sqrtf(ss), den = n + eps;
-  const float a = 1.f / den, b = n > 0.f ? dot / (den * den * n) : 0.f;
+  const bool live = n > 0.f;
+  float t = 0.f;
+  if (live)
+    for (int d = lane; d < D; d += 64) t += gr[d] * (xr[d] / n);
+  for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
+  const float c = t * eps / (den * den);
   float* o_ = dx + (size_t)row * D;
   for (int d = lane; d < D; d += 64) {
-    const float v = gr[d] * a - xr[d] * b;
+    const float u = live ? xr[d] / n : 0.f;
+    const float v = (gr[d] - u * t) / den + u * c;      // a zero row: dy / eps in one rounding
     o_[d] = accum ? o_[d] + v : v;
   }
 }

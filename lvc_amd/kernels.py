@@ -2299,8 +2299,9 @@ def knn_margins(qres, sres_max, acc, extra=0.0):
 
 
 def rownorm_h(x, mu=None, eps=1e-5, mode=0, want_rows=True, want_resid=False):
-    """`rownorm` for the two-stage kNN sweep: (y fp32 [M,D] or None, yh fp16 [M,D], den [M]); y is bit-identical to
-    `rownorm`'s output and equals (x - mu) / den[:, None] exactly.  want_resid: also resid [M] = |row - fp16(row)|_2."""
+    """`rownorm` for the two-stage kNN sweep: (y fp32 [M,D] or None, yh fp16 [M,D], den [M]); y equals (x - mu) / den[:, None]
+    exactly and is bit-identical to `rownorm`'s output, except that 16-byte aligned rows wider than 2048 are summed in another order there
+    (fp64 sums, one rounding of den: equal to fp32 rounding, bit-equal unless den falls on a rounding boundary).  want_resid: also resid [M] = |row - fp16(row)|_2."""
     _req_cuda(x, mu)
     assert x.dim() == 2 and x.stride(1) == 1 and x.dtype == torch.float32
     M, D = x.shape
@@ -3274,7 +3275,7 @@ def qkv_attention(x, pc, B, N, num_heads, scale):
 def mha_cls(qkv, B, N, num_heads, head_dim, scale):
     """qkv [B*N, 3*H*64] -> [B, H*64]: softmax(q_0 k^T scale) v for the class token of every image (the descriptor network's last block)."""
     _req_cuda(qkv)
-    assert head_dim == 64 and N <= 1024
+    assert head_dim == 64      # more than 1024 keys: refused by the entry point
     qkv = qkv.contiguous()
     out = torch.empty(B, num_heads * head_dim, device=qkv.device, dtype=torch.float32)
     check(_lib.lib().lvc_mha_cls(ptr(qkv), ptr(out), c_int(B), c_int(N), c_int(num_heads), c_float(scale), _stream(qkv)), "lvc_mha_cls")

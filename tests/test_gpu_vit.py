@@ -31,7 +31,8 @@ def test_layernorm_gelu_patchify_tokens():
 
 
 @pytest.mark.parametrize("mfma", [True, False])
-@pytest.mark.parametrize("B,N", [(2, 785), (1, 197), (3, 64), (2, 1), (1, 130)])
+@pytest.mark.parametrize("B,N", [(2, 785), (1, 197), (3, 64), (2, 1), (1, 130),
+                                 (1, 63), (1, 65), (2, 127), (1, 128), (1, 129), (1, 256)])      # either side of the 64-key tile and the 128-query block
 def test_attention_matches_torch(B, N, mfma):
     """Both attention kernels (matrix-core: lvc_mha_mfma, the default; scalar fp32: lvc_mha) against fp64, at the error level of
     torch's own fp32 CPU evaluation; token counts that are not multiples of the 64-key tile / the 128-query block."""
