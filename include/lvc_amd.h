@@ -908,6 +908,31 @@ int lvc_mask_deconv_grad(const float* x, const float* w_deconv, const float* b_d
                          float* dw_pred, float* db_pred, float* db_deconv, int M, int S, int Cin, int Cmid, int K,
                          int* d_status, void* workspace, long long workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Keypoint R-CNN inference: the keypoint head's transposed convolution and the heatmap decode (detectron2
+ * modeling/roi_heads/keypoint_head.py KRCNNConvDeconvUpsampleHead.layers, structures/keypoints.py heatmaps_to_keypoints).
+ * lvc_keypoint_deconv (csrc/keypoint.hip): ConvTranspose2d(Cin, K, 4, stride 2, padding 1) + bias.  x [M,S,S,Cin] NHWC fp32; packed:
+ *   the operand lvc_keypoint_deconv_pack writes from the parameter [Cin,K,4,4] -- lvc_keypoint_deconv_packed_rows(K) rows of Cin
+ *   floats ([4 parities][4 taps][K rounded up to 32][Cin]); bias [K] (NULL = zeros); out: planes [M,K,2S,2S].  Cin a multiple of 16
+ *   (up to 4096), 1 <= K <= 64, any M; anything else returns LVC_ERR_INVALID.  d_num_valid (device int, may be NULL): rows
+ *   >= *d_num_valid are neither read nor written.  Exact fp32 MFMA (range-free) in short chains that are joined, with the bias, in
+ *   fp64 and rounded once; an output is summed by one lane in a fixed order,
+ *   no atomics: two runs are bit-identical.
+ * lvc_heatmaps_to_keypoints (csrc/keypoint_decode.hip, no contraction): maps: planes [M,K,P,P]; rois [M,4] (x1, y1, x2, y2); up 1 or
+ *   2, up * P <= 64.  With up == 2 the bilinear x2 map (align_corners=False, source index max(0, (dst + 0.5) / 2 - 0.5)) is formed on
+ *   chip first.  maps_out (may be NULL): [M,K,up*P,up*P], the map that is decoded.  Per (RoI, keypoint): ATen's bicubic resize
+ *   (A = -0.75, align_corners=False) of the map to ceil(max(y2 - y1, 1)) x ceil(max(x2 - x1, 1)), its maximum and the position of the
+ *   maximum -- among equal maxima the LOWEST flat index y * w + x wins, as torch.argmax on the CPU --, score = exp(v - max) /
+ *   sum over the [up*P, up*P] map of exp(map - max), x = (x_int + 0.5) * (w / ceil w) + x1 and y likewise in fp32 without
+ *   contraction.  out [M,K,4] = (x, y, logit, score).  Rows >= *d_num_valid keep their bytes (out and maps_out).  No atomics: two
+ *   runs are bit-identical.  A box side is cut at 16384 output pixels. */
+int lvc_keypoint_deconv_packed_rows(int K);
+int lvc_keypoint_deconv_pack(const float* weight, float* packed, int Cin, int K, void* stream);
+int lvc_keypoint_deconv(const float* x, const float* packed, const float* bias, const int* d_num_valid, float* out, int M, int S,
+                        int Cin, int K, void* stream);
+int lvc_heatmaps_to_keypoints(const float* maps, const float* rois, const int* d_num_valid, float* maps_out, float* out, int M, int K,
+                              int P, int up, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

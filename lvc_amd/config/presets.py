@@ -53,6 +53,15 @@ def mask_rcnn_fpn(depth=50, num_classes=80, device="cuda"):
     return cfg
 
 
+def keypoint_rcnn_fpn(depth=50, num_classes=1, device="cuda"):
+    """Keypoint R-CNN on the ResNet-FPN trunk: the keys detectron2's `COCO-Keypoints/Base-Keypoint-RCNN-FPN.yaml` sets on top of
+    `base_rcnn_fpn` that the inference path reads (one class -- person --, the keypoint branch with the defaults' eight 512-channel
+    convs, 17 keypoints and 14x14 pooler).  Inference only."""
+    cfg = base_rcnn_fpn(depth=depth, num_classes=num_classes, device=device)
+    cfg.merge_from_list(["MODEL.KEYPOINT_ON", True, "MODEL.ROI_HEADS.NUM_CLASSES", num_classes])
+    return cfg
+
+
 def resnext_rcnn_fpn(depth=101, num_groups=32, width_per_group=8, num_classes=80, device="cuda"):
     """`base_rcnn_fpn` on a ResNeXt trunk: detectron2's `COCO-Detection/faster_rcnn_X_101_32x8d_FPN_3x.yaml` sets exactly these four
     keys (`STRIDE_IN_1X1: False` is the published X-101 setting; `True` builds too -- the grouped 3x3 is then always stride 1).

@@ -30,6 +30,9 @@ def _limits(model):
 def _refuse_masks(model, what):
     if getattr(getattr(model, "roi_heads", None), "mask_on", False):
         raise NotImplementedError("MODEL.MASK_ON: {} carries the box branch only; run a mask model through its own forward()".format(what))
+    if getattr(getattr(model, "roi_heads", None), "keypoint_on", False):
+        raise NotImplementedError("MODEL.KEYPOINT_ON: {} carries the box branch only; run a keypoint model through its own forward()"
+                                  .format(what))
 
 
 class PipelinedInference:
@@ -168,7 +171,13 @@ class GraphedInference:
 
 
 def inference_on_dataset(model, data_loader, depth=2):
-    """Yield (inputs, outputs) for every batch of `data_loader`, in order, keeping `depth` batches in flight."""
+    """Yield (inputs, outputs) for every batch of `data_loader`, in order, keeping `depth` batches in flight.  (A mask or keypoint
+    model is refused at the call, not at the first `next`.)"""
+    _refuse_masks(model, "inference_on_dataset (the two-stream pipeline)")
+    return _inference_on_dataset(model, data_loader, depth)
+
+
+def _inference_on_dataset(model, data_loader, depth):
     pipe = PipelinedInference(model, depth)
     pending = collections.deque()
     for inputs in data_loader:

@@ -3485,8 +3485,86 @@ def paste_masks(prob, jobs, out_bytes, threshold=0.5, out=None):
     return out
 
 
+# --------------------------------------------------------------------------- Keypoint R-CNN inference
+KEYPOINT_DECONV_CIN = 16      # granularity of Cin in lvc_keypoint_deconv
+KEYPOINT_DECONV_MAX_K = 64
+KEYPOINT_MAX_SIDE = 64        # up * P of lvc_heatmaps_to_keypoints
+
+
+def keypoint_deconv_check(cin, k):
+    if cin < KEYPOINT_DECONV_CIN or cin % KEYPOINT_DECONV_CIN or cin > 4096:
+        raise NotImplementedError("the keypoint head's transposed convolution takes input channels in multiples of {} (up to 4096), got {} "
+                                  "(MODEL.ROI_KEYPOINT_HEAD.CONV_DIMS)".format(KEYPOINT_DECONV_CIN, cin))
+    if not 1 <= k <= KEYPOINT_DECONV_MAX_K:
+        raise NotImplementedError("the keypoint head's transposed convolution takes 1 to {} keypoints, got {} "
+                                  "(MODEL.ROI_KEYPOINT_HEAD.NUM_KEYPOINTS)".format(KEYPOINT_DECONV_MAX_K, k))
+
+
+def pack_keypoint_deconv(weight):
+    """ConvTranspose2d weight [Cin, K, 4, 4] (kernel 4, stride 2, padding 1) -> the operand of `keypoint_deconv`:
+    [4 parities][4 taps][K rounded up to 32][Cin] as rows of Cin floats (csrc/keypoint.hip)."""
+    _req_cuda(weight)
+    cin, k = weight.shape[0], weight.shape[1]
+    keypoint_deconv_check(cin, k)
+    assert tuple(weight.shape[2:]) == (4, 4), weight.shape
+    w = weight.detach().contiguous().float()
+    rows = _lib.lib().lvc_keypoint_deconv_packed_rows(c_int(k))
+    packed = torch.empty(rows, cin, device=w.device, dtype=torch.float32)
+    check(_lib.lib().lvc_keypoint_deconv_pack(ptr(w), ptr(packed), c_int(cin), c_int(k), _stream(w)), "lvc_keypoint_deconv_pack")
+    return packed
+
+
+def keypoint_deconv(x, packed, bias, num_keypoints, num_valid=None, out=None):
+    """ConvTranspose2d(Cin, K, 4, stride 2, padding 1) + bias (csrc/keypoint.hip).  x [M,S,S,Cin] NHWC; packed: `pack_keypoint_deconv`;
+    bias [K] or None; num_valid: device int32 [1], rows past it are neither read nor written.  Returns the planes [M,K,2S,2S]
+    (`out` when given)."""
+    _req_cuda(x, packed, bias, num_valid)
+    M, S, S_, cin = x.shape
+    k = int(num_keypoints)
+    keypoint_deconv_check(cin, k)
+    assert S == S_ and x.is_contiguous() and x.dtype == torch.float32
+    rows = _lib.lib().lvc_keypoint_deconv_packed_rows(c_int(k))
+    assert packed.shape == (rows, cin) and packed.is_contiguous() and packed.dtype == torch.float32
+    assert bias is None or (bias.numel() == k and bias.is_contiguous() and bias.dtype == torch.float32)
+    if num_valid is not None:
+        assert num_valid.dtype == torch.int32 and num_valid.numel() == 1
+    if out is None:
+        out = torch.empty(M, k, 2 * S, 2 * S, device=x.device, dtype=torch.float32)
+    assert out.shape == (M, k, 2 * S, 2 * S) and out.is_contiguous() and out.dtype == torch.float32
+    check(_lib.lib().lvc_keypoint_deconv(ptr(x), ptr(packed), ptr(bias), ptr(num_valid), ptr(out), c_int(M), c_int(S), c_int(cin),
+                                         c_int(k), _stream(x)), "lvc_keypoint_deconv")
+    return out
+
+
+def heatmaps_to_keypoints(maps, rois, up=1, num_valid=None, maps_out=None, out=None):
+    """heatmaps_to_keypoints of every (RoI, keypoint) in one launch (csrc/keypoint_decode.hip).  maps: planes [M,K,P,P]; rois [M,4];
+    up 1 or 2 (2: the bilinear x2 map is formed on chip first); maps_out: None, or [M,K,up*P,up*P] to receive the decoded map;
+    num_valid: device int32 [1], rows past it keep their bytes.  Among equal maxima the lowest flat index y*w + x wins.
+    Returns [M,K,4] = (x, y, logit, score) (`out` when given)."""
+    _req_cuda(maps, rois, num_valid, maps_out, out)
+    assert maps.dim() == 4 and maps.shape[2] == maps.shape[3] and maps.is_contiguous() and maps.dtype == torch.float32, maps.shape
+    M, k, P, _ = maps.shape
+    if up not in (1, 2):
+        raise NotImplementedError("heatmaps_to_keypoints: up = {} (1 or 2 are built)".format(up))
+    if up * P > KEYPOINT_MAX_SIDE:
+        raise NotImplementedError("heatmaps_to_keypoints: a heatmap of side {} (up to {} is built)".format(up * P, KEYPOINT_MAX_SIDE))
+    assert rois.shape == (M, 4) and rois.is_contiguous() and rois.dtype == torch.float32, rois.shape
+    if num_valid is not None:
+        assert num_valid.dtype == torch.int32 and num_valid.numel() == 1
+    if maps_out is not None:
+        assert maps_out.shape == (M, k, up * P, up * P) and maps_out.is_contiguous() and maps_out.dtype == torch.float32
+    if out is None:
+        out = torch.empty(M, k, 4, device=maps.device, dtype=torch.float32)
+    assert out.shape == (M, k, 4) and out.is_contiguous() and out.dtype == torch.float32
+    if M == 0 or k == 0:
+        return out
+    check(_lib.lib().lvc_heatmaps_to_keypoints(ptr(maps), ptr(rois), ptr(num_valid), ptr(maps_out), ptr(out), c_int(M), c_int(k), c_int(P),
+                                               c_int(up), _stream(maps)), "lvc_heatmaps_to_keypoints")
+    return out
+
+
 # --------------------------------------------------------------------------- Mask R-CNN training
-MASK_TABLE_FIELDS = 4     # int64 words per image of lvc_mask_targets' plane table (include/lvc_amd.h)
+MASK_TABLE_FIELDS = 4    # int64 words per image of lvc_mask_targets' plane table (include/lvc_amd.h)
 
 
 def mask_targets(boxes, matched, count, planes, mask_size, out=None):

@@ -311,27 +311,34 @@ class Linear(nn.Module):
 
 class ConvTranspose2d(nn.Module):
     """torch.nn.ConvTranspose2d-compatible parameters (`weight` [in, out, kh, kw], `bias`; the reference's `ConvTranspose2d` is
-    torch's, detectron2/layers/wrappers.py) for the one transposed convolution on the path: the mask head's 2x2 stride-2 upsampling,
-    which csrc/mask_deconv.hip runs fused with the predictor.  The module holds the parameters and their packed operand; it has no
-    stand-alone forward."""
+    torch's, detectron2/layers/wrappers.py) for the two transposed convolutions on the path: the mask head's 2x2 stride-2 upsampling,
+    which csrc/mask_deconv.hip runs fused with the predictor, and the keypoint head's 4x4 stride-2 padding-1 `score_lowres`
+    (csrc/keypoint.hip).  The module holds the parameters and their packed operand; it has no stand-alone forward."""
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, bias=True):
         super().__init__()
-        if (kernel_size, stride, padding) != (2, 2, 0):
+        if (kernel_size, stride, padding) not in ((2, 2, 0), (4, 2, 1)):
+            # (the text predates the keypoint head's (4, 2, 1), which is built too; callers match on it)
             raise NotImplementedError("only the mask head's ConvTranspose2d(kernel_size=2, stride=2, padding=0) is built")
         self.in_channels, self.out_channels = in_channels, out_channels
-        self.kernel_size, self.stride, self.padding = (2, 2), (2, 2), (0, 0)
-        self.weight = nn.Parameter(torch.empty(in_channels, out_channels, 2, 2))
+        self.kernel_size, self.stride, self.padding = (kernel_size,) * 2, (stride,) * 2, (padding,) * 2
+        self.weight = nn.Parameter(torch.empty(in_channels, out_channels, kernel_size, kernel_size))
         self.bias = nn.Parameter(torch.zeros(out_channels)) if bias else None
         nn.init.kaiming_uniform_(self.weight, a=5 ** 0.5)
         self._cache = _PackedCache()
 
     def packed(self):
-        """[4 * out, in], row (dy*2+dx)*out + co: the operand of lvc_mask_deconv_predict, rebuilt when the parameter changes."""
+        """The kernel's operand, rebuilt when the parameter changes.  2x2: [4 * out, in], row (dy*2+dx)*out + co
+        (lvc_mask_deconv_predict); 4x4: `kernels.pack_keypoint_deconv` (lvc_keypoint_deconv)."""
+        if self.kernel_size == (4, 4):
+            return self._cache.get([self.weight], lambda: K.pack_keypoint_deconv(self.weight))
         return self._cache.get([self.weight], lambda: K.pack_mask_deconv(self.weight))
 
     def forward(self, x):
+        if self.kernel_size == (4, 4):
+            raise NotImplementedError("ConvTranspose2d runs only inside the keypoint head (KRCNNConvDeconvUpsampleHead.forward_nhwc)")
         raise NotImplementedError("ConvTranspose2d runs only fused with the mask predictor (MaskRCNNConvUpsampleHead.forward_nhwc)")
 
     def extra_repr(self):
-        return "{}, {}, kernel_size=(2, 2), stride=(2, 2)".format(self.in_channels, self.out_channels)
+        return "{}, {}, kernel_size={}, stride={}{}".format(self.in_channels, self.out_channels, self.kernel_size, self.stride,
+                                                           "" if self.padding == (0, 0) else ", padding={}".format(self.padding))

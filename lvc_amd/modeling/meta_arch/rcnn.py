@@ -153,6 +153,10 @@ class GeneralizedRCNN(_RCNNBase):
             return self.inference(batched_inputs)
         if self._mask_on() and not self.__dict__.get("_mask_train_enabled", False):
             raise NotImplementedError("training the mask branch (MODEL.MASK_ON: mask_rcnn_loss, gt_masks) is not built")
+        if self._keypoint_on():
+            from ..roi_heads.keypoint_head import TRAIN_REFUSAL
+
+            raise NotImplementedError(TRAIN_REFUSAL)
 
         def once():
             self.__dict__["_range_checked"] = False
@@ -284,7 +288,7 @@ class GeneralizedRCNN(_RCNNBase):
         """Reference rcnn.py:177-322 (the GeneralizedRCNN + RPN + StandardROIHeads branch)."""
         assert not self.training
         if detected_instances is not None:
-            if not self._mask_on():
+            if not (self._mask_on() or self._keypoint_on()):
                 raise NotImplementedError("forward_with_given_boxes (mask/keypoint heads) is not on the box-only path")
             return self._inference_given_boxes(batched_inputs, detected_instances, do_postprocess)
         if getattr(self, "output_layer", None) == "BoxOnlyLayersCascade":
@@ -293,6 +297,8 @@ class GeneralizedRCNN(_RCNNBase):
             return self._inference_modular(batched_inputs, do_postprocess)
         if self._mask_on():
             return run_with_fallbacks(self, lambda: self._inference_masks(batched_inputs, do_postprocess))
+        if self._keypoint_on():
+            return run_with_fallbacks(self, lambda: self._inference_keypoints(batched_inputs, do_postprocess))
         return run_with_fallbacks(self, lambda: self._inference_fast(batched_inputs, do_postprocess))
 
     def _inference_fast(self, batched_inputs, do_postprocess):
@@ -312,6 +318,9 @@ class GeneralizedRCNN(_RCNNBase):
 
     def _mask_on(self):
         return bool(getattr(self.roi_heads, "mask_on", False))
+
+    def _keypoint_on(self):
+        return bool(getattr(self.roi_heads, "keypoint_on", False))
 
     def enable_mask_training(self, on=True):
         """Switch the training forward of a MODEL.MASK_ON model on (or off again); returns self.  Without the call a mask model in
@@ -429,6 +438,56 @@ class GeneralizedRCNN(_RCNNBase):
                 inst.pred_masks = prob[r0: r0 + n][:, None]
             out.append(inst)
         return [{"instances": r} for r in out] if do_postprocess else out
+
+    def _keypoints_device(self, batched_inputs, do_postprocess):
+        """The device part of a keypoint model's forward, nothing read back: trunk -> proposals -> box branch with post=None (raw
+        boxes) -> keypoint branch on the raw boxes -> (with do_postprocess) the detection gather with an identity keep list and `post`
+        (scaled, clipped, non-empty boxes; in `rows` the keypoint row each survivor owns) -> the survivors' keypoint rows gathered
+        through `rows`, x and y scaled as detector_postprocess scales them (reference postprocessing.py:75-77: two separate fp32
+        multiplies, no clipping).
+        -> (boxes [B,T,4], scores, classes int32, count [B], keypoints [B,T,K,3] = (x, y, score), status, out_sizes)."""
+        images = self.preprocess_image(batched_inputs)
+        sizes = images.image_sizes
+        N, _, Hp, Wp = images.tensor.shape
+        x4 = images.tensor.as_strided((N, Hp, Wp, 4), (Hp * Wp * 4, Wp * 4, 4, 1), images.tensor.storage_offset())
+        dev = self.device
+        sizes_dev = self._dev_const(sizes, torch.int32)
+        feats = self.backbone.forward_nhwc(x4)
+        pboxes, _plogits, pcount = self.proposal_generator.predict_proposals_batched(feats, sizes_dev)
+        status = K.new_status(dev)
+        heads = self.roi_heads
+        ob, osc, ocl, _orow, cnt = heads.forward_batched(feats, pboxes, pcount, sizes_dev, post=None, status=status)
+        kp, rows = heads.forward_keypoints_batched(feats, ob, cnt, status=status)
+        B, T = osc.shape
+        out_sizes = [tuple(s) for s in sizes]
+        scale = None
+        if do_postprocess:
+            post_rows, out_sizes = [], []
+            for inp, (h, w) in zip(batched_inputs, sizes):
+                dh, dw = (int(inp["raw"].shape[0]), int(inp["raw"].shape[1])) if "image" not in inp else (h, w)
+                oh, ow = inp.get("height", dh), inp.get("width", dw)
+                post_rows.append([ow / w, oh / h, float(oh), float(ow)])
+                out_sizes.append((int(oh), int(ow)))
+            keep = self.__dict__.get("_identity_keep")
+            if keep is None or keep.shape != (B, T) or keep.device != osc.device:
+                keep = self.__dict__["_identity_keep"] = torch.arange(T, dtype=torch.int32, device=dev).repeat(B, 1).contiguous()
+            post = self._dev_const(post_rows, torch.float32)
+            ob, osc, ocl, rows, cnt = K.gather_detections(ob, osc, ocl, rows, keep, cnt, T, post=post)
+            scale = post[:, None, None, :2]
+        own = kp.index_select(0, rows.reshape(-1).long().clamp_(0, kp.shape[0] - 1))
+        kps = torch.cat([own[:, :, :2], own[:, :, 3:4]], 2).view(B, T, kp.shape[1], 3)      # (x, y, score); no index tensor from the host
+        if scale is not None:
+            kps[..., :2] *= scale      # x *= scale_x, y *= scale_y
+        return ob, osc, ocl, cnt, kps, status, out_sizes
+
+    def _inference_keypoints(self, batched_inputs, do_postprocess):
+        """A keypoint model's inference: `_keypoints_device`, then ONE device->host read (counts, status, range summary); every image's
+        `pred_keypoints` [n, K, 3] = (x, y, score) is a view of the batch's device tensor."""
+        ob, osc, ocl, cnt, kps, status, out_sizes = self._keypoints_device(batched_inputs, do_postprocess)
+        insts = instances_from_batched(ob, osc, ocl, cnt, out_sizes, status)
+        for i, inst in enumerate(insts):
+            inst._fields["pred_keypoints"] = kps[i, : len(inst)]
+        return [{"instances": r} for r in insts] if do_postprocess else insts
 
     def _inference_box_corrector(self, batched_inputs):
         """reference rcnn.py:201-230: evaluation of the box corrector = IoU with the matched GT before and after the

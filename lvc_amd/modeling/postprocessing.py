@@ -40,4 +40,10 @@ def detector_postprocess(results, output_height, output_width, mask_threshold=0.
     if results.has("pred_masks"):
         results.pred_masks = paste_masks_in_image(results.pred_masks[:, 0, :, :], results.pred_boxes, results.image_size,
                                                   threshold=mask_threshold)
+    if results.has("pred_keypoints"):
+        # reference postprocessing.py:75-77: x and y scaled by two separate multiplies; keypoints are not clipped
+        kp = results.pred_keypoints.clone()
+        kp[:, :, 0] *= scale_x
+        kp[:, :, 1] *= scale_y
+        results.pred_keypoints = kp
     return results

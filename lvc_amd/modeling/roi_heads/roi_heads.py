@@ -20,12 +20,17 @@ from ..sampling import subsample_labels
 from ..poolers import ROIPooler
 from .box_head import build_box_head
 from .fast_rcnn import ROI_HEADS_OUTPUT_REGISTRY
+from .keypoint_head import TRAIN_REFUSAL as KEYPOINT_TRAIN_REFUSAL
+from .keypoint_head import build_keypoint_head, keypoint_rcnn_inference
 from .mask_head import build_mask_head, mask_rcnn_inference
 
 ROI_HEADS_REGISTRY = Registry("ROI_HEADS")
 
 
 def build_roi_heads(cfg, input_shape):
+    if cfg.MODEL.KEYPOINT_ON and cfg.MODEL.ROI_HEADS.NAME != "StandardROIHeads":
+        raise NotImplementedError("MODEL.KEYPOINT_ON with MODEL.ROI_HEADS.NAME = {!r}: the keypoint branch is built for StandardROIHeads"
+                                  .format(cfg.MODEL.ROI_HEADS.NAME))
     return ROI_HEADS_REGISTRY.get(cfg.MODEL.ROI_HEADS.NAME)(cfg, input_shape)
 
 
@@ -235,6 +240,7 @@ class StandardROIHeads(ROIHeads):
     # capacity of the per-image (roi, class) candidate list of fast_rcnn_inference; None = R*K.  16 384 keeps the
     # detection-stage NMS in its one-block form; `run_with_fallbacks` switches to None after the first overflow
     det_max_candidates = 16384
+    keypoint_on = False         # (a subclass that builds its own heads has no keypoint branch)
 
     def __init__(self, cfg, input_shape):
         super().__init__(cfg, input_shape)
@@ -242,6 +248,11 @@ class StandardROIHeads(ROIHeads):
         self.mask_on = bool(cfg.MODEL.MASK_ON)
         if self.mask_on:
             self._init_mask_head(cfg)
+        self.keypoint_on = bool(cfg.MODEL.KEYPOINT_ON)
+        if self.keypoint_on:
+            if self.mask_on:
+                raise NotImplementedError("MODEL.KEYPOINT_ON together with MODEL.MASK_ON: keypoints and masks in one model are not built")
+            self._init_keypoint_head(cfg)
         if cfg.DEBUG:
             raise NotImplementedError("cfg.DEBUG heads (FastRCNNOutputsDebug) are not part of the hot path")
         if cfg.MODEL.META_ARCHITECTURE == "GeneralizedRCNN_Context":
@@ -270,6 +281,17 @@ class StandardROIHeads(ROIHeads):
         self.mask_pooler = ROIPooler(output_size=res, scales=scales, sampling_ratio=MH.POOLER_SAMPLING_RATIO, pooler_type=MH.POOLER_TYPE)
         self.mask_head = build_mask_head(cfg, ShapeSpec(channels=in_channels, width=res, height=res))
 
+    def _init_keypoint_head(self, cfg):
+        """detectron2's StandardROIHeads._init_keypoint_head (roi_heads.py:624-647): `keypoint_pooler` + `keypoint_head` over
+        ROI_HEADS.IN_FEATURES, registered after the mask modules."""
+        KH = cfg.MODEL.ROI_KEYPOINT_HEAD
+        res = KH.POOLER_RESOLUTION
+        scales = tuple(1.0 / self.feature_strides[k] for k in self.in_features)
+        in_channels = [self.feature_channels[f] for f in self.in_features][0]
+        self.keypoint_in_features = self.in_features
+        self.keypoint_pooler = ROIPooler(output_size=res, scales=scales, sampling_ratio=KH.POOLER_SAMPLING_RATIO, pooler_type=KH.POOLER_TYPE)
+        self.keypoint_head = build_keypoint_head(cfg, ShapeSpec(channels=in_channels, width=res, height=res))
+
     def pool_masks_batched(self, feats_nhwc, boxes, classes, count, status=None):
         """The mask branch's input on padded batch tensors, nothing read back: the real rows of the [B, topk] table are moved to the
         front, image after image, the others become zero boxes, and all B*topk rows go through ROIAlign over the pyramid (the
@@ -283,12 +305,13 @@ class StandardROIHeads(ROIHeads):
                                       status=status)
         return pooled, cls, rows, total
 
-    def _mask_rows(self, boxes, classes, count, num_levels):
+    def _mask_rows(self, boxes, classes, count, num_levels, pooler=None):
         """-> (rois [B*T, 5], levels [B*T] int32 or None, classes [B*T], rows [B, T] int32, total [1] int32, order [B*T] int64): the rows
-        of the [B, T] table with the real ones (the first count[b] of image b) moved to the front, image after image."""
+        of the [B, T] table with the real ones (the first count[b] of image b) moved to the front, image after image.  pooler: the
+        pooler whose level rule assigns the rows (default: the mask pooler; the keypoint branch passes its own)."""
         B, T, _ = boxes.shape
         dev = boxes.device
-        pl = self.mask_pooler
+        pl = self.mask_pooler if pooler is None else pooler
         ar = torch.arange(T, device=dev, dtype=torch.int32)
         cnt = count.clamp(min=0, max=T)
         valid = ar[None, :] < cnt[:, None]
@@ -344,11 +367,48 @@ class StandardROIHeads(ROIHeads):
         prob = self.mask_head.forward_nhwc(pooled, cls, num_valid=total, status=status)
         return prob, rows
 
+    def forward_keypoints_batched(self, feats_nhwc, boxes, count, status=None):
+        """The keypoint branch on padded batch tensors, nothing read back.  feats_nhwc: dict name -> [B,H,W,C]; boxes [B,topk,4] in
+        network coordinates; count [B] int32 (rows [0, count_b) of image b are real).
+        Returns (keypoints [B*topk, K, 4] = (x, y, logit, score) in network coordinates, rows [B,topk] int32): the real rows are moved
+        to the front exactly as `pool_masks_batched` moves them (`_mask_rows`), so that ONE number -- their total -- is the `num_valid`
+        of `score_lowres` and the decode; `rows[b, i]` is the row box i of image b owns.  Rows past the total are zero (ROIAlign and
+        the convs run on all rows: zero boxes, zero maps)."""
+        if not self.keypoint_on:
+            raise RuntimeError("forward_keypoints_batched: the model was built with MODEL.KEYPOINT_ON = False")
+        pl = self.keypoint_pooler
+        feats = [feats_nhwc[f] for f in self.keypoint_in_features]
+        B, T, _ = boxes.shape
+        dummy = torch.zeros(B, T, dtype=torch.int32, device=boxes.device)
+        rois, levels, _cls, rows, total, _order = self._mask_rows(boxes, dummy, count, len(feats), pooler=pl)
+        pooled = K.roi_align_fpn_nhwc(feats, pl.scales, rois, levels, pl.output_size[0], pl.output_size[1], pl.sampling_ratio, pl.aligned,
+                                      status=status)
+        kp = self.keypoint_head.forward_nhwc(pooled, rois[:, 1:5].contiguous(), num_valid=total, status=status)
+        return kp, rows
+
+    def _keypoints_given_boxes(self, features, instances):
+        feats = {f: to_nhwc(features[f]) for f in self.keypoint_in_features}
+        dev = feats[self.keypoint_in_features[0]].device
+        require_device(feats[self.keypoint_in_features[0]], "StandardROIHeads")
+        counts = [len(p) for p in instances]
+        B, R = len(instances), max(max(counts), 1)
+        boxes = torch.zeros(B, R, 4, device=dev)
+        for i, p in enumerate(instances):
+            boxes[i, : counts[i]] = p.pred_boxes.tensor
+        status = K.new_status(dev)
+        kp, _rows = self.forward_keypoints_batched(feats, boxes, torch.tensor(counts, dtype=torch.int32, device=dev), status=status)
+        check_status(int(status.item()))
+        keypoint_rcnn_inference(kp, instances)
+        return instances
+
     def forward_with_given_boxes(self, features, instances):
         """Reference signature (detectron2 roi_heads.py:681-706): `instances` carry `pred_boxes` and `pred_classes` (network
-        coordinates) and get `pred_masks` [n, 1, 2S, 2S], the predicted class's mask probabilities."""
+        coordinates) and get `pred_masks` [n, 1, 2S, 2S], the predicted class's mask probabilities (a mask model), or
+        `pred_keypoints` [n, K, 3] = (x, y, score) in network coordinates (a keypoint model)."""
         assert not self.training
         assert instances[0].has("pred_boxes") and instances[0].has("pred_classes")
+        if self.keypoint_on:
+            return self._keypoints_given_boxes(features, instances)
         if not self.mask_on:
             return instances
         feats = {f: to_nhwc(features[f]) for f in self.mask_in_features}
@@ -386,6 +446,8 @@ class StandardROIHeads(ROIHeads):
         if self.training:
             if self.mask_on and not self.__dict__.get("_mask_train_enabled", False):
                 raise NotImplementedError("training the mask branch (MODEL.MASK_ON: mask_rcnn_loss, gt_masks) is not built")
+            if self.keypoint_on:
+                raise NotImplementedError(KEYPOINT_TRAIN_REFUSAL)
             return self._forward_train(features, proposals, targets)
         if self.rbg:
             # reference roi_heads.py:561-562: with an RBG proposal generator the evaluation pass labels and subsamples the given
@@ -403,12 +465,16 @@ class StandardROIHeads(ROIHeads):
         status = K.new_status(dev)
         ob, osc, ocl, orow, cnt = self.forward_batched(feats, boxes, torch.tensor(counts, dtype=torch.int32, device=dev),
                                                        sizes, status=status)
-        prob = rows = None
+        prob = rows = kp = None
         if self.mask_on:
             prob, rows = self.forward_masks_batched(feats, ob, ocl, cnt, status=status)
+        if self.keypoint_on:
+            kp, rows = self.forward_keypoints_batched(feats, ob, cnt, status=status)
         insts = instances_from_batched(ob, osc, ocl, cnt, [p.image_size for p in proposals], status)
         if prob is not None:
             mask_rcnn_inference(prob, insts)      # the real rows lie image after image at the front of prob
+        if kp is not None:
+            keypoint_rcnn_inference(kp, insts)
         return insts, {}
 
 

@@ -25,11 +25,20 @@ def instances_to_coco_json(instances, img_id):
     extra = instances.has("top2_scores")
     if extra:
         t2s, t2i = instances.top2_scores.tolist(), instances.top2_inds.tolist()
+    kpts = None
+    if instances.has("pred_keypoints"):
+        # reference detectron2 coco_evaluation.py instances_to_coco_json: COCO's keypoint coordinates are pixel indices, 0.5 below the
+        # continuous coordinates the model predicts; the third value is the keypoint's score (the reference writes it in place of
+        # COCO's visibility flag), [x, y, score] flattened over the keypoints
+        kpts = instances.pred_keypoints.detach().cpu().clone()
+        kpts[:, :, :2] -= 0.5
     out = []
     for k in range(n):
         row = {"image_id": img_id, "category_id": classes[k], "bbox": boxes[k], "score": scores[k]}
         if extra:
             row.update({"top2_scores": t2s[k], "top2_inds": t2i[k]})
+        if kpts is not None:
+            row["keypoints"] = kpts[k].flatten().tolist()
         out.append(row)
     return out
 
