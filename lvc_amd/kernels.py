@@ -1294,6 +1294,13 @@ def new_status(device):
     return torch.zeros(1, dtype=torch.int32, device=device)
 
 
+# the bits of the status word, as the kernels set them (roi_heads.check_status raises for each)
+ROI_NEGATIVE_SIZE = 1     # ROIAlign: a RoI of negative width or height
+DET_OVERFLOW = 2          # lvc_fast_rcnn_inference: more (roi, class) candidates in one image than the candidate list holds
+RETINA_OVERFLOW = 4       # lvc_retinanet_select: more entries on one (image, level) than the survivor list holds
+MASK_BAD_CLASS = 8        # lvc_mask_deconv_predict / _logits / _grad: a class index outside [0, K)
+
+
 def roi_align_forward(input, rois, spatial_scale, pooled_h, pooled_w, sampling_ratio, aligned, status=None):
     """Reference-shaped op (csrc/vision.cpp:96): NCHW input, rois [K,5], returns [K,C,ph,pw]."""
     _req_cuda(input, rois)
@@ -3397,7 +3404,6 @@ def upsample2_residual_grad(g, res_shape):
 
 
 # --------------------------------------------------------------------------- Mask R-CNN inference
-MASK_BAD_CLASS = 8        # the status bit lvc_mask_deconv_predict raises for a class index outside [0, K)
 MASK_DECONV_CHANNELS = (64, 128, 192, 256)
 PASTE_FIELDS = 8          # int64 words per job of lvc_paste_masks (include/lvc_amd.h)
 

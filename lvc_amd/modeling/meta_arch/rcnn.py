@@ -90,6 +90,27 @@ class _RCNNBase(nn.Module):
                 K.preprocess_into(im, buf[i], *self._mean_std())
         return ImageList(buf.permute(0, 3, 1, 2)[:, :3], sizes)
 
+    def preprocess_nhwc(self, batched_inputs):
+        """`preprocess_image` as the device path takes it -> (x4 [N,Hp,Wp,4] fp32: the normalised, zero-padded batch in its storage
+        layout, of which the ImageList's `.tensor` is the NCHW-shaped view; sizes: the N image sizes the network sees)."""
+        images = self.preprocess_image(batched_inputs)
+        N, _, Hp, Wp = images.tensor.shape
+        x4 = images.tensor.as_strided((N, Hp, Wp, 4), (Hp * Wp * 4, Wp * 4, 4, 1), images.tensor.storage_offset())
+        return x4, images.image_sizes
+
+    @staticmethod
+    def post_rows(batched_inputs, sizes):
+        """detector_postprocess's size rule, once -> (post_rows: per image [out_w / w, out_h / h, out_h, out_w], out_sizes: per image
+        (out_h, out_w)).  sizes: what the network saw (`preprocess_nhwc`).  Results default to that size; for raw file pixels, which the
+        network saw at the ResizeShortestEdge size, to the file's size."""
+        post_rows, out_sizes = [], []
+        for inp, (h, w) in zip(batched_inputs, sizes):
+            dh, dw = (int(inp["raw"].shape[0]), int(inp["raw"].shape[1])) if "image" not in inp else (h, w)
+            oh, ow = inp.get("height", dh), inp.get("width", dw)   # DatasetMapper: height/width = the file's size
+            post_rows.append([ow / w, oh / h, float(oh), float(ow)])
+            out_sizes.append((oh, ow))
+        return post_rows, out_sizes
+
     def _preprocess_raw(self, batched_inputs):
         """Inputs that still carry the decoded file: {"raw": uint8 [H,W,3] in INPUT.FORMAT channel order, ...}.  The
         test-time ResizeShortestEdge of the reference's DatasetMapper (data/dataset_mapper.py:148-158 ->
@@ -255,18 +276,8 @@ class GeneralizedRCNN(_RCNNBase):
         (boxes [B,topk,4], scores [B,topk], classes [B,topk] int32, count [B] int32, status [1] int32).
         status: an existing status word to OR this pass's conditions into (a new one when None)."""
         assert isinstance(self.proposal_generator, RPN) and isinstance(self.roi_heads, StandardROIHeads)
-        images = self.preprocess_image(batched_inputs)
-        sizes = images.image_sizes
-        N, _, Hp, Wp = images.tensor.shape
-        x4 = images.tensor.as_strided((N, Hp, Wp, 4), (Hp * Wp * 4, Wp * 4, 4, 1), images.tensor.storage_offset())
-        post_rows = None
-        if do_postprocess:
-            post_rows = []
-            for inp, (h, w) in zip(batched_inputs, sizes):
-                dh, dw = (int(inp["raw"].shape[0]), int(inp["raw"].shape[1])) if "image" not in inp else (h, w)
-                oh, ow = inp.get("height", dh), inp.get("width", dw)   # DatasetMapper: height/width = the file's size
-                post_rows.append([ow / w, oh / h, float(oh), float(ow)])
-        return self.inference_nhwc(x4, sizes, post_rows, status)
+        x4, sizes = self.preprocess_nhwc(batched_inputs)
+        return self.inference_nhwc(x4, sizes, self.post_rows(batched_inputs, sizes)[0] if do_postprocess else None, status)
 
     def inference_nhwc(self, x4, sizes, post_rows=None, status=None):
         """`inference_batched` after `preprocess_image`: x4 [N,Hp,Wp,4] fp32 the normalised, zero-padded batch (what
@@ -302,17 +313,9 @@ class GeneralizedRCNN(_RCNNBase):
         return run_with_fallbacks(self, lambda: self._inference_fast(batched_inputs, do_postprocess))
 
     def _inference_fast(self, batched_inputs, do_postprocess):
-        ob, osc, ocl, cnt, status = self.inference_batched(batched_inputs, do_postprocess)
-        out_sizes = []
-        for inp in batched_inputs:
-            if "image" in inp:
-                h, w = int(inp["image"].shape[-2]), int(inp["image"].shape[-1])
-                dh, dw = h, w
-            else:   # raw file pixels: the network saw the ResizeShortestEdge size, results default to the file's size
-                dh, dw = int(inp["raw"].shape[0]), int(inp["raw"].shape[1])
-                t = self._test_resize.get_transform(inp["raw"])
-                h, w = (t.new_h, t.new_w) if t is not None else (dh, dw)
-            out_sizes.append((inp.get("height", dh), inp.get("width", dw)) if do_postprocess else (h, w))
+        x4, sizes = self.preprocess_nhwc(batched_inputs)
+        post_rows, out_sizes = self.post_rows(batched_inputs, sizes) if do_postprocess else (None, sizes)
+        ob, osc, ocl, cnt, status = self.inference_nhwc(x4, sizes, post_rows)
         insts = instances_from_batched(ob, osc, ocl, cnt, out_sizes, status)
         return [{"instances": r} for r in insts] if do_postprocess else insts
 
@@ -359,15 +362,13 @@ class GeneralizedRCNN(_RCNNBase):
 
     mask_threshold = 0.5      # detector_postprocess's default, the reference's only value on this path
 
-    def _masks_device(self, batched_inputs, do_postprocess):
-        """The device part of a mask model's forward, nothing read back: trunk -> proposals -> box branch with post=None (raw boxes)
-        -> mask branch on the raw boxes -> (with do_postprocess) the detection gather with an identity keep list and `post`: scaled,
-        clipped, non-empty boxes, and in `rows` the row of `prob` each survivor owns.
-        -> (boxes [B,T,4], scores, classes int32, rows int32 [B,T], count [B], prob [B*T,2S,2S], status, out_sizes)."""
-        images = self.preprocess_image(batched_inputs)
-        sizes = images.image_sizes
-        N, _, Hp, Wp = images.tensor.shape
-        x4 = images.tensor.as_strided((N, Hp, Wp, 4), (Hp * Wp * 4, Wp * 4, 4, 1), images.tensor.storage_offset())
+    def _branch_device(self, batched_inputs, do_postprocess, branch):
+        """The device part of the forward of a model with a branch beside the box branch, nothing read back: trunk -> proposals -> box
+        branch with post=None (raw boxes) -> `branch(heads, feats, boxes, classes, count, status)` on the raw boxes, which returns (out,
+        rows) -> (with do_postprocess) the detection gather with an identity keep list and `post`: scaled, clipped, non-empty boxes,
+        and in `rows` the row of `out` each survivor owns.
+        -> (boxes [B,T,4], scores, classes int32, rows int32 [B,T], count [B], out, status, out_sizes, post [B,4] or None)."""
+        x4, sizes = self.preprocess_nhwc(batched_inputs)
         dev = self.device
         sizes_dev = self._dev_const(sizes, torch.int32)
         feats = self.backbone.forward_nhwc(x4)
@@ -375,21 +376,24 @@ class GeneralizedRCNN(_RCNNBase):
         status = K.new_status(dev)
         heads = self.roi_heads
         ob, osc, ocl, _orow, cnt = heads.forward_batched(feats, pboxes, pcount, sizes_dev, post=None, status=status)
-        prob, rows = heads.forward_masks_batched(feats, ob, ocl, cnt, status=status)
-        out_sizes = [tuple(s) for s in sizes]
+        out, rows = branch(heads, feats, ob, ocl, cnt, status)
+        out_sizes, post = [tuple(s) for s in sizes], None
         if do_postprocess:
-            post_rows, out_sizes = [], []
-            for inp, (h, w) in zip(batched_inputs, sizes):
-                dh, dw = (int(inp["raw"].shape[0]), int(inp["raw"].shape[1])) if "image" not in inp else (h, w)
-                oh, ow = inp.get("height", dh), inp.get("width", dw)
-                post_rows.append([ow / w, oh / h, float(oh), float(ow)])
-                out_sizes.append((int(oh), int(ow)))
+            post_rows, out_sizes = self.post_rows(batched_inputs, sizes)
+            out_sizes = [(int(oh), int(ow)) for oh, ow in out_sizes]
             B, T = osc.shape
             keep = self.__dict__.get("_identity_keep")
             if keep is None or keep.shape != (B, T) or keep.device != osc.device:
                 keep = self.__dict__["_identity_keep"] = torch.arange(T, dtype=torch.int32, device=dev).repeat(B, 1).contiguous()
-            ob, osc, ocl, rows, cnt = K.gather_detections(ob, osc, ocl, rows, keep, cnt, T, post=self._dev_const(post_rows, torch.float32))
-        return ob, osc, ocl, rows, cnt, prob, status, out_sizes
+            post = self._dev_const(post_rows, torch.float32)
+            ob, osc, ocl, rows, cnt = K.gather_detections(ob, osc, ocl, rows, keep, cnt, T, post=post)
+        return ob, osc, ocl, rows, cnt, out, status, out_sizes, post
+
+    def _masks_device(self, batched_inputs, do_postprocess):
+        """The device part of a mask model's forward (`_branch_device` with the mask branch): in `rows` the row of `prob` each survivor
+        owns.  -> (boxes [B,T,4], scores, classes int32, rows int32 [B,T], count [B], prob [B*T,2S,2S], status, out_sizes)."""
+        return self._branch_device(batched_inputs, do_postprocess, lambda heads, feats, boxes, classes, count, status:
+                                   heads.forward_masks_batched(feats, boxes, classes, count, status=status))[:8]
 
     def _inference_masks(self, batched_inputs, do_postprocess):
         """A mask model's inference: `_masks_device`, then ONE device->host read (counts, status, range summary, and the survivors'
@@ -446,38 +450,14 @@ class GeneralizedRCNN(_RCNNBase):
         through `rows`, x and y scaled as detector_postprocess scales them (reference postprocessing.py:75-77: two separate fp32
         multiplies, no clipping).
         -> (boxes [B,T,4], scores, classes int32, count [B], keypoints [B,T,K,3] = (x, y, score), status, out_sizes)."""
-        images = self.preprocess_image(batched_inputs)
-        sizes = images.image_sizes
-        N, _, Hp, Wp = images.tensor.shape
-        x4 = images.tensor.as_strided((N, Hp, Wp, 4), (Hp * Wp * 4, Wp * 4, 4, 1), images.tensor.storage_offset())
-        dev = self.device
-        sizes_dev = self._dev_const(sizes, torch.int32)
-        feats = self.backbone.forward_nhwc(x4)
-        pboxes, _plogits, pcount = self.proposal_generator.predict_proposals_batched(feats, sizes_dev)
-        status = K.new_status(dev)
-        heads = self.roi_heads
-        ob, osc, ocl, _orow, cnt = heads.forward_batched(feats, pboxes, pcount, sizes_dev, post=None, status=status)
-        kp, rows = heads.forward_keypoints_batched(feats, ob, cnt, status=status)
+        ob, osc, ocl, rows, cnt, kp, status, out_sizes, post = self._branch_device(
+            batched_inputs, do_postprocess, lambda heads, feats, boxes, _classes, count, status:
+            heads.forward_keypoints_batched(feats, boxes, count, status=status))
         B, T = osc.shape
-        out_sizes = [tuple(s) for s in sizes]
-        scale = None
-        if do_postprocess:
-            post_rows, out_sizes = [], []
-            for inp, (h, w) in zip(batched_inputs, sizes):
-                dh, dw = (int(inp["raw"].shape[0]), int(inp["raw"].shape[1])) if "image" not in inp else (h, w)
-                oh, ow = inp.get("height", dh), inp.get("width", dw)
-                post_rows.append([ow / w, oh / h, float(oh), float(ow)])
-                out_sizes.append((int(oh), int(ow)))
-            keep = self.__dict__.get("_identity_keep")
-            if keep is None or keep.shape != (B, T) or keep.device != osc.device:
-                keep = self.__dict__["_identity_keep"] = torch.arange(T, dtype=torch.int32, device=dev).repeat(B, 1).contiguous()
-            post = self._dev_const(post_rows, torch.float32)
-            ob, osc, ocl, rows, cnt = K.gather_detections(ob, osc, ocl, rows, keep, cnt, T, post=post)
-            scale = post[:, None, None, :2]
         own = kp.index_select(0, rows.reshape(-1).long().clamp_(0, kp.shape[0] - 1))
         kps = torch.cat([own[:, :, :2], own[:, :, 3:4]], 2).view(B, T, kp.shape[1], 3)      # (x, y, score); no index tensor from the host
-        if scale is not None:
-            kps[..., :2] *= scale      # x *= scale_x, y *= scale_y
+        if post is not None:
+            kps[..., :2] *= post[:, None, None, :2]      # x *= scale_x, y *= scale_y
         return ob, osc, ocl, cnt, kps, status, out_sizes
 
     def _inference_keypoints(self, batched_inputs, do_postprocess):

@@ -400,10 +400,7 @@ class RetinaNet(_RCNNBase):
         """Whole forward with device-resident, fixed-shape outputs and no host sync, in the form of GeneralizedRCNN.inference_batched:
         (boxes [B,D,4], scores [B,D], classes [B,D] int32, count [B] int32, status [1] int32), D = TEST.DETECTIONS_PER_IMAGE."""
         with torch.no_grad():
-            images = self.preprocess_image(batched_inputs)
-            sizes = images.image_sizes
-            N, _, Hp, Wp = images.tensor.shape
-            x4 = images.tensor.as_strided((N, Hp, Wp, 4), (Hp * Wp * 4, Wp * 4, 4, 1), images.tensor.storage_offset())
+            x4, sizes = self.preprocess_nhwc(batched_inputs)
             post = None
             if do_postprocess:
                 outs = self._out_sizes(batched_inputs, sizes)

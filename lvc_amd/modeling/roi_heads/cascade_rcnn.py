@@ -25,7 +25,7 @@ from ..matcher import Matcher
 from ..poolers import ROIPooler
 from .box_head import build_box_head
 from .fast_rcnn import ROI_HEADS_OUTPUT_REGISTRY
-from .roi_heads import ROI_HEADS_REGISTRY, ROIHeads
+from .roi_heads import ROI_HEADS_REGISTRY, ROIHeads, padded_boxes
 
 
 class _ScaleGradient(torch.autograd.Function):
@@ -110,11 +110,7 @@ class CascadeROIHeads(ROIHeads):
         followed by the argsort of the kept row indices produces.  Returns (results, filtered stage-0 proposals)."""
         feats = {f: to_nhwc(features[f]) for f in self.box_in_features}
         dev = feats[self.box_in_features[0]].device
-        counts = [len(p) for p in proposals]
-        B, R = len(proposals), max(max(counts), 1)
-        boxes = torch.zeros(B, R, 4, device=dev)
-        for i, p in enumerate(proposals):
-            boxes[i, : counts[i]] = p.proposal_boxes.tensor
+        boxes, counts = padded_boxes(proposals, "proposal_boxes", dev)
         sizes = torch.tensor([list(p.image_size) for p in proposals], dtype=torch.int32, device=dev)
         out = self.refine_boxes_batched(feats, boxes, sizes)
         results, kept = [], []
@@ -133,12 +129,9 @@ class CascadeROIHeads(ROIHeads):
         target whose class is a foreground class, in input order, score 1, class = the given class."""
         feats = {f: to_nhwc(features[f]) for f in self.box_in_features}
         dev = feats[self.box_in_features[0]].device
-        counts = [len(t) for t in targets]
-        B, R = len(targets), max(max(counts), 1)
-        boxes = torch.zeros(B, R, 4, device=dev)
-        for i, t in enumerate(targets):
+        for t in targets:
             t.set("proposal_boxes", t.gt_boxes)
-            boxes[i, : counts[i]] = t.gt_boxes.tensor
+        boxes, counts = padded_boxes(targets, "gt_boxes", dev)
         sizes = torch.tensor([list(t.image_size) for t in targets], dtype=torch.int32, device=dev)
         out = self.refine_boxes_batched(feats, boxes, sizes)
         results = []
@@ -240,12 +233,9 @@ class CascadeROIHeads(ROIHeads):
         """reference :329-346.  `_ScaleGradient` (:22-30) scales the gradient flowing from the head back into the
         pooled features by 1/num_stages; with a frozen trunk that gradient is never formed and the pooled rows enter
         the head as constants."""
-        counts = [len(p) for p in proposals]
-        B, R = len(proposals), max(max(counts), 1)
         dev = feats_nhwc[0].device
-        boxes = torch.zeros(B, R, 4, device=dev)
-        for i, p in enumerate(proposals):
-            boxes[i, : counts[i]] = p.proposal_boxes.tensor
+        boxes, counts = padded_boxes(proposals, "proposal_boxes", dev)
+        R = boxes.shape[1]
         pooled = self.box_pooler.pool_nhwc(feats_nhwc, boxes)
         keep = torch.cat([torch.arange(c, device=dev) + i * R for i, c in enumerate(counts)])
         pooled = pooled[keep].contiguous()

@@ -34,6 +34,56 @@ def build_roi_heads(cfg, input_shape):
     return ROI_HEADS_REGISTRY.get(cfg.MODEL.ROI_HEADS.NAME)(cfg, input_shape)
 
 
+def padded_boxes(instances, field, device):
+    """The Boxes `field` of every Instances in one zero-padded table on `device` -> (boxes [B, R, 4] with R the largest count (at
+    least 1), counts: the B lengths)."""
+    counts = [len(p) for p in instances]
+    boxes = torch.zeros(len(instances), max(max(counts), 1), 4, device=device)
+    for i, p in enumerate(instances):
+        boxes[i, : counts[i]] = p.get(field).tensor
+    return boxes, counts
+
+
+def front_rows(boxes, count, pooler, num_levels):
+    """The rows of a padded [B, T] box table with the real ones (the first count[b] of image b) moved to the front, image after image,
+    for a branch that runs on ONE number of valid rows -> (rois [B*T, 5], levels [B*T] int32 (None with one level), rows [B, T] int32:
+    the row box i of image b owns, total [1] int32: the number of real rows, order [B*T] int64: the permutation, for whatever else the
+    caller keeps per row).  pooler: the branch's pooler, whose level rule assigns the rows.  Nothing is read back."""
+    B, T, _ = boxes.shape
+    ar = torch.arange(T, device=boxes.device, dtype=torch.int32)
+    cnt = count.clamp(min=0, max=T)
+    valid = ar[None, :] < cnt[:, None]
+    start = torch.cumsum(cnt, 0, dtype=torch.int32) - cnt
+    rows = (start[:, None] + ar[None, :]).contiguous()
+    total = cnt.sum(dtype=torch.int32).view(1)
+    # stable: the real rows first, in (image, index) order -- row start_b + i is box i of image b
+    order = torch.argsort((~valid).view(-1).to(torch.uint8), stable=True)
+    # rows past an image's count hold whatever the box branch left there: zero boxes instead (empty sampling grids)
+    boxes = torch.where(valid[:, :, None], boxes, torch.zeros_like(boxes))
+    levels, rois = K.assign_levels_rois(boxes, pooler.min_level, pooler.max_level, pooler.canonical_box_size, pooler.canonical_level)
+    rois = rois.index_select(0, order)
+    levels = None if num_levels == 1 else levels.index_select(0, order)
+    return rois, levels, rows, total, order
+
+
+def _log_sample_counts(counts):
+    """The two roi_head/num_*_samples scalars of label_and_sample_proposals from per-image (fg, bg) host counts."""
+    storage = get_event_storage()
+    n = max(1, len(counts))
+    storage.put_scalar("roi_head/num_fg_samples", sum(c[0] for c in counts) / n)
+    storage.put_scalar("roi_head/num_bg_samples", sum(c[1] for c in counts) / n)
+
+
+def _log_box_accuracy(stats, nrows):
+    """The three fast_rcnn/* scalars (reference fast_rcnn.py _log_accuracy) from the four host counts of `_box_stats`."""
+    nfg, ncorrect, nfg_correct, nfg_bg = stats
+    storage = get_event_storage()
+    storage.put_scalar("fast_rcnn/cls_accuracy", float(ncorrect) / max(1, nrows))
+    if nfg > 0:
+        storage.put_scalar("fast_rcnn/fg_cls_accuracy", float(nfg_correct) / nfg)
+        storage.put_scalar("fast_rcnn/false_negative", float(nfg_bg) / nfg)
+
+
 class ROIHeads(nn.Module):
     def __init__(self, cfg, input_shape):
         super().__init__()
@@ -114,30 +164,14 @@ class ROIHeads(nn.Module):
             # the proposals as RPN.forward made them -- one padded [B,P] table on the device -- and the concatenated ground truth: table
             # + Matcher + subsample_labels + gather for the whole batch in five launches (csrc/train_targets.hip), ONE device->host read
             pboxes, plogits, pcount, pcounts_host, gt, gt_off = batch
-            s_boxes, s_logits, s_cls, s_m, s_gtb, cnt = _sample_batched(self, pboxes, plogits, pcount, gt, gt_off, targets)
+            s_boxes, s_logits, s_cls, s_m, s_gtb, cnt = self._sample_batched(pboxes, plogits, pcount, gt, gt_off, targets)
             counts = cnt.tolist()      # the one device->host read
-            out = []
-            for i, (prop, tgt) in enumerate(zip(proposals, targets)):
-                c = counts[i][0] + counts[i][1]
-                inst = Instances(prop.image_size)
-                inst.proposal_boxes = Boxes(s_boxes[i, :c])
-                inst.objectness_logits = s_logits[i, :c]
-                inst.gt_classes = s_cls[i, :c]
-                inst.gt_boxes = Boxes(s_gtb[i, :c])
-                st = None
-                for name, val in tgt.get_fields().items():
-                    if name.startswith("gt_") and not inst.has(name) and not self._keeps_index(val):
-                        st = s_m[i, :c] if st is None else st
-                        inst.set(name, val[st])
-                inst._lvc_matched = s_m[i, :c]
-                out.append(inst)
+            out = self._sampled_instances(proposals, targets, counts, s_boxes, s_logits, s_cls, s_m, s_gtb)
             # for _forward_train: the same rows as padded batch tensors (a python attribute, not a field); the matched gt index and the
             # device counts for the mask branch
             out[0]._lvc_sampled = (s_boxes, s_cls, s_gtb, [c[0] + c[1] for c in counts], s_m, cnt)
             if log:
-                storage = get_event_storage()
-                storage.put_scalar("roi_head/num_fg_samples", sum(c[0] for c in counts) / B)
-                storage.put_scalar("roi_head/num_bg_samples", sum(c[1] for c in counts) / B)
+                _log_sample_counts(counts)
             return out
         ns = [len(p) + len(t) for p, t in zip(proposals, targets)]
         W = max(max(ns), bs)
@@ -170,6 +204,13 @@ class ROIHeads(nn.Module):
         s_cls = torch.gather(labels, 1, sampled)
         s_m = torch.gather(midx, 1, sampled)
         counts = torch.stack([npos, nneg], 1).tolist()      # the one device->host read
+        if log:
+            _log_sample_counts(counts)
+        return self._sampled_instances(proposals, targets, counts, s_boxes, s_logits, s_cls, s_m)
+
+    def _sampled_instances(self, proposals, targets, counts, s_boxes, s_logits, s_cls, s_m, s_gtb=None):
+        """Per-image Instances from the sampled rows of the padded [B, bs] tables: the first fg + bg of image i (counts[i]), with the
+        image's other gt_* fields gathered through the matched index s_m (gt_boxes too where the sampler did not hand them over)."""
         out = []
         for i, (prop, tgt) in enumerate(zip(proposals, targets)):
             c = counts[i][0] + counts[i][1]
@@ -177,17 +218,35 @@ class ROIHeads(nn.Module):
             inst.proposal_boxes = Boxes(s_boxes[i, :c])
             inst.objectness_logits = s_logits[i, :c]
             inst.gt_classes = s_cls[i, :c]
+            if s_gtb is not None:
+                inst.gt_boxes = Boxes(s_gtb[i, :c])
             st = s_m[i, :c]
             for name, val in tgt.get_fields().items():
                 if name.startswith("gt_") and not inst.has(name) and not self._keeps_index(val):
                     inst.set(name, val[st])
             inst._lvc_matched = st
             out.append(inst)
-        if log:
-            storage = get_event_storage()
-            storage.put_scalar("roi_head/num_fg_samples", sum(c[0] for c in counts) / B)
-            storage.put_scalar("roi_head/num_bg_samples", sum(c[1] for c in counts) / B)
         return out
+
+    def _sample_batched(self, pboxes, plogits, pcount, gt, gt_off, targets):
+        """Table + Matcher + subsample_labels + gather for the whole batch (csrc/train_targets.hip), nothing read back:
+        -> (boxes [B,bs,4], logits [B,bs], classes int64 [B,bs], matched gt index int64 [B,bs], matched gt boxes [B,bs,4], counts int32 [B,2])."""
+        import math
+
+        B, dev = pboxes.shape[0], pboxes.device
+        K_, bs = self.num_classes, self.batch_size_per_image
+        gt_logit = math.log((1.0 - 1e-10) / (1 - (1.0 - 1e-10)))
+        Wt = pboxes.shape[1] + max(len(t) for t in targets)
+        with torch.no_grad():
+            tb, tl, nrow = K.roi_build_table(pboxes, plogits, pcount, gt, gt_off, gt_logit, Wt)
+            m, lab = K.match_boxes_batched(gt, gt_off, B, tb, nrow, self.proposal_matcher.user_thresholds, self.proposal_matcher.labels,
+                                           self.proposal_matcher.allow_low_quality_matches)
+            key, seed = K.sampling_keys(B, Wt, dev)
+            sel, cnt = K.subsample_batched(lab, key, int(bs * self.positive_sample_fraction), bs, seed=seed)
+            gcls = torch.cat([t.gt_classes for t in targets]).to(torch.int64)
+            s_boxes, s_logits, s_cls, s_m = K.roi_gather_sampled(tb, tl, m, sel, cnt, gcls, gt_off, K_)
+            s_gtb = gt[(gt_off[:-1].long()[:, None] + s_m).clamp(max=max(gt.shape[0] - 1, 0)).view(-1)].view(B, bs, 4)
+        return s_boxes, s_logits, s_cls, s_m, s_gtb, cnt
 
     def _label_and_sample_loop(self, proposals, targets, inference=False, log=None):
         out, num_fg, num_bg = [], [], []
@@ -229,9 +288,7 @@ class ROIHeads(nn.Module):
             num_fg.append(gt_classes.numel() - num_bg[-1])
             out.append(inst)
         if (not inference) if log is None else log:
-            storage = get_event_storage()
-            storage.put_scalar("roi_head/num_fg_samples", sum(num_fg) / max(1, len(num_fg)))
-            storage.put_scalar("roi_head/num_bg_samples", sum(num_bg) / max(1, len(num_bg)))
+            _log_sample_counts(list(zip(num_fg, num_bg)))
         return out
 
 
@@ -244,15 +301,16 @@ class StandardROIHeads(ROIHeads):
 
     def __init__(self, cfg, input_shape):
         super().__init__(cfg, input_shape)
-        self._init_box_head(cfg)
+        self._init_branch(cfg, cfg.MODEL.ROI_BOX_HEAD, "box", build_box_head)
+        self.box_predictor = ROI_HEADS_OUTPUT_REGISTRY.get(cfg.MODEL.ROI_HEADS.OUTPUT_LAYER)(cfg, self.box_head.output_size)
         self.mask_on = bool(cfg.MODEL.MASK_ON)
         if self.mask_on:
-            self._init_mask_head(cfg)
+            self._init_branch(cfg, cfg.MODEL.ROI_MASK_HEAD, "mask", build_mask_head)
         self.keypoint_on = bool(cfg.MODEL.KEYPOINT_ON)
         if self.keypoint_on:
             if self.mask_on:
                 raise NotImplementedError("MODEL.KEYPOINT_ON together with MODEL.MASK_ON: keypoints and masks in one model are not built")
-            self._init_keypoint_head(cfg)
+            self._init_branch(cfg, cfg.MODEL.ROI_KEYPOINT_HEAD, "keypoint", build_keypoint_head)
         if cfg.DEBUG:
             raise NotImplementedError("cfg.DEBUG heads (FastRCNNOutputsDebug) are not part of the hot path")
         if cfg.MODEL.META_ARCHITECTURE == "GeneralizedRCNN_Context":
@@ -260,73 +318,35 @@ class StandardROIHeads(ROIHeads):
         self.rbg = cfg.MODEL.PROPOSAL_GENERATOR.NAME == "RBG"
         self.reg_off = cfg.MODEL.ROI_HEADS.REG_OFF
 
-    def _init_box_head(self, cfg):
-        BH = cfg.MODEL.ROI_BOX_HEAD
-        res = BH.POOLER_RESOLUTION
+    def _init_branch(self, cfg, node, name, build_head):
+        """`<name>_pooler` + `<name>_head` over ROI_HEADS.IN_FEATURES (`<name>_in_features`) from the branch's config node, registered
+        in that order: detectron2's StandardROIHeads._init_box_head / _init_mask_head / _init_keypoint_head (roi_heads.py:560-647)."""
+        res = node.POOLER_RESOLUTION
         scales = tuple(1.0 / self.feature_strides[k] for k in self.in_features)
         in_channels = [self.feature_channels[f] for f in self.in_features]
         assert len(set(in_channels)) == 1, in_channels
-        self.box_pooler = ROIPooler(output_size=res, scales=scales, sampling_ratio=BH.POOLER_SAMPLING_RATIO,
-                                    pooler_type=BH.POOLER_TYPE)
-        self.box_head = build_box_head(cfg, ShapeSpec(channels=in_channels[0], height=res, width=res))
-        self.box_predictor = ROI_HEADS_OUTPUT_REGISTRY.get(cfg.MODEL.ROI_HEADS.OUTPUT_LAYER)(cfg, self.box_head.output_size)
+        setattr(self, name + "_in_features", self.in_features)
+        setattr(self, name + "_pooler", ROIPooler(output_size=res, scales=scales, sampling_ratio=node.POOLER_SAMPLING_RATIO,
+                                                  pooler_type=node.POOLER_TYPE))
+        setattr(self, name + "_head", build_head(cfg, ShapeSpec(channels=in_channels[0], height=res, width=res)))
 
-    def _init_mask_head(self, cfg):
-        """detectron2's StandardROIHeads._init_mask_head (roi_heads.py:599-622): `mask_pooler` + `mask_head` over ROI_HEADS.IN_FEATURES."""
-        MH = cfg.MODEL.ROI_MASK_HEAD
-        res = MH.POOLER_RESOLUTION
-        scales = tuple(1.0 / self.feature_strides[k] for k in self.in_features)
-        in_channels = [self.feature_channels[f] for f in self.in_features][0]
-        self.mask_in_features = self.in_features
-        self.mask_pooler = ROIPooler(output_size=res, scales=scales, sampling_ratio=MH.POOLER_SAMPLING_RATIO, pooler_type=MH.POOLER_TYPE)
-        self.mask_head = build_mask_head(cfg, ShapeSpec(channels=in_channels, width=res, height=res))
-
-    def _init_keypoint_head(self, cfg):
-        """detectron2's StandardROIHeads._init_keypoint_head (roi_heads.py:624-647): `keypoint_pooler` + `keypoint_head` over
-        ROI_HEADS.IN_FEATURES, registered after the mask modules."""
-        KH = cfg.MODEL.ROI_KEYPOINT_HEAD
-        res = KH.POOLER_RESOLUTION
-        scales = tuple(1.0 / self.feature_strides[k] for k in self.in_features)
-        in_channels = [self.feature_channels[f] for f in self.in_features][0]
-        self.keypoint_in_features = self.in_features
-        self.keypoint_pooler = ROIPooler(output_size=res, scales=scales, sampling_ratio=KH.POOLER_SAMPLING_RATIO, pooler_type=KH.POOLER_TYPE)
-        self.keypoint_head = build_keypoint_head(cfg, ShapeSpec(channels=in_channels, width=res, height=res))
-
-    def pool_masks_batched(self, feats_nhwc, boxes, classes, count, status=None):
-        """The mask branch's input on padded batch tensors, nothing read back: the real rows of the [B, topk] table are moved to the
-        front, image after image, the others become zero boxes, and all B*topk rows go through ROIAlign over the pyramid (the
-        vectorised NHWC kernel `roi_align_fwd_nhwc4_kernel`, which takes no row count: a zero box costs it a store of zeros).
-        -> (pooled [B*topk, S, S, C], classes [B*topk] int32 in that order, rows [B, topk] int32: the row box i of image b owns,
-        total [1] int32: the number of real rows)."""
-        pl = self.mask_pooler
-        feats = [feats_nhwc[f] for f in self.mask_in_features]
-        rois, levels, cls, rows, total, _order = self._mask_rows(boxes, classes, count, len(feats))
+    def _pool_branch(self, name, feats_nhwc, boxes, count, status=None):
+        """The input of the mask or keypoint branch on padded batch tensors, nothing read back: the branch's feature maps, the real rows
+        of the [B, topk] table moved to the front (`front_rows`), and all B*topk rows through ROIAlign over the pyramid with the
+        branch's pooler (the vectorised NHWC kernel `roi_align_fwd_nhwc4_kernel`, which takes no row count: a zero box costs it a
+        store of zeros).  -> (pooled [B*topk, S, S, C], rois [B*topk, 5], rows [B, topk] int32, total [1] int32, order [B*topk] int64)."""
+        pl = getattr(self, name + "_pooler")
+        feats = [feats_nhwc[f] for f in getattr(self, name + "_in_features")]
+        rois, levels, rows, total, order = front_rows(boxes, count, pl, len(feats))
         pooled = K.roi_align_fpn_nhwc(feats, pl.scales, rois, levels, pl.output_size[0], pl.output_size[1], pl.sampling_ratio, pl.aligned,
                                       status=status)
-        return pooled, cls, rows, total
+        return pooled, rois, rows, total, order
 
-    def _mask_rows(self, boxes, classes, count, num_levels, pooler=None):
-        """-> (rois [B*T, 5], levels [B*T] int32 or None, classes [B*T], rows [B, T] int32, total [1] int32, order [B*T] int64): the rows
-        of the [B, T] table with the real ones (the first count[b] of image b) moved to the front, image after image.  pooler: the
-        pooler whose level rule assigns the rows (default: the mask pooler; the keypoint branch passes its own)."""
-        B, T, _ = boxes.shape
-        dev = boxes.device
-        pl = self.mask_pooler if pooler is None else pooler
-        ar = torch.arange(T, device=dev, dtype=torch.int32)
-        cnt = count.clamp(min=0, max=T)
-        valid = ar[None, :] < cnt[:, None]
-        start = torch.cumsum(cnt, 0, dtype=torch.int32) - cnt
-        rows = (start[:, None] + ar[None, :]).contiguous()
-        total = cnt.sum(dtype=torch.int32).view(1)
-        # stable: the real rows first, in (image, index) order -- row start_b + i is box i of image b
-        order = torch.argsort((~valid).view(-1).to(torch.uint8), stable=True)
-        # rows past an image's count hold whatever the box branch left there: zero boxes instead (empty sampling grids)
-        boxes = torch.where(valid[:, :, None], boxes, torch.zeros_like(boxes))
-        levels, rois = K.assign_levels_rois(boxes, pl.min_level, pl.max_level, pl.canonical_box_size, pl.canonical_level)
-        rois = rois.index_select(0, order)
-        levels = None if num_levels == 1 else levels.index_select(0, order)
-        cls = classes.reshape(-1).index_select(0, order).contiguous()
-        return rois, levels, cls, rows, total, order
+    def pool_masks_batched(self, feats_nhwc, boxes, classes, count, status=None):
+        """The mask branch's input (`_pool_branch`) and the classes in the order of its rows -> (pooled [B*topk, S, S, C], classes
+        [B*topk] int32, rows [B, topk] int32: the row box i of image b owns, total [1] int32: the number of real rows)."""
+        pooled, _rois, rows, total, order = self._pool_branch("mask", feats_nhwc, boxes, count, status=status)
+        return pooled, classes.reshape(-1).index_select(0, order).contiguous(), rows, total
 
     def mask_loss_batched(self, feats_nhwc, s_boxes, s_cls, s_m, fg_count, gt_masks, status=None):
         """The mask branch's training loss on the sampler's padded tables, with no device->host read (reference roi_heads.py
@@ -349,7 +369,8 @@ class StandardROIHeads(ROIHeads):
         side = 2 * self.mask_pooler.output_size[0]
         targets = K.mask_targets(boxes, matched, count, planes, side)
         feats = [feats_nhwc[f] for f in self.mask_in_features]
-        rois, levels, cls, _rows, total, order = self._mask_rows(boxes, s_cls[:, :R].to(torch.int32), count, len(feats))
+        rois, levels, _rows, total, order = front_rows(boxes, count, self.mask_pooler, len(feats))
+        cls = s_cls[:, :R].to(torch.int32).reshape(-1).index_select(0, order).contiguous()
         targets = targets.index_select(0, order)
         pooled = self.mask_pooler.pool_rois_nhwc(feats, rois, levels, num_valid=total, status=status)
         loss, _sum, counts = self.mask_head.loss_nhwc(pooled, cls, targets, num_valid=total, status=status)
@@ -371,18 +392,12 @@ class StandardROIHeads(ROIHeads):
         """The keypoint branch on padded batch tensors, nothing read back.  feats_nhwc: dict name -> [B,H,W,C]; boxes [B,topk,4] in
         network coordinates; count [B] int32 (rows [0, count_b) of image b are real).
         Returns (keypoints [B*topk, K, 4] = (x, y, logit, score) in network coordinates, rows [B,topk] int32): the real rows are moved
-        to the front exactly as `pool_masks_batched` moves them (`_mask_rows`), so that ONE number -- their total -- is the `num_valid`
+        to the front exactly as `pool_masks_batched` moves them (`front_rows`), so that ONE number -- their total -- is the `num_valid`
         of `score_lowres` and the decode; `rows[b, i]` is the row box i of image b owns.  Rows past the total are zero (ROIAlign and
         the convs run on all rows: zero boxes, zero maps)."""
         if not self.keypoint_on:
             raise RuntimeError("forward_keypoints_batched: the model was built with MODEL.KEYPOINT_ON = False")
-        pl = self.keypoint_pooler
-        feats = [feats_nhwc[f] for f in self.keypoint_in_features]
-        B, T, _ = boxes.shape
-        dummy = torch.zeros(B, T, dtype=torch.int32, device=boxes.device)
-        rois, levels, _cls, rows, total, _order = self._mask_rows(boxes, dummy, count, len(feats), pooler=pl)
-        pooled = K.roi_align_fpn_nhwc(feats, pl.scales, rois, levels, pl.output_size[0], pl.output_size[1], pl.sampling_ratio, pl.aligned,
-                                      status=status)
+        pooled, rois, rows, total, _order = self._pool_branch("keypoint", feats_nhwc, boxes, count, status=status)
         kp = self.keypoint_head.forward_nhwc(pooled, rois[:, 1:5].contiguous(), num_valid=total, status=status)
         return kp, rows
 
@@ -390,11 +405,7 @@ class StandardROIHeads(ROIHeads):
         feats = {f: to_nhwc(features[f]) for f in self.keypoint_in_features}
         dev = feats[self.keypoint_in_features[0]].device
         require_device(feats[self.keypoint_in_features[0]], "StandardROIHeads")
-        counts = [len(p) for p in instances]
-        B, R = len(instances), max(max(counts), 1)
-        boxes = torch.zeros(B, R, 4, device=dev)
-        for i, p in enumerate(instances):
-            boxes[i, : counts[i]] = p.pred_boxes.tensor
+        boxes, counts = padded_boxes(instances, "pred_boxes", dev)
         status = K.new_status(dev)
         kp, _rows = self.forward_keypoints_batched(feats, boxes, torch.tensor(counts, dtype=torch.int32, device=dev), status=status)
         check_status(int(status.item()))
@@ -414,12 +425,9 @@ class StandardROIHeads(ROIHeads):
         feats = {f: to_nhwc(features[f]) for f in self.mask_in_features}
         dev = feats[self.mask_in_features[0]].device
         require_device(feats[self.mask_in_features[0]], "StandardROIHeads")
-        counts = [len(p) for p in instances]
-        B, R = len(instances), max(max(counts), 1)
-        boxes = torch.zeros(B, R, 4, device=dev)
-        classes = torch.zeros(B, R, dtype=torch.int32, device=dev)
+        boxes, counts = padded_boxes(instances, "pred_boxes", dev)
+        classes = torch.zeros(boxes.shape[:2], dtype=torch.int32, device=dev)
         for i, p in enumerate(instances):
-            boxes[i, : counts[i]] = p.pred_boxes.tensor
             classes[i, : counts[i]] = p.pred_classes.to(torch.int32)
         status = K.new_status(dev)
         prob, _rows = self.forward_masks_batched(feats, boxes, classes, torch.tensor(counts, dtype=torch.int32, device=dev), status=status)
@@ -456,11 +464,7 @@ class StandardROIHeads(ROIHeads):
         feats = {f: to_nhwc(features[f]) for f in self.in_features}
         dev = feats[self.in_features[0]].device
         require_device(feats[self.in_features[0]], "StandardROIHeads")
-        counts = [len(p) for p in proposals]
-        B, R = len(proposals), max(max(counts), 1)
-        boxes = torch.zeros(B, R, 4, device=dev)
-        for i, p in enumerate(proposals):
-            boxes[i, : counts[i]] = p.proposal_boxes.tensor
+        boxes, counts = padded_boxes(proposals, "proposal_boxes", dev)
         sizes = torch.tensor([list(p.image_size) for p in proposals], dtype=torch.int32, device=dev)
         status = K.new_status(dev)
         ob, osc, ocl, orow, cnt = self.forward_batched(feats, boxes, torch.tensor(counts, dtype=torch.int32, device=dev),
@@ -477,153 +481,129 @@ class StandardROIHeads(ROIHeads):
             keypoint_rcnn_inference(kp, insts)
         return insts, {}
 
+    def can_batch_train(self, targets):
+        return (self.batched_sampling and self.batched_targets and self.proposal_append_gt and not self.rbg and self.batch_size_per_image <= 1024
+                and type(self)._forward_train is StandardROIHeads._forward_train and targets is not None and len(targets) > 0
+                and all(0 < len(t) <= 512 and not (self.relabel_ignored_gt and t.has("gt_ignores")) for t in targets)
+                and len(self.proposal_matcher.user_thresholds) in (1, 2))
 
-def _sample_batched(self, pboxes, plogits, pcount, gt, gt_off, targets):
-    """Table + Matcher + subsample_labels + gather for the whole batch (csrc/train_targets.hip), nothing read back:
-    -> (boxes [B,bs,4], logits [B,bs], classes int64 [B,bs], matched gt index int64 [B,bs], matched gt boxes [B,bs,4], counts int32 [B,2])."""
-    import math
-
-    B, dev = pboxes.shape[0], pboxes.device
-    K_, bs = self.num_classes, self.batch_size_per_image
-    gt_logit = math.log((1.0 - 1e-10) / (1 - (1.0 - 1e-10)))
-    Wt = pboxes.shape[1] + max(len(t) for t in targets)
-    with torch.no_grad():
-        tb, tl, nrow = K.roi_build_table(pboxes, plogits, pcount, gt, gt_off, gt_logit, Wt)
-        m, lab = K.match_boxes_batched(gt, gt_off, B, tb, nrow, self.proposal_matcher.user_thresholds, self.proposal_matcher.labels,
-                                       self.proposal_matcher.allow_low_quality_matches)
-        key, seed = K.sampling_keys(B, Wt, dev)
-        sel, cnt = K.subsample_batched(lab, key, int(bs * self.positive_sample_fraction), bs, seed=seed)
-        gcls = torch.cat([t.gt_classes for t in targets]).to(torch.int64)
-        s_boxes, s_logits, s_cls, s_m = K.roi_gather_sampled(tb, tl, m, sel, cnt, gcls, gt_off, K_)
-        s_gtb = gt[(gt_off[:-1].long()[:, None] + s_m).clamp(max=max(gt.shape[0] - 1, 0)).view(-1)].view(B, bs, 4)
-    return s_boxes, s_logits, s_cls, s_m, s_gtb, cnt
-
-
-def can_batch_train(self, targets):
-    return (self.batched_sampling and self.batched_targets and self.proposal_append_gt and not self.rbg and self.batch_size_per_image <= 1024
-            and type(self)._forward_train is _forward_train and targets is not None and len(targets) > 0
-            and all(0 < len(t) <= 512 and not (self.relabel_ignored_gt and t.has("gt_ignores")) for t in targets)
-            and len(self.proposal_matcher.user_thresholds) in (1, 2))
-
-
-def forward_train_batched(self, features, pboxes, plogits, pcount, gt, gt_off, targets):
-    """StandardROIHeads' training branch on the proposal generator's batch tensors, without a device->host read: the sampled rows stay
-    one padded [B, bs] table, ROIAlign / box head / losses run on all B * bs rows as if every image had filled its quota (the usual case;
-    padding rows are zero boxes labelled background) and -> (losses, counts int32 [B,2], accuracy counts int64 [4]).  The CALLER reads the
-    counts with the step's other scalars and, if some image did fall short of bs rows, discards these losses and runs the per-image path
-    (`forward`) instead -- the reference's normalisation is by the true row count."""
-    from .fast_rcnn import fast_rcnn_losses
-
-    s_boxes, _s_logits, s_cls, s_m, s_gtb, cnt = _sample_batched(self, pboxes, plogits, pcount, gt, gt_off, targets)
-    feats = [to_nhwc(features[f]) for f in self.in_features]
-    if self.mask_on:
-        return _forward_train_batched_masks(self, features, feats, s_boxes, s_cls, s_m, s_gtb, cnt, targets)
-    below = any(f.requires_grad for f in feats) or any(p.requires_grad for p in self.box_head.parameters())
-    with torch.set_grad_enabled(below and torch.is_grad_enabled()):
-        h = self.box_head.forward_nhwc(self.box_pooler.pool_nhwc(feats, s_boxes))
-    gc = s_cls.view(-1)
-    losses, pred = fast_rcnn_losses(self.box_predictor, h, s_boxes.view(-1, 4), s_gtb.view(-1, 4), gc)
-    with torch.no_grad():
+    def _box_stats(self, pred, gc):
+        """The four counts of FastRCNNOutputs._log_accuracy as one int64 [4] device tensor: foreground rows, correct rows, correct
+        foreground rows, foreground rows predicted as background."""
         fg = (gc >= 0) & (gc < self.num_classes)
         hit = pred == gc
-        stats = torch.stack([fg.sum(), hit.sum(), (hit & fg).sum(), ((pred == self.num_classes) & fg).sum()])
-    return losses, cnt, stats
+        return torch.stack([fg.sum(), hit.sum(), (hit & fg).sum(), ((pred == self.num_classes) & fg).sum()])
 
+    def forward_train_batched(self, features, pboxes, plogits, pcount, gt, gt_off, targets):
+        """StandardROIHeads' training branch on the proposal generator's batch tensors, without a device->host read: the sampled rows stay
+        one padded [B, bs] table, ROIAlign / box head / losses run on all B * bs rows as if every image had filled its quota (the usual case;
+        padding rows are zero boxes labelled background) and -> (losses, counts int32 [B,2], accuracy counts int64 [4]).  The CALLER reads the
+        counts with the step's other scalars and, if some image did fall short of bs rows, discards these losses and runs the per-image path
+        (`forward`) instead -- the reference's normalisation is by the true row count.
+        A mask model: then the mask branch on the same sampled table.  The accuracy counts grow to int64 [9]: the four of the box branch,
+        the loss kernel's three (incorrect, positive, false-positive pixels), the number of mask rows and the mask kernels' status word
+        -- all read by the caller with the step's other scalars."""
+        from .fast_rcnn import fast_rcnn_losses
 
-def _box_stats(self, pred, gc):
-    fg = (gc >= 0) & (gc < self.num_classes)
-    hit = pred == gc
-    return torch.stack([fg.sum(), hit.sum(), (hit & fg).sum(), ((pred == self.num_classes) & fg).sum()])
+        s_boxes, _s_logits, s_cls, s_m, s_gtb, cnt = self._sample_batched(pboxes, plogits, pcount, gt, gt_off, targets)
+        feats = [to_nhwc(features[f]) for f in self.in_features]
+        below = any(f.requires_grad for f in feats) or any(p.requires_grad for p in self.box_head.parameters())
+        with torch.set_grad_enabled(below and torch.is_grad_enabled()):
+            h = self.box_head.forward_nhwc(self.box_pooler.pool_nhwc(feats, s_boxes))
+        gc = s_cls.view(-1)
+        losses, pred = fast_rcnn_losses(self.box_predictor, h, s_boxes.view(-1, 4), s_gtb.view(-1, 4), gc)
+        with torch.no_grad():
+            stats = self._box_stats(pred, gc)
+        if self.mask_on:
+            mfeats = {f: to_nhwc(features[f]) for f in self.mask_in_features}
+            status = K.new_status(s_boxes.device)
+            loss_mask, mcounts, total = self.mask_loss_batched(mfeats, s_boxes, s_cls, s_m, cnt[:, 0], _gt_masks_of(targets), status=status)
+            losses = dict(losses)
+            losses["loss_mask"] = loss_mask
+            with torch.no_grad():
+                stats = torch.cat([stats, mcounts, total.long(), status.long()])
+        return losses, cnt, stats
 
+    def log_train_scalars(self, counts, stats, nrows):
+        """EventStorage scalars of label_and_sample_proposals and FastRCNNOutputs._log_accuracy from host values (a mask model: also the
+        three mask_rcnn/* scalars, from the counts `forward_train_batched` appended)."""
+        _log_sample_counts(counts)
+        if len(stats) > 4:
+            self._log_mask_scalars(stats[4:])
+        _log_box_accuracy(stats[:4], nrows)
 
-def _forward_train_batched_masks(self, features, feats, s_boxes, s_cls, s_m, s_gtb, cnt, targets):
-    """`forward_train_batched` of a mask model: the box branch as there, then the mask branch on the same sampled table.  The accuracy
-    counts grow to int64 [9]: the four of the box branch, the loss kernel's three (incorrect, positive, false-positive pixels), the
-    number of mask rows and the mask kernels' status word -- all read by the caller with the step's other scalars."""
-    from .fast_rcnn import fast_rcnn_losses
-
-    h = self.box_head.forward_nhwc(self.box_pooler.pool_nhwc(feats, s_boxes))
-    gc = s_cls.view(-1)
-    losses, pred = fast_rcnn_losses(self.box_predictor, h, s_boxes.view(-1, 4), s_gtb.view(-1, 4), gc)
-    mfeats = {f: to_nhwc(features[f]) for f in self.mask_in_features}
-    status = K.new_status(s_boxes.device)
-    loss_mask, mcounts, total = self.mask_loss_batched(mfeats, s_boxes, s_cls, s_m, cnt[:, 0], _gt_masks_of(targets), status=status)
-    losses = dict(losses)
-    losses["loss_mask"] = loss_mask
-    with torch.no_grad():
-        stats = torch.cat([_box_stats(self, pred, gc), mcounts, total.long(), status.long()])
-    return losses, cnt, stats
-
-
-def log_train_scalars(self, counts, stats, nrows):
-    """EventStorage scalars of label_and_sample_proposals and FastRCNNOutputs._log_accuracy from host values (a mask model: also the
-    three mask_rcnn/* scalars, from the counts `_forward_train_batched_masks` appended)."""
-    storage = get_event_storage()
-    B = len(counts)
-    storage.put_scalar("roi_head/num_fg_samples", sum(c[0] for c in counts) / B)
-    storage.put_scalar("roi_head/num_bg_samples", sum(c[1] for c in counts) / B)
-    if len(stats) > 4:
+    def _log_mask_scalars(self, meta):
+        """meta: the host values of (the loss kernel's three counts, the number of mask rows, the mask kernels' status word)."""
         from .mask_head import log_mask_scalars
 
-        check_status(stats[8])
+        check_status(meta[4])
         side = 2 * self.mask_pooler.output_size[0]
-        log_mask_scalars(stats[4:7], stats[7] * side * side)
-        stats = stats[:4]
-    nfg, ncorrect, nfg_correct, nfg_bg = stats
-    storage.put_scalar("fast_rcnn/cls_accuracy", float(ncorrect) / max(1, nrows))
-    if nfg > 0:
-        storage.put_scalar("fast_rcnn/fg_cls_accuracy", float(nfg_correct) / nfg)
-        storage.put_scalar("fast_rcnn/false_negative", float(nfg_bg) / nfg)
+        log_mask_scalars(meta[:3], meta[3] * side * side)
 
+    def _forward_train(self, features, proposals, targets):
+        """StandardROIHeads training branch (reference roi_heads.py:554-629 + FastRCNNOutputs.losses)."""
+        from .fast_rcnn import fast_rcnn_losses
 
-def _forward_train(self, features, proposals, targets):
-    """StandardROIHeads training branch (reference roi_heads.py:554-629 + FastRCNNOutputs.losses)."""
-    from .fast_rcnn import fast_rcnn_losses
-
-    proposals = self.label_and_sample_proposals(proposals, targets)
-    feats = [to_nhwc(features[f]) for f in self.in_features]
-    dev = feats[0].device
-    counts = [len(p) for p in proposals]
-    B, R = len(proposals), max(max(counts), 1)
-    sampled = getattr(proposals[0], "_lvc_sampled", None) if proposals else None
-    if sampled is not None and sampled[3] == counts and sampled[0].shape[1] == R:
-        boxes = sampled[0]          # the sampler's own padded [B,R,4] table: no per-image copies
-    else:
-        sampled = None
-        boxes = torch.zeros(B, R, 4, device=dev)
-        for i, p in enumerate(proposals):
-            boxes[i, : counts[i]] = p.proposal_boxes.tensor
-    full = all(c == R for c in counts)
-    # no graph when everything below the predictor is frozen (ft_novel yaml); otherwise ROIAlign backward into the
-    # pyramid and the fused Linear autograd of the box head (base / ft_all yamls)
-    below = any(f.requires_grad for f in feats) or any(p.requires_grad for p in self.box_head.parameters())
-    with torch.set_grad_enabled(below and torch.is_grad_enabled()):
-        pooled = self.box_pooler.pool_nhwc(feats, boxes)
-        if full:                    # every image filled its quota (the usual case): the pooled rows are the head's input as they lie
-            h = self.box_head.forward_nhwc(pooled)
+        proposals = self.label_and_sample_proposals(proposals, targets)
+        feats = [to_nhwc(features[f]) for f in self.in_features]
+        dev = feats[0].device
+        counts = [len(p) for p in proposals]
+        R = max(max(counts), 1)
+        sampled = getattr(proposals[0], "_lvc_sampled", None) if proposals else None
+        if sampled is not None and sampled[3] == counts and sampled[0].shape[1] == R:
+            boxes = sampled[0]          # the sampler's own padded [B,R,4] table: no per-image copies
         else:
-            keep = torch.cat([torch.arange(c, device=dev) + i * R for i, c in enumerate(counts)])
-            h = self.box_head.forward_nhwc(pooled[keep].contiguous())
-    if sampled is not None and full:
-        pb, gc, gb = sampled[0].view(-1, 4), sampled[1].view(-1), sampled[2].view(-1, 4)
-    else:
-        pb = torch.cat([p.proposal_boxes.tensor for p in proposals], 0)
-        gb = torch.cat([p.gt_boxes.tensor for p in proposals], 0)
-        gc = torch.cat([p.gt_classes for p in proposals], 0)
-    losses, pred = fast_rcnn_losses(self.box_predictor, h, pb, gb, gc)
-    # accuracy scalars (reference fast_rcnn.py _log_accuracy): the four counts in ONE device->host read
-    storage = get_event_storage()
-    fg = (gc >= 0) & (gc < self.num_classes)
-    hit = pred == gc
-    nfg, ncorrect, nfg_correct, nfg_bg = torch.stack([fg.sum(), hit.sum(), (hit & fg).sum(), ((pred == self.num_classes) & fg).sum()]).tolist()
-    storage.put_scalar("fast_rcnn/cls_accuracy", float(ncorrect) / max(1, gc.numel()))
-    if nfg > 0:
-        storage.put_scalar("fast_rcnn/fg_cls_accuracy", float(nfg_correct) / nfg)
-        storage.put_scalar("fast_rcnn/false_negative", float(nfg_bg) / nfg)
-    if self.mask_on:
-        losses = dict(losses)
-        losses["loss_mask"] = _mask_loss_from_lists(self, features, proposals, targets, sampled if full else None)
-    return proposals, losses
+            sampled = None
+            boxes, _ = padded_boxes(proposals, "proposal_boxes", dev)
+        full = all(c == R for c in counts)
+        # no graph when everything below the predictor is frozen (ft_novel yaml); otherwise ROIAlign backward into the
+        # pyramid and the fused Linear autograd of the box head (base / ft_all yamls)
+        below = any(f.requires_grad for f in feats) or any(p.requires_grad for p in self.box_head.parameters())
+        with torch.set_grad_enabled(below and torch.is_grad_enabled()):
+            pooled = self.box_pooler.pool_nhwc(feats, boxes)
+            if full:                    # every image filled its quota (the usual case): the pooled rows are the head's input as they lie
+                h = self.box_head.forward_nhwc(pooled)
+            else:
+                keep = torch.cat([torch.arange(c, device=dev) + i * R for i, c in enumerate(counts)])
+                h = self.box_head.forward_nhwc(pooled[keep].contiguous())
+        if sampled is not None and full:
+            pb, gc, gb = sampled[0].view(-1, 4), sampled[1].view(-1), sampled[2].view(-1, 4)
+        else:
+            pb = torch.cat([p.proposal_boxes.tensor for p in proposals], 0)
+            gb = torch.cat([p.gt_boxes.tensor for p in proposals], 0)
+            gc = torch.cat([p.gt_classes for p in proposals], 0)
+        losses, pred = fast_rcnn_losses(self.box_predictor, h, pb, gb, gc)
+        # accuracy scalars (reference fast_rcnn.py _log_accuracy): the four counts in ONE device->host read
+        _log_box_accuracy(self._box_stats(pred, gc).tolist(), gc.numel())
+        if self.mask_on:
+            losses = dict(losses)
+            losses["loss_mask"] = self._mask_loss_from_lists(features, proposals, targets, sampled if full else None)
+        return proposals, losses
+
+    def _mask_loss_from_lists(self, features, proposals, targets, sampled):
+        """The per-image path's mask loss: the tables `mask_loss_batched` takes, built from the sampled Instances (or the sampler's own
+        tables when they are at hand), then one read for the three logged counts."""
+        dev = proposals[0].proposal_boxes.tensor.device
+        if sampled is not None and len(sampled) >= 6:
+            s_boxes, s_cls, s_m, fg_count = sampled[0], sampled[1], sampled[4], sampled[5][:, 0]
+        else:
+            s_boxes, counts = padded_boxes(proposals, "proposal_boxes", dev)
+            s_cls = torch.full(s_boxes.shape[:2], -1, dtype=torch.int64, device=dev)
+            s_m = torch.zeros(s_boxes.shape[:2], dtype=torch.int64, device=dev)
+            for i, p in enumerate(proposals):
+                s_cls[i, : counts[i]] = p.gt_classes
+                matched = getattr(p, "_lvc_matched", None)
+                if matched is None and counts[i] and len(targets[i]) > 0:
+                    raise RuntimeError("the mask branch needs the matched gt index of every sampled row (label_and_sample_proposals)")
+                if counts[i] and matched is not None:      # (an image without ground truth has background rows only)
+                    s_m[i, : counts[i]] = matched
+            # foreground precedes background in a sampled table: the foreground rows are the first fg_count[b]
+            fg_count = ((s_cls >= 0) & (s_cls < self.num_classes)).sum(1).to(torch.int32)
+        mfeats = {f: to_nhwc(features[f]) for f in self.mask_in_features}
+        status = K.new_status(dev)
+        loss_mask, mcounts, total = self.mask_loss_batched(mfeats, s_boxes, s_cls, s_m, fg_count, _gt_masks_of(targets), status=status)
+        self._log_mask_scalars(torch.cat([mcounts, total.long(), status.long()]).tolist())
+        return loss_mask
 
 
 def _gt_masks_of(targets):
@@ -640,47 +620,6 @@ def _gt_masks_of(targets):
         else:
             raise ValueError("training the mask branch: an image's ground truth has no `gt_masks` field")
     return out
-
-
-def _mask_loss_from_lists(self, features, proposals, targets, sampled):
-    """The per-image path's mask loss: the tables `mask_loss_batched` takes, built from the sampled Instances (or the sampler's own
-    tables when they are at hand), then one read for the three logged counts."""
-    from .mask_head import log_mask_scalars
-
-    dev = proposals[0].proposal_boxes.tensor.device
-    B = len(proposals)
-    if sampled is not None and len(sampled) >= 6:
-        s_boxes, s_cls, s_m, fg_count = sampled[0], sampled[1], sampled[4], sampled[5][:, 0]
-    else:
-        counts = [len(p) for p in proposals]
-        R = max(max(counts), 1)
-        s_boxes = torch.zeros(B, R, 4, device=dev)
-        s_cls = torch.full((B, R), -1, dtype=torch.int64, device=dev)
-        s_m = torch.zeros(B, R, dtype=torch.int64, device=dev)
-        for i, p in enumerate(proposals):
-            s_boxes[i, : counts[i]] = p.proposal_boxes.tensor
-            s_cls[i, : counts[i]] = p.gt_classes
-            matched = getattr(p, "_lvc_matched", None)
-            if matched is None and counts[i] and len(targets[i]) > 0:
-                raise RuntimeError("the mask branch needs the matched gt index of every sampled row (label_and_sample_proposals)")
-            if counts[i] and matched is not None:      # (an image without ground truth has background rows only)
-                s_m[i, : counts[i]] = matched
-        # foreground precedes background in a sampled table: the foreground rows are the first fg_count[b]
-        fg_count = ((s_cls >= 0) & (s_cls < self.num_classes)).sum(1).to(torch.int32)
-    mfeats = {f: to_nhwc(features[f]) for f in self.mask_in_features}
-    status = K.new_status(dev)
-    loss_mask, mcounts, total = self.mask_loss_batched(mfeats, s_boxes, s_cls, s_m, fg_count, _gt_masks_of(targets), status=status)
-    meta = torch.cat([mcounts, total.long(), status.long()]).tolist()
-    check_status(meta[4])
-    side = 2 * self.mask_pooler.output_size[0]
-    log_mask_scalars(meta[:3], meta[3] * side * side)
-    return loss_mask
-
-
-StandardROIHeads._forward_train = _forward_train
-StandardROIHeads.can_batch_train = can_batch_train
-StandardROIHeads.forward_train_batched = forward_train_batched
-StandardROIHeads.log_train_scalars = log_train_scalars
 
 
 def widen_limits(model, exc):
@@ -777,14 +716,14 @@ class CandidateOverflow(RuntimeError):
 
 def check_status(st):
     """Device status word written by the kernels (no sync on the hot path; read with the results)."""
-    if st & 1:
+    if st & K.ROI_NEGATIVE_SIZE:
         raise RuntimeError("ROIs in ROIAlign cannot have non-negative size!")  # reference ROIAlign_cpu.cpp:149-152
-    if st & 2:
+    if st & K.DET_OVERFLOW:
         raise CandidateOverflow("lvc_fast_rcnn_inference: more (roi, class) candidates above SCORE_THRESH_TEST in one "
                                 "image than the candidate list holds; re-run with max_candidates=None (= R*K)")
-    if st & 8:
+    if st & K.MASK_BAD_CLASS:
         raise IndexError("lvc_mask_deconv_predict / lvc_mask_deconv_logits / lvc_mask_deconv_grad: a class index lies outside the mask "
                          "predictor's [0, K)")
-    if st & 4:
+    if st & K.RETINA_OVERFLOW:
         raise CandidateOverflow("lvc_retinanet_select: more entries above SCORE_THRESH_TEST on one (image, level) than the survivor "
                                 "list holds; re-run with max_survivors=None (= H*W*A*K)")

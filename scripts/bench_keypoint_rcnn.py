@@ -92,6 +92,7 @@ def main():
     from lvc_amd import kernels as K
     from lvc_amd.config.presets import base_rcnn_fpn, keypoint_rcnn_fpn
     from lvc_amd.modeling import build_model
+    from lvc_amd.modeling.roi_heads.roi_heads import front_rows
     from lvc_amd.utils import synthetic as syn
 
     torch.cuda.set_device(0)
@@ -117,10 +118,9 @@ def main():
         boxes = torch.cat([xy, xy + wh], 2).to(dev)
         M = B * T
         count = torch.full((B,), T, dtype=torch.int32, device=dev)
-        dummy = torch.zeros(B, T, dtype=torch.int32, device=dev)
 
         def pooler():
-            rois, levels, _c, _rows, _total, _order = heads._mask_rows(boxes, dummy, count, len(fl), pooler=pl)
+            rois, levels, _rows, _total, _order = front_rows(boxes, count, pl, len(fl))
             return K.roi_align_fpn_nhwc(fl, pl.scales, rois, levels, pl.output_size[0], pl.output_size[1], pl.sampling_ratio, pl.aligned)
 
         pooled = pooler()

@@ -457,10 +457,7 @@ def _forward_logits(model):
     from lvc_amd import kernels as K
 
     inputs = _inputs(_dev())
-    images = model.preprocess_image(inputs)
-    sizes = images.image_sizes
-    N, _, Hp, Wp = images.tensor.shape
-    x4 = images.tensor.as_strided((N, Hp, Wp, 4), (Hp * Wp * 4, Wp * 4, 4, 1), images.tensor.storage_offset())
+    x4, sizes = model.preprocess_nhwc(inputs)
     sizes_dev = model._dev_const(sizes, torch.int32)
     feats = model.backbone.forward_nhwc(x4)
     pboxes, _pl, pcount = model.proposal_generator.predict_proposals_batched(feats, sizes_dev)
