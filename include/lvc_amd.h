@@ -933,6 +933,49 @@ int lvc_keypoint_deconv(const float* x, const float* packed, const float* bias, 
 int lvc_heatmaps_to_keypoints(const float* maps, const float* rois, const int* d_num_valid, float* maps_out, float* out, int M, int K,
                               int P, int up, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Keypoint R-CNN training: heatmap targets, the loss, and the backward of the head's transposed convolution (detectron2
+ * structures/keypoints.py _keypoints_to_heatmap, modeling/roi_heads/roi_heads.py select_proposals_with_visible_keypoints,
+ * modeling/roi_heads/keypoint_head.py keypoint_rcnn_loss).  Every kernel: rows >= *d_num_valid (device int, may be NULL) are neither
+ * read nor written; no float atomics; two runs are bit-identical.
+ * lvc_keypoint_targets (csrc/keypoint_targets.hip, no contraction, one launch): boxes [B,R,4]; matched int64 [B,R]: the row's
+ *   instance among its image's; count int32 [B] with stride count_stride: rows [0, count_b) of image b are real; h_table / d_table:
+ *   B x 2 int64 words per image (device pointer of the image's keypoints [n_b,K,3] fp32 = (x, y, v), n_b) on the host (checked) and on
+ *   the device (read by the kernel).  target int32 [B*R,K] = (y * size + x) * valid with x = floor((x - x1) * (size / (x2 - x1))),
+ *   x == x2 -> size - 1 (y likewise); valid uint8 [B*R,K] = inside [0, size) and v > 0; selected uint8 [B*R] = any keypoint with
+ *   v >= 1 inside the box, both ends inclusive; sel_count int32 [B] = selected rows per image.  apply_selection != 0: valid &=
+ *   selected[row].  A box of non-positive width or height, or a matched index outside [0, n_b): invalid, not selected.
+ * lvc_keypoint_loss (csrc/keypoint_train.hip, two launches): low: planes [M,K,2S,2S] (lvc_keypoint_deconv), S <= 16; target int32 /
+ *   valid uint8 [M,K].  Per valid entry the bilinear x2 map [4S,4S] is formed on chip with the decode's fp32 expression and
+ *   term = logsumexp - z[target] in fp64; term fp64 [M,K], plane_max fp32 [M,K] and plane_lse fp64 [M,K] (log of sum exp(z - max))
+ *   are written for valid entries only.  out_sum fp64 [1]: the ordered sum of the terms; out_count int64 [1]: the entries summed;
+ *   out_loss fp32 [1] = sum / (normalizer > 0 ? normalizer : count) * loss_weight, exactly 0 when count is 0.  A target outside
+ *   [0, 16 S^2) on a valid entry sets status bit 16 and the entry is skipped (here and in lvc_keypoint_loss_grad).
+ * lvc_keypoint_loss_grad: dlow = the adjoint of the bilinear x2 applied to (softmax - onehot) * *d_upstream / normaliser * loss_weight
+ *   (d_count: lvc_keypoint_loss's out_count, on the device), gathered per low-resolution pixel in fp64 in a fixed order and rounded
+ *   once; zeros for invalid entries.  dlow is CHANNELS-LAST [M,2S,2S,Kc], Kc = lvc_keypoint_dlow_channels(K) = K rounded up to 4,
+ *   padding channels zero.
+ * lvc_keypoint_deconv_dx: dx [M,S,S,Cin] = sum_k sum_{ky,kx} dlow[m, 2iy-1+ky, 2ix-1+kx, k] W[ci,k,ky,kx] on fp32 MFMA (exact
+ *   products, range-free); packed: [Cin][16*Kc] from lvc_keypoint_deconv_dx_pack (column (ky*4+kx)*Kc + k).  Cin a multiple of 16.
+ * lvc_keypoint_deconv_wgrad (four launches): dw_packed [Cin][16*Kc] (the same packing) = sum over rows of x[row,ci] * dlow[tap], and
+ *   db [K] = sum dlow, on fp32 MFMA over row slices fixed by M and S, the slices added in index order from `workspace`. */
+int lvc_keypoint_targets(const float* boxes, const long long* matched, const int* count, int count_stride, const long long* h_table,
+                         const long long* d_table, int B, int R, int K, int size, int apply_selection, int* target,
+                         unsigned char* valid, unsigned char* selected, int* sel_count, void* stream);
+int lvc_keypoint_dlow_channels(int K);
+int lvc_keypoint_loss(const float* low, const int* target, const unsigned char* valid, const int* d_num_valid, int M, int K, int S,
+                      double normalizer, double loss_weight, double* term, float* plane_max, double* plane_lse, float* out_loss,
+                      double* out_sum, long long* out_count, int* d_status, void* stream);
+int lvc_keypoint_loss_grad(const float* low, const int* target, const unsigned char* valid, const float* plane_max,
+                           const double* plane_lse, const long long* d_count, const float* d_upstream, const int* d_num_valid, int M,
+                           int K, int S, double normalizer, double loss_weight, float* dlow, void* stream);
+int lvc_keypoint_deconv_dx_pack(const float* weight, float* packed, int Cin, int K, void* stream);
+int lvc_keypoint_deconv_dx(const float* dlow, const float* packed, const int* d_num_valid, float* dx, int M, int S, int Cin, int K,
+                           void* stream);
+long long lvc_keypoint_deconv_wgrad_workspace_bytes(int M, int S, int Cin, int K);
+int lvc_keypoint_deconv_wgrad(const float* x, const float* dlow, const int* d_num_valid, float* dw_packed, float* db, int M, int S,
+                              int Cin, int K, void* workspace, long long workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -55,8 +55,12 @@ def mask_rcnn_fpn(depth=50, num_classes=80, device="cuda"):
 
 def keypoint_rcnn_fpn(depth=50, num_classes=1, device="cuda"):
     """Keypoint R-CNN on the ResNet-FPN trunk: the keys detectron2's `COCO-Keypoints/Base-Keypoint-RCNN-FPN.yaml` sets on top of
-    `base_rcnn_fpn` that the inference path reads (one class -- person --, the keypoint branch with the defaults' eight 512-channel
-    convs, 17 keypoints and 14x14 pooler).  Inference only."""
+    `base_rcnn_fpn` that the model reads (one class -- person --, the keypoint branch with the defaults' eight 512-channel convs,
+    17 keypoints and 14x14 pooler).  Training is opt-in: `build_model(cfg).enable_keypoint_training()`; it reads
+    `MODEL.ROI_KEYPOINT_HEAD.LOSS_WEIGHT`, `MODEL.ROI_KEYPOINT_HEAD.NORMALIZE_LOSS_BY_VISIBLE_KEYPOINTS` (False: the summed loss is
+    divided by images x NUM_KEYPOINTS x `MODEL.ROI_HEADS.BATCH_SIZE_PER_IMAGE` x `MODEL.ROI_HEADS.POSITIVE_FRACTION`) and the
+    sampler's keys; every image's ground truth carries `gt_keypoints` (structures.Keypoints).  `MIN_KEYPOINTS_PER_IMAGE` is a
+    dataset filter and is not read."""
     cfg = base_rcnn_fpn(depth=depth, num_classes=num_classes, device=device)
     cfg.merge_from_list(["MODEL.KEYPOINT_ON", True, "MODEL.ROI_HEADS.NUM_CLASSES", num_classes])
     return cfg

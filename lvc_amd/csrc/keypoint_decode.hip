@@ -19,6 +19,7 @@
 #include <stdint.h>
 
 #include "common.h"
+#include "keypoint_upsample.h"
 
 #define KP_TW 64           // output columns per strip
 #define KP_MAX_SIDE 64     // up * P at most (LDS: two [side][64] float arrays)
@@ -78,15 +79,7 @@ __global__ __launch_bounds__(256) void heatmaps_to_keypoints_kernel(const float*
   } else {
     for (int i = tid; i < side * side; i += 256) {
       const int oy = i / side, ox = i - oy * side;
-      float sy = ((float)oy + 0.5f) * 0.5f - 0.5f, sx = ((float)ox + 0.5f) * 0.5f - 0.5f;
-      sy = sy < 0.f ? 0.f : sy;
-      sx = sx < 0.f ? 0.f : sx;
-      const int y0 = (int)sy, x0 = (int)sx;
-      const int y1 = y0 + (y0 < P - 1 ? 1 : 0), x1 = x0 + (x0 < P - 1 ? 1 : 0);
-      const float ly1 = sy - (float)y0, ly0 = 1.f - ly1, lx1 = sx - (float)x0, lx0 = 1.f - lx1;
-      const float t0 = src[y0 * P + x0] * lx0 + src[y0 * P + x1] * lx1;
-      const float t1 = src[y1 * P + x0] * lx0 + src[y1 * P + x1] * lx1;
-      smap[i] = t0 * ly0 + t1 * ly1;
+      smap[i] = kp_up2(src, P, oy, ox);      // (keypoint_upsample.h: the expression the training loss uses too)
     }
   }
   __syncthreads();

@@ -1299,6 +1299,7 @@ ROI_NEGATIVE_SIZE = 1     # ROIAlign: a RoI of negative width or height
 DET_OVERFLOW = 2          # lvc_fast_rcnn_inference: more (roi, class) candidates in one image than the candidate list holds
 RETINA_OVERFLOW = 4       # lvc_retinanet_select: more entries on one (image, level) than the survivor list holds
 MASK_BAD_CLASS = 8        # lvc_mask_deconv_predict / _logits / _grad: a class index outside [0, K)
+KEYPOINT_BAD_TARGET = 16  # lvc_keypoint_loss: a heatmap target outside [0, 16 S^2) on a valid entry (the entry is skipped)
 
 
 def roi_align_forward(input, rois, spatial_scale, pooled_h, pooled_w, sampling_ratio, aligned, status=None):
@@ -3696,3 +3697,170 @@ def mask_deconv_grad(x, w_deconv, b_deconv, w_pred, classes, logits, targets, nu
         dx = torch.zeros(0, S, S, cin, device=dev) if need_dx else None
         dwd = torch.zeros(cin, cmid, 2, 2, device=dev) if need_dw else None
     return dx, dwd, dbd, dwp, dbp
+
+
+# --------------------------------------------------------------------------- Keypoint R-CNN training
+KEYPOINT_TABLE_FIELDS = 2    # int64 words per image of lvc_keypoint_targets' keypoint table (include/lvc_amd.h)
+KEYPOINT_TRAIN_MAX_S = 16    # lvc_keypoint_loss forms the [4S,4S] map in LDS: side at most 64, as the decode
+
+
+def keypoint_targets(boxes, matched, count, keypoints, size, apply_selection=True):
+    """Keypoints.to_heatmap and select_proposals_with_visible_keypoints for the first count[b] rows of every image in one launch
+    (csrc/keypoint_targets.hip).  boxes [B,R,4] fp32; matched int64 [B,R]: the row's instance among its image's; count int32 [B] (or
+    a strided [B] view); keypoints: B tensors fp32 [n_b,K,3] = (x, y, v), each contiguous on the device, gathered by the kernel.
+    -> (target int32 [B*R,K], valid uint8 [B*R,K], selected uint8 [B*R], sel_count int32 [B]); with apply_selection valid is
+    valid & selected[row].  Rows past an image's count are zero (allocated so; the kernel does not write them).  No host read."""
+    import numpy as np
+
+    _req_cuda(boxes, matched, count, *keypoints)
+    B, R, _ = boxes.shape
+    assert boxes.is_contiguous() and boxes.dtype == torch.float32 and boxes.shape == (B, R, 4)
+    assert matched.dtype == torch.int64 and matched.is_contiguous() and matched.shape == (B, R)
+    assert count.dtype == torch.int32 and count.dim() == 1 and count.shape[0] == B and len(keypoints) == B
+    k = None
+    table = np.zeros((max(B, 1), KEYPOINT_TABLE_FIELDS), dtype=np.int64)
+    for b, kp in enumerate(keypoints):
+        assert kp.dim() == 3 and kp.shape[2] == 3 and kp.is_contiguous() and kp.dtype == torch.float32, "keypoints: contiguous fp32 [n,K,3]"
+        assert k is None or kp.shape[1] == k, "keypoints: every image with the same K"
+        k = kp.shape[1]
+        table[b] = (kp.data_ptr() if kp.numel() else 0, kp.shape[0])
+    dev = boxes.device
+    k = int(k or 1)
+    target = torch.zeros(B * R, k, dtype=torch.int32, device=dev)
+    valid = torch.zeros(B * R, k, dtype=torch.uint8, device=dev)
+    selected = torch.zeros(B * R, dtype=torch.uint8, device=dev)
+    sel_count = torch.zeros(B, dtype=torch.int32, device=dev)
+    if B == 0:
+        return target, valid, selected, sel_count
+    # pinned and asynchronous: the upload is ordered on the stream, the host does not wait for the device
+    d_table = torch.from_numpy(table).pin_memory().to(dev, non_blocking=True)
+    check(_lib.lib().lvc_keypoint_targets(ptr(boxes), ptr(matched), ptr(count), c_int(count.stride(0)), c_void_p(table.ctypes.data),
+                                          ptr(d_table), c_int(B), c_int(R), c_int(k), c_int(int(size)), c_int(1 if apply_selection else 0),
+                                          ptr(target), ptr(valid), ptr(selected), ptr(sel_count), _stream(boxes)), "lvc_keypoint_targets")
+    return target, valid, selected, sel_count
+
+
+def keypoint_dlow_channels(k):
+    """Channels of `keypoint_loss_grad`'s channels-last dlow: K rounded up to 4."""
+    return (int(k) + 3) // 4 * 4
+
+
+def _keypoint_entry_args(low, target, valid, num_valid):
+    assert low.dim() == 4 and low.shape[2] == low.shape[3] and low.shape[2] % 2 == 0 and low.is_contiguous() and low.dtype == torch.float32
+    M, k, P, _ = low.shape
+    if P // 2 > KEYPOINT_TRAIN_MAX_S:
+        raise NotImplementedError("keypoint loss: a pooled side of {} (up to {} is built: MODEL.ROI_KEYPOINT_HEAD.POOLER_RESOLUTION)"
+                                  .format(P // 2, KEYPOINT_TRAIN_MAX_S))
+    keypoint_deconv_check(KEYPOINT_DECONV_CIN, k)
+    assert target.dtype == torch.int32 and target.is_contiguous() and target.numel() == M * k
+    assert valid.dtype == torch.uint8 and valid.is_contiguous() and valid.numel() == M * k
+    if num_valid is not None:
+        assert num_valid.dtype == torch.int32 and num_valid.numel() == 1
+    return M, k, P // 2
+
+
+def keypoint_loss(low, target, valid, num_valid=None, normalizer=None, loss_weight=1.0, status=None, out=None):
+    """Softmax cross-entropy over the bilinear x2 map of every valid (row, keypoint) (csrc/keypoint_train.hip).  low: planes
+    [M,K,2S,2S] (`keypoint_deconv`); target int32 / valid uint8 [M,K]; normalizer: None = the counted valid entries, else the number.
+    -> (loss fp32 [1], sum fp64 [1], count int64 [1], term fp64 [M,K], plane_max fp32 [M,K], plane_lse fp64 [M,K]); the last three are
+    written for valid entries below num_valid only (`out`: those three tensors, else zeros).  Sets KEYPOINT_BAD_TARGET in `status`.
+    No host read; count 0 gives a loss of exactly 0."""
+    _req_cuda(low, target, valid, num_valid, status)
+    M, k, S = _keypoint_entry_args(low, target, valid, num_valid)
+    dev = low.device
+    if out is None:
+        out = (torch.zeros(M, k, dtype=torch.float64, device=dev), torch.zeros(M, k, dtype=torch.float32, device=dev),
+               torch.zeros(M, k, dtype=torch.float64, device=dev))
+    term, pmax, plse = out
+    assert term.dtype == torch.float64 and pmax.dtype == torch.float32 and plse.dtype == torch.float64
+    assert all(t.is_contiguous() and t.numel() == M * k for t in out)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    total = torch.empty(1, dtype=torch.float64, device=dev)
+    count = torch.empty(1, dtype=torch.int64, device=dev)
+    check(_lib.lib().lvc_keypoint_loss(ptr(low), ptr(target), ptr(valid), ptr(num_valid), c_int(M), c_int(k), c_int(S),
+                                       c_double(0.0 if normalizer is None else float(normalizer)), c_double(float(loss_weight)),
+                                       ptr(term), ptr(pmax), ptr(plse), ptr(loss), ptr(total), ptr(count), ptr(status), _stream(low)),
+          "lvc_keypoint_loss")
+    return loss, total, count, term, pmax, plse
+
+
+def keypoint_loss_grad(low, target, valid, pmax, plse, count, upstream, num_valid=None, normalizer=None, loss_weight=1.0, out=None):
+    """dlow of `keypoint_loss`: the adjoint of the bilinear x2 applied to (softmax - onehot) * upstream / normaliser * loss_weight
+    (csrc/keypoint_train.hip).  pmax / plse / count: `keypoint_loss`'s; upstream: fp32 [1] ON THE DEVICE.  -> dlow, CHANNELS-LAST
+    [M,2S,2S,Kc] with Kc = `keypoint_dlow_channels(K)` (padding channels zero; rows past num_valid are not written)."""
+    _req_cuda(low, target, valid, pmax, plse, count, upstream, num_valid)
+    M, k, S = _keypoint_entry_args(low, target, valid, num_valid)
+    assert pmax.dtype == torch.float32 and plse.dtype == torch.float64 and pmax.numel() == M * k and plse.numel() == M * k
+    assert count.dtype == torch.int64 and count.numel() == 1 and upstream.dtype == torch.float32 and upstream.numel() == 1
+    kc = keypoint_dlow_channels(k)
+    if out is None:
+        out = torch.empty(M, 2 * S, 2 * S, kc, dtype=torch.float32, device=low.device)
+    assert out.shape == (M, 2 * S, 2 * S, kc) and out.is_contiguous() and out.dtype == torch.float32
+    check(_lib.lib().lvc_keypoint_loss_grad(ptr(low), ptr(target), ptr(valid), ptr(pmax), ptr(plse), ptr(count), ptr(upstream),
+                                            ptr(num_valid), c_int(M), c_int(k), c_int(S),
+                                            c_double(0.0 if normalizer is None else float(normalizer)), c_double(float(loss_weight)),
+                                            ptr(out), _stream(low)), "lvc_keypoint_loss_grad")
+    return out
+
+
+def pack_keypoint_deconv_dx(weight):
+    """ConvTranspose2d weight [Cin, K, 4, 4] -> the weight operand of `keypoint_deconv_dx`: [Cin][16*Kc], column (ky*4+kx)*Kc + k."""
+    _req_cuda(weight)
+    cin, k = weight.shape[0], weight.shape[1]
+    keypoint_deconv_check(cin, k)
+    assert tuple(weight.shape[2:]) == (4, 4), weight.shape
+    w = weight.detach().contiguous().float()
+    packed = torch.empty(cin, 16 * keypoint_dlow_channels(k), device=w.device, dtype=torch.float32)
+    check(_lib.lib().lvc_keypoint_deconv_dx_pack(ptr(w), ptr(packed), c_int(cin), c_int(k), _stream(w)), "lvc_keypoint_deconv_dx_pack")
+    return packed
+
+
+def unpack_keypoint_deconv_dx(packed, k):
+    """The packing of `pack_keypoint_deconv_dx` back to the parameter's [Cin, K, 4, 4] (a layout change of dW, 16*K*Cin floats)."""
+    cin, kc = packed.shape[0], keypoint_dlow_channels(k)
+    return packed.view(cin, 16, kc)[:, :, :k].permute(0, 2, 1).reshape(cin, k, 4, 4).contiguous()
+
+
+def keypoint_deconv_dx(dlow, packed, num_keypoints, num_valid=None, out=None):
+    """The backward of `keypoint_deconv` into its input on fp32 MFMA (csrc/keypoint_train.hip): dlow channels-last [M,2S,2S,Kc];
+    packed: `pack_keypoint_deconv_dx`.  -> dx [M,S,S,Cin] (`out` when given, else zeros: rows past num_valid are not written)."""
+    _req_cuda(dlow, packed, num_valid, out)
+    k = int(num_keypoints)
+    kc = keypoint_dlow_channels(k)
+    M, P, P_, kc_ = dlow.shape
+    cin = packed.shape[0]
+    keypoint_deconv_check(cin, k)
+    assert P == P_ and P % 2 == 0 and kc_ == kc and dlow.is_contiguous() and dlow.dtype == torch.float32, dlow.shape
+    assert packed.shape == (cin, 16 * kc) and packed.is_contiguous() and packed.dtype == torch.float32
+    if num_valid is not None:
+        assert num_valid.dtype == torch.int32 and num_valid.numel() == 1
+    S = P // 2
+    if out is None:
+        out = torch.zeros(M, S, S, cin, device=dlow.device, dtype=torch.float32)
+    assert out.shape == (M, S, S, cin) and out.is_contiguous() and out.dtype == torch.float32
+    check(_lib.lib().lvc_keypoint_deconv_dx(ptr(dlow), ptr(packed), ptr(num_valid), ptr(out), c_int(M), c_int(S), c_int(cin), c_int(k),
+                                            _stream(dlow)), "lvc_keypoint_deconv_dx")
+    return out
+
+
+def keypoint_deconv_wgrad(x, dlow, num_keypoints, num_valid=None):
+    """The backward of `keypoint_deconv` into weight and bias on fp32 MFMA, ordered slices (csrc/keypoint_train.hip).  x [M,S,S,Cin];
+    dlow channels-last [M,2S,2S,Kc].  -> (dW [Cin,K,4,4], db [K]); bit-identical between runs."""
+    _req_cuda(x, dlow, num_valid)
+    k = int(num_keypoints)
+    kc = keypoint_dlow_channels(k)
+    M, S, S_, cin = x.shape
+    keypoint_deconv_check(cin, k)
+    assert S == S_ and x.is_contiguous() and x.dtype == torch.float32
+    assert dlow.shape == (M, 2 * S, 2 * S, kc) and dlow.is_contiguous() and dlow.dtype == torch.float32, dlow.shape
+    if num_valid is not None:
+        assert num_valid.dtype == torch.int32 and num_valid.numel() == 1
+    lib = _lib.lib()
+    lib.lvc_keypoint_deconv_wgrad_workspace_bytes.restype = c_longlong
+    nbytes = lib.lvc_keypoint_deconv_wgrad_workspace_bytes(c_int(M), c_int(S), c_int(cin), c_int(k))
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=x.device)
+    dw = torch.empty(cin, 16 * kc, dtype=torch.float32, device=x.device)
+    db = torch.empty(k, dtype=torch.float32, device=x.device)
+    check(lib.lvc_keypoint_deconv_wgrad(ptr(x), ptr(dlow), ptr(num_valid), ptr(dw), ptr(db), c_int(M), c_int(S), c_int(cin), c_int(k),
+                                        ptr(ws), c_longlong(ws.numel() * 8), _stream(x)), "lvc_keypoint_deconv_wgrad")
+    return unpack_keypoint_deconv_dx(dw, k), db

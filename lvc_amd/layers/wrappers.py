@@ -334,6 +334,15 @@ class ConvTranspose2d(nn.Module):
             return self._cache.get([self.weight], lambda: K.pack_keypoint_deconv(self.weight))
         return self._cache.get([self.weight], lambda: K.pack_mask_deconv(self.weight))
 
+    def packed_dx(self):
+        """4x4 only: the weight operand of the layer's backward into its input (`kernels.pack_keypoint_deconv_dx`, training), cached
+        like `packed()` and rebuilt when the parameter changes."""
+        assert self.kernel_size == (4, 4), self.kernel_size
+        cache = self.__dict__.get("_cache_dx")
+        if cache is None:
+            cache = self.__dict__["_cache_dx"] = _PackedCache()
+        return cache.get([self.weight], lambda: K.pack_keypoint_deconv_dx(self.weight))
+
     def forward(self, x):
         if self.kernel_size == (4, 4):
             raise NotImplementedError("ConvTranspose2d runs only inside the keypoint head (KRCNNConvDeconvUpsampleHead.forward_nhwc)")

@@ -174,7 +174,7 @@ class GeneralizedRCNN(_RCNNBase):
             return self.inference(batched_inputs)
         if self._mask_on() and not self.__dict__.get("_mask_train_enabled", False):
             raise NotImplementedError("training the mask branch (MODEL.MASK_ON: mask_rcnn_loss, gt_masks) is not built")
-        if self._keypoint_on():
+        if self._keypoint_on() and not self.__dict__.get("_keypoint_train_enabled", False):
             from ..roi_heads.keypoint_head import TRAIN_REFUSAL
 
             raise NotImplementedError(TRAIN_REFUSAL)
@@ -246,7 +246,7 @@ class GeneralizedRCNN(_RCNNBase):
         detector_losses, cnt, stats = heads.forward_train_batched(features, boxes, logits, count, gt, gt_off, gt_instances)
         B, bs = boxes.shape[0], heads.batch_size_per_image
         meta = torch.cat([count.long(), rpn_counts.view(-1).long(), cnt.view(-1).long(), stats.long(), K.range_summary(self.device).long()]).tolist()
-        pc, rc, cc, st, flagged = meta[:B], meta[B:3 * B], meta[3 * B:5 * B], meta[5 * B:-1], meta[-1]      # (st: 4 counts; a mask model: 9)
+        pc, rc, cc, st, flagged = meta[:B], meta[B:3 * B], meta[3 * B:5 * B], meta[5 * B:-1], meta[-1]      # (st: 4 counts; a mask model: 9; a keypoint model: 4 + 2B + 2)
         if flagged:
             K.check_conv_error_word(self.device)      # re-routes the layers concerned and raises: `run_with_fallbacks` repeats the pass
         self.__dict__["_range_checked"] = True
@@ -340,6 +340,21 @@ class GeneralizedRCNN(_RCNNBase):
                 raise NotImplementedError("VIS_PERIOD > 0: visualising the mask predictions is not built")
         for owner in (self, heads, heads.mask_head):
             owner.__dict__["_mask_train_enabled"] = bool(on)
+        return self
+
+    def enable_keypoint_training(self, on=True):
+        """Switch the training forward of a MODEL.KEYPOINT_ON model on (or off again); returns self.  Without the call a keypoint model
+        in training mode refuses, as before.  The ground truth of every image carries `gt_keypoints` (structures.Keypoints [n, K, 3]);
+        the losses gain `loss_keypoint`, the logged scalars `keypoint_head/num_fg_samples` and, for a step without a valid
+        keypoint, `kpts_num_skipped_batches`."""
+        heads = self.roi_heads
+        if type(heads) is not StandardROIHeads:
+            raise NotImplementedError("MODEL.ROI_HEADS.NAME = {}: the keypoint branch and its training are built for StandardROIHeads"
+                                      .format(type(heads).__name__))
+        if not self._keypoint_on():
+            raise ValueError("enable_keypoint_training: the model was built with MODEL.KEYPOINT_ON = False")
+        for owner in (self, heads, heads.keypoint_head):
+            owner.__dict__["_keypoint_train_enabled"] = bool(on)
         return self
 
     def _inference_given_boxes(self, batched_inputs, detected_instances, do_postprocess):

@@ -376,6 +376,37 @@ class StandardROIHeads(ROIHeads):
         loss, _sum, counts = self.mask_head.loss_nhwc(pooled, cls, targets, num_valid=total, status=status)
         return loss, counts, total
 
+    def keypoint_loss_batched(self, feats_nhwc, s_boxes, s_cls, s_m, fg_count, gt_keypoints, status=None):
+        """The keypoint branch's training loss on the sampler's padded tables, with no device->host read (reference roi_heads.py
+        `_forward_keypoint` + `select_foreground_proposals` + `select_proposals_with_visible_keypoints` + keypoint_rcnn_loss).
+        s_boxes [B, R, 4], s_cls [B, R], s_m [B, R] int64 (the matched gt index of every sampled row), fg_count [B] int32 on the
+        device: foreground comes before background in the sampled table, so the foreground rows of image b are its first
+        fg_count[b], at most int(BATCH_SIZE_PER_IMAGE * POSITIVE_FRACTION); gt_keypoints: one Keypoints per image.  One launch makes
+        targets, valid flags and the row selection (a foreground row the reference would drop keeps its place and contributes
+        nothing: its valid flags are cleared); the foreground rows move to the front (`front_rows`), the keypoint pooler and the
+        conv_fcn convs run under autograd on ALL padded rows (zero boxes), and the total of foreground rows is the `num_valid` of
+        `score_lowres`, loss and backward.
+        -> (loss_keypoint scalar, valid count int64 [1], selected rows per image int32 [B], foreground rows per image int32 [B])."""
+        if not self.keypoint_on:
+            raise RuntimeError("keypoint_loss_batched: the model was built with MODEL.KEYPOINT_ON = False")
+        cap = max(int(self.batch_size_per_image * self.positive_sample_fraction), 1)
+        R = min(cap, s_boxes.shape[1])
+        B = s_boxes.shape[0]
+        boxes = s_boxes[:, :R].detach().contiguous()
+        matched = s_m[:, :R].to(torch.int64).contiguous()
+        count = fg_count.to(torch.int32).clamp(min=0, max=R)
+        head = self.keypoint_head
+        side = 2 * head.up_scale * self.keypoint_pooler.output_size[0]
+        with torch.no_grad():
+            target, valid, _selected, sel_count = K.keypoint_targets(boxes, matched, count, [k.tensor.contiguous() for k in gt_keypoints], side)
+        feats = [feats_nhwc[f] for f in self.keypoint_in_features]
+        rois, levels, _rows, total, order = front_rows(boxes, count, self.keypoint_pooler, len(feats))
+        target = target.index_select(0, order)
+        valid = valid.index_select(0, order)
+        pooled = self.keypoint_pooler.pool_rois_nhwc(feats, rois, levels, num_valid=total, status=status)
+        loss, _sum, vcount = head.loss_nhwc(pooled, target, valid, num_valid=total, status=status, num_images=B)
+        return loss, vcount, sel_count, count
+
     def forward_masks_batched(self, feats_nhwc, boxes, classes, count, status=None):
         """The mask branch on padded batch tensors, nothing read back.  feats_nhwc: dict name -> [B,H,W,C]; boxes [B,topk,4] in network
         coordinates; classes [B,topk] int32; count [B] int32 (rows [0, count_b) of image b are real).
@@ -454,7 +485,7 @@ class StandardROIHeads(ROIHeads):
         if self.training:
             if self.mask_on and not self.__dict__.get("_mask_train_enabled", False):
                 raise NotImplementedError("training the mask branch (MODEL.MASK_ON: mask_rcnn_loss, gt_masks) is not built")
-            if self.keypoint_on:
+            if self.keypoint_on and not self.__dict__.get("_keypoint_train_enabled", False):
                 raise NotImplementedError(KEYPOINT_TRAIN_REFUSAL)
             return self._forward_train(features, proposals, targets)
         if self.rbg:
@@ -522,13 +553,25 @@ class StandardROIHeads(ROIHeads):
             losses["loss_mask"] = loss_mask
             with torch.no_grad():
                 stats = torch.cat([stats, mcounts, total.long(), status.long()])
+        if self.keypoint_on:
+            # a keypoint model: the accuracy counts grow to int64 [4 + 2B + 2] -- the valid (row, keypoint) entries, the selected rows
+            # and the foreground rows of every image, the keypoint kernels' status word
+            kfeats = {f: to_nhwc(features[f]) for f in self.keypoint_in_features}
+            status = K.new_status(s_boxes.device)
+            loss_kp, vcount, sel_count, fg = self.keypoint_loss_batched(kfeats, s_boxes, s_cls, s_m, cnt[:, 0], _gt_keypoints_of(targets, self.keypoint_head.num_keypoints), status=status)
+            losses = dict(losses)
+            losses["loss_keypoint"] = loss_kp
+            with torch.no_grad():
+                stats = torch.cat([stats, vcount, sel_count.long(), fg.long(), status.long()])
         return losses, cnt, stats
 
     def log_train_scalars(self, counts, stats, nrows):
         """EventStorage scalars of label_and_sample_proposals and FastRCNNOutputs._log_accuracy from host values (a mask model: also the
         three mask_rcnn/* scalars, from the counts `forward_train_batched` appended)."""
         _log_sample_counts(counts)
-        if len(stats) > 4:
+        if self.keypoint_on:
+            self._log_keypoint_scalars(stats[4:])
+        elif len(stats) > 4:
             self._log_mask_scalars(stats[4:])
         _log_box_accuracy(stats[:4], nrows)
 
@@ -539,6 +582,20 @@ class StandardROIHeads(ROIHeads):
         check_status(meta[4])
         side = 2 * self.mask_pooler.output_size[0]
         log_mask_scalars(meta[:3], meta[3] * side * side)
+
+    def _log_keypoint_scalars(self, meta):
+        """meta: the host values of (the valid count, the selected rows of every image, the foreground rows of every image, the
+        keypoint kernels' status word).  keypoint_head/num_fg_samples: the mean of the selected counts over the images that had
+        foreground rows (reference roi_heads.py:95-119); kpts_num_skipped_batches whenever no entry was valid."""
+        from .keypoint_head import check_keypoint_status, log_skipped_batch
+
+        B = (len(meta) - 2) // 2
+        check_keypoint_status(meta[-1])
+        kept = [s for s, f in zip(meta[1:1 + B], meta[1 + B:1 + 2 * B]) if f > 0]
+        if kept:
+            get_event_storage().put_scalar("keypoint_head/num_fg_samples", sum(kept) / len(kept))
+        if meta[0] == 0:
+            log_skipped_batch()
 
     def _forward_train(self, features, proposals, targets):
         """StandardROIHeads training branch (reference roi_heads.py:554-629 + FastRCNNOutputs.losses)."""
@@ -578,27 +635,46 @@ class StandardROIHeads(ROIHeads):
         if self.mask_on:
             losses = dict(losses)
             losses["loss_mask"] = self._mask_loss_from_lists(features, proposals, targets, sampled if full else None)
+        if self.keypoint_on:
+            losses = dict(losses)
+            losses["loss_keypoint"] = self._keypoint_loss_from_lists(features, proposals, targets, sampled if full else None)
         return proposals, losses
+
+    def _sampled_tables(self, proposals, targets, sampled, branch):
+        """(s_boxes [B,R,4], s_cls [B,R], s_m [B,R] int64, fg_count [B] int32) of the sampled Instances, for the per-image path's mask
+        or keypoint loss: the sampler's own tables when they are at hand, else built from the lists."""
+        dev = proposals[0].proposal_boxes.tensor.device
+        if sampled is not None and len(sampled) >= 6:
+            return sampled[0], sampled[1], sampled[4], sampled[5][:, 0]
+        s_boxes, counts = padded_boxes(proposals, "proposal_boxes", dev)
+        s_cls = torch.full(s_boxes.shape[:2], -1, dtype=torch.int64, device=dev)
+        s_m = torch.zeros(s_boxes.shape[:2], dtype=torch.int64, device=dev)
+        for i, p in enumerate(proposals):
+            s_cls[i, : counts[i]] = p.gt_classes
+            matched = getattr(p, "_lvc_matched", None)
+            if matched is None and counts[i] and len(targets[i]) > 0:
+                raise RuntimeError("the {} branch needs the matched gt index of every sampled row (label_and_sample_proposals)".format(branch))
+            if counts[i] and matched is not None:      # (an image without ground truth has background rows only)
+                s_m[i, : counts[i]] = matched
+        # foreground precedes background in a sampled table: the foreground rows are the first fg_count[b]
+        fg_count = ((s_cls >= 0) & (s_cls < self.num_classes)).sum(1).to(torch.int32)
+        return s_boxes, s_cls, s_m, fg_count
+
+    def _keypoint_loss_from_lists(self, features, proposals, targets, sampled):
+        """The per-image path's keypoint loss: the tables `keypoint_loss_batched` takes, then one read for the logged values."""
+        dev = proposals[0].proposal_boxes.tensor.device
+        s_boxes, s_cls, s_m, fg_count = self._sampled_tables(proposals, targets, sampled, "keypoint")
+        kfeats = {f: to_nhwc(features[f]) for f in self.keypoint_in_features}
+        status = K.new_status(dev)
+        loss_kp, vcount, sel_count, fg = self.keypoint_loss_batched(kfeats, s_boxes, s_cls, s_m, fg_count, _gt_keypoints_of(targets, self.keypoint_head.num_keypoints), status=status)
+        self._log_keypoint_scalars(torch.cat([vcount, sel_count.long(), fg.long(), status.long()]).tolist())
+        return loss_kp
 
     def _mask_loss_from_lists(self, features, proposals, targets, sampled):
         """The per-image path's mask loss: the tables `mask_loss_batched` takes, built from the sampled Instances (or the sampler's own
         tables when they are at hand), then one read for the three logged counts."""
         dev = proposals[0].proposal_boxes.tensor.device
-        if sampled is not None and len(sampled) >= 6:
-            s_boxes, s_cls, s_m, fg_count = sampled[0], sampled[1], sampled[4], sampled[5][:, 0]
-        else:
-            s_boxes, counts = padded_boxes(proposals, "proposal_boxes", dev)
-            s_cls = torch.full(s_boxes.shape[:2], -1, dtype=torch.int64, device=dev)
-            s_m = torch.zeros(s_boxes.shape[:2], dtype=torch.int64, device=dev)
-            for i, p in enumerate(proposals):
-                s_cls[i, : counts[i]] = p.gt_classes
-                matched = getattr(p, "_lvc_matched", None)
-                if matched is None and counts[i] and len(targets[i]) > 0:
-                    raise RuntimeError("the mask branch needs the matched gt index of every sampled row (label_and_sample_proposals)")
-                if counts[i] and matched is not None:      # (an image without ground truth has background rows only)
-                    s_m[i, : counts[i]] = matched
-            # foreground precedes background in a sampled table: the foreground rows are the first fg_count[b]
-            fg_count = ((s_cls >= 0) & (s_cls < self.num_classes)).sum(1).to(torch.int32)
+        s_boxes, s_cls, s_m, fg_count = self._sampled_tables(proposals, targets, sampled, "mask")
         mfeats = {f: to_nhwc(features[f]) for f in self.mask_in_features}
         status = K.new_status(dev)
         loss_mask, mcounts, total = self.mask_loss_batched(mfeats, s_boxes, s_cls, s_m, fg_count, _gt_masks_of(targets), status=status)
@@ -619,6 +695,27 @@ def _gt_masks_of(targets):
             out.append(BitMasks(torch.zeros(0, h, w, dtype=torch.bool, device=t.gt_boxes.tensor.device)))
         else:
             raise ValueError("training the mask branch: an image's ground truth has no `gt_masks` field")
+    return out
+
+
+def _gt_keypoints_of(targets, num_keypoints):
+    """The ground-truth keypoints of every image; an image without ground truth may come without the field: no instances."""
+    from ...structures import Keypoints
+
+    out = []
+    for t in targets:
+        if t.has("gt_keypoints"):
+            kp = t.gt_keypoints
+            if not isinstance(kp, Keypoints):
+                raise ValueError("training the keypoint branch: `gt_keypoints` must be a structures.Keypoints, got {}".format(type(kp).__name__))
+            if kp.tensor.shape[1] != num_keypoints:
+                raise ValueError("training the keypoint branch: gt_keypoints with {} keypoints, MODEL.ROI_KEYPOINT_HEAD.NUM_KEYPOINTS = {}"
+                                 .format(kp.tensor.shape[1], num_keypoints))
+            out.append(kp)
+        elif len(t) == 0:
+            out.append(Keypoints(torch.zeros(0, num_keypoints, 3, device=t.gt_boxes.tensor.device)))
+        else:
+            raise ValueError("training the keypoint branch: an image's ground truth has no `gt_keypoints` field")
     return out
 
 
@@ -724,6 +821,8 @@ def check_status(st):
     if st & K.MASK_BAD_CLASS:
         raise IndexError("lvc_mask_deconv_predict / lvc_mask_deconv_logits / lvc_mask_deconv_grad: a class index lies outside the mask "
                          "predictor's [0, K)")
+    if st & K.KEYPOINT_BAD_TARGET:
+        raise IndexError("lvc_keypoint_loss: a heatmap target lies outside the keypoint map")
     if st & K.RETINA_OVERFLOW:
         raise CandidateOverflow("lvc_retinanet_select: more entries above SCORE_THRESH_TEST on one (image, level) than the survivor "
                                 "list holds; re-run with max_survivors=None (= H*W*A*K)")
