@@ -35,9 +35,6 @@ def lib():
             )
         L = ctypes.CDLL(_SO)
         L.lvc_last_error.restype = ctypes.c_char_p
-        L.lvc_batched_nms_workspace_bytes.restype = c_longlong
-        L.lvc_tta_merge_workspace_bytes.restype = c_longlong
-        L.lvc_group_norm_workspace_bytes.restype = c_longlong
         L.lvc_abi_version.restype = c_int
         L.lvc_set_wino_streamk.restype = None
         if os.environ.get("LVC_WINO_STREAMK", "0") != "0":
@@ -60,6 +57,17 @@ def check(status, what=""):
         # later un-slotted launches would raise that layer's word instead of the shared one
         lib().lvc_set_range_slot(0)
         raise LvcNativeError("{} failed (status {}): {}".format(what or "lvc_amd native call", status, msg))
+
+
+def size_query(name, *args):
+    """What a `*_workspace_bytes` entry answers for these C arguments, as a Python int: the entries return long long (ctypes' default
+    restype would cut the size to 32 bits), and a negative answer means arguments outside the kernel's range."""
+    fn = getattr(lib(), name)
+    fn.restype = c_longlong
+    nbytes = fn(*args)
+    if nbytes < 0:
+        raise LvcNativeError("{} answered {}: arguments outside the kernel's range".format(name, nbytes))
+    return nbytes
 
 
 def ptr(t):

@@ -27,6 +27,7 @@
 //     operand [4 parities][4 taps][Kp][Cin], Kp = K rounded up to 32 with zero rows, so no weight read needs a bound.
 //   * Rows past *d_num_valid are neither read nor written; a neighbour of a real pixel lies in the same RoI, so it is real too.
 #include "conv_common.h"
+#include "rows_common.h"
 
 #define KD_TM 64      // rows (input pixels) per workgroup
 #define KD_TN 32      // output channels per workgroup (two 16-channel blocks)
@@ -40,11 +41,7 @@ __global__ __launch_bounds__(512) void keypoint_deconv_kernel(const float* __res
   const int j = lane & 15, kq = lane >> 4;
   const int py = q >> 1, px = q & 1;
   const int S2 = S * S;
-  int Mv = M;
-  if (d_num_valid) {
-    const int nv = *d_num_valid;
-    Mv = nv < 0 ? 0 : (nv < M ? nv : M);
-  }
+  const int Mv = lvc_valid_rows(d_num_valid, M);
   const long long R = (long long)Mv * S2;
   const long long r0 = (long long)blockIdx.x * KD_TM;
   if (r0 >= R) return;      // (uniform) rows past num_valid are neither read nor written

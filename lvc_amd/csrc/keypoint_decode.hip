@@ -20,6 +20,7 @@
 
 #include "common.h"
 #include "keypoint_upsample.h"
+#include "rows_common.h"
 
 #define KP_TW 64           // output columns per strip
 #define KP_MAX_SIDE 64     // up * P at most (LDS: two [side][64] float arrays)
@@ -63,11 +64,7 @@ __global__ __launch_bounds__(256) void heatmaps_to_keypoints_kernel(const float*
   __shared__ float red_s[4];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int Mv = M;
-  if (d_num_valid) {
-    const int nv = *d_num_valid;
-    Mv = nv < 0 ? 0 : (nv < M ? nv : M);
-  }
+  const int Mv = lvc_valid_rows(d_num_valid, M);
   const int m = blockIdx.x / K, k = blockIdx.x - m * K;
   if (m >= Mv) return;      // (uniform)
   const int side = up * P;

@@ -33,6 +33,7 @@
 // Every kernel: rows past *d_num_valid are neither read nor written; no float atomics; two runs give the same bits.
 #include "conv_common.h"
 #include "keypoint_upsample.h"
+#include "rows_common.h"
 
 #define KL_MAX_P 32               // 2S at most (the x2 map's side is at most 64, as in keypoint_decode.hip)
 #define KL_STATUS_TARGET 16       // status bit: a target outside [0, 16 S^2) on a valid entry
@@ -42,12 +43,6 @@
 #define KW_SLICE_ROWS 2048        // wgrad: rows per slice (a multiple of KW_KC) ...
 #define KW_MAX_SLICES 64          // ... unless that would make more slices than this
 #define KB_PIXELS 512             // db: low-resolution pixels per workgroup
-
-__device__ __forceinline__ int kl_valid_rows(const int* d_num_valid, int M) {
-  if (!d_num_valid) return M;
-  const int nv = *d_num_valid;
-  return nv < 0 ? 0 : (nv < M ? nv : M);
-}
 
 static int kl_channels(int K) { return (K + 3) / 4 * 4; }
 
@@ -63,7 +58,7 @@ __global__ __launch_bounds__(256) void keypoint_loss_kernel(const float* __restr
   __shared__ float redf[4];
   __shared__ double redd[4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int Mv = kl_valid_rows(d_num_valid, M);
+  const int Mv = lvc_valid_rows(d_num_valid, M);
   const int e = blockIdx.x, m = e / K;
   if (m >= Mv) return;            // (uniform)
   if (!valid[e]) return;          // (uniform)
@@ -108,7 +103,7 @@ __global__ __launch_bounds__(256) void keypoint_loss_finish_kernel(const double*
   __shared__ double ss[256];
   __shared__ long long sc[256];
   const int tid = threadIdx.x;
-  const long long N = (long long)kl_valid_rows(d_num_valid, M) * K;
+  const long long N = (long long)lvc_valid_rows(d_num_valid, M) * K;
   double s = 0.0;
   long long c = 0;
   for (long long e = tid; e < N; e += 256) {
@@ -165,7 +160,7 @@ __global__ __launch_bounds__(256) void keypoint_loss_grad_kernel(const float* __
   __shared__ float slow[KL_MAX_P * KL_MAX_P];
   __shared__ double sg[4 * KL_MAX_P * KL_MAX_P];
   const int tid = threadIdx.x;
-  const int Mv = kl_valid_rows(d_num_valid, M);
+  const int Mv = lvc_valid_rows(d_num_valid, M);
   const int e = blockIdx.x, m = e / K, k = e - m * K;
   if (m >= Mv) return;            // (uniform)
   const int side = 2 * P, n = side * side, PP = P * P;
@@ -250,7 +245,7 @@ __global__ __launch_bounds__(256) void keypoint_dx_kernel(const float* __restric
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int j = lane & 15, kq = lane >> 4;
   const int S2 = S * S, P = 2 * S, E = 16 * Kc;
-  const long long R = (long long)kl_valid_rows(d_num_valid, M) * S2;
+  const long long R = (long long)lvc_valid_rows(d_num_valid, M) * S2;
   const long long r0 = (long long)blockIdx.x * KX_TM;
   if (r0 >= R) return;      // (uniform) rows past num_valid are neither read nor written
   const int cb0 = blockIdx.y * 4, ncb = Cin >> 4;
@@ -316,18 +311,7 @@ extern "C" int lvc_keypoint_deconv_dx(const float* dlow, const float* packed, co
 }
 
 // ------------------------------------------------------------------------------------------------- dW, db
-static long long kw_slice_rows(int M, int S) {
-  const long long R = (long long)M * S * S;
-  long long per = KW_SLICE_ROWS;
-  if ((R + per - 1) / per > KW_MAX_SLICES) per = ((R + KW_MAX_SLICES - 1) / KW_MAX_SLICES + KW_KC - 1) / KW_KC * KW_KC;
-  return per;
-}
-
-static int kw_slices(int M, int S) {
-  const long long R = (long long)M * S * S, per = kw_slice_rows(M, S);
-  const long long n = (R + per - 1) / per;
-  return n < 1 ? 1 : (int)n;
-}
+static LvcSliceCut kw_cut(int M, int S) { return lvc_slice_cut((long long)M * S * S, KW_SLICE_ROWS, KW_MAX_SLICES, KW_KC); }
 
 // D[16 e][16 ci] += A[16 e][4 rows] B[4 rows][16 ci]; the workgroup's (64 e x 64 ci) tile: wave w owns e block w and the four ci blocks
 __global__ __launch_bounds__(256) void keypoint_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ dlow,
@@ -338,7 +322,7 @@ __global__ __launch_bounds__(256) void keypoint_wgrad_kernel(const float* __rest
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int j = lane & 15, kq = lane >> 4;
   const int S2 = S * S, P = 2 * S, E = 16 * Kc;
-  const long long R = (long long)kl_valid_rows(d_num_valid, M) * S2;      // rows past it are never read
+  const long long R = (long long)lvc_valid_rows(d_num_valid, M) * S2;      // rows past it are never read
   const int ne = E / 64;
   const int e0 = (blockIdx.x % ne) * 64, c0 = (blockIdx.x / ne) * 64;
   const long long rb = (long long)blockIdx.y * slice_rows;
@@ -421,7 +405,7 @@ __global__ __launch_bounds__(256) void keypoint_dbias_kernel(const float* __rest
                                                              double* __restrict__ pb, int M, int S, int Kc) {
   __shared__ double sa[4][64];
   const int c = threadIdx.x & 63, ph = threadIdx.x >> 6;
-  const long long N = (long long)kl_valid_rows(d_num_valid, M) * 4 * S * S;
+  const long long N = (long long)lvc_valid_rows(d_num_valid, M) * 4 * S * S;
   const long long p0 = (long long)blockIdx.x * KB_PIXELS;
   long long p1 = p0 + KB_PIXELS;
   if (p1 > N) p1 = N;
@@ -467,7 +451,7 @@ static long long kb_chunks(int M, int S) {
 extern "C" long long lvc_keypoint_deconv_wgrad_workspace_bytes(int M, int S, int Cin, int K) {
   if (M < 0 || S < 1 || Cin < 1 || K < 1) return -1;
   const long long Kc = kl_channels(K);
-  return (long long)kw_slices(M, S) * 16LL * Kc * Cin * 4 + kb_chunks(M, S) * Kc * 8;
+  return (long long)kw_cut(M, S).slices * 16LL * Kc * Cin * 4 + kb_chunks(M, S) * Kc * 8;
 }
 
 extern "C" int lvc_keypoint_deconv_wgrad(const float* x, const float* dlow, const int* d_num_valid, float* dw_packed, float* db, int M,
@@ -478,8 +462,9 @@ extern "C" int lvc_keypoint_deconv_wgrad(const float* x, const float* dlow, cons
   LVC_CHECK_ARG((((uintptr_t)workspace | (uintptr_t)dw_packed) & 15) == 0, "16-byte aligned operands");
   LVC_CHECK_ARG((long long)M * S * S < (1LL << 31) - KX_TM, "too many rows");
   LVC_CHECK_ARG(workspace_bytes >= lvc_keypoint_deconv_wgrad_workspace_bytes(M, S, Cin, K), "workspace too small");
-  const int Kc = kl_channels(K), E = 16 * Kc, slices = kw_slices(M, S);
-  const long long n = (long long)E * Cin, per = kw_slice_rows(M, S);
+  const LvcSliceCut cut = kw_cut(M, S);
+  const int Kc = kl_channels(K), E = 16 * Kc, slices = cut.slices;
+  const long long n = (long long)E * Cin, per = cut.rows;
   hipStream_t st = (hipStream_t)stream;
   const long long chunks = kb_chunks(M, S);
   LVC_CHECK_ARG(chunks < (1LL << 31), "too many rows");

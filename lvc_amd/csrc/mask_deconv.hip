@@ -22,6 +22,7 @@
 //     the same order.  Nothing of size Cmid (2S)^2 leaves the workgroup; no atomics on data: two runs are bit-identical.
 //   * A class outside [0, K) sets bit 3 (value 8) of the status word and is computed as class 0: nothing is read out of bounds.
 #include "conv_common.h"
+#include "rows_common.h"
 
 #define MD_TM 64            // rows (pixels) per workgroup
 #define MD_PAD 4            // floats of padding per LDS row
@@ -43,11 +44,7 @@ __global__ __launch_bounds__(256) void mask_deconv_kernel(const float* __restric
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int j = lane & 15, kq = lane >> 4;
   const int S2 = S * S;
-  int Mv = M;
-  if (d_num_valid) {
-    const int nv = *d_num_valid;
-    Mv = nv < 0 ? 0 : (nv < M ? nv : M);
-  }
+  const int Mv = lvc_valid_rows(d_num_valid, M);
   const long long R = (long long)Mv * S2;
   const long long r0 = (long long)blockIdx.x * MD_TM;
   if (r0 >= R) return;      // (uniform) rows past num_valid are neither read nor written

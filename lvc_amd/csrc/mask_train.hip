@@ -22,6 +22,7 @@
 //   rows cut into a number of slices fixed by M alone, a workgroup per (256 x 64 output tile, slice) that writes its partial tile, and a
 //   second launch that adds the slices in index order.  Rows of x and dh past num_valid are not read: slices past it add exact zeros.
 #include "conv_common.h"
+#include "rows_common.h"
 
 #define MG_TM 64            // rows (pixels of one RoI) per workgroup
 #define MG_PAD 4            // floats of padding per LDS row
@@ -34,11 +35,7 @@ __global__ __launch_bounds__(256) void mask_loss_kernel(const float* __restrict_
                                                         double* __restrict__ psum, long long* __restrict__ pcnt) {
   __shared__ double ssum[4];
   __shared__ long long scnt[4][3];
-  int Mv = M;
-  if (d_num_valid) {
-    const int nv = *d_num_valid;
-    Mv = nv < 0 ? 0 : (nv < M ? nv : M);
-  }
+  const int Mv = lvc_valid_rows(d_num_valid, M);
   const long long total = (long long)Mv * P;
   const long long i0 = (long long)blockIdx.x * chunk;
   long long i1 = i0 + chunk;
@@ -80,11 +77,7 @@ __global__ __launch_bounds__(64) void mask_loss_finish_kernel(const double* __re
                                                               float* __restrict__ out_loss, double* __restrict__ out_sum,
                                                               long long* __restrict__ out_counts) {
   if (threadIdx.x != 0) return;
-  int Mv = M;
-  if (d_num_valid) {
-    const int nv = *d_num_valid;
-    Mv = nv < 0 ? 0 : (nv < M ? nv : M);
-  }
+  const int Mv = lvc_valid_rows(d_num_valid, M);
   double s = 0.0;
   long long c[3] = {0, 0, 0};
   for (int g = 0; g < G; ++g) {
@@ -147,11 +140,7 @@ __global__ __launch_bounds__(256) void mask_deconv_grad_kernel(const float* __re
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int j = lane & 15, kq = lane >> 4;
   const int S2 = S * S;
-  int Mv = M;
-  if (d_num_valid) {
-    const int nv = *d_num_valid;
-    Mv = nv < 0 ? 0 : (nv < M ? nv : M);
-  }
+  const int Mv = lvc_valid_rows(d_num_valid, M);
   const int m = blockIdx.x / tiles, tile = blockIdx.x - m * tiles;
   const int p0 = tile * MG_TM;
   const int rows = S2 - p0 < MG_TM ? S2 - p0 : MG_TM;
@@ -277,11 +266,7 @@ __global__ __launch_bounds__(256) void mask_deconv_grad_finish_kernel(const floa
                                                                       float* __restrict__ dbp) {
   __shared__ float sa[4][64];
   __shared__ float sb[4];
-  int Mv = M;
-  if (d_num_valid) {
-    const int nv = *d_num_valid;
-    Mv = nv < 0 ? 0 : (nv < M ? nv : M);
-  }
+  const int Mv = lvc_valid_rows(d_num_valid, M);
   const int k = blockIdx.x, col = threadIdx.x & 63, ph = threadIdx.x >> 6;
   const int co = blockIdx.y * 64 + col;
   float a = 0.f, b = 0.f;
@@ -308,11 +293,7 @@ __global__ __launch_bounds__(256) void mask_deconv_grad_finish_kernel(const floa
 __global__ __launch_bounds__(256) void mask_deconv_grad_dbd_kernel(const float* __restrict__ pw, const int* __restrict__ d_num_valid, int M,
                                                                    int tiles, int Cmid, float* __restrict__ dbd) {
   __shared__ float sa[16][16];
-  int Mv = M;
-  if (d_num_valid) {
-    const int nv = *d_num_valid;
-    Mv = nv < 0 ? 0 : (nv < M ? nv : M);
-  }
+  const int Mv = lvc_valid_rows(d_num_valid, M);
   const int col = threadIdx.x & 15, ph = threadIdx.x >> 4;
   const int co = blockIdx.x * 16 + col;
   const long long parts = (long long)Mv * tiles;
@@ -403,18 +384,7 @@ extern "C" int lvc_mask_deconv_grad(const float* x, const float* w_deconv, const
 #define MW_SLICE_ROWS 2048  // rows per slice (a multiple of MW_KC) ...
 #define MW_MAX_SLICES 64    // ... unless that would make more slices than this
 
-static long long mask_wgrad_slice_rows(int M, int S) {
-  const long long R = (long long)M * S * S;
-  long long per = MW_SLICE_ROWS;
-  if ((R + per - 1) / per > MW_MAX_SLICES) per = ((R + MW_MAX_SLICES - 1) / MW_MAX_SLICES + MW_KC - 1) / MW_KC * MW_KC;
-  return per;
-}
-
-static int mask_wgrad_slices(int M, int S) {
-  const long long R = (long long)M * S * S, per = mask_wgrad_slice_rows(M, S);
-  const long long n = (R + per - 1) / per;
-  return n < 1 ? 1 : (int)n;
-}
+static LvcSliceCut mask_wgrad_cut(int M, int S) { return lvc_slice_cut((long long)M * S * S, MW_SLICE_ROWS, MW_MAX_SLICES, MW_KC); }
 
 __global__ __launch_bounds__(256) void mask_wgrad_kernel(const float* __restrict__ dh, const float* __restrict__ x,
                                                          const int* __restrict__ d_num_valid, float* __restrict__ part, int M, int S2,
@@ -423,11 +393,7 @@ __global__ __launch_bounds__(256) void mask_wgrad_kernel(const float* __restrict
   __shared__ __attribute__((aligned(16))) float sB[MW_KC * MW_LDB];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int j = lane & 15, kq = lane >> 4;
-  int Mv = M;
-  if (d_num_valid) {
-    const int nv = *d_num_valid;
-    Mv = nv < 0 ? 0 : (nv < M ? nv : M);
-  }
+  const int Mv = lvc_valid_rows(d_num_valid, M);
   const long long R = (long long)Mv * S2;      // the rows past it are never read (x may hold anything there)
   const int nt = N4 / MW_TN;
   const int tn = blockIdx.x % nt, tc = blockIdx.x / nt;
@@ -499,7 +465,7 @@ __global__ __launch_bounds__(256) void mask_wgrad_finish_kernel(const float* __r
 
 extern "C" long long lvc_mask_deconv_wgrad_workspace_bytes(int M, int S, int Cin, int Cmid) {
   if (M < 0 || S < 1 || Cin < 1 || Cmid < 1) return -1;
-  return (long long)mask_wgrad_slices(M, S) * 4 * Cmid * Cin * 4;
+  return (long long)mask_wgrad_cut(M, S).slices * 4 * Cmid * Cin * 4;
 }
 
 extern "C" int lvc_mask_deconv_wgrad(const float* dh, const float* x, const int* d_num_valid, float* dw_packed, int M, int S, int Cin,
@@ -511,12 +477,13 @@ extern "C" int lvc_mask_deconv_wgrad(const float* dh, const float* x, const int*
   LVC_CHECK_ARG((((uintptr_t)dh | (uintptr_t)workspace) & 15) == 0, "16-byte aligned operands");
   LVC_CHECK_ARG((long long)M * S * S < (1LL << 31), "too many rows");
   LVC_CHECK_ARG(workspace_bytes >= lvc_mask_deconv_wgrad_workspace_bytes(M, S, Cin, Cmid), "workspace too small");
-  const int N4 = 4 * Cmid, slices = mask_wgrad_slices(M, S);
+  const LvcSliceCut cut = mask_wgrad_cut(M, S);
+  const int N4 = 4 * Cmid, slices = cut.slices;
   const long long n = (long long)N4 * Cin;
   hipStream_t st = (hipStream_t)stream;
   float* part = reinterpret_cast<float*>(workspace);
   hipLaunchKernelGGL(mask_wgrad_kernel, dim3((unsigned)((N4 / MW_TN) * (Cin / MW_TC)), (unsigned)slices), dim3(256), 0, st, dh, x, d_num_valid,
-                     part, M, S * S, N4, Cin, mask_wgrad_slice_rows(M, S));
+                     part, M, S * S, N4, Cin, cut.rows);
   hipLaunchKernelGGL(mask_wgrad_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, part, slices, n, dw_packed);
   LVC_CHECK_LAUNCH();
   return LVC_OK;

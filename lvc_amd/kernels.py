@@ -379,11 +379,10 @@ def conv_workspace(device):
     ws = _CONV_WS.get(key)
     if ws is None:
         lib = _lib.lib()
-        lib.lvc_conv_workspace_bytes.restype = c_longlong
         if _ERR_OFF is None:
             lib.lvc_conv_range_words_offset.restype = c_longlong
             _ERR_OFF = lib.lvc_conv_range_words_offset()
-        ws = torch.zeros(lib.lvc_conv_workspace_bytes(), dtype=torch.uint8, device=device)
+        ws = torch.zeros(_lib.size_query("lvc_conv_workspace_bytes"), dtype=torch.uint8, device=device)
         _CONV_WS[key] = ws
     return ws
 
@@ -1430,7 +1429,7 @@ def batched_nms_batch(boxes, scores, idxs, counts, iou_threshold, max_keep=0):
         assert idxs.dtype == torch.int32
     keep = torch.empty(B, Nmax, dtype=torch.int32, device=boxes.device)
     num_keep = torch.empty(B, dtype=torch.int32, device=boxes.device)
-    wsb = _lib.lib().lvc_batched_nms_workspace_bytes(c_int(B), c_int(Nmax))
+    wsb = _lib.size_query("lvc_batched_nms_workspace_bytes", c_int(B), c_int(Nmax))
     ws = torch.empty(wsb, dtype=torch.uint8, device=boxes.device)
     st = _lib.lib().lvc_batched_nms(
         ptr(boxes), ptr(scores), ptr(idxs), ptr(counts), c_int(B), c_int(Nmax), c_double(iou_threshold),
@@ -1493,8 +1492,7 @@ def rpn_proposals(logits, deltas, cell_anchors, strides, image_sizes, pre_nms_to
     ldd = IP(*[t.stride(2) for t in deltas])
     hs, ws_, st = IP(*Hs), IP(*Ws), IP(*strides)
     lib = _lib.lib()
-    lib.lvc_rpn_proposals_workspace_bytes.restype = c_longlong
-    nbytes = lib.lvc_rpn_proposals_workspace_bytes(c_int(B), c_int(L), c_int(A), hs, ws_, c_int(pre_nms_topk))
+    nbytes = _lib.size_query("lvc_rpn_proposals_workspace_bytes", c_int(B), c_int(L), c_int(A), hs, ws_, c_int(pre_nms_topk))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     boxes = torch.empty(B, post_nms_topk, 4, device=dev, dtype=torch.float32)
     olog = torch.empty(B, post_nms_topk, device=dev, dtype=torch.float32)
@@ -1542,9 +1540,8 @@ def fast_rcnn_inference(cls_logits, deltas, proposals, prop_count, image_sizes, 
     if status is None:
         status = new_status(dev)
     lib = _lib.lib()
-    lib.lvc_fast_rcnn_inference_workspace_bytes.restype = c_longlong
     max_candidates = max(1, R * K) if max_candidates is None else min(max_candidates, max(1, R * K))
-    nbytes = lib.lvc_fast_rcnn_inference_workspace_bytes(c_int(B), c_int(max_candidates))
+    nbytes = _lib.size_query("lvc_fast_rcnn_inference_workspace_bytes", c_int(B), c_int(max_candidates))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     ob = torch.empty(B, topk, 4, device=dev, dtype=torch.float32)
     osc = torch.empty(B, topk, device=dev, dtype=torch.float32)
@@ -1611,10 +1608,10 @@ def retinanet_select(logits, deltas, cell_anchors, strides, anchor_offset, num_c
     ldd = IP(*[t.stride(2) for t in deltas])
     hs, ws_, st = IP(*Hs), IP(*Ws), IP(*[int(s) for s in strides])
     lib = _lib.lib()
-    lib.lvc_retinanet_select_workspace_bytes.restype = c_longlong
-    nbytes = lib.lvc_retinanet_select_workspace_bytes(c_int(B), c_int(L), c_int(A), c_int(K), hs, ws_, c_int(topk), c_int(max_survivors))
-    if nbytes < 0:
-        raise ValueError("retinanet_select: shapes outside the kernel's range")
+    try:
+        nbytes = _lib.size_query("lvc_retinanet_select_workspace_bytes", c_int(B), c_int(L), c_int(A), c_int(K), hs, ws_, c_int(topk), c_int(max_survivors))
+    except _lib.LvcNativeError:
+        raise ValueError("retinanet_select: shapes outside the kernel's range") from None
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     rows = L * topk
     boxes = torch.empty(B, rows, 4, device=dev, dtype=torch.float32)
@@ -1708,10 +1705,10 @@ def retinanet_loss(args, normalizer_in, normalizer_out, momentum=0.9, one_minus_
         raise ValueError("retinanet_loss: normalizer_in / normalizer_out must be two different float64 [1] device tensors")
     lib = _lib.lib()
     IP = c_int * args.L
-    lib.lvc_retinanet_loss_workspace_bytes.restype = c_longlong
-    nbytes = lib.lvc_retinanet_loss_workspace_bytes(c_int(args.B), c_int(args.L), c_int(args.A), c_int(args.K), IP(*args.Hs), IP(*args.Ws))
-    if nbytes < 0:
-        raise ValueError("retinanet_loss: shapes outside the kernel's range")
+    try:
+        nbytes = _lib.size_query("lvc_retinanet_loss_workspace_bytes", c_int(args.B), c_int(args.L), c_int(args.A), c_int(args.K), IP(*args.Hs), IP(*args.Ws))
+    except _lib.LvcNativeError:
+        raise ValueError("retinanet_loss: shapes outside the kernel's range") from None
     ws = torch.empty(nbytes, dtype=torch.uint8, device=args.dev)
     out = torch.empty(2, dtype=torch.float32, device=args.dev)
     num_pos = torch.empty(1, dtype=torch.int32, device=args.dev)
@@ -2180,7 +2177,7 @@ def tta_merge(boxes, scores, classes, counts, params, tab, num_images, nmax, sco
     cnt = torch.zeros(B, device=dev, dtype=torch.int32)
     if topk == 0 or B == 0:
         return ob[:, :0], osc[:, :0], ocl[:, :0], cnt
-    wsb = _lib.lib().lvc_tta_merge_workspace_bytes(c_int(B), c_int(nmax))
+    wsb = _lib.size_query("lvc_tta_merge_workspace_bytes", c_int(B), c_int(nmax))
     ws = torch.empty(wsb + 256, dtype=torch.uint8, device=dev)
     off = (-ws.data_ptr()) % 256
     ws = ws[off:off + wsb]
@@ -2467,13 +2464,12 @@ def subsample_batched(labels, keys, cap_pos, bs, seed=0):
     counts = torch.empty(B, 2, dtype=torch.int32, device=labels.device)
     nbits = max(1, int(B * N - 1).bit_length())
     lib = _lib.lib()
-    lib.lvc_subsample_workspace_bytes.restype = c_longlong
     key = (labels.device.index, torch.cuda.current_stream(labels.device).cuda_stream, B)
     ws = _SUBSAMPLE_WS.get(key)
     if ws is None:      # zeroed once; the kernels leave it zeroed (per stream: two launches in flight must not share the histograms)
         if len(_SUBSAMPLE_WS) > 16:
             _SUBSAMPLE_WS.clear()
-        ws = _SUBSAMPLE_WS[key] = torch.zeros(lib.lvc_subsample_workspace_bytes(c_int(B)), dtype=torch.uint8, device=labels.device)
+        ws = _SUBSAMPLE_WS[key] = torch.zeros(_lib.size_query("lvc_subsample_workspace_bytes", c_int(B)), dtype=torch.uint8, device=labels.device)
     from ctypes import c_ulonglong
 
     rc = lib.lvc_subsample_batched(ptr(labels.contiguous()), ptr(keys.contiguous() if keys is not None else None), c_ulonglong(int(seed)),
@@ -2681,8 +2677,7 @@ def conv_wgrad_grouped(x, dy, scale, groups, stride):
     if x.numel() == 0:
         return dw.zero_()
     lib = _lib.lib()
-    lib.lvc_conv3x3_grouped_wgrad_workspace_bytes.restype = c_longlong
-    nbytes = lib.lvc_conv3x3_grouped_wgrad_workspace_bytes(c_int(N), c_int(H), c_int(W), c_int(C), c_int(groups), c_int(stride))
+    nbytes = _lib.size_query("lvc_conv3x3_grouped_wgrad_workspace_bytes", c_int(N), c_int(H), c_int(W), c_int(C), c_int(groups), c_int(stride))
     scratch = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
 
     def run():
@@ -3263,13 +3258,12 @@ def qkv_attention(x, pc, B, N, num_heads, scale):
     x = x.contiguous()
     dev = x.device
     lib = _lib.lib()
-    lib.lvc_mha_workspace_bytes.restype = c_longlong
     key = (dev.index, torch.cuda.current_stream(dev).cuda_stream, B, N, num_heads)
     ws = _MHA_PLANES_WS.get(key)
     if ws is None:      # zeroed ONCE: the epilogue never writes the padding rows N..Npad-1, which must stay zero
         if len(_MHA_PLANES_WS) > 8:
             _MHA_PLANES_WS.clear()
-        ws = _MHA_PLANES_WS[key] = torch.zeros(max(16, lib.lvc_mha_workspace_bytes(c_int(B), c_int(N), c_int(num_heads))), dtype=torch.uint8, device=dev)
+        ws = _MHA_PLANES_WS[key] = torch.zeros(max(16, _lib.size_query("lvc_mha_workspace_bytes", c_int(B), c_int(N), c_int(num_heads))), dtype=torch.uint8, device=dev)
     planes, scale2 = pc.split2s()
     pc.last_one = True
     _launch(None, 0.0, 0.0, pc.slot, "lvc_conv1x1_qkv_planes_f16s1", lambda: lib.lvc_conv1x1_qkv_planes_f16s1(
@@ -3300,8 +3294,7 @@ def mha(qkv, B, N, num_heads, head_dim, scale, mfma=None):
     out = torch.empty(B * N, num_heads * head_dim, device=qkv.device, dtype=torch.float32)
     if ((MHA_MFMA and CONV_SPLIT == "f16x2") if mfma is None else mfma) and head_dim == 64:
         lib = _lib.lib()
-        lib.lvc_mha_workspace_bytes.restype = c_longlong
-        ws = torch.empty(max(16, lib.lvc_mha_workspace_bytes(c_int(B), c_int(N), c_int(num_heads))), dtype=torch.uint8, device=qkv.device)
+        ws = torch.empty(max(16, _lib.size_query("lvc_mha_workspace_bytes", c_int(B), c_int(N), c_int(num_heads))), dtype=torch.uint8, device=qkv.device)
         check(lib.lvc_mha_mfma(ptr(qkv), ptr(out), ptr(ws), c_int(B), c_int(N), c_int(num_heads), c_float(scale),
                                    ptr(_conv_error_view(qkv.device)), _stream(qkv)), "lvc_mha_mfma")
         return out
@@ -3328,7 +3321,7 @@ def _gn_tile_rows(N, H, W):
 
 
 def _gn_workspace(x, N, H, W, C, G, rows, backward):
-    nbytes = _lib.lib().lvc_group_norm_workspace_bytes(c_int(N), c_int(H), c_int(W), c_int(C), c_int(G), c_int(rows), c_int(backward))
+    nbytes = _lib.size_query("lvc_group_norm_workspace_bytes", c_int(N), c_int(H), c_int(W), c_int(C), c_int(G), c_int(rows), c_int(backward))
     return torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None, nbytes
 
 
@@ -3422,11 +3415,13 @@ def pack_mask_deconv(weight):
     return weight.detach().permute(2, 3, 1, 0).reshape(4 * cmid, cin).contiguous().float()
 
 
-def mask_deconv_predict(x, w_deconv, b_deconv, w_pred, b_pred, classes=None, num_valid=None, status=None, out=None):
-    """Deconv 2x2 s2 + bias + ReLU + 1x1 predictor of one class per row + bias + sigmoid (csrc/mask_deconv.hip).
-    x [M,S,S,Cin] NHWC; w_deconv [4*Cmid,Cin] (`pack_mask_deconv`); w_pred [K,Cmid]; classes [M] int32 or None (class 0);
-    num_valid: device int32, rows past it are neither read nor written.  Returns prob [M,2S,2S] (`out` when given)."""
-    _req_cuda(x, w_deconv, b_deconv, w_pred, b_pred, classes, num_valid, status)
+def _check_num_valid(num_valid):
+    """The `num_valid` operand of the mask and keypoint kernels: None or ONE device int32."""
+    if num_valid is not None:
+        assert num_valid.dtype == torch.int32 and num_valid.numel() == 1
+
+
+def _mask_tail_args(x, w_deconv, b_deconv, w_pred, b_pred, classes, num_valid):
     M, S, S_, cin = x.shape
     assert S == S_ and x.is_contiguous() and x.dtype == torch.float32
     cmid = w_deconv.shape[0] // 4
@@ -3439,8 +3434,16 @@ def mask_deconv_predict(x, w_deconv, b_deconv, w_pred, b_pred, classes=None, num
         assert b is None or (b.numel() == n and b.is_contiguous() and b.dtype == torch.float32)
     if classes is not None:
         assert classes.dtype == torch.int32 and classes.is_contiguous() and classes.numel() == M
-    if num_valid is not None:
-        assert num_valid.dtype == torch.int32 and num_valid.numel() == 1
+    _check_num_valid(num_valid)
+    return M, S, cin, cmid, Kc, w_pred
+
+
+def mask_deconv_predict(x, w_deconv, b_deconv, w_pred, b_pred, classes=None, num_valid=None, status=None, out=None):
+    """Deconv 2x2 s2 + bias + ReLU + 1x1 predictor of one class per row + bias + sigmoid (csrc/mask_deconv.hip).
+    x [M,S,S,Cin] NHWC; w_deconv [4*Cmid,Cin] (`pack_mask_deconv`); w_pred [K,Cmid]; classes [M] int32 or None (class 0);
+    num_valid: device int32, rows past it are neither read nor written.  Returns prob [M,2S,2S] (`out` when given)."""
+    _req_cuda(x, w_deconv, b_deconv, w_pred, b_pred, classes, num_valid, status)
+    M, S, cin, cmid, Kc, w_pred = _mask_tail_args(x, w_deconv, b_deconv, w_pred, b_pred, classes, num_valid)
     if out is None:
         out = torch.empty(M, 2 * S, 2 * S, device=x.device, dtype=torch.float32)
     assert out.shape == (M, 2 * S, 2 * S) and out.is_contiguous() and out.dtype == torch.float32
@@ -3533,8 +3536,7 @@ def keypoint_deconv(x, packed, bias, num_keypoints, num_valid=None, out=None):
     rows = _lib.lib().lvc_keypoint_deconv_packed_rows(c_int(k))
     assert packed.shape == (rows, cin) and packed.is_contiguous() and packed.dtype == torch.float32
     assert bias is None or (bias.numel() == k and bias.is_contiguous() and bias.dtype == torch.float32)
-    if num_valid is not None:
-        assert num_valid.dtype == torch.int32 and num_valid.numel() == 1
+    _check_num_valid(num_valid)
     if out is None:
         out = torch.empty(M, k, 2 * S, 2 * S, device=x.device, dtype=torch.float32)
     assert out.shape == (M, k, 2 * S, 2 * S) and out.is_contiguous() and out.dtype == torch.float32
@@ -3556,8 +3558,7 @@ def heatmaps_to_keypoints(maps, rois, up=1, num_valid=None, maps_out=None, out=N
     if up * P > KEYPOINT_MAX_SIDE:
         raise NotImplementedError("heatmaps_to_keypoints: a heatmap of side {} (up to {} is built)".format(up * P, KEYPOINT_MAX_SIDE))
     assert rois.shape == (M, 4) and rois.is_contiguous() and rois.dtype == torch.float32, rois.shape
-    if num_valid is not None:
-        assert num_valid.dtype == torch.int32 and num_valid.numel() == 1
+    _check_num_valid(num_valid)
     if maps_out is not None:
         assert maps_out.shape == (M, k, up * P, up * P) and maps_out.is_contiguous() and maps_out.dtype == torch.float32
     if out is None:
@@ -3603,24 +3604,6 @@ def mask_targets(boxes, matched, count, planes, mask_size, out=None):
     return out
 
 
-def _mask_tail_args(x, w_deconv, b_deconv, w_pred, b_pred, classes, num_valid):
-    M, S, S_, cin = x.shape
-    assert S == S_ and x.is_contiguous() and x.dtype == torch.float32
-    cmid = w_deconv.shape[0] // 4
-    mask_deconv_check(cin, cmid)
-    Kc = w_pred.shape[0]
-    assert w_deconv.shape == (4 * cmid, cin) and w_deconv.is_contiguous() and w_deconv.dtype == torch.float32
-    w_pred = w_pred.reshape(Kc, -1)
-    assert w_pred.shape == (Kc, cmid) and w_pred.is_contiguous() and w_pred.dtype == torch.float32
-    for b, n in ((b_deconv, cmid), (b_pred, Kc)):
-        assert b is None or (b.numel() == n and b.is_contiguous() and b.dtype == torch.float32)
-    if classes is not None:
-        assert classes.dtype == torch.int32 and classes.is_contiguous() and classes.numel() == M
-    if num_valid is not None:
-        assert num_valid.dtype == torch.int32 and num_valid.numel() == 1
-    return M, S, cin, cmid, Kc, w_pred
-
-
 def mask_deconv_logits(x, w_deconv, b_deconv, w_pred, b_pred, classes=None, num_valid=None, status=None, out=None):
     """`mask_deconv_predict` without the sigmoid: the logits [M,2S,2S] of each row's class (training: the ground-truth class)."""
     _req_cuda(x, w_deconv, b_deconv, w_pred, b_pred, classes, num_valid, status)
@@ -3642,11 +3625,9 @@ def mask_loss(logits, targets, num_valid=None):
     M, P, P_ = logits.shape
     assert P == P_ and P % 2 == 0 and logits.is_contiguous() and logits.dtype == torch.float32
     assert targets.shape == logits.shape and targets.is_contiguous() and targets.dtype in (torch.uint8, torch.bool)
-    if num_valid is not None:
-        assert num_valid.dtype == torch.int32 and num_valid.numel() == 1
+    _check_num_valid(num_valid)
     lib = _lib.lib()
-    lib.lvc_mask_loss_workspace_bytes.restype = c_longlong
-    nbytes = lib.lvc_mask_loss_workspace_bytes(c_int(M), c_int(P // 2))
+    nbytes = _lib.size_query("lvc_mask_loss_workspace_bytes", c_int(M), c_int(P // 2))
     dev = logits.device
     ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
     loss = torch.empty(1, dtype=torch.float32, device=dev)
@@ -3670,8 +3651,7 @@ def mask_deconv_grad(x, w_deconv, b_deconv, w_pred, classes, logits, targets, nu
     assert upstream.dtype == torch.float32 and upstream.numel() == 1
     dev = x.device
     lib = _lib.lib()
-    lib.lvc_mask_deconv_grad_workspace_bytes.restype = c_longlong
-    nbytes = lib.lvc_mask_deconv_grad_workspace_bytes(c_int(M), c_int(S), c_int(cmid))
+    nbytes = _lib.size_query("lvc_mask_deconv_grad_workspace_bytes", c_int(M), c_int(S), c_int(cmid))
     ws = torch.empty((nbytes + 15) // 16 * 4, dtype=torch.float32, device=dev)
     dh = torch.empty(M * S * S, 4 * cmid, dtype=torch.float32, device=dev)
     dwp = torch.empty(Kc, cmid, dtype=torch.float32, device=dev)
@@ -3685,8 +3665,7 @@ def mask_deconv_grad(x, w_deconv, b_deconv, w_pred, classes, logits, targets, nu
     if M > 0 and need_dx:       # dx = dh @ Wd_packed on the forward GEMM kernel (range-free split: unscaled gradients are tiny)
         dx = linear_backward(x.view(M * S * S, cin), w_deconv, dh, need_dx=True, need_dw=False)[0].view(M, S, S, cin)      # (x: its shape only)
     if M > 0 and need_dw:       # dWd = dh^T @ x: conv_wgrad joins its pixel slices with atomics, this product must be bit-stable
-        lib.lvc_mask_deconv_wgrad_workspace_bytes.restype = c_longlong
-        wbytes = lib.lvc_mask_deconv_wgrad_workspace_bytes(c_int(M), c_int(S), c_int(cin), c_int(cmid))
+        wbytes = _lib.size_query("lvc_mask_deconv_wgrad_workspace_bytes", c_int(M), c_int(S), c_int(cin), c_int(cmid))
         wws = torch.empty(wbytes // 4, dtype=torch.float32, device=dev)
         dw = torch.empty(4 * cmid, cin, dtype=torch.float32, device=dev)
         check(lib.lvc_mask_deconv_wgrad(ptr(dh), ptr(x), ptr(num_valid), ptr(dw), c_int(M), c_int(S), c_int(cin), c_int(cmid), ptr(wws),
@@ -3754,8 +3733,7 @@ def _keypoint_entry_args(low, target, valid, num_valid):
     keypoint_deconv_check(KEYPOINT_DECONV_CIN, k)
     assert target.dtype == torch.int32 and target.is_contiguous() and target.numel() == M * k
     assert valid.dtype == torch.uint8 and valid.is_contiguous() and valid.numel() == M * k
-    if num_valid is not None:
-        assert num_valid.dtype == torch.int32 and num_valid.numel() == 1
+    _check_num_valid(num_valid)
     return M, k, P // 2
 
 
@@ -3832,8 +3810,7 @@ def keypoint_deconv_dx(dlow, packed, num_keypoints, num_valid=None, out=None):
     keypoint_deconv_check(cin, k)
     assert P == P_ and P % 2 == 0 and kc_ == kc and dlow.is_contiguous() and dlow.dtype == torch.float32, dlow.shape
     assert packed.shape == (cin, 16 * kc) and packed.is_contiguous() and packed.dtype == torch.float32
-    if num_valid is not None:
-        assert num_valid.dtype == torch.int32 and num_valid.numel() == 1
+    _check_num_valid(num_valid)
     S = P // 2
     if out is None:
         out = torch.zeros(M, S, S, cin, device=dlow.device, dtype=torch.float32)
@@ -3853,11 +3830,9 @@ def keypoint_deconv_wgrad(x, dlow, num_keypoints, num_valid=None):
     keypoint_deconv_check(cin, k)
     assert S == S_ and x.is_contiguous() and x.dtype == torch.float32
     assert dlow.shape == (M, 2 * S, 2 * S, kc) and dlow.is_contiguous() and dlow.dtype == torch.float32, dlow.shape
-    if num_valid is not None:
-        assert num_valid.dtype == torch.int32 and num_valid.numel() == 1
+    _check_num_valid(num_valid)
     lib = _lib.lib()
-    lib.lvc_keypoint_deconv_wgrad_workspace_bytes.restype = c_longlong
-    nbytes = lib.lvc_keypoint_deconv_wgrad_workspace_bytes(c_int(M), c_int(S), c_int(cin), c_int(k))
+    nbytes = _lib.size_query("lvc_keypoint_deconv_wgrad_workspace_bytes", c_int(M), c_int(S), c_int(cin), c_int(k))
     ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=x.device)
     dw = torch.empty(cin, 16 * kc, dtype=torch.float32, device=x.device)
     db = torch.empty(k, dtype=torch.float32, device=x.device)

@@ -243,10 +243,10 @@ class GeneralizedRCNN(_RCNNBase):
 
         rpn, heads = self.proposal_generator, self.roi_heads
         boxes, logits, count, proposal_losses, rpn_counts, gt, gt_off = rpn.forward_train_batched(images, features, gt_instances)
-        detector_losses, cnt, stats = heads.forward_train_batched(features, boxes, logits, count, gt, gt_off, gt_instances)
+        detector_losses, cnt, (stats, layout) = heads.forward_train_batched(features, boxes, logits, count, gt, gt_off, gt_instances)
         B, bs = boxes.shape[0], heads.batch_size_per_image
         meta = torch.cat([count.long(), rpn_counts.view(-1).long(), cnt.view(-1).long(), stats.long(), K.range_summary(self.device).long()]).tolist()
-        pc, rc, cc, st, flagged = meta[:B], meta[B:3 * B], meta[3 * B:5 * B], meta[5 * B:-1], meta[-1]      # (st: 4 counts; a mask model: 9; a keypoint model: 4 + 2B + 2)
+        pc, rc, cc, st, flagged = meta[:B], meta[B:3 * B], meta[3 * B:5 * B], meta[5 * B:-1], meta[-1]      # (st: the heads' counts, named by `layout`)
         if flagged:
             K.check_conv_error_word(self.device)      # re-routes the layers concerned and raises: `run_with_fallbacks` repeats the pass
         self.__dict__["_range_checked"] = True
@@ -255,7 +255,7 @@ class GeneralizedRCNN(_RCNNBase):
         storage.put_scalar("rpn/num_neg_anchors", sum(rc[1::2]) / B)
         counts = [(cc[2 * i], cc[2 * i + 1]) for i in range(B)]
         if all(a + b == bs for a, b in counts):
-            heads.log_train_scalars(counts, st, B * bs)
+            heads.log_train_scalars(counts, st, layout, B * bs)
         else:
             proposals = []
             for i, size in enumerate(images.image_sizes):
@@ -325,37 +325,32 @@ class GeneralizedRCNN(_RCNNBase):
     def _keypoint_on(self):
         return bool(getattr(self.roi_heads, "keypoint_on", False))
 
+    def _enable_branch_training(self, name, on):
+        heads = self.roi_heads
+        if type(heads) is not StandardROIHeads:      # (CascadeROIHeads builds no mask branch whatever MODEL.MASK_ON says)
+            raise NotImplementedError("MODEL.ROI_HEADS.NAME = {}: the {} branch and its training are built for StandardROIHeads"
+                                      .format(type(heads).__name__, name))
+        if not getattr(heads, name + "_on", False):
+            raise ValueError("enable_{}_training: the model was built with MODEL.{}_ON = False".format(name, name.upper()))
+        head = getattr(heads, name + "_head")
+        if on and getattr(head, "vis_period", 0) > 0:
+            raise NotImplementedError("VIS_PERIOD > 0: visualising the mask predictions is not built")
+        for owner in (self, heads, head):
+            owner.__dict__["_{}_train_enabled".format(name)] = bool(on)
+        return self
+
     def enable_mask_training(self, on=True):
         """Switch the training forward of a MODEL.MASK_ON model on (or off again); returns self.  Without the call a mask model in
         training mode refuses, as before.  Settings the training path does not build raise here, on the host, naming their key;
         ground-truth masks that are not BitMasks raise in the step (INPUT.MASK_FORMAT "bitmask")."""
-        heads = self.roi_heads
-        if type(heads) is not StandardROIHeads:      # (CascadeROIHeads builds no mask branch whatever MODEL.MASK_ON says)
-            raise NotImplementedError("MODEL.ROI_HEADS.NAME = {}: the mask branch and its training are built for StandardROIHeads"
-                                      .format(type(heads).__name__))
-        if not self._mask_on():
-            raise ValueError("enable_mask_training: the model was built with MODEL.MASK_ON = False")
-        if on:
-            if heads.mask_head.vis_period > 0:
-                raise NotImplementedError("VIS_PERIOD > 0: visualising the mask predictions is not built")
-        for owner in (self, heads, heads.mask_head):
-            owner.__dict__["_mask_train_enabled"] = bool(on)
-        return self
+        return self._enable_branch_training("mask", on)
 
     def enable_keypoint_training(self, on=True):
         """Switch the training forward of a MODEL.KEYPOINT_ON model on (or off again); returns self.  Without the call a keypoint model
         in training mode refuses, as before.  The ground truth of every image carries `gt_keypoints` (structures.Keypoints [n, K, 3]);
         the losses gain `loss_keypoint`, the logged scalars `keypoint_head/num_fg_samples` and, for a step without a valid
         keypoint, `kpts_num_skipped_batches`."""
-        heads = self.roi_heads
-        if type(heads) is not StandardROIHeads:
-            raise NotImplementedError("MODEL.ROI_HEADS.NAME = {}: the keypoint branch and its training are built for StandardROIHeads"
-                                      .format(type(heads).__name__))
-        if not self._keypoint_on():
-            raise ValueError("enable_keypoint_training: the model was built with MODEL.KEYPOINT_ON = False")
-        for owner in (self, heads, heads.keypoint_head):
-            owner.__dict__["_keypoint_train_enabled"] = bool(on)
-        return self
+        return self._enable_branch_training("keypoint", on)
 
     def _inference_given_boxes(self, batched_inputs, detected_instances, do_postprocess):
         """reference detectron2 rcnn.py `inference(detected_instances=...)`: the given boxes and classes (network coordinates) get the

@@ -25,6 +25,7 @@ from ...layers import Conv2d, ConvTranspose2d, ShapeSpec
 from ...layers.layout import to_nhwc
 from ...utils.events import get_event_storage
 from ...utils.registry import Registry
+from .tail import Tail, tail_loss_of_instances
 
 ROI_KEYPOINT_HEAD_REGISTRY = Registry("ROI_KEYPOINT_HEAD")
 
@@ -93,21 +94,7 @@ class KeypointTailLoss(torch.autograd.Function):
         return (dx, dw if need[1] else None, db if has_bias and need[2] else None) + (None,) * 8
 
 
-class KeypointTail:
-    """What `KRCNNConvDeconvUpsampleHead.layers` returns in the reference -- the logits [M, K, 4S, 4S] -- as the operands they would be
-    computed from: `x` [M, S, S, C] (channels-last, after the conv_fcn convs) and the head that owns `score_lowres`."""
-
-    def __init__(self, x, head):
-        self.x, self.head = x, head
-
-    @property
-    def shape(self):
-        M, S = self.x.shape[0], self.x.shape[1]
-        side = 2 * self.head.up_scale * S
-        return (M, self.head.num_keypoints, side, side)
-
-    def size(self, dim):
-        return self.shape[dim]
+KeypointTail = Tail      # (the logits [M, K, 4S, 4S] as their operands)
 
 
 def keypoint_rcnn_loss(pred_keypoint_logits, instances, normalizer):
@@ -118,26 +105,19 @@ def keypoint_rcnn_loss(pred_keypoint_logits, instances, normalizer):
     if not isinstance(pred_keypoint_logits, KeypointTail):
         raise TypeError("keypoint_rcnn_loss takes the head's KeypointTail: the logits [M, K, 4S, 4S] are never formed")
     tail = pred_keypoint_logits
-    side = tail.shape[2]
-    dev = tail.x.device
-    heatmaps, valid = [], []
-    for per_image in instances:
-        if len(per_image) == 0:
-            continue
-        h, v = per_image.gt_keypoints.to_heatmap(per_image.proposal_boxes.tensor.to(dev), side)
-        heatmaps.append(h)
-        valid.append(v)
-    if len(heatmaps) == 0:
-        log_skipped_batch()
-        return tail.x.sum() * 0
-    target = torch.cat(heatmaps, 0).to(torch.int32).contiguous()
-    vflag = torch.cat(valid, 0).to(torch.uint8).contiguous()
-    assert target.shape[0] == tail.x.shape[0], "keypoint_rcnn_loss: {} rows of features, {} instances".format(tail.x.shape[0], target.shape[0])
-    status = K.new_status(dev)
-    loss, _total, count = tail.head.tail_loss(tail.x, target, vflag, status=status, normalizer=normalizer, loss_weight=1.0)
-    meta = torch.cat([count, status.long()]).tolist()      # the reference reads valid.numel() here
-    check_keypoint_status(meta[1], side)
-    if meta[0] == 0:
+
+    def per_image(inst, side):
+        return inst.gt_keypoints.to_heatmap(inst.proposal_boxes.tensor.to(tail.x.device), side)
+
+    def tail_loss(rows, status):
+        loss, _total, count = tail.head.tail_loss(tail.x, rows[0].to(torch.int32), rows[1].to(torch.uint8), status=status, normalizer=normalizer,
+                                                  loss_weight=1.0)
+        return loss, count
+
+    loss, meta = tail_loss_of_instances("keypoint", tail, instances, per_image, tail_loss)
+    if meta is not None:      # (meta: the reference reads valid.numel() here)
+        check_keypoint_status(meta[1], tail.shape[2])
+    if meta is None or meta[0] == 0:
         log_skipped_batch()
     return loss
 
@@ -149,6 +129,8 @@ def check_keypoint_status(st, side=None):
 
 @ROI_KEYPOINT_HEAD_REGISTRY.register()
 class KRCNNConvDeconvUpsampleHead(nn.Module):
+    loss_takes_classes = False      # `train_loss` takes the targets only
+
     def __init__(self, cfg, input_shape: ShapeSpec):
         super().__init__()
         H = cfg.MODEL.ROI_KEYPOINT_HEAD
@@ -160,6 +142,7 @@ class KRCNNConvDeconvUpsampleHead(nn.Module):
         else:
             self.loss_normalizer = float(self.num_keypoints * cfg.MODEL.ROI_HEADS.BATCH_SIZE_PER_IMAGE * cfg.MODEL.ROI_HEADS.POSITIVE_FRACTION)
         self.up_scale = 2
+        self.map_scale = 2 * self.up_scale      # the maps are map_scale x the pooled side
         conv_dims = list(H.CONV_DIMS)
         self.blocks = []
         cur = input_shape.channels
@@ -177,11 +160,18 @@ class KRCNNConvDeconvUpsampleHead(nn.Module):
                 # Caffe2's MSRAFill (reference keypoint_head.py:242-248)
                 nn.init.kaiming_normal_(param, mode="fan_out", nonlinearity="relu")
 
-    def lowres_nhwc(self, pooled, num_valid=None):
-        """pooled [M, S, S, C] channels-last -> the low-resolution logit planes [M, K, 2S, 2S] (rows past num_valid are not written)."""
-        x = pooled
+    @property
+    def num_maps(self):
+        return self.num_keypoints
+
+    def _convs_nhwc(self, x):
         for layer in self.blocks:
             x = layer.forward_nhwc(x)
+        return x
+
+    def lowres_nhwc(self, pooled, num_valid=None):
+        """pooled [M, S, S, C] channels-last -> the low-resolution logit planes [M, K, 2S, 2S] (rows past num_valid are not written)."""
+        x = self._convs_nhwc(pooled)
         return K.keypoint_deconv(x.contiguous(), self.score_lowres.packed(), self.score_lowres.bias, self.num_keypoints,
                                  num_valid=num_valid)
 
@@ -214,10 +204,20 @@ class KRCNNConvDeconvUpsampleHead(nn.Module):
         (`kernels.keypoint_targets`); num_valid: device int32 [1] (the convs run on all rows, `score_lowres`, loss and backward on
         the rows below it); num_images: the images of the batch (the fixed normaliser's factor).
         -> (loss_keypoint scalar, LOSS_WEIGHT applied; fp64 sum [1]; valid count int64 [1])."""
-        x = pooled
-        for layer in self.blocks:
-            x = layer.forward_nhwc(x)
-        return self.tail_loss(x, target, valid, num_valid=num_valid, status=status, normalizer=self.normalizer(num_images))
+        return self.tail_loss(self._convs_nhwc(pooled), target, valid, num_valid=num_valid, status=status, normalizer=self.normalizer(num_images))
+
+    def train_targets(self, boxes, matched, count, gt_keypoints, side):
+        """The branch's targets on the padded tables (`StandardROIHeads._branch_loss_batched`): boxes [B, R, 4], matched int64 [B, R],
+        count int32 [B], gt_keypoints: one Keypoints per image; one launch makes targets, valid flags and the row selection
+        -> ((target int32, valid uint8 [B*R, K]), its counts by name: the selected and the foreground rows of every image)."""
+        with torch.no_grad():
+            target, valid, _selected, sel_count = K.keypoint_targets(boxes, matched, count, [k.tensor.contiguous() for k in gt_keypoints], side)
+        return (target, valid), {"selected": sel_count, "fg": count}
+
+    def train_loss(self, pooled, rows, num_valid, status, num_images):
+        """rows: (target, valid) in the order of `pooled` -> (loss_keypoint, its counts by name)."""
+        loss, _sum, vcount = self.loss_nhwc(pooled, rows[0], rows[1], num_valid=num_valid, status=status, num_images=num_images)
+        return loss, {"valid": vcount}
 
     def layers(self, x):
         """Reference signature: x [M, C, S, S] -> the logits [M, K, 4S, 4S] (the decode kernel's `maps_out`; the boxes are dummies)."""
@@ -239,8 +239,7 @@ class KRCNNConvDeconvUpsampleHead(nn.Module):
                 raise NotImplementedError(TRAIN_REFUSAL)
             h = to_nhwc(x).contiguous()
             if h.shape[0] > 0:      # (no instance at all: the convs take no empty batch, and the loss below is x.sum() * 0)
-                for layer in self.blocks:
-                    h = layer.forward_nhwc(h)
+                h = self._convs_nhwc(h)
             loss = keypoint_rcnn_loss(KeypointTail(h, self), instances, normalizer=self.normalizer(len(instances)))
             return {"loss_keypoint": loss * self.loss_weight}
         boxes = torch.cat([i.pred_boxes.tensor for i in instances]).to(torch.float32)

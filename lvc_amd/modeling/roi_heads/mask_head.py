@@ -23,6 +23,7 @@ from ...layers.layout import to_nhwc
 from ...utils import weight_init
 from ...utils.events import get_event_storage
 from ...utils.registry import Registry
+from .tail import Tail, tail_loss_of_instances
 
 ROI_MASK_HEAD_REGISTRY = Registry("ROI_MASK_HEAD")
 
@@ -69,16 +70,7 @@ class MaskTailLoss(torch.autograd.Function):
         return dx, dwd, dbd, dwp.view(wp_shape), dbp, None, None, None, None, None
 
 
-class MaskTail:
-    """What `MaskRCNNConvUpsampleHead.layers` would return in the reference -- the all-class logits [M, K, 2S, 2S] -- as the operands
-    they would be computed from: `x` [M, S, S, C] (channels-last, after the mask_fcn convs) and the head that owns deconv and predictor."""
-
-    def __init__(self, x, head):
-        self.x, self.head = x, head
-
-    def size(self, dim):
-        M, S = self.x.shape[0], self.x.shape[1]
-        return (M, self.head.num_classes, 2 * S, 2 * S)[dim]
+MaskTail = Tail      # (the all-class logits [M, K, 2S, 2S] as their operands)
 
 
 def mask_scalars(counts, numel):
@@ -113,30 +105,32 @@ def mask_rcnn_loss(pred_mask_logits, instances, vis_period=0):
         raise NotImplementedError("VIS_PERIOD > 0: visualising the mask predictions is not built")
     if not isinstance(pred_mask_logits, MaskTail):
         raise TypeError("mask_rcnn_loss takes the head's MaskTail: the all-class logits [M, K, 2S, 2S] are never formed")
-    tail, head = pred_mask_logits, pred_mask_logits.head
-    side = tail.size(2)
-    gt_classes, gt_masks = [], []
-    for per_image in instances:
-        if len(per_image) == 0:
-            continue
-        gt_classes.append(per_image.gt_classes.to(torch.int32))
-        gt_masks.append(_require_bitmasks(per_image.gt_masks).crop_and_resize(per_image.proposal_boxes.tensor, side))
-    if len(gt_masks) == 0:
-        return tail.x.sum() * 0
-    targets = torch.cat(gt_masks, dim=0).to(tail.x.device).contiguous()
-    assert targets.shape[0] == tail.x.shape[0], "mask_rcnn_loss: {} rows of features, {} instances".format(tail.x.shape[0], targets.shape[0])
-    classes = None if head.cls_agnostic_mask else torch.cat(gt_classes).to(tail.x.device).contiguous()
-    status = K.new_status(tail.x.device)
-    loss, _total, counts = head.tail_loss(tail.x, classes, targets, status=status)
-    meta = torch.cat([counts, status.long()]).tolist()      # the reference reads its three scalars with .item()
-    if meta[3] & K.MASK_BAD_CLASS:
+    head = pred_mask_logits.head
+
+    def per_image(inst, side):
+        classes = inst.gt_classes.to(torch.int32)
+        planes = _require_bitmasks(inst.gt_masks).crop_and_resize(inst.proposal_boxes.tensor, side)
+        return (planes,) if head.cls_agnostic_mask else (classes, planes)
+
+    def tail_loss(rows, status):
+        loss, _total, counts = head.tail_loss(pred_mask_logits.x, rows[0] if len(rows) == 2 else None, rows[-1], status=status)
+        return loss, counts
+
+    loss, meta = tail_loss_of_instances("mask", pred_mask_logits, instances, per_image, tail_loss)
+    if meta is None:
+        return loss
+    if meta[3] & K.MASK_BAD_CLASS:      # (meta: the reference reads its three scalars with .item())
         raise IndexError("mask head: a ground-truth class lies outside [0, {})".format(head.num_classes))
-    log_mask_scalars(meta[:3], targets.numel())
+    side = pred_mask_logits.shape[2]
+    log_mask_scalars(meta[:3], pred_mask_logits.x.shape[0] * side * side)
     return loss
 
 
 @ROI_MASK_HEAD_REGISTRY.register()
 class MaskRCNNConvUpsampleHead(nn.Module):
+    map_scale = 2                   # the maps are map_scale x the pooled side
+    loss_takes_classes = True       # `train_loss` takes the rows' classes before the targets
+
     def __init__(self, cfg, input_shape: ShapeSpec):
         super().__init__()
         H = cfg.MODEL.ROI_MASK_HEAD
@@ -162,6 +156,15 @@ class MaskRCNNConvUpsampleHead(nn.Module):
         nn.init.normal_(self.predictor.weight, std=0.001)
         nn.init.constant_(self.predictor.bias, 0)
 
+    @property
+    def num_maps(self):
+        return self.num_classes
+
+    def _convs_nhwc(self, x):
+        for layer in self.conv_norm_relus:
+            x = layer.forward_nhwc(x)
+        return x
+
     def forward_nhwc(self, pooled, classes=None, num_valid=None, status=None):
         """pooled [M, S, S, C] channels-last RoI maps; classes [M] int32 (ignored with CLS_AGNOSTIC_MASK); num_valid: device int32,
         rows past it are skipped by the tail kernel.  Returns prob [M, 2S, 2S]: the predicted class's mask probabilities."""
@@ -169,8 +172,7 @@ class MaskRCNNConvUpsampleHead(nn.Module):
         M, S = x.shape[0], x.shape[1]
         if M == 0:
             return x.new_zeros((0, 2 * S, 2 * S))
-        for layer in self.conv_norm_relus:
-            x = layer.forward_nhwc(x)
+        x = self._convs_nhwc(x)
         if self.cls_agnostic_mask:
             classes = None
         elif classes is None:
@@ -185,9 +187,7 @@ class MaskRCNNConvUpsampleHead(nn.Module):
         if self.training:
             if not self.__dict__.get("_mask_train_enabled", False):
                 raise NotImplementedError("training the mask branch (mask_rcnn_loss) is not built")
-            h = to_nhwc(x).contiguous()
-            for layer in self.conv_norm_relus:
-                h = layer.forward_nhwc(h)
+            h = self._convs_nhwc(to_nhwc(x).contiguous())
             return {"loss_mask": mask_rcnn_loss(MaskTail(h, self), instances, self.vis_period)}
         classes = None
         if not self.cls_agnostic_mask:
@@ -211,10 +211,18 @@ class MaskRCNNConvUpsampleHead(nn.Module):
         """Training on padded rows, nothing read back: pooled [M, S, S, C]; classes int32 [M]: the ground-truth classes; targets uint8
         [M, 2S, 2S]; num_valid: device int32 [1] (the convs run on all rows, tail and loss on the rows below it).
         -> (loss scalar, fp64 sum [1], counts int64 [3])."""
-        x = pooled
-        for layer in self.conv_norm_relus:
-            x = layer.forward_nhwc(x)
-        return self.tail_loss(x, classes, targets, num_valid=num_valid, status=status)
+        return self.tail_loss(self._convs_nhwc(pooled), classes, targets, num_valid=num_valid, status=status)
+
+    def train_targets(self, boxes, matched, count, gt_masks, side):
+        """The branch's targets on the padded tables (`StandardROIHeads._branch_loss_batched`): boxes [B, R, 4], matched int64 [B, R],
+        count int32 [B], gt_masks: one BitMasks per image -> ((targets uint8 [B*R, side, side],), no counts of its own)."""
+        planes = [_require_bitmasks(m).tensor.contiguous() for m in gt_masks]
+        return (K.mask_targets(boxes, matched, count, planes, side),), {}
+
+    def train_loss(self, pooled, rows, num_valid, status, num_images):
+        """rows: (classes int32, targets) in the order of `pooled` -> (loss_mask, its counts by name)."""
+        loss, _sum, counts = self.loss_nhwc(pooled, rows[0].contiguous(), rows[1], num_valid=num_valid, status=status)
+        return loss, {"pixels": counts, "rows": num_valid}
 
     def layers(self, x):
         raise NotImplementedError("MaskRCNNConvUpsampleHead.layers (all-class mask logits) is not built: the kernel computes the "

@@ -348,64 +348,33 @@ class StandardROIHeads(ROIHeads):
         pooled, _rois, rows, total, order = self._pool_branch("mask", feats_nhwc, boxes, count, status=status)
         return pooled, classes.reshape(-1).index_select(0, order).contiguous(), rows, total
 
-    def mask_loss_batched(self, feats_nhwc, s_boxes, s_cls, s_m, fg_count, gt_masks, status=None):
-        """The mask branch's training loss on the sampler's padded tables, with no device->host read (reference roi_heads.py
-        `_forward_mask` + `select_foreground_proposals` + mask_rcnn_loss).  s_boxes [B, R, 4], s_cls [B, R], s_m [B, R] int64 (the
-        matched gt index of every sampled row), fg_count [B] int32 on the device: foreground comes before background in the sampled
-        table, so the foreground rows of image b are its first fg_count[b], at most int(BATCH_SIZE_PER_IMAGE * POSITIVE_FRACTION);
-        gt_masks: one BitMasks per image.  The foreground rows move to the front (as `pool_masks_batched` does), the mask pooler and
-        the mask_fcn convs run under autograd on ALL padded rows (zero boxes), and the total of foreground rows is the `num_valid` of
-        tail, loss and backward.  -> (loss_mask scalar, counts int64 [3], total int32 [1])."""
-        from .mask_head import _require_bitmasks
-
-        if not self.mask_on:
-            raise RuntimeError("mask_loss_batched: the model was built with MODEL.MASK_ON = False")
+    def _branch_loss_batched(self, name, feats_nhwc, s_boxes, s_cls, s_m, fg_count, gt, status):
+        """The training loss of the mask or keypoint branch `name` on the sampler's padded tables, with no device->host read (reference
+        roi_heads.py `_forward_mask` / `_forward_keypoint` + `select_foreground_proposals` + the branch's loss).  s_boxes [B, R, 4], s_cls
+        [B, R], s_m [B, R] int64 (the matched gt index of every sampled row), fg_count [B] int32 on the device: foreground comes before
+        background in the sampled table, so the foreground rows of image b are its first fg_count[b], at most
+        int(BATCH_SIZE_PER_IMAGE * POSITIVE_FRACTION); gt: one BitMasks / Keypoints per image.  One launch makes the targets (the head's
+        `train_targets`; a foreground row the reference's keypoint selection would drop keeps its place and contributes nothing), the
+        foreground rows move to the front (`front_rows`), the branch's pooler and convs run under autograd on ALL padded rows (zero
+        boxes), and the total of foreground rows is the `num_valid` of tail, loss and backward (the head's `train_loss`).
+        -> (loss scalar, the branch's counts: "<name>.<count>" -> device tensor, in the order they are packed; the last is the status word)."""
+        if not getattr(self, name + "_on"):
+            raise RuntimeError("{}_loss_batched: the model was built with MODEL.{}_ON = False".format(name, name.upper()))
+        head, pooler = getattr(self, name + "_head"), getattr(self, name + "_pooler")
         cap = max(int(self.batch_size_per_image * self.positive_sample_fraction), 1)
         R = min(cap, s_boxes.shape[1])
         boxes = s_boxes[:, :R].detach().contiguous()
         matched = s_m[:, :R].to(torch.int64).contiguous()
         count = fg_count.to(torch.int32).clamp(min=0, max=R)
-        planes = [_require_bitmasks(m).tensor.contiguous() for m in gt_masks]
-        side = 2 * self.mask_pooler.output_size[0]
-        targets = K.mask_targets(boxes, matched, count, planes, side)
-        feats = [feats_nhwc[f] for f in self.mask_in_features]
-        rois, levels, _rows, total, order = front_rows(boxes, count, self.mask_pooler, len(feats))
-        cls = s_cls[:, :R].to(torch.int32).reshape(-1).index_select(0, order).contiguous()
-        targets = targets.index_select(0, order)
-        pooled = self.mask_pooler.pool_rois_nhwc(feats, rois, levels, num_valid=total, status=status)
-        loss, _sum, counts = self.mask_head.loss_nhwc(pooled, cls, targets, num_valid=total, status=status)
-        return loss, counts, total
-
-    def keypoint_loss_batched(self, feats_nhwc, s_boxes, s_cls, s_m, fg_count, gt_keypoints, status=None):
-        """The keypoint branch's training loss on the sampler's padded tables, with no device->host read (reference roi_heads.py
-        `_forward_keypoint` + `select_foreground_proposals` + `select_proposals_with_visible_keypoints` + keypoint_rcnn_loss).
-        s_boxes [B, R, 4], s_cls [B, R], s_m [B, R] int64 (the matched gt index of every sampled row), fg_count [B] int32 on the
-        device: foreground comes before background in the sampled table, so the foreground rows of image b are its first
-        fg_count[b], at most int(BATCH_SIZE_PER_IMAGE * POSITIVE_FRACTION); gt_keypoints: one Keypoints per image.  One launch makes
-        targets, valid flags and the row selection (a foreground row the reference would drop keeps its place and contributes
-        nothing: its valid flags are cleared); the foreground rows move to the front (`front_rows`), the keypoint pooler and the
-        conv_fcn convs run under autograd on ALL padded rows (zero boxes), and the total of foreground rows is the `num_valid` of
-        `score_lowres`, loss and backward.
-        -> (loss_keypoint scalar, valid count int64 [1], selected rows per image int32 [B], foreground rows per image int32 [B])."""
-        if not self.keypoint_on:
-            raise RuntimeError("keypoint_loss_batched: the model was built with MODEL.KEYPOINT_ON = False")
-        cap = max(int(self.batch_size_per_image * self.positive_sample_fraction), 1)
-        R = min(cap, s_boxes.shape[1])
-        B = s_boxes.shape[0]
-        boxes = s_boxes[:, :R].detach().contiguous()
-        matched = s_m[:, :R].to(torch.int64).contiguous()
-        count = fg_count.to(torch.int32).clamp(min=0, max=R)
-        head = self.keypoint_head
-        side = 2 * head.up_scale * self.keypoint_pooler.output_size[0]
-        with torch.no_grad():
-            target, valid, _selected, sel_count = K.keypoint_targets(boxes, matched, count, [k.tensor.contiguous() for k in gt_keypoints], side)
-        feats = [feats_nhwc[f] for f in self.keypoint_in_features]
-        rois, levels, _rows, total, order = front_rows(boxes, count, self.keypoint_pooler, len(feats))
-        target = target.index_select(0, order)
-        valid = valid.index_select(0, order)
-        pooled = self.keypoint_pooler.pool_rois_nhwc(feats, rois, levels, num_valid=total, status=status)
-        loss, _sum, vcount = head.loss_nhwc(pooled, target, valid, num_valid=total, status=status, num_images=B)
-        return loss, vcount, sel_count, count
+        rows, target_counts = head.train_targets(boxes, matched, count, gt, head.map_scale * pooler.output_size[0])
+        feats = [feats_nhwc[f] for f in getattr(self, name + "_in_features")]
+        rois, levels, _rows, total, order = front_rows(boxes, count, pooler, len(feats))
+        if head.loss_takes_classes:
+            rows = (s_cls[:, :R].to(torch.int32).reshape(-1),) + rows
+        rows = [t.index_select(0, order) for t in rows]
+        pooled = pooler.pool_rois_nhwc(feats, rois, levels, num_valid=total, status=status)
+        loss, counts = head.train_loss(pooled, rows, total, status, s_boxes.shape[0])
+        return loss, {name + "." + k: v for k, v in dict(counts, **target_counts, status=status).items()}
 
     def forward_masks_batched(self, feats_nhwc, boxes, classes, count, status=None):
         """The mask branch on padded batch tensors, nothing read back.  feats_nhwc: dict name -> [B,H,W,C]; boxes [B,topk,4] in network
@@ -432,38 +401,32 @@ class StandardROIHeads(ROIHeads):
         kp = self.keypoint_head.forward_nhwc(pooled, rois[:, 1:5].contiguous(), num_valid=total, status=status)
         return kp, rows
 
-    def _keypoints_given_boxes(self, features, instances):
-        feats = {f: to_nhwc(features[f]) for f in self.keypoint_in_features}
-        dev = feats[self.keypoint_in_features[0]].device
-        require_device(feats[self.keypoint_in_features[0]], "StandardROIHeads")
-        boxes, counts = padded_boxes(instances, "pred_boxes", dev)
-        status = K.new_status(dev)
-        kp, _rows = self.forward_keypoints_batched(feats, boxes, torch.tensor(counts, dtype=torch.int32, device=dev), status=status)
-        check_status(int(status.item()))
-        keypoint_rcnn_inference(kp, instances)
-        return instances
-
     def forward_with_given_boxes(self, features, instances):
         """Reference signature (detectron2 roi_heads.py:681-706): `instances` carry `pred_boxes` and `pred_classes` (network
         coordinates) and get `pred_masks` [n, 1, 2S, 2S], the predicted class's mask probabilities (a mask model), or
         `pred_keypoints` [n, K, 3] = (x, y, score) in network coordinates (a keypoint model)."""
         assert not self.training
         assert instances[0].has("pred_boxes") and instances[0].has("pred_classes")
-        if self.keypoint_on:
-            return self._keypoints_given_boxes(features, instances)
-        if not self.mask_on:
+        if not self._branches():
             return instances
-        feats = {f: to_nhwc(features[f]) for f in self.mask_in_features}
-        dev = feats[self.mask_in_features[0]].device
-        require_device(feats[self.mask_in_features[0]], "StandardROIHeads")
+        name = self._branches()[-1]
+        in_features = getattr(self, name + "_in_features")
+        feats = {f: to_nhwc(features[f]) for f in in_features}
+        dev = feats[in_features[0]].device
+        require_device(feats[in_features[0]], "StandardROIHeads")
         boxes, counts = padded_boxes(instances, "pred_boxes", dev)
-        classes = torch.zeros(boxes.shape[:2], dtype=torch.int32, device=dev)
-        for i, p in enumerate(instances):
-            classes[i, : counts[i]] = p.pred_classes.to(torch.int32)
+        if name == "mask":
+            classes = torch.zeros(boxes.shape[:2], dtype=torch.int32, device=dev)
+            for i, p in enumerate(instances):
+                classes[i, : counts[i]] = p.pred_classes.to(torch.int32)
         status = K.new_status(dev)
-        prob, _rows = self.forward_masks_batched(feats, boxes, classes, torch.tensor(counts, dtype=torch.int32, device=dev), status=status)
+        count = torch.tensor(counts, dtype=torch.int32, device=dev)
+        if name == "mask":
+            out, _rows = self.forward_masks_batched(feats, boxes, classes, count, status=status)
+        else:
+            out, _rows = self.forward_keypoints_batched(feats, boxes, count, status=status)
         check_status(int(status.item()))
-        mask_rcnn_inference(prob, instances)
+        (mask_rcnn_inference if name == "mask" else keypoint_rcnn_inference)(out, instances)
         return instances
 
     def forward_batched(self, feats_nhwc, prop_boxes, prop_count, image_sizes_dev, post=None, status=None):
@@ -528,12 +491,12 @@ class StandardROIHeads(ROIHeads):
     def forward_train_batched(self, features, pboxes, plogits, pcount, gt, gt_off, targets):
         """StandardROIHeads' training branch on the proposal generator's batch tensors, without a device->host read: the sampled rows stay
         one padded [B, bs] table, ROIAlign / box head / losses run on all B * bs rows as if every image had filled its quota (the usual case;
-        padding rows are zero boxes labelled background) and -> (losses, counts int32 [B,2], accuracy counts int64 [4]).  The CALLER reads the
-        counts with the step's other scalars and, if some image did fall short of bs rows, discards these losses and runs the per-image path
-        (`forward`) instead -- the reference's normalisation is by the true row count.
-        A mask model: then the mask branch on the same sampled table.  The accuracy counts grow to int64 [9]: the four of the box branch,
-        the loss kernel's three (incorrect, positive, false-positive pixels), the number of mask rows and the mask kernels' status word
-        -- all read by the caller with the step's other scalars."""
+        padding rows are zero boxes labelled background) and -> (losses, counts int32 [B,2], the step's counts as `pack_step_counts` made
+        them: (int64 vector, layout)).  The CALLER reads the counts with the step's other scalars and, if some image did fall short of bs
+        rows, discards these losses and runs the per-image path (`forward`) instead -- the reference's normalisation is by the true row count.
+        Packed: `box`, the four accuracy counts; then for a mask model `mask.pixels` (the loss kernel's incorrect, positive and
+        false-positive pixels), `mask.rows` and `mask.status`; for a keypoint model `keypoint.valid`, `keypoint.selected` and
+        `keypoint.fg` (the selected and the foreground rows of every image) and `keypoint.status`."""
         from .fast_rcnn import fast_rcnn_losses
 
         s_boxes, _s_logits, s_cls, s_m, s_gtb, cnt = self._sample_batched(pboxes, plogits, pcount, gt, gt_off, targets)
@@ -545,56 +508,54 @@ class StandardROIHeads(ROIHeads):
         losses, pred = fast_rcnn_losses(self.box_predictor, h, s_boxes.view(-1, 4), s_gtb.view(-1, 4), gc)
         with torch.no_grad():
             stats = self._box_stats(pred, gc)
-        if self.mask_on:
-            mfeats = {f: to_nhwc(features[f]) for f in self.mask_in_features}
-            status = K.new_status(s_boxes.device)
-            loss_mask, mcounts, total = self.mask_loss_batched(mfeats, s_boxes, s_cls, s_m, cnt[:, 0], _gt_masks_of(targets), status=status)
+        parts = {"box": stats}
+        for name in self._branches():
+            bfeats = {f: to_nhwc(features[f]) for f in getattr(self, name + "_in_features")}
+            loss, counts = self._branch_loss_batched(name, bfeats, s_boxes, s_cls, s_m, cnt[:, 0], self._gt_of(name, targets),
+                                                     K.new_status(s_boxes.device))
             losses = dict(losses)
-            losses["loss_mask"] = loss_mask
-            with torch.no_grad():
-                stats = torch.cat([stats, mcounts, total.long(), status.long()])
-        if self.keypoint_on:
-            # a keypoint model: the accuracy counts grow to int64 [4 + 2B + 2] -- the valid (row, keypoint) entries, the selected rows
-            # and the foreground rows of every image, the keypoint kernels' status word
-            kfeats = {f: to_nhwc(features[f]) for f in self.keypoint_in_features}
-            status = K.new_status(s_boxes.device)
-            loss_kp, vcount, sel_count, fg = self.keypoint_loss_batched(kfeats, s_boxes, s_cls, s_m, cnt[:, 0], _gt_keypoints_of(targets, self.keypoint_head.num_keypoints), status=status)
-            losses = dict(losses)
-            losses["loss_keypoint"] = loss_kp
-            with torch.no_grad():
-                stats = torch.cat([stats, vcount, sel_count.long(), fg.long(), status.long()])
-        return losses, cnt, stats
+            losses["loss_" + name] = loss
+            parts.update(counts)
+        with torch.no_grad():
+            return losses, cnt, pack_step_counts(parts)
 
-    def log_train_scalars(self, counts, stats, nrows):
-        """EventStorage scalars of label_and_sample_proposals and FastRCNNOutputs._log_accuracy from host values (a mask model: also the
-        three mask_rcnn/* scalars, from the counts `forward_train_batched` appended)."""
+    def _branches(self):
+        """The enabled branches behind the box branch, in the order they run."""
+        return [name for name in ("mask", "keypoint") if getattr(self, name + "_on", False)]
+
+    def _gt_of(self, name, targets):
+        return _gt_masks_of(targets) if name == "mask" else _gt_keypoints_of(targets, self.keypoint_head.num_keypoints)
+
+    def log_train_scalars(self, counts, values, layout, nrows):
+        """EventStorage scalars of label_and_sample_proposals, FastRCNNOutputs._log_accuracy and the enabled branches from host values:
+        the (fg, bg) rows of every image, and the step's counts as `forward_train_batched` packed them (values: the host list, layout: the
+        pack's)."""
+        named = unpack_step_counts(values, layout)
         _log_sample_counts(counts)
-        if self.keypoint_on:
-            self._log_keypoint_scalars(stats[4:])
-        elif len(stats) > 4:
-            self._log_mask_scalars(stats[4:])
-        _log_box_accuracy(stats[:4], nrows)
+        for name in self._branches():
+            getattr(self, "_log_{}_scalars".format(name))(named)
+        _log_box_accuracy(named["box"], nrows)
 
-    def _log_mask_scalars(self, meta):
-        """meta: the host values of (the loss kernel's three counts, the number of mask rows, the mask kernels' status word)."""
+    def _log_mask_scalars(self, c):
+        """c: the host values of the step's counts by name -- `mask.pixels`: the loss kernel's three, `mask.rows`: the number of mask
+        rows, `mask.status`: the mask kernels' status word."""
         from .mask_head import log_mask_scalars
 
-        check_status(meta[4])
-        side = 2 * self.mask_pooler.output_size[0]
-        log_mask_scalars(meta[:3], meta[3] * side * side)
+        check_status(c["mask.status"][0])
+        side = self.mask_head.map_scale * self.mask_pooler.output_size[0]
+        log_mask_scalars(c["mask.pixels"], c["mask.rows"][0] * side * side)
 
-    def _log_keypoint_scalars(self, meta):
-        """meta: the host values of (the valid count, the selected rows of every image, the foreground rows of every image, the
-        keypoint kernels' status word).  keypoint_head/num_fg_samples: the mean of the selected counts over the images that had
-        foreground rows (reference roi_heads.py:95-119); kpts_num_skipped_batches whenever no entry was valid."""
+    def _log_keypoint_scalars(self, c):
+        """c: the host values of the step's counts by name -- `keypoint.valid`: the valid (row, keypoint) entries, `keypoint.selected` /
+        `keypoint.fg`: the selected and the foreground rows of every image, `keypoint.status`: the keypoint kernels' status word.
+        keypoint_head/num_fg_samples: the mean of the selected counts over the images that had foreground rows (reference roi_heads.py:95-119); kpts_num_skipped_batches whenever no entry was valid."""
         from .keypoint_head import check_keypoint_status, log_skipped_batch
 
-        B = (len(meta) - 2) // 2
-        check_keypoint_status(meta[-1])
-        kept = [s for s, f in zip(meta[1:1 + B], meta[1 + B:1 + 2 * B]) if f > 0]
+        check_keypoint_status(c["keypoint.status"][0])
+        kept = [s for s, f in zip(c["keypoint.selected"], c["keypoint.fg"]) if f > 0]
         if kept:
             get_event_storage().put_scalar("keypoint_head/num_fg_samples", sum(kept) / len(kept))
-        if meta[0] == 0:
+        if c["keypoint.valid"][0] == 0:
             log_skipped_batch()
 
     def _forward_train(self, features, proposals, targets):
@@ -632,12 +593,9 @@ class StandardROIHeads(ROIHeads):
         losses, pred = fast_rcnn_losses(self.box_predictor, h, pb, gb, gc)
         # accuracy scalars (reference fast_rcnn.py _log_accuracy): the four counts in ONE device->host read
         _log_box_accuracy(self._box_stats(pred, gc).tolist(), gc.numel())
-        if self.mask_on:
+        for name in self._branches():
             losses = dict(losses)
-            losses["loss_mask"] = self._mask_loss_from_lists(features, proposals, targets, sampled if full else None)
-        if self.keypoint_on:
-            losses = dict(losses)
-            losses["loss_keypoint"] = self._keypoint_loss_from_lists(features, proposals, targets, sampled if full else None)
+            losses["loss_" + name] = self._branch_loss_from_lists(name, features, proposals, targets, sampled if full else None)
         return proposals, losses
 
     def _sampled_tables(self, proposals, targets, sampled, branch):
@@ -660,63 +618,72 @@ class StandardROIHeads(ROIHeads):
         fg_count = ((s_cls >= 0) & (s_cls < self.num_classes)).sum(1).to(torch.int32)
         return s_boxes, s_cls, s_m, fg_count
 
-    def _keypoint_loss_from_lists(self, features, proposals, targets, sampled):
-        """The per-image path's keypoint loss: the tables `keypoint_loss_batched` takes, then one read for the logged values."""
+    def _branch_loss_from_lists(self, name, features, proposals, targets, sampled):
+        """The per-image path's mask or keypoint loss: the tables `_branch_loss_batched` takes, built from the sampled Instances (or the
+        sampler's own tables when they are at hand), then one read for the logged counts."""
         dev = proposals[0].proposal_boxes.tensor.device
-        s_boxes, s_cls, s_m, fg_count = self._sampled_tables(proposals, targets, sampled, "keypoint")
-        kfeats = {f: to_nhwc(features[f]) for f in self.keypoint_in_features}
-        status = K.new_status(dev)
-        loss_kp, vcount, sel_count, fg = self.keypoint_loss_batched(kfeats, s_boxes, s_cls, s_m, fg_count, _gt_keypoints_of(targets, self.keypoint_head.num_keypoints), status=status)
-        self._log_keypoint_scalars(torch.cat([vcount, sel_count.long(), fg.long(), status.long()]).tolist())
-        return loss_kp
+        s_boxes, s_cls, s_m, fg_count = self._sampled_tables(proposals, targets, sampled, name)
+        bfeats = {f: to_nhwc(features[f]) for f in getattr(self, name + "_in_features")}
+        loss, counts = self._branch_loss_batched(name, bfeats, s_boxes, s_cls, s_m, fg_count, self._gt_of(name, targets), K.new_status(dev))
+        vec, layout = pack_step_counts(counts)
+        getattr(self, "_log_{}_scalars".format(name))(unpack_step_counts(vec.tolist(), layout))
+        return loss
 
-    def _mask_loss_from_lists(self, features, proposals, targets, sampled):
-        """The per-image path's mask loss: the tables `mask_loss_batched` takes, built from the sampled Instances (or the sampler's own
-        tables when they are at hand), then one read for the three logged counts."""
-        dev = proposals[0].proposal_boxes.tensor.device
-        s_boxes, s_cls, s_m, fg_count = self._sampled_tables(proposals, targets, sampled, "mask")
-        mfeats = {f: to_nhwc(features[f]) for f in self.mask_in_features}
-        status = K.new_status(dev)
-        loss_mask, mcounts, total = self.mask_loss_batched(mfeats, s_boxes, s_cls, s_m, fg_count, _gt_masks_of(targets), status=status)
-        self._log_mask_scalars(torch.cat([mcounts, total.long(), status.long()]).tolist())
-        return loss_mask
+
+def pack_step_counts(parts):
+    """The counts a training step reads back, as ONE int64 device vector: parts: name -> integer device tensor, in the order packed.
+    -> (vector, layout: ((name, length), ...)); a single part is handed over as it is (no copy)."""
+    tensors = [v.reshape(-1).long() for v in parts.values()]
+    return (tensors[0] if len(tensors) == 1 else torch.cat(tensors)), tuple((k, t.numel()) for k, t in zip(parts, tensors))
+
+
+def unpack_step_counts(values, layout):
+    """The host list read from `pack_step_counts`' vector, back under its names: -> {name: list of that part's values}."""
+    if len(values) != sum(n for _name, n in layout):
+        raise ValueError("unpack_step_counts: {} values for the layout {} ({} values)".format(len(values), layout, sum(n for _name, n in layout)))
+    out, at = {}, 0
+    for name, n in layout:
+        out[name] = values[at:at + n]
+        at += n
+    return out
+
+
+def _gt_field_of(targets, field, branch, check, empty):
+    """The ground-truth `field` of every image (check(value) raises on one the branch does not take); an image without ground truth
+    may come without the field: empty(instances)."""
+    out = []
+    for t in targets:
+        if t.has(field):
+            check(t.get(field))
+            out.append(t.get(field))
+        elif len(t) == 0:
+            out.append(empty(t))
+        else:
+            raise ValueError("training the {} branch: an image's ground truth has no `{}` field".format(branch, field))
+    return out
 
 
 def _gt_masks_of(targets):
     """The ground-truth masks of every image; an image without ground truth may come without the field: no planes."""
     from ...structures import BitMasks
 
-    out = []
-    for t in targets:
-        if t.has("gt_masks"):
-            out.append(t.gt_masks)
-        elif len(t) == 0:
-            h, w = t.image_size
-            out.append(BitMasks(torch.zeros(0, h, w, dtype=torch.bool, device=t.gt_boxes.tensor.device)))
-        else:
-            raise ValueError("training the mask branch: an image's ground truth has no `gt_masks` field")
-    return out
+    return _gt_field_of(targets, "gt_masks", "mask", lambda m: None,
+                        lambda t: BitMasks(torch.zeros(0, *t.image_size, dtype=torch.bool, device=t.gt_boxes.tensor.device)))
 
 
 def _gt_keypoints_of(targets, num_keypoints):
     """The ground-truth keypoints of every image; an image without ground truth may come without the field: no instances."""
     from ...structures import Keypoints
 
-    out = []
-    for t in targets:
-        if t.has("gt_keypoints"):
-            kp = t.gt_keypoints
-            if not isinstance(kp, Keypoints):
-                raise ValueError("training the keypoint branch: `gt_keypoints` must be a structures.Keypoints, got {}".format(type(kp).__name__))
-            if kp.tensor.shape[1] != num_keypoints:
-                raise ValueError("training the keypoint branch: gt_keypoints with {} keypoints, MODEL.ROI_KEYPOINT_HEAD.NUM_KEYPOINTS = {}"
-                                 .format(kp.tensor.shape[1], num_keypoints))
-            out.append(kp)
-        elif len(t) == 0:
-            out.append(Keypoints(torch.zeros(0, num_keypoints, 3, device=t.gt_boxes.tensor.device)))
-        else:
-            raise ValueError("training the keypoint branch: an image's ground truth has no `gt_keypoints` field")
-    return out
+    def check(kp):
+        if not isinstance(kp, Keypoints):
+            raise ValueError("training the keypoint branch: `gt_keypoints` must be a structures.Keypoints, got {}".format(type(kp).__name__))
+        if kp.tensor.shape[1] != num_keypoints:
+            raise ValueError("training the keypoint branch: gt_keypoints with {} keypoints, MODEL.ROI_KEYPOINT_HEAD.NUM_KEYPOINTS = {}"
+                             .format(kp.tensor.shape[1], num_keypoints))
+
+    return _gt_field_of(targets, "gt_keypoints", "keypoint", check,
+                        lambda t: Keypoints(torch.zeros(0, num_keypoints, 3, device=t.gt_boxes.tensor.device)))
 
 
 def widen_limits(model, exc):

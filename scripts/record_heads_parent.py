@@ -11,7 +11,12 @@ images of 128x160 and 120x176; the mask_train fixture's batch with 128 rows per 
 Every case runs twice, on freshly built models: `exact_names` lists the arrays the two runs gave bit for bit, `margin_names` those they
 did not (held to 1e-6 of the array's largest entry by the test).  Boolean masks are packed with np.packbits; a reproduced array of more
 than 64 KiB is stored as the SHA-256 of its bytes (`digest`), which holds every bit of it.
-Run from the root of the tree to record; argv: the mask_train fixture npz, output npz.  TEST INFRASTRUCTURE ONLY."""
+tests/golden/heads_train_parent.npz is `record_train` run the same way on the commit before the mask and keypoint TRAINING branches
+were put on one path: `keypoint_train_case` (the keypoint_train fixture's batch: every loss, the box predictor's bias gradients,
+score_lowres.weight.grad and .bias.grad, the scalars) at the full quota, and both `*train_case`s with POST_NMS_TOPK_TRAIN = SHORT_TOPK,
+where no image fills its 128 rows and the deferred step falls back to the per-image heads.
+Run from the root of the tree to record; argv: the mask_train fixture npz, output npz -- or `--train`, the mask_train and the
+keypoint_train fixture npz, output npz (the training cases of heads_train_parent.npz only).  TEST INFRASTRUCTURE ONLY."""
 import os
 import sys
 
@@ -21,6 +26,7 @@ import torch
 SIZES = ((128, 160, 3), (120, 176, 4))
 MODELS = ("box", "mask", "keypoint")
 BATCH_SIZE_PER_IMAGE = 128
+SHORT_TOPK = 64     # proposals per image that leave every image short of BATCH_SIZE_PER_IMAGE sampled rows
 DIGEST, DIGEST_BYTES = "sha256.", 1 << 16
 
 
@@ -44,14 +50,29 @@ def build_model(name):
     return load(build(cfg).eval())
 
 
-def build_train_model():
+def build_train_model(topk=None):
     from lvc_amd.config.presets import mask_rcnn_fpn
     from lvc_amd.modeling import build_model as build
     from lvc_amd.utils import synthetic as syn
 
     cfg = mask_rcnn_fpn(num_classes=20)
     cfg.MODEL.ROI_HEADS.BATCH_SIZE_PER_IMAGE = BATCH_SIZE_PER_IMAGE
+    if topk is not None:
+        cfg.MODEL.RPN.POST_NMS_TOPK_TRAIN = topk
     return syn.conditioned_mask_head_(build(cfg)).train().enable_mask_training()
+
+
+def build_keypoint_train_model(topk=None):
+    """The training model of tests/test_gpu_keypoint_train.py."""
+    from lvc_amd.config.presets import keypoint_rcnn_fpn
+    from lvc_amd.modeling import build_model as build
+    from lvc_amd.utils import synthetic as syn
+
+    cfg = keypoint_rcnn_fpn(num_classes=1)
+    cfg.MODEL.ROI_HEADS.BATCH_SIZE_PER_IMAGE = BATCH_SIZE_PER_IMAGE
+    if topk is not None:
+        cfg.MODEL.RPN.POST_NMS_TOPK_TRAIN = topk
+    return syn.conditioned_keypoint_head_(build(cfg)).train().enable_keypoint_training()
 
 
 def inputs():
@@ -122,12 +143,42 @@ def train_batch(g):
     return batch
 
 
-def train_case(model, g, deferred):
-    """One step (forward + backward of the summed losses) with torch.randperm = arange -> {"train.deferred<0|1>.*"}."""
+def keypoint_train_batch(g):
+    """The keypoint_train fixture's batch (g: the npz as numpy arrays or tensors)."""
+    from lvc_amd.structures import Boxes, Instances, Keypoints
+    from lvc_amd.utils import synthetic as syn
+
+    batch = []
+    for i, (h, w, seed) in enumerate(SIZES):
+        inst = Instances((h, w))
+        inst.gt_boxes = Boxes(torch.as_tensor(np.asarray(g["gt_boxes%d" % i])))
+        inst.gt_classes = torch.as_tensor(np.asarray(g["gt_classes%d" % i]))
+        inst.gt_keypoints = Keypoints(torch.as_tensor(np.asarray(g["gt_keypoints%d" % i])).clone())
+        batch.append({"image": syn.synthetic_image(seed, h, w), "instances": inst, "height": h, "width": w})
+    return batch
+
+
+def train_case(model, g, deferred, tag="train"):
+    """One step of the mask model -> {"<tag>.deferred<0|1>.*"}: losses, the bias gradients of the box and mask predictors,
+    mask_head.deconv.weight.grad, scalars."""
+    return _step_case(tag, model, train_batch(g), deferred, lambda n: n == "roi_heads.mask_head.deconv.weight"
+                      or (n.endswith("bias") and ("box_predictor" in n or "mask_head.predictor" in n)))
+
+
+def keypoint_train_case(model, g, deferred, tag="keypoint_train"):
+    """One step of the keypoint model -> {"<tag>.deferred<0|1>.*"}: losses, the bias gradients of the box predictor,
+    score_lowres.weight.grad and score_lowres.bias.grad, scalars."""
+    return _step_case(tag, model, keypoint_train_batch(g), deferred,
+                      lambda n: "keypoint_head.score_lowres." in n or (n.endswith("bias") and "box_predictor" in n))
+
+
+def _step_case(tag, model, batch, deferred, recorded):
+    """One step (forward + backward of the summed losses) with torch.randperm = arange; recorded(name): whether a parameter's
+    gradient is recorded."""
     from lvc_amd.modeling.meta_arch.rcnn import GeneralizedRCNN
     from lvc_amd.utils.events import EventStorage
 
-    tag = "train.deferred%d" % int(deferred)
+    tag = "%s.deferred%d" % (tag, int(deferred))
     randperm, was = torch.randperm, GeneralizedRCNN.deferred_reads
     torch.randperm = lambda n, **kw: torch.arange(n, **{k: v for k, v in kw.items() if k in ("device", "dtype")})
     GeneralizedRCNN.deferred_reads = bool(deferred)
@@ -135,15 +186,14 @@ def train_case(model, g, deferred):
         for p in model.parameters():
             p.grad = None
         with EventStorage(0) as storage:
-            losses = model(train_batch(g))
+            losses = model(batch)
             sum(losses.values()).backward()
             scalars = {k: (v[0] if isinstance(v, tuple) else v) for k, v in storage.latest().items()}
     finally:
         torch.randperm, GeneralizedRCNN.deferred_reads = randperm, was
     d = {"%s.loss.%s" % (tag, k): _flat(v).reshape(-1) for k, v in losses.items()}
     for n, p in model.named_parameters():
-        if p.grad is not None and (n == "roi_heads.mask_head.deconv.weight"
-                                   or (n.endswith("bias") and ("box_predictor" in n or "mask_head.predictor" in n))):
+        if p.grad is not None and recorded(n):
             d["%s.grad.%s" % (tag, n)] = _flat(p.grad)
     for k, v in scalars.items():
         d["%s.scalar.%s" % (tag, k)] = np.array([float(v)], dtype=np.float64)
@@ -162,11 +212,39 @@ def record(g):
     return d
 
 
+TRAIN_CASES = (("keypoint_train", "keypoint", None), ("keypoint_short", "keypoint", SHORT_TOPK), ("mask_short", "mask", SHORT_TOPK))
+
+
+def build_train_case_model(case):
+    _tag, kind, topk = next(c for c in TRAIN_CASES if c[0] == case)
+    return (build_keypoint_train_model if kind == "keypoint" else build_train_model)(topk)
+
+
+def run_train_case(case, model, gm, gk, deferred):
+    """gm / gk: the mask_train / keypoint_train fixture."""
+    _tag, kind, _topk = next(c for c in TRAIN_CASES if c[0] == case)
+    return keypoint_train_case(model, gk, deferred, tag=case) if kind == "keypoint" else train_case(model, gm, deferred, tag=case)
+
+
+def record_train(gm, gk):
+    d = {}
+    for case, _kind, _topk in TRAIN_CASES:
+        model = build_train_case_model(case)
+        for deferred in (True, False):
+            d.update(run_train_case(case, model, gm, gk, deferred))
+    return d
+
+
 if __name__ == "__main__":
     sys.dont_write_bytecode = True
     sys.path.insert(0, os.getcwd())
-    g = np.load(sys.argv[1])
-    a, b = record(g), record(g)
+    if sys.argv[1] == "--train":
+        gm, gk = np.load(sys.argv[2]), np.load(sys.argv[3])
+        del sys.argv[1:3]
+        a, b = record_train(gm, gk), record_train(gm, gk)
+    else:
+        g = np.load(sys.argv[1])
+        a, b = record(g), record(g)
     assert list(a) == list(b)
     exact = [k for k in a if a[k].dtype == b[k].dtype and a[k].shape == b[k].shape and a[k].tobytes() == b[k].tobytes()]
     margin = [k for k in a if k not in exact]

@@ -511,13 +511,14 @@ def test_sampled_instances_carry_no_full_size_planes(monkeypatch, step_model):
     _identity_randperm(monkeypatch)
     monkeypatch.setattr(GeneralizedRCNN, "deferred_reads", False)
     seen = []
-    orig = type(step_model.roi_heads).mask_loss_batched
+    orig = type(step_model.roi_heads)._branch_loss_batched
 
-    def spy(self, feats, s_boxes, s_cls, s_m, fg_count, gt_masks, status=None):
+    def spy(self, name, feats, s_boxes, s_cls, s_m, fg_count, gt_masks, status):
+        assert name == "mask"
         seen.append((s_boxes.shape, [tuple(getattr(m, "tensor", m).shape) for m in gt_masks]))
-        return orig(self, feats, s_boxes, s_cls, s_m, fg_count, gt_masks, status=status)
+        return orig(self, name, feats, s_boxes, s_cls, s_m, fg_count, gt_masks, status)
 
-    monkeypatch.setattr(type(step_model.roi_heads), "mask_loss_batched", spy)
+    monkeypatch.setattr(type(step_model.roi_heads), "_branch_loss_batched", spy)
     heads = step_model.roi_heads
     sample = heads.label_and_sample_proposals
     for batched in (True, False):      # the one-read sampler and the per-image loop
