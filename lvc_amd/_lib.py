@@ -7,21 +7,73 @@ int status, non-zero is re-raised here as RuntimeError carrying `lvc_last_error(
 """
 import ctypes
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # LVC_AMD_LIB: another build of the same library (A/B measurements of one kernel against its predecessor in alternating processes)
 _SO = os.environ.get("LVC_AMD_LIB") or os.path.join(_HERE, "liblvc_amd.so")
+_HEADER = os.path.join(os.path.dirname(_HERE), "include", "lvc_amd.h")
 _lib = None
+_signatures = None
 
 c_void_p = ctypes.c_void_p
 c_int = ctypes.c_int
 c_float = ctypes.c_float
-c_double = ctypes.c_double
 c_longlong = ctypes.c_longlong
+
+_SCALARS = {"int": c_int, "long long": c_longlong, "unsigned long long": ctypes.c_ulonglong, "float": c_float, "double": ctypes.c_double}
 
 
 class LvcNativeError(RuntimeError):
     pass
+
+
+def parse_header(text):
+    """{entry point: (restype, [argtypes])} from the text of include/lvc_amd.h, the one statement of the ABI.  The header is plain
+    C99 without typedefs, structs or function pointers, so a declaration is `ret name(type name, ...);`.  Every pointer parameter is
+    a c_void_p, whatever it points to (it takes `ptr(t)`, None, a ctypes host array and `byref`); a type that is not listed here is
+    an error that names the declaration, never a default.  The variadic lvc_set_error is not bound."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*|^[ \t]*#[^\n]*|extern\s+\"C\"\s*\{|^\s*\}\s*$", " ", text, flags=re.M)
+    table = {}
+    for decl in filter(None, (" ".join(d.split()) for d in text.split(";"))):
+        m = re.fullmatch(r"(.+?)\b(lvc_\w+) ?\((.*)\)", decl)
+        if m is None:
+            raise ValueError("lvc_amd.h: cannot read the declaration `{}`".format(decl))
+        ret, name, params = m.group(1).strip(), m.group(2), m.group(3).strip()
+        if "..." in params:
+            continue
+        if ret == "const char*":
+            restype = ctypes.c_char_p
+        elif ret == "void":
+            restype = None
+        elif ret in _SCALARS:
+            restype = _SCALARS[ret]
+        else:
+            raise ValueError("lvc_amd.h: unknown return type `{}` in `{}`".format(ret, decl))
+        argtypes = []
+        for param in ([] if params == "void" else params.split(",")):
+            if "*" in param:
+                argtypes.append(c_void_p)
+                continue
+            ctype = " ".join(t for t in param.split()[:-1] if t != "const")      # the last word is the parameter's name
+            if ctype not in _SCALARS:
+                raise ValueError("lvc_amd.h: unknown parameter type in `{}` of `{}`".format(param.strip(), decl))
+            argtypes.append(_SCALARS[ctype])
+        table[name] = (restype, argtypes)
+    return table
+
+
+def signatures():
+    """The parsed header, read once per process.  Needs no liblvc_amd.so (scripts/conv_dispatch_trace.py records without one)."""
+    global _signatures
+    if _signatures is None:
+        if not os.path.exists(_HEADER):
+            raise ImportError("lvc_amd: the C ABI header {} not found; the native calls are bound from it "
+                              "(there is no hand-written table to fall back on)".format(_HEADER))
+        with open(_HEADER) as f:
+            _signatures = parse_header(f.read())
+    return _signatures
 
 
 def lib():
@@ -33,19 +85,19 @@ def lib():
                 "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C lvc_amd/csrc` "
                 "(there is no CPU fallback)".format(_SO)
             )
+        sigs = signatures()
         L = ctypes.CDLL(_SO)
-        L.lvc_last_error.restype = ctypes.c_char_p
-        L.lvc_abi_version.restype = c_int
-        L.lvc_set_wino_streamk.restype = None
+        # every call is checked by ctypes against the header from here on: the number of arguments (too few), an int for an int, a
+        # pointer for a pointer, and a `long long` travels whole
+        for name, (restype, argtypes) in sigs.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
         if os.environ.get("LVC_WINO_STREAMK", "0") != "0":
-            L.lvc_set_wino_streamk(c_int(int(os.environ["LVC_WINO_STREAMK"])))
-        L.lvc_set_nms_reduce_global.restype = None
-        L.lvc_set_halo_test_hooks.restype = None
+            L.lvc_set_wino_streamk(int(os.environ["LVC_WINO_STREAMK"]))
         if os.environ.get("LVC_NMS_REDUCE_GLOBAL", "0") != "0":      # read once, here: the library itself never looks at the environment
-            L.lvc_set_nms_reduce_global(c_int(1))
-        L.lvc_set_select_onelaunch.restype = None
+            L.lvc_set_nms_reduce_global(1)
         if os.environ.get("LVC_SELECT_ONELAUNCH", "3") != "3":
-            L.lvc_set_select_onelaunch(c_int(int(os.environ["LVC_SELECT_ONELAUNCH"])))
+            L.lvc_set_select_onelaunch(int(os.environ["LVC_SELECT_ONELAUNCH"]))
         _lib = L
     return _lib
 
@@ -60,11 +112,9 @@ def check(status, what=""):
 
 
 def size_query(name, *args):
-    """What a `*_workspace_bytes` entry answers for these C arguments, as a Python int: the entries return long long (ctypes' default
-    restype would cut the size to 32 bits), and a negative answer means arguments outside the kernel's range."""
-    fn = getattr(lib(), name)
-    fn.restype = c_longlong
-    nbytes = fn(*args)
+    """What a `*_workspace_bytes` entry answers for these C arguments, as a Python int (the header gives them a long long return);
+    a negative answer means arguments outside the kernel's range."""
+    nbytes = getattr(lib(), name)(*args)
     if nbytes < 0:
         raise LvcNativeError("{} answered {}: arguments outside the kernel's range".format(name, nbytes))
     return nbytes

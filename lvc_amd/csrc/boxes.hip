@@ -19,11 +19,6 @@
 #include <stdlib.h>
 
 
-extern "C" int lvc_batched_nms(const float*, const float*, const int*, const int*, int, int, double, int,
-                               int*, int*, void*, long long, void*);
-extern "C" long long lvc_batched_nms_workspace_bytes(int, int);
-extern "C" int lvc_select_onelaunch(void);
-
 #define MAXL 8
 
 

@@ -5,14 +5,13 @@
 #include <stdio.h>
 #include <string.h>
 
-#define LVC_OK 0
-#define LVC_ERR_INVALID 1   // bad argument (shape / alignment / null)
-#define LVC_ERR_HIP 2       // a HIP runtime call failed (see lvc_last_error)
-#define LVC_ERR_DOMAIN 3    // data-dependent precondition violated (e.g. negative RoI size)
+// The C ABI: every entry point's definition is compiled against its public declaration, so a parameter list that drifts from the
+// header is a compile error (conflicting types for an extern "C" function), and no file restates another file's prototype.
+#include "../../include/lvc_amd.h"
 
-extern "C" void lvc_set_error(const char* fmt, ...);
-extern "C" int lvc_range_slot(void);   // see common.cpp
-extern "C" int lvc_range_slots(void);
+// LVC_OK 0, LVC_ERR_INVALID 1 (bad argument: shape / alignment / null) and LVC_ERR_HIP 2 (a HIP runtime call failed, see
+// lvc_last_error) are the header's
+#define LVC_ERR_DOMAIN 3    // data-dependent precondition violated (e.g. negative RoI size)
 
 #define LVC_CHECK_ARG(cond, msg)                       \
   do {                                                 \

@@ -349,11 +349,6 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_halo_kernel(HaloArgs p) {
   }
 }
 
-extern "C" int lvc_conv2d_nhwc_bf16x3(const float* x, const unsigned short* w_split, const float* scale,
-                                      const float* shift, const float* residual, float* y, int N, int H, int W, int C,
-                                      int K, int R, int S, int stride, int pad, int Kg, int relu, int res_mode, int ldy,
-                                      int ldr, void* workspace, void* stream);
-
 // Patch shape for an H x W output: PH * PW <= 256 pixels, (PH + 2) * (PW + 2) <= HALO_MAX halo pixels, fewest patches
 // (every patch costs a full 256-row MFMA tile whatever its fill); ties go to the smaller halo.
 static void pick_patch(int H, int W, int* PH, int* PW) {

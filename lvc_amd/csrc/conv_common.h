@@ -35,10 +35,7 @@ static inline int lvc_ws_range_index(int slot) { return LVC_MAX_WORKERS + slot; 
 
 // ---------------------------------------------------------------------------------------------------------------- host launch helpers
 extern "C" int lvc_cu_count(void);   // compute units of the current device, read once (256 if the query fails); common.cpp
-// 0: one patch shape per map in the 3x3 kernels; 1 (default): up to two regions with a shape each (patch_plan.h) in the Winograd
-// kernel (bit-identical outputs); 2: in the direct kernel too (its stream-K boundaries, hence last bits, move).
-// lvc_set_patch_plan, or LVC_PATCH_PLAN in the environment, read once at the first call; common.cpp
-extern "C" int lvc_patch_plan(void);
+// (lvc_patch_plan(), the patch decomposition switch of the 3x3 kernels, is public: include/lvc_amd.h states its values; common.cpp)
 
 // Stream-K split of `units` equal work items over at most `cap` workers, none with fewer than `min_units` (except when there are
 // fewer units than that): every worker gets units_per_worker contiguous units, the last one the remainder.

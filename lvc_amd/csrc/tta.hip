@@ -18,12 +18,7 @@
 //
 // Byte streams and latency-bound bookkeeping: built with the EXACT flags (-ffp-contract=off -fno-fast-math): the fp32 steps of the
 // inverse transforms and the normaliser must round exactly as numpy / preprocess_image do.
-#include "input_common.h"
-
-extern "C" long long lvc_batched_nms_workspace_bytes(int B, int Nmax);   // nms.hip
-extern "C" int lvc_batched_nms(const float* boxes, const float* scores, const int* idxs, const int* d_counts, int B, int Nmax,
-                               double iou_threshold, int max_keep, int* keep, int* d_num_keep, void* workspace,
-                               long long workspace_bytes, void* stream);
+#include "input_common.h"   // lvc_batched_nms (nms.hip) comes with the public header
 
 #define TTA_MAX_JOBS 16
 #define TTA_MAX_STEPS 4

@@ -9,7 +9,7 @@ import ctypes
 import torch
 
 from . import _lib
-from ._lib import LvcNativeError, c_double, c_float, c_int, c_longlong, c_void_p, check, ptr
+from ._lib import LvcNativeError, c_float, c_int, c_longlong, c_void_p, check, ptr      # the c_* types build host arrays only
 
 BK = 32  # gemm-K chunk of the implicit-GEMM kernel
 BN = 128
@@ -81,7 +81,7 @@ class PackedConv:
         dt = torch.bfloat16 if planes == 3 else torch.float16
         out = torch.empty((planes,) + tuple(self.w.shape), device=self.w.device, dtype=dt)
         err = _conv_error_view(self.w.device) if planes == 2 else None
-        check(_lib.lib().lvc_split_weights(ptr(self.w), c_longlong(n), c_int(planes), ptr(out), ptr(err), _stream(self.w)),
+        check(_lib.lib().lvc_split_weights(ptr(self.w), n, planes, ptr(out), ptr(err), _stream(self.w)),
               "lvc_split_weights")
         return out
 
@@ -109,7 +109,7 @@ class PackedConv:
             rows, Kg = self.w.shape
             planes = torch.empty((2, rows, Kg), device=self.w.device, dtype=torch.float16)
             fac = torch.empty(rows, device=self.w.device, dtype=torch.float32)
-            check(_lib.lib().lvc_split_weights_rowscaled(ptr(self.w), c_int(rows), c_int(Kg), ptr(planes), ptr(fac), _stream(self.w)),
+            check(_lib.lib().lvc_split_weights_rowscaled(ptr(self.w), rows, Kg, ptr(planes), ptr(fac), _stream(self.w)),
                   "lvc_split_weights_rowscaled")
             fac = fac[: self.K]
             self._w2s = (planes, (fac * self.scale if self.scale is not None else fac).contiguous())
@@ -164,12 +164,12 @@ def _pack_weights(weight, scale, rows_pad, cin_pad, mode, planes=0):
     if planes:
         out = torch.empty((planes,) + tuple(wp.shape), device=w.device, dtype=torch.float16 if planes == 2 else torch.bfloat16)
         err = _conv_error_view(w.device) if planes == 2 else None
-        check(_lib.lib().lvc_pack_split_conv_weights(ptr(w), ptr(scale), ptr(wp), ptr(out), c_int(planes), ptr(err), c_int(K),
-                                                     c_int(C), c_int(R), c_int(S), c_int(rows_pad), c_int(cin_pad),
-                                                     c_int(mode), _stream(w)), "lvc_pack_split_conv_weights")
+        check(_lib.lib().lvc_pack_split_conv_weights(ptr(w), ptr(scale), ptr(wp), ptr(out), planes, ptr(err), K,
+                                                     C, R, S, rows_pad, cin_pad,
+                                                     mode, _stream(w)), "lvc_pack_split_conv_weights")
         return wp, out
-    check(_lib.lib().lvc_pack_conv_weights(ptr(w), ptr(scale), ptr(wp), c_int(K), c_int(C), c_int(R), c_int(S),
-                                           c_int(rows_pad), c_int(cin_pad), c_int(mode), _stream(w)),
+    check(_lib.lib().lvc_pack_conv_weights(ptr(w), ptr(scale), ptr(wp), K, C, R, S,
+                                           rows_pad, cin_pad, mode, _stream(w)),
           "lvc_pack_conv_weights")
     return wp, None
 
@@ -220,9 +220,8 @@ def _pack_grouped(weight, scale, groups, mode):
     if w.dtype != torch.float32 or not w.is_contiguous():
         w = w.float().contiguous()
     lib = _lib.lib()
-    lib.lvc_conv3x3_grouped_packed_floats.restype = c_longlong
-    wp = torch.empty(lib.lvc_conv3x3_grouped_packed_floats(c_int(K), c_int(groups)), device=w.device, dtype=torch.float32)
-    check(lib.lvc_pack_conv3x3_grouped(ptr(w), ptr(scale), ptr(wp), c_int(K), c_int(groups), c_int(mode), _stream(w)),
+    wp = torch.empty(lib.lvc_conv3x3_grouped_packed_floats(K, groups), device=w.device, dtype=torch.float32)
+    check(lib.lvc_pack_conv3x3_grouped(ptr(w), ptr(scale), ptr(wp), K, groups, mode, _stream(w)),
           "lvc_pack_conv3x3_grouped")
     return wp
 
@@ -351,7 +350,7 @@ class PrepackPlan:
             pc._w3 = pl if fmt == 3 else None
             pc._w2s = (pl, fac) if fmt == 4 else None
             pc.state.pop("_wino", None)
-        check(_lib.lib().lvc_pack_group(c_int(self.n), self.ptrs, self.shapes, ptr(self._err), _stream(self.buf)), "lvc_pack_group")
+        check(_lib.lib().lvc_pack_group(self.n, self.ptrs, self.shapes, ptr(self._err), _stream(self.buf)), "lvc_pack_group")
 
 
 def prepack_group(jobs):
@@ -378,10 +377,8 @@ def conv_workspace(device):
     key = (device.index, torch.cuda.current_stream(device).cuda_stream)
     ws = _CONV_WS.get(key)
     if ws is None:
-        lib = _lib.lib()
         if _ERR_OFF is None:
-            lib.lvc_conv_range_words_offset.restype = c_longlong
-            _ERR_OFF = lib.lvc_conv_range_words_offset()
+            _ERR_OFF = _lib.lib().lvc_conv_range_words_offset()
         ws = torch.zeros(_lib.size_query("lvc_conv_workspace_bytes"), dtype=torch.uint8, device=device)
         _CONV_WS[key] = ws
     return ws
@@ -619,11 +616,11 @@ def _launch(tag, flops, nbytes, slot, what, call):
     if slot is None:
         st = call()
     else:
-        _lib.lib().lvc_set_range_slot(c_int(slot))
+        _lib.lib().lvc_set_range_slot(slot)
         try:
             st = call()
         finally:
-            _lib.lib().lvc_set_range_slot(c_int(0))
+            _lib.lib().lvc_set_range_slot(0)
     check(st, what)
     if timer is not None:
         e1.record()
@@ -772,13 +769,13 @@ def conv3x3_conv1x1_presplit(x, pc2, pc3, residual=None, relu=True):
     pc3.last_one = True
     _launch("f16x2_halo", 2.0 * rows * pc2.K * C * 9, 4.0 * (rows * C + rows * pc2.K + pc2.K * C * 9), pc2.slot,
             "lvc_conv3x3_nhwc_f16s1_presplit", lambda: _lib.lib().lvc_conv3x3_nhwc_f16s1_presplit(
-                ptr(x), ptr(planes2), ptr(scale2), ptr(pc2.shift), ptr(mid), c_int(N), c_int(H), c_int(W), c_int(C), c_int(pc2.K),
-                c_int(pc2.Kg), c_int(pc3.slot), ws, _stream(x)))
+                ptr(x), ptr(planes2), ptr(scale2), ptr(pc2.shift), ptr(mid), N, H, W, C, pc2.K,
+                pc2.Kg, pc3.slot, ws, _stream(x)))
     _launch("f16x2_pws1", 2.0 * rows * pc3.K * pc3.C,
             4.0 * (rows * pc3.C + rows * pc3.K + (residual.numel() if residual is not None else 0) + pc3.K * pc3.C), pc3.slot,
             "lvc_conv1x1_nhwc_f16s1_presplit", lambda: _lib.lib().lvc_conv1x1_nhwc_f16s1_presplit(
-                ptr(mid), ptr(planes3), ptr(scale3), ptr(pc3.shift), ptr(residual), ptr(out), c_int(N), c_int(H), c_int(W), c_int(pc3.C),
-                c_int(pc3.K), c_int(1 if relu else 0), c_int(1 if residual is not None else 0), c_int(pc3.K), c_int(ldr), ws, _stream(x)))
+                ptr(mid), ptr(planes3), ptr(scale3), ptr(pc3.shift), ptr(residual), ptr(out), N, H, W, pc3.C,
+                pc3.K, 1 if relu else 0, 1 if residual is not None else 0, pc3.K, ldr, ws, _stream(x)))
     return out
 
 
@@ -843,7 +840,7 @@ def conv2d_nhwc(x, pc, relu=False, residual=None, res_mode=0, out=None, split=No
                           ((pc.split2h() if operand == "h" else pc.split3() if operand == "3" else pc.w), pc.scale))
             ints = (N, H, W, C, pc.K) + tail(pc, wts) + (code, res_mode, ldo, ldr) + last(pc)
             return getattr(_lib.lib(), entry)(ptr(x), ptr(wts), ptr(scale), ptr(pc.shift), ptr(residual), ptr(out),
-                                              *[c_int(v) for v in ints], ptr(conv_workspace(x.device)), _stream(x))
+                                              *ints, ptr(conv_workspace(x.device)), _stream(x))
     c_real = 3 if pc.mode == 1 else C
     # algorithmic bytes of the launch: the input pixels it needs, its output, the residual operand, the weights -- each once
     nbytes = 4.0 * (N * (Ho * Wo if (pc.R == 1 and pc.S == 1) else H * W) * c_real + N * Ho * Wo * pc.K + res_numel
@@ -853,7 +850,7 @@ def conv2d_nhwc(x, pc, relu=False, residual=None, res_mode=0, out=None, split=No
         nbytes = 4.0 * (N * H * W * C + N * Ho * Wo * pc.K + res_numel + pc.K * c_real * 9)
     _launch(route.engine, 2.0 * N * Ho * Wo * pc.K * c_real * pc.R * pc.S, nbytes, pc.slot if route.slotted else None, entry, call)
     if act == "gelu":
-        check(_lib.lib().lvc_gelu(ptr(out), ptr(out), c_longlong(out.numel()), _stream(out)), "lvc_gelu")
+        check(_lib.lib().lvc_gelu(ptr(out), ptr(out), out.numel(), _stream(out)), "lvc_gelu")
     elif act is not None:
         raise ValueError("unknown activation {!r}".format(act))
     return out
@@ -879,7 +876,7 @@ def _chain_planes(pc):
     wperm = pc.w[:, idx].contiguous()
     planes = torch.empty((2, rows, Kg), device=pc.w.device, dtype=torch.float16)
     fac = torch.empty(rows, device=pc.w.device, dtype=torch.float32)
-    check(_lib.lib().lvc_split_weights_rowscaled(ptr(wperm), c_int(rows), c_int(Kg), ptr(planes), ptr(fac), _stream(pc.w)),
+    check(_lib.lib().lvc_split_weights_rowscaled(ptr(wperm), rows, Kg, ptr(planes), ptr(fac), _stream(pc.w)),
           "lvc_split_weights_rowscaled")
     fac = fac[: pc.K]
     return planes, (fac * pc.scale if pc.scale is not None else fac).contiguous()
@@ -897,7 +894,7 @@ WINO_STREAMK = int(_os.environ.get("LVC_WINO_STREAMK", "0"))
 def set_wino_streamk(mode):
     global WINO_STREAMK
     WINO_STREAMK = int(mode)
-    _lib.lib().lvc_set_wino_streamk(c_int(int(mode)))
+    _lib.lib().lvc_set_wino_streamk(int(mode))
 # The RPN head's large levels on the Winograd kernel too (kernels.conv3x3_levels_pred).  Off: its single-accumulator form puts p2 proposal
 # boxes of the bench batch up to 3.5e-3 px from the exact (fp64) box, past the post-trunk chain test's bar (2 x the oracle's own fp32
 # error, ~1.3e-3 px); the two-accumulator direct kernel stays within it for all levels, at +0.3 ms per 8-image step.
@@ -923,7 +920,7 @@ def pack_wino(pc):
     flat[:K] = U.reshape(K, C * 12)
     planes = torch.empty(2, Kpad, C * 12, dtype=torch.int16, device=pc.w.device)
     fac = torch.empty(Kpad, device=pc.w.device)
-    check(_lib.lib().lvc_split_weights_rowscaled(ptr(flat), c_int(Kpad), c_int(C * 12), ptr(planes), ptr(fac), _stream(flat)), "lvc_split_weights_rowscaled")
+    check(_lib.lib().lvc_split_weights_rowscaled(ptr(flat), Kpad, C * 12, ptr(planes), ptr(fac), _stream(flat)), "lvc_split_weights_rowscaled")
     u = planes.view(2, Kpad, C // 16, 16, 3, 4).permute(4, 2, 5, 0, 1, 3).contiguous()                 # [r][kc][p][plane][Kpad][16]
     scale = (fac[:K] * pc.scale if pc.scale is not None else fac[:K]).contiguous()
     pc.state["_wino"] = (pc.w, u, scale)
@@ -934,8 +931,8 @@ def _wino_launch(x, pc, relu, out):
     _req_cuda(x)
     N, H, W, C = x.shape
     u, scale = pack_wino(pc)
-    return _lib.lib().lvc_conv3x3_nhwc_wino(ptr(x), ptr(u), ptr(scale), ptr(pc.shift), ptr(out), c_int(N), c_int(H), c_int(W), c_int(C), c_int(pc.K),
-                                            c_int(u.shape[4]), c_int(1 if relu else 0), c_int(out.stride(2)), ptr(conv_workspace(x.device)), _stream(x))
+    return _lib.lib().lvc_conv3x3_nhwc_wino(ptr(x), ptr(u), ptr(scale), ptr(pc.shift), ptr(out), N, H, W, C, pc.K,
+                                            u.shape[4], 1 if relu else 0, out.stride(2), ptr(conv_workspace(x.device)), _stream(x))
 
 
 def conv3x3_wino(x, pc, relu=False, out=None):
@@ -1046,8 +1043,8 @@ def conv3x3_levels(xs, pc, relu=False, outs=None):
     px = sum(x.shape[0] * x.shape[1] * x.shape[2] for x in xs)
     _launch("f16x2_halo", 2.0 * px * p0.K * C * 9, 4.0 * (px * C + px * p0.K + (1 if shared else L) * p0.K * C * 9),
             p0.slot if shared else _group_slot(pcs), entry, lambda: getattr(_lib.lib(), entry)(
-                c_int(1 if one else 0), xp, yp, hs, ws, c_int(L), *weights, c_int(N), c_int(C), c_int(p0.K), c_int(p0.Kg),
-                c_int(1 if relu else 0), ptr(conv_workspace(xs[0].device)), _stream(xs[0])))
+                1 if one else 0, xp, yp, hs, ws, L, *weights, N, C, p0.K, p0.Kg,
+                1 if relu else 0, ptr(conv_workspace(xs[0].device)), _stream(xs[0])))
     return outs
 
 
@@ -1092,9 +1089,9 @@ def conv3x3_levels_pred(xs, pc, pred, relu=True, _outs=None):
                 px = x.shape[0] * x.shape[1] * x.shape[2]
                 _launch("f16x2_wino", 2.0 * px * pc.K * (C * 9 + pred.K), 4.0 * (px * C + px * pred.K + pc.K * (C * 9 + pred.K)), pc.slot,
                         "lvc_conv3x3_nhwc_wino_pred", lambda: _lib.lib().lvc_conv3x3_nhwc_wino_pred(
-                            ptr(x), ptr(u), ptr(scale), ptr(pc.shift), ptr(o), c_int(N), c_int(x.shape[1]), c_int(x.shape[2]),
-                            c_int(C), c_int(pc.K), c_int(u.shape[4]), c_int(1 if relu else 0), c_int(pred.K), ptr(pplanes),
-                            ptr(pred.scale), ptr(pred.shift), c_int(pred.K), c_int(pred.w.shape[0]), c_int(pred.slot),
+                            ptr(x), ptr(u), ptr(scale), ptr(pc.shift), ptr(o), N, x.shape[1], x.shape[2],
+                            C, pc.K, u.shape[4], 1 if relu else 0, pred.K, ptr(pplanes),
+                            ptr(pred.scale), ptr(pred.shift), pred.K, pred.w.shape[0], pred.slot,
                             ptr(conv_workspace(x.device)), _stream(x)))
             if rest:
                 sub = conv3x3_levels_pred([xs[i] for i in rest], pc, pred, relu=relu, _outs=[outs[i] for i in rest])
@@ -1110,10 +1107,10 @@ def conv3x3_levels_pred(xs, pc, pred, relu=True, _outs=None):
     px = sum(ms)
     _launch("f16x2_halo", 2.0 * px * pc.K * (C * 9 + pred.K), 4.0 * (px * C + px * pred.K + pc.K * (C * 9 + pred.K)), pc.slot,
             "lvc_conv3x3_nhwc_f16_levels_pred", lambda: _lib.lib().lvc_conv3x3_nhwc_f16_levels_pred(
-                c_int(0), xp, yp, hs, ws, c_int(L), ptr(planes), ptr(pc.scale), ptr(pc.shift), c_int(N),
-                c_int(C), c_int(pc.K), c_int(pc.Kg), c_int(1 if relu else 0), ptr(pplanes),
-                ptr(pred.scale), ptr(pred.shift), c_int(pred.K), c_int(pred.w.shape[0]),
-                c_int(pred.K), c_int(pred.slot), ptr(conv_workspace(xs[0].device)), _stream(xs[0])))
+                0, xp, yp, hs, ws, L, ptr(planes), ptr(pc.scale), ptr(pc.shift), N,
+                C, pc.K, pc.Kg, 1 if relu else 0, ptr(pplanes),
+                ptr(pred.scale), ptr(pred.shift), pred.K, pred.w.shape[0],
+                pred.K, pred.slot, ptr(conv_workspace(xs[0].device)), _stream(xs[0])))
     return outs
 
 
@@ -1148,10 +1145,10 @@ def conv1x1_chain(x, ch, residual=None, relu1=True, relu2=True, out1=None, out2=
     nbytes = 4.0 * (M * (ch.K1 + ch.N1 + ch.N2 + (ch.N1 if residual is not None else 0)) + ch.K1 * ch.N1 + ch.N1 * ch.N2)
     _launch("f16s1_chain", 2.0 * M * (ch.K1 * ch.N1 + ch.N1 * ch.N2), nbytes, ch.slot, "lvc_conv1x1_chain_nhwc_f16s1",
             lambda: _lib.lib().lvc_conv1x1_chain_nhwc_f16s1(
-                ptr(x), c_int(x.shape[-1]), ptr(ch.wa), c_int(ch.wa.shape[1]), ptr(ch.sa), ptr(ch.ta), ptr(residual),
-                c_int(residual.shape[-1] if residual is not None else 0), ptr(out1), c_int(out1.shape[-1]), c_int(1 if relu1 else 0),
-                ptr(ch.wb), c_int(ch.wb.shape[1]), ptr(ch.sb), ptr(ch.tb), ptr(out2), c_int(out2.shape[-1]), c_int(1 if relu2 else 0),
-                c_int(M), c_int(ch.K1), c_int(ch.N1), c_int(ch.N2), ptr(conv_workspace(x.device)), _stream(x)))
+                ptr(x), x.shape[-1], ptr(ch.wa), ch.wa.shape[1], ptr(ch.sa), ptr(ch.ta), ptr(residual),
+                residual.shape[-1] if residual is not None else 0, ptr(out1), out1.shape[-1], 1 if relu1 else 0,
+                ptr(ch.wb), ch.wb.shape[1], ptr(ch.sb), ptr(ch.tb), ptr(out2), out2.shape[-1], 1 if relu2 else 0,
+                M, ch.K1, ch.N1, ch.N2, ptr(conv_workspace(x.device)), _stream(x)))
     return out1, out2
 
 
@@ -1217,7 +1214,7 @@ def pack_bottleneck(pc1, pc2, pc3, proj, state=None):
         nrows, Kg = pc.w.shape
         planes = torch.empty((2, nrows, Kg), device=dev, dtype=torch.float16)
         fac = torch.empty(nrows, device=dev, dtype=torch.float32)
-        check(_lib.lib().lvc_split_weights_rowscaled(ptr(pc.w), c_int(nrows), c_int(Kg), ptr(planes), ptr(fac), _stream(pc.w)),
+        check(_lib.lib().lvc_split_weights_rowscaled(ptr(pc.w), nrows, Kg, ptr(planes), ptr(fac), _stream(pc.w)),
               "lvc_split_weights_rowscaled")
         parts.append(planes[pl, rows, cols].reshape(-1))
         fac = fac[: pc.K]
@@ -1240,8 +1237,8 @@ def bottleneck_fused(x, bk, out=None):
     kk = bk.cin * 64 + 64 * 64 * 9 + 64 * 256 + (bk.cin * 256 if bk.proj else 0)
     _launch("f16s1_bneck", 2.0 * M * kk, 4.0 * (M * (bk.cin + 256) + kk), bk.slot, "lvc_bottleneck_nhwc_f16s1",
             lambda: _lib.lib().lvc_bottleneck_nhwc_f16s1(
-                ptr(x), c_int(ldx), ptr(out), c_int(out.shape[-1]), c_int(N), c_int(H), c_int(W),
-                c_int(bk.cin), c_int(1 if bk.proj else 0), ptr(bk.w), ptr(bk.s1), ptr(bk.t1), ptr(bk.s2),
+                ptr(x), ldx, ptr(out), out.shape[-1], N, H, W,
+                bk.cin, 1 if bk.proj else 0, ptr(bk.w), ptr(bk.s1), ptr(bk.t1), ptr(bk.s2),
                 ptr(bk.t2), ptr(bk.s3), ptr(bk.t3), ptr(conv_workspace(x.device)), _stream(x)))
     return out
 
@@ -1251,7 +1248,7 @@ def split_planes_f16x2(w):
     _req_cuda(w)
     w = w.detach().float().contiguous()
     out = torch.empty((2,) + tuple(w.shape), device=w.device, dtype=torch.float16)
-    check(_lib.lib().lvc_split_weights(ptr(w), c_longlong(w.numel()), c_int(2), ptr(out), ptr(_conv_error_view(w.device)), _stream(w)),
+    check(_lib.lib().lvc_split_weights(ptr(w), w.numel(), 2, ptr(out), ptr(_conv_error_view(w.device)), _stream(w)),
           "lvc_split_weights")
     return out
 
@@ -1272,9 +1269,9 @@ def stem_conv_pool(x4, pc, relu=True, second=None):
     if CONV_SPLIT == "f16x2":
         err = _conv_error_view(x4.device)   # the conv error word
         st = _lib.lib().lvc_stem_conv_pool_nhwc4_f16x2(ptr(x4), ptr(pc.split2h()), ptr(pc.scale), ptr(pc.shift), ptr(out),
-                                                       c_int(N), c_int(H), c_int(W), c_int(pc.w.shape[0]),
-                                                       c_int(1 if relu else 0), ptr(err), ptr(y2),
-                                                       c_int(y2.stride(2) if y2 is not None else 0), _stream(x4))
+                                                       N, H, W, pc.w.shape[0],
+                                                       1 if relu else 0, ptr(err), ptr(y2),
+                                                       y2.stride(2) if y2 is not None else 0, _stream(x4))
         check(st, "lvc_stem_conv_pool_nhwc4_f16x2")
         return out
     raise RuntimeError("the fused stem exists for the fp16 split only; BasicStem runs conv + max-pool as two launches otherwise")
@@ -1310,9 +1307,9 @@ def roi_align_forward(input, rois, spatial_scale, pooled_h, pooled_w, sampling_r
     K = rois.shape[0]
     out = torch.empty(K, C, pooled_h, pooled_w, device=input.device, dtype=torch.float32)
     st = _lib.lib().lvc_roi_align_forward_nchw(
-        ptr(input), ptr(rois), ptr(out), c_int(B), c_int(C), c_int(H), c_int(W), c_int(K),
-        c_int(pooled_h), c_int(pooled_w), c_float(spatial_scale), c_int(sampling_ratio),
-        c_int(1 if aligned else 0), ptr(status), _stream(input))
+        ptr(input), ptr(rois), ptr(out), B, C, H, W, K,
+        pooled_h, pooled_w, spatial_scale, sampling_ratio,
+        1 if aligned else 0, ptr(status), _stream(input))
     check(st, "lvc_roi_align_forward_nchw")
     return out
 
@@ -1349,13 +1346,13 @@ def roi_align_fpn_nhwc(feats, scales, rois, levels, pooled_h, pooled_w, sampling
         order = torch.empty(K, device=rois.device, dtype=torch.int32)
         if B <= 16:
             # image b's RoIs on XCD b % 8, inside an image by (level, band of rows): what an XCD reads close in time shares its L2
-            check(_lib.lib().lvc_roi_work_order_xcd(ptr(rois), ptr(levels), c_int(K), c_int(B), ptr(order), _stream(rois)), "lvc_roi_work_order_xcd")
+            check(_lib.lib().lvc_roi_work_order_xcd(ptr(rois), ptr(levels), K, B, ptr(order), _stream(rois)), "lvc_roi_work_order_xcd")
         else:
-            check(_lib.lib().lvc_roi_work_order(ptr(rois), ptr(levels), sc, c_int(L), c_int(K), c_int(pooled_h), ptr(order), _stream(rois)),
+            check(_lib.lib().lvc_roi_work_order(ptr(rois), ptr(levels), sc, L, K, pooled_h, ptr(order), _stream(rois)),
                   "lvc_roi_work_order")
     st = _lib.lib().lvc_roi_align_fpn_nhwc_ordered(
-        fp, hs, ws, sc, c_int(L), c_int(B), c_int(C), ptr(rois), ptr(levels), ptr(num_valid), c_int(K),
-        c_int(pooled_h), c_int(pooled_w), c_int(sampling_ratio), c_int(1 if aligned else 0), ptr(out),
+        fp, hs, ws, sc, L, B, C, ptr(rois), ptr(levels), ptr(num_valid), K,
+        pooled_h, pooled_w, sampling_ratio, 1 if aligned else 0, ptr(out),
         ptr(status), ptr(order), _stream(rois))
     check(st, "lvc_roi_align_fpn_nhwc")
     return out
@@ -1371,9 +1368,9 @@ def roi_align_backward(grad, rois, spatial_scale, pooled_h, pooled_w, batch_size
     assert grad.shape == (K, channels, pooled_h, pooled_w)
     gin = torch.empty(batch_size, channels, height, width, device=grad.device, dtype=torch.float32)
     st = _lib.lib().lvc_roi_align_backward_nchw(
-        ptr(grad), ptr(rois), ptr(gin), c_int(batch_size), c_int(channels), c_int(height), c_int(width), c_int(K),
-        c_int(pooled_h), c_int(pooled_w), c_float(spatial_scale), c_int(sampling_ratio),
-        c_int(1 if aligned else 0), ptr(status), _stream(grad))
+        ptr(grad), ptr(rois), ptr(gin), batch_size, channels, height, width, K,
+        pooled_h, pooled_w, spatial_scale, sampling_ratio,
+        1 if aligned else 0, ptr(status), _stream(grad))
     check(st, "lvc_roi_align_backward_nchw")
     return gin
 
@@ -1396,8 +1393,8 @@ def roi_align_fpn_backward_nhwc(grad, shapes, scales, rois, levels, sampling_rat
         assert levels.dtype == torch.int32 and levels.is_contiguous()
     st = _lib.lib().lvc_roi_align_fpn_backward_nhwc(
         ptr(grad), FP(*[o.data_ptr() for o in outs]), IP(*[sh[1] for sh in shapes]), IP(*[sh[2] for sh in shapes]),
-        FL(*[float(s) for s in scales]), c_int(L), c_int(B), c_int(C), ptr(rois), ptr(levels), ptr(num_valid),
-        c_int(K), c_int(ph), c_int(pw), c_int(sampling_ratio), c_int(1 if aligned else 0), ptr(status),
+        FL(*[float(s) for s in scales]), L, B, C, ptr(rois), ptr(levels), ptr(num_valid),
+        K, ph, pw, sampling_ratio, 1 if aligned else 0, ptr(status),
         _stream(grad))
     check(st, "lvc_roi_align_fpn_backward_nhwc")
     return outs
@@ -1414,7 +1411,7 @@ SELECT_ONELAUNCH = int(_os.environ.get("LVC_SELECT_ONELAUNCH", "3"))
 def set_select_onelaunch(mode):
     global SELECT_ONELAUNCH
     SELECT_ONELAUNCH = int(mode)
-    _lib.lib().lvc_set_select_onelaunch(c_int(int(mode)))
+    _lib.lib().lvc_set_select_onelaunch(int(mode))
 
 
 def batched_nms_batch(boxes, scores, idxs, counts, iou_threshold, max_keep=0):
@@ -1429,11 +1426,11 @@ def batched_nms_batch(boxes, scores, idxs, counts, iou_threshold, max_keep=0):
         assert idxs.dtype == torch.int32
     keep = torch.empty(B, Nmax, dtype=torch.int32, device=boxes.device)
     num_keep = torch.empty(B, dtype=torch.int32, device=boxes.device)
-    wsb = _lib.size_query("lvc_batched_nms_workspace_bytes", c_int(B), c_int(Nmax))
+    wsb = _lib.size_query("lvc_batched_nms_workspace_bytes", B, Nmax)
     ws = torch.empty(wsb, dtype=torch.uint8, device=boxes.device)
     st = _lib.lib().lvc_batched_nms(
-        ptr(boxes), ptr(scores), ptr(idxs), ptr(counts), c_int(B), c_int(Nmax), c_double(iou_threshold),
-        c_int(max_keep), ptr(keep), ptr(num_keep), ptr(ws), c_longlong(wsb), _stream(boxes))
+        ptr(boxes), ptr(scores), ptr(idxs), ptr(counts), B, Nmax, iou_threshold,
+        max_keep, ptr(keep), ptr(num_keep), ptr(ws), wsb, _stream(boxes))
     check(st, "lvc_batched_nms")
     return keep, num_keep
 
@@ -1492,16 +1489,16 @@ def rpn_proposals(logits, deltas, cell_anchors, strides, image_sizes, pre_nms_to
     ldd = IP(*[t.stride(2) for t in deltas])
     hs, ws_, st = IP(*Hs), IP(*Ws), IP(*strides)
     lib = _lib.lib()
-    nbytes = _lib.size_query("lvc_rpn_proposals_workspace_bytes", c_int(B), c_int(L), c_int(A), hs, ws_, c_int(pre_nms_topk))
+    nbytes = _lib.size_query("lvc_rpn_proposals_workspace_bytes", B, L, A, hs, ws_, pre_nms_topk)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     boxes = torch.empty(B, post_nms_topk, 4, device=dev, dtype=torch.float32)
     olog = torch.empty(B, post_nms_topk, device=dev, dtype=torch.float32)
     count = torch.empty(B, dtype=torch.int32, device=dev)
     assert image_sizes.dtype == torch.int32 and image_sizes.is_contiguous()
-    rc = lib.lvc_rpn_proposals(lp, ldl, dp, ldd, ap, hs, ws_, st, c_int(L), c_int(A), c_int(B), ptr(image_sizes),
-                               c_int(pre_nms_topk), c_int(post_nms_topk), c_double(nms_thresh),
-                               c_float(min_box_size), c_float(SCALE_CLAMP), ptr(boxes), ptr(olog), ptr(count),
-                               ptr(ws), c_longlong(nbytes), _stream(boxes))
+    rc = lib.lvc_rpn_proposals(lp, ldl, dp, ldd, ap, hs, ws_, st, L, A, B, ptr(image_sizes),
+                               pre_nms_topk, post_nms_topk, nms_thresh,
+                               min_box_size, SCALE_CLAMP, ptr(boxes), ptr(olog), ptr(count),
+                               ptr(ws), nbytes, _stream(boxes))
     check(rc, "lvc_rpn_proposals")
     return boxes, olog, count
 
@@ -1513,8 +1510,8 @@ def assign_levels_rois(boxes, min_level, max_level, canonical_box_size=224, cano
     boxes = boxes.contiguous()
     levels = torch.empty(B * R, dtype=torch.int32, device=boxes.device)
     rois = torch.empty(B * R, 5, dtype=torch.float32, device=boxes.device)
-    rc = _lib.lib().lvc_assign_levels_rois(ptr(boxes), c_int(B), c_int(R), c_int(min_level), c_int(max_level),
-                                           c_int(canonical_box_size), c_int(canonical_level), ptr(levels), ptr(rois),
+    rc = _lib.lib().lvc_assign_levels_rois(ptr(boxes), B, R, min_level, max_level,
+                                           canonical_box_size, canonical_level, ptr(levels), ptr(rois),
                                            _stream(boxes))
     check(rc, "lvc_assign_levels_rois")
     return levels, rois
@@ -1541,7 +1538,7 @@ def fast_rcnn_inference(cls_logits, deltas, proposals, prop_count, image_sizes, 
         status = new_status(dev)
     lib = _lib.lib()
     max_candidates = max(1, R * K) if max_candidates is None else min(max_candidates, max(1, R * K))
-    nbytes = _lib.size_query("lvc_fast_rcnn_inference_workspace_bytes", c_int(B), c_int(max_candidates))
+    nbytes = _lib.size_query("lvc_fast_rcnn_inference_workspace_bytes", B, max_candidates)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     ob = torch.empty(B, topk, 4, device=dev, dtype=torch.float32)
     osc = torch.empty(B, topk, device=dev, dtype=torch.float32)
@@ -1550,11 +1547,11 @@ def fast_rcnn_inference(cls_logits, deltas, proposals, prop_count, image_sizes, 
     cnt = torch.empty(B, device=dev, dtype=torch.int32)
     wx, wy, ww, wh = box_weights
     rc = lib.lvc_fast_rcnn_inference(
-        ptr(cls_logits), c_int(cls_logits.stride(0)), ptr(deltas), c_int(deltas.stride(0)), c_int(K),
-        c_int(cls_agnostic), ptr(proposals.contiguous()), ptr(prop_count), c_int(B), c_int(R), ptr(image_sizes),
-        c_float(wx), c_float(wy), c_float(ww), c_float(wh), c_float(SCALE_CLAMP), c_float(score_thresh),
-        c_double(nms_thresh), c_int(topk), c_int(max_candidates), ptr(post), ptr(ob), ptr(osc), ptr(ocl), ptr(orow),
-        ptr(cnt), ptr(status), ptr(ws), c_longlong(nbytes), _stream(proposals))
+        ptr(cls_logits), cls_logits.stride(0), ptr(deltas), deltas.stride(0), K,
+        cls_agnostic, ptr(proposals.contiguous()), ptr(prop_count), B, R, ptr(image_sizes),
+        wx, wy, ww, wh, SCALE_CLAMP, score_thresh,
+        nms_thresh, topk, max_candidates, ptr(post), ptr(ob), ptr(osc), ptr(ocl), ptr(orow),
+        ptr(cnt), ptr(status), ptr(ws), nbytes, _stream(proposals))
     check(rc, "lvc_fast_rcnn_inference")
     return ob, osc, ocl, orow, cnt
 
@@ -1609,7 +1606,7 @@ def retinanet_select(logits, deltas, cell_anchors, strides, anchor_offset, num_c
     hs, ws_, st = IP(*Hs), IP(*Ws), IP(*[int(s) for s in strides])
     lib = _lib.lib()
     try:
-        nbytes = _lib.size_query("lvc_retinanet_select_workspace_bytes", c_int(B), c_int(L), c_int(A), c_int(K), hs, ws_, c_int(topk), c_int(max_survivors))
+        nbytes = _lib.size_query("lvc_retinanet_select_workspace_bytes", B, L, A, K, hs, ws_, topk, max_survivors)
     except _lib.LvcNativeError:
         raise ValueError("retinanet_select: shapes outside the kernel's range") from None
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
@@ -1620,10 +1617,10 @@ def retinanet_select(logits, deltas, cell_anchors, strides, anchor_offset, num_c
     index = torch.empty(B, rows, device=dev, dtype=torch.int32)
     count = torch.empty(B, device=dev, dtype=torch.int32)
     wx, wy, ww, wh = [float(v) for v in box_weights]
-    rc = lib.lvc_retinanet_select(lp, ldl, dp, ldd, ap, hs, ws_, st, c_float(anchor_offset), c_int(L), c_int(A), c_int(K), c_int(B),
-                                  c_int(topk), c_float(score_thresh), c_float(wx), c_float(wy), c_float(ww), c_float(wh),
-                                  c_float(SCALE_CLAMP), c_int(max_survivors), ptr(boxes), ptr(scores), ptr(classes), ptr(index),
-                                  ptr(count), ptr(status), ptr(ws), c_longlong(nbytes), _stream(boxes))
+    rc = lib.lvc_retinanet_select(lp, ldl, dp, ldd, ap, hs, ws_, st, anchor_offset, L, A, K, B,
+                                  topk, score_thresh, wx, wy, ww, wh,
+                                  SCALE_CLAMP, max_survivors, ptr(boxes), ptr(scores), ptr(classes), ptr(index),
+                                  ptr(count), ptr(status), ptr(ws), nbytes, _stream(boxes))
     check(rc, "lvc_retinanet_select")
     return boxes, scores, classes, index, count, status
 
@@ -1688,8 +1685,8 @@ class RetinaNetLossArgs:
         lp, ldl = self._levels(self.logits)
         dp, ldd = self._levels(self.deltas)
         IP = c_int * self.L
-        return ([lp, ldl, dp, ldd, IP(*self.Hs), IP(*self.Ws), c_int(self.L), c_int(self.A), c_int(self.K), c_int(self.B)]
-                + [ptr(t) for t in self.tensors] + [c_double(v) for v in self.scalars])
+        return ([lp, ldl, dp, ldd, IP(*self.Hs), IP(*self.Ws), self.L, self.A, self.K, self.B]
+                + [ptr(t) for t in self.tensors] + list(self.scalars))
 
 
 def retinanet_loss(args, normalizer_in, normalizer_out, momentum=0.9, one_minus_momentum=1 - 0.9, return_sums=False):
@@ -1706,15 +1703,15 @@ def retinanet_loss(args, normalizer_in, normalizer_out, momentum=0.9, one_minus_
     lib = _lib.lib()
     IP = c_int * args.L
     try:
-        nbytes = _lib.size_query("lvc_retinanet_loss_workspace_bytes", c_int(args.B), c_int(args.L), c_int(args.A), c_int(args.K), IP(*args.Hs), IP(*args.Ws))
+        nbytes = _lib.size_query("lvc_retinanet_loss_workspace_bytes", args.B, args.L, args.A, args.K, IP(*args.Hs), IP(*args.Ws))
     except _lib.LvcNativeError:
         raise ValueError("retinanet_loss: shapes outside the kernel's range") from None
     ws = torch.empty(nbytes, dtype=torch.uint8, device=args.dev)
     out = torch.empty(2, dtype=torch.float32, device=args.dev)
     num_pos = torch.empty(1, dtype=torch.int32, device=args.dev)
     sums = torch.empty(2, dtype=torch.float64, device=args.dev) if return_sums else None
-    rc = lib.lvc_retinanet_loss(*args.common(), c_double(momentum), c_double(one_minus_momentum), ptr(normalizer_in), ptr(normalizer_out),
-                                ptr(out), ptr(sums), ptr(num_pos), ptr(ws), c_longlong(nbytes), _stream(out))
+    rc = lib.lvc_retinanet_loss(*args.common(), momentum, one_minus_momentum, ptr(normalizer_in), ptr(normalizer_out),
+                                ptr(out), ptr(sums), ptr(num_pos), ptr(ws), nbytes, _stream(out))
     check(rc, "lvc_retinanet_loss")
     return (out, num_pos, sums) if return_sums else (out, num_pos)
 
@@ -1759,8 +1756,8 @@ def gather_detections(boxes, scores, classes, rows, keep, num_keep, topk, post=N
     ocl = torch.empty(B, topk, device=dev, dtype=torch.int32)
     orow = torch.empty(B, topk, device=dev, dtype=torch.int32)
     cnt = torch.empty(B, device=dev, dtype=torch.int32)
-    check(_lib.lib().lvc_gather_detections(ptr(boxes), ptr(scores), ptr(classes), ptr(rows), ptr(keep), ptr(num_keep), c_int(B), c_int(Nmax),
-                                           c_int(topk), ptr(post), ptr(ob), ptr(osc), ptr(ocl), ptr(orow), ptr(cnt), _stream(boxes)),
+    check(_lib.lib().lvc_gather_detections(ptr(boxes), ptr(scores), ptr(classes), ptr(rows), ptr(keep), ptr(num_keep), B, Nmax,
+                                           topk, ptr(post), ptr(ob), ptr(osc), ptr(ocl), ptr(orow), ptr(cnt), _stream(boxes)),
           "lvc_gather_detections")
     return ob, osc, ocl, orow, cnt
 
@@ -1781,8 +1778,8 @@ def preprocess_into(image, out_slot, mean, std):
     assert four == 4 and out_slot.is_contiguous()
     m = _float3(mean)
     s = _float3(std)
-    rc = _lib.lib().lvc_preprocess_nhwc4(ptr(image), c_int(dt), c_int(image.shape[1]), c_int(image.shape[2]), m, s,
-                                         ptr(out_slot), c_int(Hp), c_int(Wp), _stream(image))
+    rc = _lib.lib().lvc_preprocess_nhwc4(ptr(image), dt, image.shape[1], image.shape[2], m, s,
+                                         ptr(out_slot), Hp, Wp, _stream(image))
     check(rc, "lvc_preprocess_nhwc4")
 
 
@@ -1806,8 +1803,8 @@ def preprocess_batch_into(images, out, mean, std):
     ws = (c_int * B)(*[int(im.shape[2]) for im in imgs])
     m = _float3(mean)
     s_ = _float3(std)
-    rc = _lib.lib().lvc_preprocess_batch_nhwc4(P, c_int(1 if u8 else 0), hs, ws, c_int(B), m, s_, ptr(out), c_int(out.shape[1]),
-                                               c_int(out.shape[2]), _stream(out))
+    rc = _lib.lib().lvc_preprocess_batch_nhwc4(P, 1 if u8 else 0, hs, ws, B, m, s_, ptr(out), out.shape[1],
+                                               out.shape[2], _stream(out))
     check(rc, "lvc_preprocess_batch_nhwc4")
     return imgs   # keeps converted copies alive until the caller drops them (the launch is asynchronous)
 
@@ -1836,9 +1833,9 @@ def resize_bilinear_u8(img, new_h, new_w, coeffs_fn, out_slot=None, mean=None, s
         assert four == 4 and out_slot.is_contiguous() and out_slot.dtype == torch.float32
         m = _float3(mean)
         s = _float3(std)
-    rc = _lib.lib().lvc_resize_bilinear_u8(ptr(img), c_int(H), c_int(W), c_int(new_h), c_int(new_w), ptr(xb), ptr(xk),
-                                           c_int(kxs), ptr(yb), ptr(yk), c_int(kys), ptr(tmp), ptr(out), ptr(out_slot),
-                                           c_int(Hp), c_int(Wp), m, s, _stream(img))
+    rc = _lib.lib().lvc_resize_bilinear_u8(ptr(img), H, W, new_h, new_w, ptr(xb), ptr(xk),
+                                           kxs, ptr(yb), ptr(yk), kys, ptr(tmp), ptr(out), ptr(out_slot),
+                                           Hp, Wp, m, s, _stream(img))
     check(rc, "lvc_resize_bilinear_u8")
     return out
 
@@ -1873,8 +1870,8 @@ def tta_resize_u8(img, H, W, strides, hjobs, vjobs, mean, std):
     m = _float3(mean)
     s = _float3(std)
     sy, sx, sc = strides
-    rc = _lib.lib().lvc_tta_resize_u8(ptr(img), c_int(H), c_int(W), c_longlong(sy), c_longlong(sx), c_longlong(sc), hj,
-                                      c_int(len(hjobs)), vj, c_int(len(vjobs)), m, s, _stream(img))
+    rc = _lib.lib().lvc_tta_resize_u8(ptr(img), H, W, sy, sx, sc, hj,
+                                      len(hjobs), vj, len(vjobs), m, s, _stream(img))
     check(rc, "lvc_tta_resize_u8")
 
 
@@ -1986,8 +1983,8 @@ def _train_input_call(entry, log, ws, tab, tables, tmp_bytes, out, mean, std):
     """Upload the blob and call one of the three lvc_train_input*_u8 entries (one signature) on out's current stream."""
     nbytes = ws.upload(tab, tables, tmp_bytes, out.device)
     n = c_int(0)
-    rc = getattr(_lib.lib(), entry)(ptr(ws.host), ptr(ws.dev), c_longlong(nbytes), c_int(len(tab)), ptr(ws.scratch), c_longlong(ws.scratch.numel()),
-                                    ptr(out), c_int(out.shape[0]), c_int(out.shape[1]), c_int(out.shape[2]), _float3(mean), _float3(std),
+    rc = getattr(_lib.lib(), entry)(ptr(ws.host), ptr(ws.dev), nbytes, len(tab), ptr(ws.scratch), ws.scratch.numel(),
+                                    ptr(out), out.shape[0], out.shape[1], out.shape[2], _float3(mean), _float3(std),
                                     ctypes.byref(n), _stream(out))
     check(rc, entry)
     _log_launches(log, n.value)
@@ -2148,8 +2145,8 @@ def color_jitter_tiles_u8(items, workspace=None, table_hook=None, device=None):
         table_hook(tab)
     nbytes = ws.upload(tab, [], out_off, ws.device)
     n = c_int(0)
-    rc = _lib.lib().lvc_color_jitter_tiles_u8(ptr(ws.host), ptr(ws.dev), c_longlong(nbytes), c_int(B), ptr(ws.scratch),
-                                              c_longlong(ws.scratch.numel()), ctypes.byref(n), _stream(ws.scratch))
+    rc = _lib.lib().lvc_color_jitter_tiles_u8(ptr(ws.host), ptr(ws.dev), nbytes, B, ptr(ws.scratch),
+                                              ws.scratch.numel(), ctypes.byref(n), _stream(ws.scratch))
     check(rc, "lvc_color_jitter_tiles_u8")
     _log_launches(COLOR_JITTER_LAUNCHES, n.value)
     return [ws.scratch[off:off + h * w * 3].view(h, w, 3) for off, h, w in shapes]
@@ -2177,13 +2174,13 @@ def tta_merge(boxes, scores, classes, counts, params, tab, num_images, nmax, sco
     cnt = torch.zeros(B, device=dev, dtype=torch.int32)
     if topk == 0 or B == 0:
         return ob[:, :0], osc[:, :0], ocl[:, :0], cnt
-    wsb = _lib.size_query("lvc_tta_merge_workspace_bytes", c_int(B), c_int(nmax))
+    wsb = _lib.size_query("lvc_tta_merge_workspace_bytes", B, nmax)
     ws = torch.empty(wsb + 256, dtype=torch.uint8, device=dev)
     off = (-ws.data_ptr()) % 256
     ws = ws[off:off + wsb]
-    rc = _lib.lib().lvc_tta_merge(ptr(boxes.contiguous()), ptr(scores.contiguous()), ptr(classes.contiguous()), ptr(counts), c_int(T),
-                                  ptr(params), ptr(tab), c_int(B), c_int(nmax), c_float(score_thresh), c_double(nms_thresh),
-                                  c_int(topk), ptr(ob), ptr(osc), ptr(ocl), ptr(cnt), ptr(ws), c_longlong(wsb), _stream(boxes))
+    rc = _lib.lib().lvc_tta_merge(ptr(boxes.contiguous()), ptr(scores.contiguous()), ptr(classes.contiguous()), ptr(counts), T,
+                                  ptr(params), ptr(tab), B, nmax, score_thresh, nms_thresh,
+                                  topk, ptr(ob), ptr(osc), ptr(ocl), ptr(cnt), ptr(ws), wsb, _stream(boxes))
     check(rc, "lvc_tta_merge")
     return ob, osc, ocl, cnt
 
@@ -2195,8 +2192,8 @@ def maxpool2d_nhwc(x, k, stride, pad):
     Ho = (H + 2 * pad - k) // stride + 1
     Wo = (W + 2 * pad - k) // stride + 1
     y = torch.empty(N, Ho, Wo, C, device=x.device, dtype=torch.float32)
-    rc = _lib.lib().lvc_maxpool2d_nhwc(ptr(x), ptr(y), c_int(N), c_int(H), c_int(W), c_int(C), c_int(k), c_int(stride),
-                                       c_int(pad), _stream(x))
+    rc = _lib.lib().lvc_maxpool2d_nhwc(ptr(x), ptr(y), N, H, W, C, k, stride,
+                                       pad, _stream(x))
     check(rc, "lvc_maxpool2d_nhwc")
     return y
 
@@ -2208,8 +2205,8 @@ def rownorm(x, mu=None, eps=1e-5, mode=0, out=None):
     M, D = x.shape
     if out is None:
         out = torch.empty(M, D, device=x.device, dtype=torch.float32)
-    rc = _lib.lib().lvc_rownorm(ptr(x), ptr(mu), ptr(out), c_int(M), c_int(D), c_int(x.stride(0)), c_int(out.stride(0)),
-                                c_float(eps), c_int(mode), _stream(x))
+    rc = _lib.lib().lvc_rownorm(ptr(x), ptr(mu), ptr(out), M, D, x.stride(0), out.stride(0),
+                                eps, mode, _stream(x))
     check(rc, "lvc_rownorm")
     return out
 
@@ -2221,8 +2218,8 @@ def rownorm_backward(x, dy, eps=1e-5, accumulate_into=None):
     M, D = x.shape
     dx = accumulate_into if accumulate_into is not None else torch.empty_like(x)
     assert dx.is_contiguous() and dx.shape == x.shape
-    check(_lib.lib().lvc_rownorm_backward(ptr(x), ptr(dy), ptr(dx), c_int(M), c_int(D), c_float(eps),
-                                          c_int(1 if accumulate_into is not None else 0), _stream(x)), "lvc_rownorm_backward")
+    check(_lib.lib().lvc_rownorm_backward(ptr(x), ptr(dy), ptr(dx), M, D, eps,
+                                          1 if accumulate_into is not None else 0, _stream(x)), "lvc_rownorm_backward")
     return dx
 
 
@@ -2231,7 +2228,7 @@ def colmean(x):
     _req_cuda(x)
     assert x.dim() == 2 and x.stride(1) == 1 and x.dtype == torch.float32
     mu = torch.empty(x.shape[1], device=x.device, dtype=torch.float32)
-    rc = _lib.lib().lvc_colmean(ptr(x), ptr(mu), c_int(x.shape[0]), c_int(x.shape[1]), c_int(x.stride(0)), _stream(x))
+    rc = _lib.lib().lvc_colmean(ptr(x), ptr(mu), x.shape[0], x.shape[1], x.stride(0), _stream(x))
     check(rc, "lvc_colmean")
     return mu
 
@@ -2247,8 +2244,8 @@ def knn_topk_vote(sims, num_shots, shot_classes, det_classes, k):
     if det_classes is not None:
         det_classes = det_classes.contiguous()
         assert det_classes.dtype == torch.int64
-    rc = _lib.lib().lvc_knn_topk_vote(ptr(sims), c_int(sims.stride(0)), c_int(Q), c_int(num_shots), ptr(shot_classes),
-                                      ptr(det_classes), c_int(k), ptr(top), ptr(keep), _stream(sims))
+    rc = _lib.lib().lvc_knn_topk_vote(ptr(sims), sims.stride(0), Q, num_shots, ptr(shot_classes),
+                                      ptr(det_classes), k, ptr(top), ptr(keep), _stream(sims))
     check(rc, "lvc_knn_topk_vote")
     return top, keep
 
@@ -2269,14 +2266,14 @@ def knn_topk_vote_blocks(sims, num_shots, shot_classes, det_classes, k, block=40
     lib = _lib.lib()
     for b in range(nblk):
         s0, s1 = b * per, min(num_shots, (b + 1) * per)
-        check(lib.lvc_knn_topk_candidates(ptr(sims[:, s0:]), c_int(sims.stride(0)), c_int(Q), c_int(s1 - s0), c_int(s0), ptr(cv[b]),
+        check(lib.lvc_knn_topk_candidates(ptr(sims[:, s0:]), sims.stride(0), Q, s1 - s0, s0, ptr(cv[b]),
                                           ptr(ci[b]), _stream(sims)), "lvc_knn_topk_candidates")
     top = torch.empty(Q, 10, dtype=torch.int64, device=sims.device)
     keep = torch.empty(Q, dtype=torch.int64, device=sims.device) if det_classes is not None else None
     if det_classes is not None:
         det_classes = det_classes.contiguous()
         assert det_classes.dtype == torch.int64
-    check(lib.lvc_knn_merge_vote(ptr(cv), ptr(ci), c_int(nblk), c_int(Q), ptr(shot_classes), ptr(det_classes), c_int(k), ptr(top),
+    check(lib.lvc_knn_merge_vote(ptr(cv), ptr(ci), nblk, Q, ptr(shot_classes), ptr(det_classes), k, ptr(top),
                                  ptr(keep), _stream(sims)), "lvc_knn_merge_vote")
     return top, keep
 
@@ -2287,7 +2284,7 @@ def max_f32(x):
     x = x.contiguous()
     assert x.dtype == torch.float32
     out = torch.empty(1, dtype=torch.float32, device=x.device)
-    check(_lib.lib().lvc_max_f32(ptr(x), c_longlong(x.numel()), ptr(out), _stream(x)), "lvc_max_f32")
+    check(_lib.lib().lvc_max_f32(ptr(x), x.numel(), ptr(out), _stream(x)), "lvc_max_f32")
     return out
 
 
@@ -2298,7 +2295,7 @@ def knn_margins(qres, sres_max, acc, extra=0.0):
     qres = qres.contiguous()
     assert qres.dtype == torch.float32 and sres_max.dtype == torch.float32 and sres_max.numel() == 1
     out = torch.empty_like(qres)
-    check(_lib.lib().lvc_knn_margins(ptr(qres), ptr(sres_max), c_float(acc), c_float(extra), c_int(qres.numel()), ptr(out), _stream(qres)),
+    check(_lib.lib().lvc_knn_margins(ptr(qres), ptr(sres_max), acc, extra, qres.numel(), ptr(out), _stream(qres)),
           "lvc_knn_margins")
     return out
 
@@ -2314,8 +2311,8 @@ def rownorm_h(x, mu=None, eps=1e-5, mode=0, want_rows=True, want_resid=False):
     yh = torch.empty(M, D, device=x.device, dtype=torch.float16)
     den = torch.empty(M, device=x.device, dtype=torch.float32)
     resid = torch.empty(M, device=x.device, dtype=torch.float32) if want_resid else None
-    rc = _lib.lib().lvc_rownorm_h(ptr(x), ptr(mu), ptr(y), ptr(yh), ptr(den), ptr(resid), c_int(M), c_int(D), c_int(x.stride(0)),
-                                  c_float(eps), c_int(mode), _stream(x))
+    rc = _lib.lib().lvc_rownorm_h(ptr(x), ptr(mu), ptr(y), ptr(yh), ptr(den), ptr(resid), M, D, x.stride(0),
+                                  eps, mode, _stream(x))
     check(rc, "lvc_rownorm_h")
     return (y, yh, den, resid) if want_resid else (y, yh, den)
 
@@ -2334,11 +2331,11 @@ def gemm_f16(a, b, n=None, ldb=None, q15=False):
     if q15:
         ld = (N + 7) // 8 * 8
         y = torch.empty(M, ld, device=a.device, dtype=torch.int16)
-        rc = _lib.lib().lvc_gemm_f16_q15(ptr(a), ptr(b), c_int(ldb), ptr(y), c_int(M), c_int(N), c_int(C), c_int(ld), _stream(a))
+        rc = _lib.lib().lvc_gemm_f16_q15(ptr(a), ptr(b), ldb, ptr(y), M, N, C, ld, _stream(a))
         check(rc, "lvc_gemm_f16_q15")
         return y[:, :N]
     y = torch.empty(M, N, device=a.device, dtype=torch.float32)
-    rc = _lib.lib().lvc_gemm_f16(ptr(a), ptr(b), c_int(ldb), ptr(y), c_int(M), c_int(N), c_int(C), c_int(N), _stream(a))
+    rc = _lib.lib().lvc_gemm_f16(ptr(a), ptr(b), ldb, ptr(y), M, N, C, N, _stream(a))
     check(rc, "lvc_gemm_f16")
     return y
 
@@ -2362,9 +2359,9 @@ def knn_verify_topk_vote(approx, q, sn, margin, shot_classes, det_classes, k, mu
         assert det_classes.dtype == torch.int64
     fn = _lib.lib().lvc_knn_verify_topk_vote_q15 if approx.dtype == torch.int16 else _lib.lib().lvc_knn_verify_topk_vote
     assert approx.dtype in (torch.int16, torch.float32)
-    rc = fn(ptr(approx), c_int(approx.stride(0)), c_int(Q), c_int(S), ptr(q), c_int(q.stride(0)),
-            ptr(mu), ptr(den), ptr(sn), c_int(sn.shape[1]), c_float(margin), ptr(margins),
-            ptr(shot_classes), ptr(det_classes), c_int(k), ptr(top), ptr(keep), _stream(approx))
+    rc = fn(ptr(approx), approx.stride(0), Q, S, ptr(q), q.stride(0),
+            ptr(mu), ptr(den), ptr(sn), sn.shape[1], margin, ptr(margins),
+            ptr(shot_classes), ptr(det_classes), k, ptr(top), ptr(keep), _stream(approx))
     check(rc, "lvc_knn_verify_topk_vote")
     return top, keep
 
@@ -2386,9 +2383,9 @@ def match_boxes(gt_boxes, boxes, thresholds, labels, allow_low_quality_matches):
     assert nthr in (1, 2) and len(labels) == nthr + 1
     t = list(thresholds) + [0.0]
     lab = list(labels) + [0]
-    rc = _lib.lib().lvc_match_boxes(ptr(gt_boxes), c_int(G), ptr(boxes), c_int(N), c_float(t[0]), c_float(t[1]),
-                                    c_int(nthr), c_int(lab[0]), c_int(lab[1]), c_int(lab[2]),
-                                    c_int(1 if allow_low_quality_matches else 0), ptr(matches), ptr(mlabels), ptr(vals),
+    rc = _lib.lib().lvc_match_boxes(ptr(gt_boxes), G, ptr(boxes), N, t[0], t[1],
+                                    nthr, lab[0], lab[1], lab[2],
+                                    1 if allow_low_quality_matches else 0, ptr(matches), ptr(mlabels), ptr(vals),
                                     ptr(scratch), _stream(boxes))
     check(rc, "lvc_match_boxes")
     return matches, mlabels, vals
@@ -2426,9 +2423,9 @@ def match_boxes_batched(gt, gt_off, B, boxes, nbox, thresholds, labels, allow_lo
     assert nthr in (1, 2) and len(labels) == nthr + 1
     t = list(thresholds) + [0.0]
     lab = list(labels) + [0]
-    rc = _lib.lib().lvc_match_boxes_batched(ptr(gt.contiguous()), ptr(gt_off), c_int(G), c_int(B), ptr(boxes), c_longlong(0 if shared else N * 4),
-                                            ptr(nbox), c_int(N), c_float(t[0]), c_float(t[1]), c_int(nthr), c_int(lab[0]), c_int(lab[1]),
-                                            c_int(lab[2]), c_int(1 if allow_low_quality_matches else 0), ptr(matches), ptr(mlabels), ptr(vals),
+    rc = _lib.lib().lvc_match_boxes_batched(ptr(gt.contiguous()), ptr(gt_off), G, B, ptr(boxes), 0 if shared else N * 4,
+                                            ptr(nbox), N, t[0], t[1], nthr, lab[0], lab[1],
+                                            lab[2], 1 if allow_low_quality_matches else 0, ptr(matches), ptr(mlabels), ptr(vals),
                                             ptr(scratch), _stream(boxes))
     check(rc, "lvc_match_boxes_batched")
     if return_vals:
@@ -2469,11 +2466,10 @@ def subsample_batched(labels, keys, cap_pos, bs, seed=0):
     if ws is None:      # zeroed once; the kernels leave it zeroed (per stream: two launches in flight must not share the histograms)
         if len(_SUBSAMPLE_WS) > 16:
             _SUBSAMPLE_WS.clear()
-        ws = _SUBSAMPLE_WS[key] = torch.zeros(_lib.size_query("lvc_subsample_workspace_bytes", c_int(B)), dtype=torch.uint8, device=labels.device)
-    from ctypes import c_ulonglong
+        ws = _SUBSAMPLE_WS[key] = torch.zeros(_lib.size_query("lvc_subsample_workspace_bytes", B), dtype=torch.uint8, device=labels.device)
 
-    rc = lib.lvc_subsample_batched(ptr(labels.contiguous()), ptr(keys.contiguous() if keys is not None else None), c_ulonglong(int(seed)),
-                                   c_int(B), c_int(N), c_int(nbits), c_int(cap_pos), c_int(bs), ptr(sel), ptr(counts), ptr(ws), _stream(labels))
+    rc = lib.lvc_subsample_batched(ptr(labels.contiguous()), ptr(keys.contiguous() if keys is not None else None), int(seed),
+                                   B, N, nbits, cap_pos, bs, ptr(sel), ptr(counts), ptr(ws), _stream(labels))
     check(rc, "lvc_subsample_batched")
     return sel, counts
 
@@ -2498,7 +2494,7 @@ def rpn_gather_sampled(fused, A, cell_anchors, strides, sel, counts, matches, gt
     cells = [c.contiguous() for c in cell_anchors]
     rc = _lib.lib().lvc_rpn_gather_sampled(VP(*[t.data_ptr() for t in fused]), IP(*[t.stride(2) for t in fused]), VP(*[c.data_ptr() for c in cells]),
                                            IP(*[t.shape[1] for t in fused]), IP(*[t.shape[2] for t in fused]), IP(*[int(s) for s in strides]),
-                                           c_int(L), c_int(A), c_int(B), c_int(bs), ptr(sel), ptr(counts), ptr(matches), ptr(gt), ptr(gt_off),
+                                           L, A, B, bs, ptr(sel), ptr(counts), ptr(matches), ptr(gt), ptr(gt_off),
                                            ptr(logits), ptr(deltas), ptr(anchors), ptr(gtb), ptr(labels), _stream(sel))
     check(rc, "lvc_rpn_gather_sampled")
     return logits, deltas, anchors, gtb, labels
@@ -2513,8 +2509,8 @@ def roi_build_table(pboxes, plogits, pcount, gt, gt_off, gt_logit, Wt):
     boxes = torch.empty(B, Wt, 4, device=dev)
     logits = torch.empty(B, Wt, device=dev)
     nrow = torch.empty(B, dtype=torch.int32, device=dev)
-    rc = _lib.lib().lvc_roi_build_table(ptr(pboxes.contiguous()), ptr(plogits.contiguous()), ptr(pcount), c_int(B), c_int(P), ptr(gt), ptr(gt_off),
-                                        c_float(gt_logit), c_int(Wt), ptr(boxes), ptr(logits), ptr(nrow), _stream(pboxes))
+    rc = _lib.lib().lvc_roi_build_table(ptr(pboxes.contiguous()), ptr(plogits.contiguous()), ptr(pcount), B, P, ptr(gt), ptr(gt_off),
+                                        gt_logit, Wt, ptr(boxes), ptr(logits), ptr(nrow), _stream(pboxes))
     check(rc, "lvc_roi_build_table")
     return boxes, logits, nrow
 
@@ -2533,7 +2529,7 @@ def roi_gather_sampled(boxes, logits, matches, sel, counts, gt_classes, gt_off, 
     sm = torch.empty(B, bs, dtype=torch.int64, device=dev)
     assert gt_classes.dtype == torch.int64
     rc = _lib.lib().lvc_roi_gather_sampled(ptr(boxes), ptr(logits), ptr(matches), ptr(sel), ptr(counts), ptr(gt_classes.contiguous()), ptr(gt_off),
-                                           c_int(B), c_int(Wt), c_int(bs), c_int(num_classes), ptr(sb), ptr(sl), ptr(sc), ptr(sm), _stream(boxes))
+                                           B, Wt, bs, num_classes, ptr(sb), ptr(sl), ptr(sc), ptr(sm), _stream(boxes))
     check(rc, "lvc_roi_gather_sampled")
     return sb, sl, sc, sm
 
@@ -2554,10 +2550,10 @@ def fast_rcnn_losses(logits, deltas, proposals, gt_boxes, gt_classes, num_classe
     row_terms = torch.empty(2 * R, device=dev, dtype=torch.float64)
     wx, wy, ww, wh = box_weights
     assert logits.stride(1) == 1 and deltas.stride(1) == 1 and gt_classes.dtype == torch.int64
-    rc = _lib.lib().lvc_fast_rcnn_losses(ptr(logits), c_int(logits.stride(0)), ptr(deltas), c_int(deltas.stride(0)), c_int(K),
-                                         c_int(1 if nreg == 4 else 0), ptr(proposals.contiguous()), ptr(gt_boxes.contiguous()),
-                                         ptr(gt_classes.contiguous()), c_int(R), c_float(wx), c_float(wy), c_float(ww),
-                                         c_float(wh), c_float(smooth_l1_beta), ptr(out), ptr(dl), ptr(dd), ptr(row_terms),
+    rc = _lib.lib().lvc_fast_rcnn_losses(ptr(logits), logits.stride(0), ptr(deltas), deltas.stride(0), K,
+                                         1 if nreg == 4 else 0, ptr(proposals.contiguous()), ptr(gt_boxes.contiguous()),
+                                         ptr(gt_classes.contiguous()), R, wx, wy, ww,
+                                         wh, smooth_l1_beta, ptr(out), ptr(dl), ptr(dd), ptr(row_terms),
                                          _stream(logits))
     check(rc, "lvc_fast_rcnn_losses")
     return out, dl, dd
@@ -2572,10 +2568,10 @@ def giou_box_loss(deltas, proposals, gt_boxes, gt_classes, num_classes, box_weig
     dd = torch.empty(R, 4, device=deltas.device, dtype=torch.float32)
     wx, wy, ww, wh = box_weights
     assert deltas.stride(1) == 1 and gt_classes.dtype == torch.int64
-    rc = _lib.lib().lvc_giou_box_loss(ptr(deltas), c_int(deltas.stride(0)), ptr(proposals.contiguous()),
-                                      ptr(gt_boxes.contiguous()), ptr(gt_classes.contiguous()), c_int(R),
-                                      c_int(num_classes), c_float(wx), c_float(wy), c_float(ww), c_float(wh),
-                                      c_float(scale_clamp), c_int(1 if iterate else 0), c_float(lambda_), ptr(out),
+    rc = _lib.lib().lvc_giou_box_loss(ptr(deltas), deltas.stride(0), ptr(proposals.contiguous()),
+                                      ptr(gt_boxes.contiguous()), ptr(gt_classes.contiguous()), R,
+                                      num_classes, wx, wy, ww, wh,
+                                      scale_clamp, 1 if iterate else 0, lambda_, ptr(out),
                                       ptr(dd), _stream(deltas))
     check(rc, "lvc_giou_box_loss")
     return out, dd
@@ -2585,7 +2581,7 @@ def relu_backward(dy, y):
     _req_cuda(dy, y)
     dy, y = dy.contiguous(), y.contiguous()
     out = torch.empty_like(dy)
-    check(_lib.lib().lvc_relu_backward(ptr(dy), ptr(y), c_longlong(dy.numel()), ptr(out), _stream(dy)), "lvc_relu_backward")
+    check(_lib.lib().lvc_relu_backward(ptr(dy), ptr(y), dy.numel(), ptr(out), _stream(dy)), "lvc_relu_backward")
     return out
 
 
@@ -2601,7 +2597,7 @@ def colsum(x):
     x = x.contiguous()
     M, N = x.shape
     out = torch.empty(N, device=x.device, dtype=torch.float32)
-    check(_lib.lib().lvc_colsum(ptr(x), c_int(M), c_int(N), c_int(N), ptr(out), _stream(x)), "lvc_colsum")
+    check(_lib.lib().lvc_colsum(ptr(x), M, N, N, ptr(out), _stream(x)), "lvc_colsum")
     return out
 
 
@@ -2611,7 +2607,7 @@ def colsum_rows(x2d):
     x2d = x2d.contiguous()
     M, N = x2d.shape
     out = torch.empty(N, device=x2d.device, dtype=torch.float32)
-    check(_lib.lib().lvc_colsum_atomic(ptr(x2d), c_int(M), c_int(N), c_int(N), ptr(out), _stream(x2d)), "lvc_colsum_atomic")
+    check(_lib.lib().lvc_colsum_atomic(ptr(x2d), M, N, N, ptr(out), _stream(x2d)), "lvc_colsum_atomic")
     return out
 
 
@@ -2651,14 +2647,14 @@ def _conv_wgrad(x, dy, scale, R, S, stride, pad, split=None):
     assert dy.shape[0] == N and dy.shape[1] == (H + 2 * pad - R) // stride + 1 and dy.shape[2] == (W + 2 * pad - S) // stride + 1
     dw = torch.empty(K, R, S, C, device=x.device, dtype=torch.float32)
     if (split or DGRAD_SPLIT) == "f16x2":   # gradients scaled into fp16's range (solver.LossScaler): fp16 MFMA path
-        check(_lib.lib().lvc_conv_wgrad_nhwc_f16x2(ptr(x), ptr(dy), ptr(scale), ptr(dw), c_int(N), c_int(H), c_int(W),
-                                                   c_int(C), c_int(K), c_int(R), c_int(S), c_int(stride), c_int(pad),
-                                                   c_int(K), ptr(_conv_error_view(x.device)), _stream(x)),
+        check(_lib.lib().lvc_conv_wgrad_nhwc_f16x2(ptr(x), ptr(dy), ptr(scale), ptr(dw), N, H, W,
+                                                   C, K, R, S, stride, pad,
+                                                   K, ptr(_conv_error_view(x.device)), _stream(x)),
               "lvc_conv_wgrad_nhwc_f16x2")
         return dw
     fn = "lvc_conv_wgrad_nhwc_bf16x3" if WGRAD_ENGINE == "bf16x3" else "lvc_conv_wgrad_nhwc"
-    check(getattr(_lib.lib(), fn)(ptr(x), ptr(dy), ptr(scale), ptr(dw), c_int(N), c_int(H), c_int(W), c_int(C), c_int(K),
-                                  c_int(R), c_int(S), c_int(stride), c_int(pad), c_int(K), _stream(x)), fn)
+    check(getattr(_lib.lib(), fn)(ptr(x), ptr(dy), ptr(scale), ptr(dw), N, H, W, C, K,
+                                  R, S, stride, pad, K, _stream(x)), fn)
     return dw
 
 
@@ -2677,12 +2673,12 @@ def conv_wgrad_grouped(x, dy, scale, groups, stride):
     if x.numel() == 0:
         return dw.zero_()
     lib = _lib.lib()
-    nbytes = _lib.size_query("lvc_conv3x3_grouped_wgrad_workspace_bytes", c_int(N), c_int(H), c_int(W), c_int(C), c_int(groups), c_int(stride))
+    nbytes = _lib.size_query("lvc_conv3x3_grouped_wgrad_workspace_bytes", N, H, W, C, groups, stride)
     scratch = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
 
     def run():
-        check(lib.lvc_conv3x3_grouped_wgrad_nhwc(ptr(x), ptr(dy), ptr(scale), ptr(dw), c_int(N), c_int(H), c_int(W), c_int(C), c_int(groups),
-                                                 c_int(stride), c_int(C), ptr(scratch), _stream(x)), "lvc_conv3x3_grouped_wgrad_nhwc")
+        check(lib.lvc_conv3x3_grouped_wgrad_nhwc(ptr(x), ptr(dy), ptr(scale), ptr(dw), N, H, W, C, groups,
+                                                 stride, C, ptr(scratch), _stream(x)), "lvc_conv3x3_grouped_wgrad_nhwc")
         return dw
 
     return _bwd_timed("wgrad", "f32_grouped", 2.0 * dy.numel() * cg * 9, 4.0 * (x.numel() + dy.numel() + dw.numel()), run,
@@ -2887,10 +2883,10 @@ def flush_wgrad(final=False):
     st = c_void_p(side.cuda_stream)
 
     def launch():
-        check(_lib.lib().lvc_conv_wgrad_group_bf16x3(c_int(n), xs, dys, scs, dws, shapes, st), "lvc_conv_wgrad_group_bf16x3")
+        check(_lib.lib().lvc_conv_wgrad_group_bf16x3(n, xs, dys, scs, dws, shapes, st), "lvc_conv_wgrad_group_bf16x3")
 
     _bwd_timed("wgrad", "bf16x3", flops, nbytes, launch, "group of %d" % n)
-    check(_lib.lib().lvc_wgrad_finalize_group(c_int(nf), srcs, dsts, fshapes, st), "lvc_wgrad_finalize_group")
+    check(_lib.lib().lvc_wgrad_finalize_group(nf, srcs, dsts, fshapes, st), "lvc_wgrad_finalize_group")
     if side is main:
         _deliver_wgrad(outs)
         return
@@ -2923,7 +2919,7 @@ def scatter_stride2(x, H, W):
     N, Hs, Ws, C = x.shape
     assert Hs == (H - 1) // 2 + 1 and Ws == (W - 1) // 2 + 1
     y = torch.empty(N, H, W, C, device=x.device, dtype=torch.float32)
-    check(_lib.lib().lvc_scatter_stride2_nhwc(ptr(x), ptr(y), c_int(N), c_int(H), c_int(W), c_int(C), _stream(x)),
+    check(_lib.lib().lvc_scatter_stride2_nhwc(ptr(x), ptr(y), N, H, W, C, _stream(x)),
           "lvc_scatter_stride2_nhwc")
     return y
 
@@ -2937,7 +2933,7 @@ def subsample2_into(x, out):
     assert x.is_contiguous() and x.dtype == torch.float32 and out.dtype == torch.float32 and out.shape == (N, Hs, Ws, C)
     ld = out.stride(2)
     assert out.stride(3) == 1 and out.stride(1) == Ws * ld and out.stride(0) == Hs * Ws * ld
-    check(_lib.lib().lvc_subsample2_nhwc(ptr(x), ptr(out), c_int(N), c_int(H), c_int(W), c_int(C), c_int(ld), _stream(x)),
+    check(_lib.lib().lvc_subsample2_nhwc(ptr(x), ptr(out), N, H, W, C, ld, _stream(x)),
           "lvc_subsample2_nhwc")
     return out
 
@@ -2949,7 +2945,7 @@ def downsum2x2(x):
     N, H, W, C = x.shape
     assert H % 2 == 0 and W % 2 == 0
     y = torch.empty(N, H // 2, W // 2, C, device=x.device, dtype=torch.float32)
-    check(_lib.lib().lvc_downsum2x2_nhwc(ptr(x), ptr(y), c_int(N), c_int(H // 2), c_int(W // 2), c_int(C), _stream(x)),
+    check(_lib.lib().lvc_downsum2x2_nhwc(ptr(x), ptr(y), N, H // 2, W // 2, C, _stream(x)),
           "lvc_downsum2x2_nhwc")
     return y
 
@@ -3000,7 +2996,7 @@ def avgpool2_into(x, out=None):
     if out is None:
         out, ldo = torch.empty(N, H // 2, W // 2, C, device=x.device, dtype=torch.float32), C
     if N:
-        check(_lib.lib().lvc_avgpool2_nhwc(ptr(x), ptr(out), c_int(N), c_int(H), c_int(W), c_int(C), c_int(ldo), _stream(x)),
+        check(_lib.lib().lvc_avgpool2_nhwc(ptr(x), ptr(out), N, H, W, C, ldo, _stream(x)),
               "lvc_avgpool2_nhwc")
     return out
 
@@ -3014,7 +3010,7 @@ def avgpool2_backward(dy, H, W):
     _req_cuda(dy)
     dx = torch.empty(N, H, W, C, device=dy.device, dtype=torch.float32)
     if N:
-        check(_lib.lib().lvc_avgpool2_bwd_nhwc(ptr(dy), ptr(dx), c_int(N), c_int(H), c_int(W), c_int(C), c_int(ldi), _stream(dy)),
+        check(_lib.lib().lvc_avgpool2_bwd_nhwc(ptr(dy), ptr(dx), N, H, W, C, ldi, _stream(dy)),
               "lvc_avgpool2_bwd_nhwc")
     return dx
 
@@ -3138,14 +3134,14 @@ def rpn_losses(logits, deltas, anchors, gt_boxes, labels, smooth_l1_beta, normal
         dl = torch.empty(S, device=logits.device, dtype=torch.float32)
         dd = torch.empty(S, 4, device=logits.device, dtype=torch.float32)
         rc = _lib.lib().lvc_rpn_losses_grad(ptr(logits.contiguous()), ptr(deltas.contiguous()), ptr(anchors.contiguous()),
-                                            ptr(gt_boxes.contiguous()), ptr(labels.contiguous()), c_int(S),
-                                            c_float(smooth_l1_beta), c_float(normalizer), ptr(out), ptr(dl), ptr(dd),
+                                            ptr(gt_boxes.contiguous()), ptr(labels.contiguous()), S,
+                                            smooth_l1_beta, normalizer, ptr(out), ptr(dl), ptr(dd),
                                             _stream(logits))
         check(rc, "lvc_rpn_losses_grad")
         return out, dl, dd
     rc = _lib.lib().lvc_rpn_losses(ptr(logits.contiguous()), ptr(deltas.contiguous()), ptr(anchors.contiguous()),
-                                   ptr(gt_boxes.contiguous()), ptr(labels.contiguous()), c_int(S), c_float(smooth_l1_beta),
-                                   c_float(normalizer), ptr(out), _stream(logits))
+                                   ptr(gt_boxes.contiguous()), ptr(labels.contiguous()), S, smooth_l1_beta,
+                                   normalizer, ptr(out), _stream(logits))
     check(rc, "lvc_rpn_losses")
     return out
 
@@ -3158,8 +3154,8 @@ def decode_boxes(deltas, boxes, weights, image_sizes=None):
     out = torch.empty_like(boxes)
     assert deltas.stride(1) == 1 and deltas.shape[0] == B * R
     wx, wy, ww, wh = weights
-    rc = _lib.lib().lvc_decode_boxes(ptr(deltas), c_int(deltas.stride(0)), ptr(boxes), c_int(B * R), c_int(R), ptr(image_sizes),
-                                     c_float(wx), c_float(wy), c_float(ww), c_float(wh), c_float(SCALE_CLAMP), ptr(out),
+    rc = _lib.lib().lvc_decode_boxes(ptr(deltas), deltas.stride(0), ptr(boxes), B * R, R, ptr(image_sizes),
+                                     wx, wy, ww, wh, SCALE_CLAMP, ptr(out),
                                      _stream(boxes))
     check(rc, "lvc_decode_boxes")
     return out
@@ -3173,7 +3169,7 @@ def crop_resize_nearest(image, windows, out_size=224):
     image = image.contiguous().float()
     assert windows.dtype == torch.int32 and windows.is_contiguous()
     out = torch.empty(Kn, C, out_size, out_size, device=image.device, dtype=torch.float32)
-    rc = _lib.lib().lvc_crop_resize_nearest(ptr(image), c_int(C), c_int(H), c_int(W), ptr(windows), c_int(Kn), c_int(out_size),
+    rc = _lib.lib().lvc_crop_resize_nearest(ptr(image), C, H, W, ptr(windows), Kn, out_size,
                                             ptr(out), _stream(image))
     check(rc, "lvc_crop_resize_nearest")
     return out
@@ -3193,10 +3189,10 @@ def vit_patchify(img, patch_size, kpad=None, mean=None, std=None):
         if mean is not None:
             m = (c_float * C)(*[float(v) for v in mean])
             s_ = (c_float * C)(*[float(v) for v in std])
-            check(_lib.lib().lvc_vit_patchify_norm(ptr(img), m, s_, ptr(out), c_int(B), c_int(C), c_int(H), c_int(W), c_int(patch_size),
+            check(_lib.lib().lvc_vit_patchify_norm(ptr(img), m, s_, ptr(out), B, C, H, W, patch_size,
                                                    _stream(img)), "lvc_vit_patchify_norm")
             return out
-        check(_lib.lib().lvc_vit_patchify(ptr(img), ptr(out), c_int(B), c_int(C), c_int(H), c_int(W), c_int(patch_size), _stream(img)),
+        check(_lib.lib().lvc_vit_patchify(ptr(img), ptr(out), B, C, H, W, patch_size, _stream(img)),
               "lvc_vit_patchify")
         return out
     tmp = vit_patchify(img, patch_size, mean=mean, std=std)
@@ -3211,7 +3207,7 @@ def vit_tokens(emb, cls, pos, B):
     P = emb.shape[0] // B
     out = torch.empty(B * (P + 1), D, device=emb.device, dtype=torch.float32)
     check(_lib.lib().lvc_vit_tokens(ptr(emb.contiguous()), ptr(cls.detach().contiguous()), ptr(pos.detach().contiguous()), ptr(out),
-                                    c_int(B), c_int(P), c_int(D), _stream(emb)), "lvc_vit_tokens")
+                                    B, P, D, _stream(emb)), "lvc_vit_tokens")
     return out
 
 
@@ -3220,8 +3216,8 @@ def layernorm(x, weight, bias, eps):
     assert x.dim() == 2 and x.stride(1) == 1 and x.dtype == torch.float32
     M, D = x.shape
     y = torch.empty(M, D, device=x.device, dtype=torch.float32)
-    check(_lib.lib().lvc_layernorm(ptr(x), c_int(x.stride(0)), ptr(weight.detach()), ptr(bias.detach()), ptr(y), c_int(D), c_int(M),
-                                   c_int(D), c_float(eps), _stream(x)), "lvc_layernorm")
+    check(_lib.lib().lvc_layernorm(ptr(x), x.stride(0), ptr(weight.detach()), ptr(bias.detach()), ptr(y), D, M,
+                                   D, eps, _stream(x)), "lvc_layernorm")
     return y
 
 
@@ -3229,7 +3225,7 @@ def gelu(x):
     _req_cuda(x)
     x = x.contiguous()
     y = torch.empty_like(x)
-    check(_lib.lib().lvc_gelu(ptr(x), ptr(y), c_longlong(x.numel()), _stream(x)), "lvc_gelu")
+    check(_lib.lib().lvc_gelu(ptr(x), ptr(y), x.numel(), _stream(x)), "lvc_gelu")
     return y
 
 
@@ -3263,14 +3259,14 @@ def qkv_attention(x, pc, B, N, num_heads, scale):
     if ws is None:      # zeroed ONCE: the epilogue never writes the padding rows N..Npad-1, which must stay zero
         if len(_MHA_PLANES_WS) > 8:
             _MHA_PLANES_WS.clear()
-        ws = _MHA_PLANES_WS[key] = torch.zeros(max(16, _lib.size_query("lvc_mha_workspace_bytes", c_int(B), c_int(N), c_int(num_heads))), dtype=torch.uint8, device=dev)
+        ws = _MHA_PLANES_WS[key] = torch.zeros(max(16, _lib.size_query("lvc_mha_workspace_bytes", B, N, num_heads)), dtype=torch.uint8, device=dev)
     planes, scale2 = pc.split2s()
     pc.last_one = True
     _launch(None, 0.0, 0.0, pc.slot, "lvc_conv1x1_qkv_planes_f16s1", lambda: lib.lvc_conv1x1_qkv_planes_f16s1(
-        ptr(x), ptr(planes), ptr(scale2), ptr(pc.shift), ptr(ws), c_int(B), c_int(N), c_int(pc.C), c_int(num_heads), c_float(scale),
+        ptr(x), ptr(planes), ptr(scale2), ptr(pc.shift), ptr(ws), B, N, pc.C, num_heads, scale,
         ptr(_conv_error_view(dev)), ptr(conv_workspace(dev)), _stream(x)))
     out = torch.empty(B * N, num_heads * 64, device=dev, dtype=torch.float32)
-    check(lib.lvc_mha_mfma_planes(ptr(ws), ptr(out), c_int(B), c_int(N), c_int(num_heads), _stream(x)), "lvc_mha_mfma_planes")
+    check(lib.lvc_mha_mfma_planes(ptr(ws), ptr(out), B, N, num_heads, _stream(x)), "lvc_mha_mfma_planes")
     return out
 
 
@@ -3280,7 +3276,7 @@ def mha_cls(qkv, B, N, num_heads, head_dim, scale):
     assert head_dim == 64      # more than 1024 keys: refused by the entry point
     qkv = qkv.contiguous()
     out = torch.empty(B, num_heads * head_dim, device=qkv.device, dtype=torch.float32)
-    check(_lib.lib().lvc_mha_cls(ptr(qkv), ptr(out), c_int(B), c_int(N), c_int(num_heads), c_float(scale), _stream(qkv)), "lvc_mha_cls")
+    check(_lib.lib().lvc_mha_cls(ptr(qkv), ptr(out), B, N, num_heads, scale, _stream(qkv)), "lvc_mha_cls")
     return out
 
 
@@ -3294,11 +3290,11 @@ def mha(qkv, B, N, num_heads, head_dim, scale, mfma=None):
     out = torch.empty(B * N, num_heads * head_dim, device=qkv.device, dtype=torch.float32)
     if ((MHA_MFMA and CONV_SPLIT == "f16x2") if mfma is None else mfma) and head_dim == 64:
         lib = _lib.lib()
-        ws = torch.empty(max(16, _lib.size_query("lvc_mha_workspace_bytes", c_int(B), c_int(N), c_int(num_heads))), dtype=torch.uint8, device=qkv.device)
-        check(lib.lvc_mha_mfma(ptr(qkv), ptr(out), ptr(ws), c_int(B), c_int(N), c_int(num_heads), c_float(scale),
+        ws = torch.empty(max(16, _lib.size_query("lvc_mha_workspace_bytes", B, N, num_heads)), dtype=torch.uint8, device=qkv.device)
+        check(lib.lvc_mha_mfma(ptr(qkv), ptr(out), ptr(ws), B, N, num_heads, scale,
                                    ptr(_conv_error_view(qkv.device)), _stream(qkv)), "lvc_mha_mfma")
         return out
-    check(_lib.lib().lvc_mha(ptr(qkv), ptr(out), c_int(B), c_int(N), c_int(num_heads), c_int(head_dim), c_float(scale), _stream(qkv)),
+    check(_lib.lib().lvc_mha(ptr(qkv), ptr(out), B, N, num_heads, head_dim, scale, _stream(qkv)),
           "lvc_mha")
     return out
 
@@ -3321,12 +3317,12 @@ def _gn_tile_rows(N, H, W):
 
 
 def _gn_workspace(x, N, H, W, C, G, rows, backward):
-    nbytes = _lib.size_query("lvc_group_norm_workspace_bytes", c_int(N), c_int(H), c_int(W), c_int(C), c_int(G), c_int(rows), c_int(backward))
+    nbytes = _lib.size_query("lvc_group_norm_workspace_bytes", N, H, W, C, G, rows, backward)
     return torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None, nbytes
 
 
 def _gn_strides(x):
-    return tuple(c_longlong(s) for s in x.stride())
+    return tuple(s for s in x.stride())
 
 
 def group_norm_nhwc(x, gamma, beta, num_groups, eps=1e-5, relu=False, residual=None, res_mode=0):
@@ -3353,9 +3349,9 @@ def group_norm_nhwc(x, gamma, beta, num_groups, eps=1e-5, relu=False, residual=N
         return y, mean, rstd
     rows = _gn_tile_rows(N, H, W)
     ws, nbytes = _gn_workspace(x, N, H, W, C, G, rows, 0)
-    rc = _lib.lib().lvc_group_norm_fwd_nhwc(ptr(x), ptr(gamma), ptr(beta), ptr(residual), ptr(y), ptr(mean), ptr(rstd), c_int(N), c_int(H),
-                                            c_int(W), c_int(C), c_int(G), *_gn_strides(x), c_float(eps), c_int(1 if relu else 0),
-                                            c_int(res_mode), c_int(rows), ptr(ws), c_longlong(nbytes), _stream(x))
+    rc = _lib.lib().lvc_group_norm_fwd_nhwc(ptr(x), ptr(gamma), ptr(beta), ptr(residual), ptr(y), ptr(mean), ptr(rstd), N, H,
+                                            W, C, G, *_gn_strides(x), eps, 1 if relu else 0,
+                                            res_mode, rows, ptr(ws), nbytes, _stream(x))
     check(rc, "lvc_group_norm_fwd_nhwc")
     return y, mean, rstd
 
@@ -3375,8 +3371,8 @@ def group_norm_backward_nhwc(dy, x, mean, rstd, gamma, beta, num_groups, relu=Fa
     rows = _gn_tile_rows(N, H, W)
     ws, nbytes = _gn_workspace(x, N, H, W, C, G, rows, 1)
     rc = _lib.lib().lvc_group_norm_bwd_nhwc(ptr(dy), ptr(x), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(dx), ptr(dgamma), ptr(dbeta),
-                                            c_int(N), c_int(H), c_int(W), c_int(C), c_int(G), *_gn_strides(x), c_int(1 if relu else 0),
-                                            c_int(rows), ptr(ws), c_longlong(nbytes), _stream(x))
+                                            N, H, W, C, G, *_gn_strides(x), 1 if relu else 0,
+                                            rows, ptr(ws), nbytes, _stream(x))
     check(rc, "lvc_group_norm_bwd_nhwc")
     return dx, dgamma, dbeta
 
@@ -3391,7 +3387,7 @@ def upsample2_residual_grad(g, res_shape):
         out = downsum2x2(g)
     else:
         out = torch.empty(N, (H + 1) // 2, (W + 1) // 2, C, device=g.device, dtype=torch.float32)
-        check(_lib.lib().lvc_upsample2_add_grad_nhwc(ptr(g), ptr(out), c_int(N), c_int(H), c_int(W), c_int(C), _stream(g)),
+        check(_lib.lib().lvc_upsample2_add_grad_nhwc(ptr(g), ptr(out), N, H, W, C, _stream(g)),
               "lvc_upsample2_add_grad_nhwc")
     assert tuple(out.shape) == tuple(res_shape)
     return out
@@ -3448,7 +3444,7 @@ def mask_deconv_predict(x, w_deconv, b_deconv, w_pred, b_pred, classes=None, num
         out = torch.empty(M, 2 * S, 2 * S, device=x.device, dtype=torch.float32)
     assert out.shape == (M, 2 * S, 2 * S) and out.is_contiguous() and out.dtype == torch.float32
     check(_lib.lib().lvc_mask_deconv_predict(ptr(x), ptr(w_deconv), ptr(b_deconv), ptr(w_pred), ptr(b_pred), ptr(classes), ptr(num_valid),
-                                             ptr(out), c_int(M), c_int(S), c_int(cin), c_int(cmid), c_int(Kc), ptr(status), _stream(x)),
+                                             ptr(out), M, S, cin, cmid, Kc, ptr(status), _stream(x)),
           "lvc_mask_deconv_predict")
     return out
 
@@ -3489,8 +3485,8 @@ def paste_masks(prob, jobs, out_bytes, threshold=0.5, out=None):
         return out
     # pinned and asynchronous: the upload is ordered on the stream, the host does not wait for the device
     d_jobs = torch.from_numpy(jobs).pin_memory().to(prob.device, non_blocking=True)
-    check(_lib.lib().lvc_paste_masks(ptr(prob), c_int(prob.shape[0]), c_int(prob.shape[1]), c_void_p(jobs.ctypes.data), ptr(d_jobs),
-                                     c_int(n), ptr(out), c_longlong(padded), c_float(threshold), _stream(prob)),
+    check(_lib.lib().lvc_paste_masks(ptr(prob), prob.shape[0], prob.shape[1], c_void_p(jobs.ctypes.data), ptr(d_jobs),
+                                     n, ptr(out), padded, threshold, _stream(prob)),
           "lvc_paste_masks")
     return out
 
@@ -3518,9 +3514,9 @@ def pack_keypoint_deconv(weight):
     keypoint_deconv_check(cin, k)
     assert tuple(weight.shape[2:]) == (4, 4), weight.shape
     w = weight.detach().contiguous().float()
-    rows = _lib.lib().lvc_keypoint_deconv_packed_rows(c_int(k))
+    rows = _lib.lib().lvc_keypoint_deconv_packed_rows(k)
     packed = torch.empty(rows, cin, device=w.device, dtype=torch.float32)
-    check(_lib.lib().lvc_keypoint_deconv_pack(ptr(w), ptr(packed), c_int(cin), c_int(k), _stream(w)), "lvc_keypoint_deconv_pack")
+    check(_lib.lib().lvc_keypoint_deconv_pack(ptr(w), ptr(packed), cin, k, _stream(w)), "lvc_keypoint_deconv_pack")
     return packed
 
 
@@ -3533,15 +3529,15 @@ def keypoint_deconv(x, packed, bias, num_keypoints, num_valid=None, out=None):
     k = int(num_keypoints)
     keypoint_deconv_check(cin, k)
     assert S == S_ and x.is_contiguous() and x.dtype == torch.float32
-    rows = _lib.lib().lvc_keypoint_deconv_packed_rows(c_int(k))
+    rows = _lib.lib().lvc_keypoint_deconv_packed_rows(k)
     assert packed.shape == (rows, cin) and packed.is_contiguous() and packed.dtype == torch.float32
     assert bias is None or (bias.numel() == k and bias.is_contiguous() and bias.dtype == torch.float32)
     _check_num_valid(num_valid)
     if out is None:
         out = torch.empty(M, k, 2 * S, 2 * S, device=x.device, dtype=torch.float32)
     assert out.shape == (M, k, 2 * S, 2 * S) and out.is_contiguous() and out.dtype == torch.float32
-    check(_lib.lib().lvc_keypoint_deconv(ptr(x), ptr(packed), ptr(bias), ptr(num_valid), ptr(out), c_int(M), c_int(S), c_int(cin),
-                                         c_int(k), _stream(x)), "lvc_keypoint_deconv")
+    check(_lib.lib().lvc_keypoint_deconv(ptr(x), ptr(packed), ptr(bias), ptr(num_valid), ptr(out), M, S, cin,
+                                         k, _stream(x)), "lvc_keypoint_deconv")
     return out
 
 
@@ -3566,8 +3562,8 @@ def heatmaps_to_keypoints(maps, rois, up=1, num_valid=None, maps_out=None, out=N
     assert out.shape == (M, k, 4) and out.is_contiguous() and out.dtype == torch.float32
     if M == 0 or k == 0:
         return out
-    check(_lib.lib().lvc_heatmaps_to_keypoints(ptr(maps), ptr(rois), ptr(num_valid), ptr(maps_out), ptr(out), c_int(M), c_int(k), c_int(P),
-                                               c_int(up), _stream(maps)), "lvc_heatmaps_to_keypoints")
+    check(_lib.lib().lvc_heatmaps_to_keypoints(ptr(maps), ptr(rois), ptr(num_valid), ptr(maps_out), ptr(out), M, k, P,
+                                               up, _stream(maps)), "lvc_heatmaps_to_keypoints")
     return out
 
 
@@ -3599,8 +3595,8 @@ def mask_targets(boxes, matched, count, planes, mask_size, out=None):
         return out
     # pinned and asynchronous: the upload is ordered on the stream, the host does not wait for the device
     d_table = torch.from_numpy(table).pin_memory().to(boxes.device, non_blocking=True)
-    check(_lib.lib().lvc_mask_targets(ptr(boxes), ptr(matched), ptr(count), c_int(count.stride(0)), c_void_p(table.ctypes.data), ptr(d_table),
-                                      c_int(B), c_int(R), c_int(T), ptr(out), _stream(boxes)), "lvc_mask_targets")
+    check(_lib.lib().lvc_mask_targets(ptr(boxes), ptr(matched), ptr(count), count.stride(0), c_void_p(table.ctypes.data), ptr(d_table),
+                                      B, R, T, ptr(out), _stream(boxes)), "lvc_mask_targets")
     return out
 
 
@@ -3612,7 +3608,7 @@ def mask_deconv_logits(x, w_deconv, b_deconv, w_pred, b_pred, classes=None, num_
         out = torch.empty(M, 2 * S, 2 * S, device=x.device, dtype=torch.float32)
     assert out.shape == (M, 2 * S, 2 * S) and out.is_contiguous() and out.dtype == torch.float32
     check(_lib.lib().lvc_mask_deconv_logits(ptr(x), ptr(w_deconv), ptr(b_deconv), ptr(w_pred), ptr(b_pred), ptr(classes), ptr(num_valid),
-                                            ptr(out), c_int(M), c_int(S), c_int(cin), c_int(cmid), c_int(Kc), ptr(status), _stream(x)),
+                                            ptr(out), M, S, cin, cmid, Kc, ptr(status), _stream(x)),
           "lvc_mask_deconv_logits")
     return out
 
@@ -3627,14 +3623,14 @@ def mask_loss(logits, targets, num_valid=None):
     assert targets.shape == logits.shape and targets.is_contiguous() and targets.dtype in (torch.uint8, torch.bool)
     _check_num_valid(num_valid)
     lib = _lib.lib()
-    nbytes = _lib.size_query("lvc_mask_loss_workspace_bytes", c_int(M), c_int(P // 2))
+    nbytes = _lib.size_query("lvc_mask_loss_workspace_bytes", M, P // 2)
     dev = logits.device
     ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
     loss = torch.empty(1, dtype=torch.float32, device=dev)
     total = torch.empty(1, dtype=torch.float64, device=dev)
     counts = torch.empty(3, dtype=torch.int64, device=dev)
-    check(lib.lvc_mask_loss(ptr(logits), ptr(targets), ptr(num_valid), c_int(M), c_int(P // 2), ptr(loss), ptr(total), ptr(counts), ptr(ws),
-                            c_longlong(nbytes), _stream(logits)), "lvc_mask_loss")
+    check(lib.lvc_mask_loss(ptr(logits), ptr(targets), ptr(num_valid), M, P // 2, ptr(loss), ptr(total), ptr(counts), ptr(ws),
+                            nbytes, _stream(logits)), "lvc_mask_loss")
     return loss, total, counts
 
 
@@ -3651,25 +3647,25 @@ def mask_deconv_grad(x, w_deconv, b_deconv, w_pred, classes, logits, targets, nu
     assert upstream.dtype == torch.float32 and upstream.numel() == 1
     dev = x.device
     lib = _lib.lib()
-    nbytes = _lib.size_query("lvc_mask_deconv_grad_workspace_bytes", c_int(M), c_int(S), c_int(cmid))
+    nbytes = _lib.size_query("lvc_mask_deconv_grad_workspace_bytes", M, S, cmid)
     ws = torch.empty((nbytes + 15) // 16 * 4, dtype=torch.float32, device=dev)
     dh = torch.empty(M * S * S, 4 * cmid, dtype=torch.float32, device=dev)
     dwp = torch.empty(Kc, cmid, dtype=torch.float32, device=dev)
     dbp = torch.empty(Kc, dtype=torch.float32, device=dev)
     dbd = torch.empty(cmid, dtype=torch.float32, device=dev)
     check(lib.lvc_mask_deconv_grad(ptr(x), ptr(w_deconv), ptr(b_deconv), ptr(w_pred), ptr(classes), ptr(logits), ptr(targets),
-                                   ptr(num_valid), ptr(upstream), ptr(dh), ptr(dwp), ptr(dbp), ptr(dbd), c_int(M), c_int(S),
-                                   c_int(cin), c_int(cmid), c_int(Kc), ptr(status), ptr(ws), c_longlong(ws.numel() * 4), _stream(x)),
+                                   ptr(num_valid), ptr(upstream), ptr(dh), ptr(dwp), ptr(dbp), ptr(dbd), M, S,
+                                   cin, cmid, Kc, ptr(status), ptr(ws), ws.numel() * 4, _stream(x)),
           "lvc_mask_deconv_grad")
     dx = dwd = None
     if M > 0 and need_dx:       # dx = dh @ Wd_packed on the forward GEMM kernel (range-free split: unscaled gradients are tiny)
         dx = linear_backward(x.view(M * S * S, cin), w_deconv, dh, need_dx=True, need_dw=False)[0].view(M, S, S, cin)      # (x: its shape only)
     if M > 0 and need_dw:       # dWd = dh^T @ x: conv_wgrad joins its pixel slices with atomics, this product must be bit-stable
-        wbytes = _lib.size_query("lvc_mask_deconv_wgrad_workspace_bytes", c_int(M), c_int(S), c_int(cin), c_int(cmid))
+        wbytes = _lib.size_query("lvc_mask_deconv_wgrad_workspace_bytes", M, S, cin, cmid)
         wws = torch.empty(wbytes // 4, dtype=torch.float32, device=dev)
         dw = torch.empty(4 * cmid, cin, dtype=torch.float32, device=dev)
-        check(lib.lvc_mask_deconv_wgrad(ptr(dh), ptr(x), ptr(num_valid), ptr(dw), c_int(M), c_int(S), c_int(cin), c_int(cmid), ptr(wws),
-                                        c_longlong(wbytes), _stream(x)), "lvc_mask_deconv_wgrad")
+        check(lib.lvc_mask_deconv_wgrad(ptr(dh), ptr(x), ptr(num_valid), ptr(dw), M, S, cin, cmid, ptr(wws),
+                                        wbytes, _stream(x)), "lvc_mask_deconv_wgrad")
         # packed row (dy*2+dx)*Cmid + co -> the parameter's [Cin, Cmid, 2, 2]
         dwd = dw.view(2, 2, cmid, cin).permute(3, 2, 0, 1).contiguous()
     if M == 0:
@@ -3713,8 +3709,8 @@ def keypoint_targets(boxes, matched, count, keypoints, size, apply_selection=Tru
         return target, valid, selected, sel_count
     # pinned and asynchronous: the upload is ordered on the stream, the host does not wait for the device
     d_table = torch.from_numpy(table).pin_memory().to(dev, non_blocking=True)
-    check(_lib.lib().lvc_keypoint_targets(ptr(boxes), ptr(matched), ptr(count), c_int(count.stride(0)), c_void_p(table.ctypes.data),
-                                          ptr(d_table), c_int(B), c_int(R), c_int(k), c_int(int(size)), c_int(1 if apply_selection else 0),
+    check(_lib.lib().lvc_keypoint_targets(ptr(boxes), ptr(matched), ptr(count), count.stride(0), c_void_p(table.ctypes.data),
+                                          ptr(d_table), B, R, k, int(size), 1 if apply_selection else 0,
                                           ptr(target), ptr(valid), ptr(selected), ptr(sel_count), _stream(boxes)), "lvc_keypoint_targets")
     return target, valid, selected, sel_count
 
@@ -3755,8 +3751,8 @@ def keypoint_loss(low, target, valid, num_valid=None, normalizer=None, loss_weig
     loss = torch.empty(1, dtype=torch.float32, device=dev)
     total = torch.empty(1, dtype=torch.float64, device=dev)
     count = torch.empty(1, dtype=torch.int64, device=dev)
-    check(_lib.lib().lvc_keypoint_loss(ptr(low), ptr(target), ptr(valid), ptr(num_valid), c_int(M), c_int(k), c_int(S),
-                                       c_double(0.0 if normalizer is None else float(normalizer)), c_double(float(loss_weight)),
+    check(_lib.lib().lvc_keypoint_loss(ptr(low), ptr(target), ptr(valid), ptr(num_valid), M, k, S,
+                                       0.0 if normalizer is None else float(normalizer), float(loss_weight),
                                        ptr(term), ptr(pmax), ptr(plse), ptr(loss), ptr(total), ptr(count), ptr(status), _stream(low)),
           "lvc_keypoint_loss")
     return loss, total, count, term, pmax, plse
@@ -3775,8 +3771,8 @@ def keypoint_loss_grad(low, target, valid, pmax, plse, count, upstream, num_vali
         out = torch.empty(M, 2 * S, 2 * S, kc, dtype=torch.float32, device=low.device)
     assert out.shape == (M, 2 * S, 2 * S, kc) and out.is_contiguous() and out.dtype == torch.float32
     check(_lib.lib().lvc_keypoint_loss_grad(ptr(low), ptr(target), ptr(valid), ptr(pmax), ptr(plse), ptr(count), ptr(upstream),
-                                            ptr(num_valid), c_int(M), c_int(k), c_int(S),
-                                            c_double(0.0 if normalizer is None else float(normalizer)), c_double(float(loss_weight)),
+                                            ptr(num_valid), M, k, S,
+                                            0.0 if normalizer is None else float(normalizer), float(loss_weight),
                                             ptr(out), _stream(low)), "lvc_keypoint_loss_grad")
     return out
 
@@ -3789,7 +3785,7 @@ def pack_keypoint_deconv_dx(weight):
     assert tuple(weight.shape[2:]) == (4, 4), weight.shape
     w = weight.detach().contiguous().float()
     packed = torch.empty(cin, 16 * keypoint_dlow_channels(k), device=w.device, dtype=torch.float32)
-    check(_lib.lib().lvc_keypoint_deconv_dx_pack(ptr(w), ptr(packed), c_int(cin), c_int(k), _stream(w)), "lvc_keypoint_deconv_dx_pack")
+    check(_lib.lib().lvc_keypoint_deconv_dx_pack(ptr(w), ptr(packed), cin, k, _stream(w)), "lvc_keypoint_deconv_dx_pack")
     return packed
 
 
@@ -3815,7 +3811,7 @@ def keypoint_deconv_dx(dlow, packed, num_keypoints, num_valid=None, out=None):
     if out is None:
         out = torch.zeros(M, S, S, cin, device=dlow.device, dtype=torch.float32)
     assert out.shape == (M, S, S, cin) and out.is_contiguous() and out.dtype == torch.float32
-    check(_lib.lib().lvc_keypoint_deconv_dx(ptr(dlow), ptr(packed), ptr(num_valid), ptr(out), c_int(M), c_int(S), c_int(cin), c_int(k),
+    check(_lib.lib().lvc_keypoint_deconv_dx(ptr(dlow), ptr(packed), ptr(num_valid), ptr(out), M, S, cin, k,
                                             _stream(dlow)), "lvc_keypoint_deconv_dx")
     return out
 
@@ -3832,10 +3828,10 @@ def keypoint_deconv_wgrad(x, dlow, num_keypoints, num_valid=None):
     assert dlow.shape == (M, 2 * S, 2 * S, kc) and dlow.is_contiguous() and dlow.dtype == torch.float32, dlow.shape
     _check_num_valid(num_valid)
     lib = _lib.lib()
-    nbytes = _lib.size_query("lvc_keypoint_deconv_wgrad_workspace_bytes", c_int(M), c_int(S), c_int(cin), c_int(k))
+    nbytes = _lib.size_query("lvc_keypoint_deconv_wgrad_workspace_bytes", M, S, cin, k)
     ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=x.device)
     dw = torch.empty(cin, 16 * kc, dtype=torch.float32, device=x.device)
     db = torch.empty(k, dtype=torch.float32, device=x.device)
-    check(lib.lvc_keypoint_deconv_wgrad(ptr(x), ptr(dlow), ptr(num_valid), ptr(dw), ptr(db), c_int(M), c_int(S), c_int(cin), c_int(k),
-                                        ptr(ws), c_longlong(ws.numel() * 8), _stream(x)), "lvc_keypoint_deconv_wgrad")
+    check(lib.lvc_keypoint_deconv_wgrad(ptr(x), ptr(dlow), ptr(num_valid), ptr(dw), ptr(db), M, S, cin, k,
+                                        ptr(ws), ws.numel() * 8, _stream(x)), "lvc_keypoint_deconv_wgrad")
     return unpack_keypoint_deconv_dx(dw, k), db

@@ -100,10 +100,8 @@ def main():
 
         boxes, scores, classes, index, count, status = select()
         IP = ctypes.c_int * len(lg)
-        wsb = K._lib.lib().lvc_retinanet_select_workspace_bytes
-        wsb.restype = ctypes.c_longlong
         cap = model.max_survivors if model.max_survivors is not None else (1 << 30)
-        workspace = int(wsb(8, len(lg), A, Kc, IP(*[x.shape[1] for x in lg]), IP(*[x.shape[2] for x in lg]), model.topk_candidates, cap))
+        workspace = int(K._lib.lib().lvc_retinanet_select_workspace_bytes(8, len(lg), A, Kc, IP(*[x.shape[1] for x in lg]), IP(*[x.shape[2] for x in lg]), model.topk_candidates, cap))
         post = torch.tensor([[1.0, 1.0, 800.0, 1333.0]] * 8, device=dev)
         D = model.max_detections_per_image
 

@@ -29,42 +29,43 @@ if ROOT not in sys.path:
 
 import torch  # noqa: E402
 
+from lvc_amd import _lib  # noqa: E402
+
 
 # ------------------------------------------------------------------------------------------------ the recording library
-def _arg(a):
-    """('i', value) for an integer / float argument, ('p', is NULL) for a pointer, lists for ctypes arrays."""
-    if isinstance(a, (ctypes.c_void_p, ctypes.c_char_p)):
-        return "p", 0 if a.value else 1
-    if isinstance(a, ctypes._SimpleCData):
-        return "i", a.value
+def _arg(ctype, a):
+    """('i', value) for a scalar parameter of the header's type `ctype`, ('p', is NULL) for a pointer one; a ctypes host array in a
+    pointer's place is recorded by its entries."""
+    if ctype is not ctypes.c_void_p:
+        return "i", a.value if isinstance(a, ctype) else ctype(a).value      # ctype(a): what ctypes passes, or its TypeError
     if isinstance(a, ctypes.Array):
         if issubclass(a._type_, ctypes.c_void_p):
             return "p", [0 if v else 1 for v in a]
         return "i", [v for v in a]
-    if isinstance(a, int):
-        return "i", a
+    if isinstance(a, ctypes.c_void_p):
+        return "p", 0 if a.value else 1
     if a is None or isinstance(a, ctypes._Pointer) or type(a).__name__ == "CArgObject":
         return "p", 1 if a is None else 0
-    raise TypeError("unexpected native argument {!r}".format(a))
+    raise TypeError("unexpected native argument {!r} for a pointer parameter".format(a))
 
 
 class _Fn:
-    """One entry point of the recorder: records, then returns the recorder's status or forwards to the real function."""
+    """One entry point of the recorder: checks the call against the header (ctypes itself lets extra arguments through), records,
+    then returns the recorder's status or forwards to the real function."""
 
     def __init__(self, rec, name, real):
-        self.__dict__.update(_rec=rec, _name=name, _real=real)
-
-    def __setattr__(self, k, v):      # `.restype = ...` reaches the real function
-        if self._real is not None:
-            setattr(self._real, k, v)
+        self._rec, self._name, self._real = rec, name, real
+        self._argtypes = _lib.signatures()[name][1]      # KeyError: not an entry point of include/lvc_amd.h
 
     def __call__(self, *args):
         rec = self._rec
         if self._name == "lvc_last_error":
             return self._real(*args) if self._real is not None else b"recorded failure"
+        if len(args) != len(self._argtypes):
+            raise TypeError("{} takes {} arguments ({} given)".format(self._name, len(self._argtypes), len(args)))
         ints, nulls = [], []
-        for a in args:
-            kind, v = _arg(a)
+        for ctype, a in zip(self._argtypes, args):
+            kind, v = _arg(ctype, a)
             (ints if kind == "i" else nulls).append(v)
         rec.raw.append((self._name, ints))
         if self._name == "lvc_set_range_slot":
@@ -118,7 +119,6 @@ class install_stubs:
         self.rec = rec
 
     def __enter__(self):
-        from lvc_amd import _lib
         from lvc_amd import kernels as K
 
         self.saved = [(_lib, "lib", _lib.lib), (torch.cuda, "Event", torch.cuda.Event)] + [
@@ -473,7 +473,6 @@ def dumps(c, rows=("signatures", "cells")):
 def model_stream(out_path):
     """Launch stream of one `inference_batched` of the bench model on the bench input, and of one training step (bench.py's cfg 3:
     R50-FPN novel fine-tune), through the real library.  Every native call is kept, not only the conv/GEMM ones."""
-    from lvc_amd import _lib
     from lvc_amd import kernels as K  # noqa: F401
     from lvc_amd.config import set_global_cfg
     from lvc_amd.config.presets import base_rcnn_fpn

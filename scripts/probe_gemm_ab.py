@@ -4,7 +4,7 @@ import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from lvc_amd import kernels as K, _lib
-from lvc_amd.kernels import ptr, c_int
+from lvc_amd.kernels import ptr
 dev = torch.device("cuda:0")
 g = torch.Generator().manual_seed(0)
 Q, S, D = 120000, 2400, 1024
@@ -18,9 +18,9 @@ y32 = torch.empty(Q, S, dtype=torch.float32, device=dev)
 st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 def run(L, q15):
     if q15:
-        rc = L.lvc_gemm_f16_q15(ptr(qh), ptr(sh), c_int(D), ptr(y16), c_int(Q), c_int(S), c_int(D), c_int(S), st)
+        rc = L.lvc_gemm_f16_q15(ptr(qh), ptr(sh), D, ptr(y16), Q, S, D, S, st)
     else:
-        rc = L.lvc_gemm_f16(ptr(qh), ptr(sh), c_int(D), ptr(y32), c_int(Q), c_int(S), c_int(D), c_int(S), st)
+        rc = L.lvc_gemm_f16(ptr(qh), ptr(sh), D, ptr(y32), Q, S, D, S, st)
     assert rc == 0
 res = {}
 for rnd in range(6):

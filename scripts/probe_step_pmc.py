@@ -5,7 +5,7 @@ import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from lvc_amd import _lib, kernels as K
-from lvc_amd._lib import c_longlong, ptr
+from lvc_amd._lib import ptr
 from lvc_amd.config.presets import base_rcnn_fpn
 from lvc_amd.modeling import build_model
 from lvc_amd.utils import synthetic as syn
@@ -19,7 +19,7 @@ mark = torch.zeros(4, device=dev)
 
 
 def marker():
-    _lib.check(_lib.lib().lvc_gelu(ptr(mark), ptr(mark), c_longlong(4), K._stream(mark)), "lvc_gelu")
+    _lib.check(_lib.lib().lvc_gelu(ptr(mark), ptr(mark), 4, K._stream(mark)), "lvc_gelu")
 
 
 with torch.no_grad():
