@@ -421,6 +421,12 @@ int lvc_roi_align_fpn_backward_nhwc(const float* grad, float* const* grad_feats,
                                     const float* scales, int L, int B, int C, const float* rois, const int* levels,
                                     const int* d_num_valid, int K, int pooled_h, int pooled_w, int sampling_ratio,
                                     int aligned, int* d_status, void* stream);
+/* The kernel a ROIAlign call of these shapes runs, on plain numbers ([host] only, no launch): the one dispatch both directions use.
+ *   forward (backward = 0): 0 scalar (NCHW, C % 4 != 0 or d_num_valid given), 1 one wave per output bin (dwordx4 taps), 2 one wave
+ *   per output row (separable sums; pooled_h <= 8, pooled_w == 7); backward: 0 per-sample scatter, 1 separable rows (NHWC, 7 x 7).
+ *   largest_level_elems: max over the levels of H_l * W_l * C (the row form keeps 32-bit offsets inside one image of a level). */
+int lvc_roi_align_route(int backward, int nhwc, int C, int pooled_h, int pooled_w, int has_num_valid,
+                        long long largest_level_elems);
 
 /* ---------------------------------------------------------------------------------------------------
  * Batched NMS, B images per call.  Replaces torchvision.ops.boxes.batched_nms / nms as called from

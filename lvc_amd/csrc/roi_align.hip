@@ -387,17 +387,32 @@ __global__ __launch_bounds__(512) void roi_align_fwd_nhwc_wave_kernel(RoiAlignAr
   }
 }
 
+// The dispatch of both directions on plain numbers (no device, no launch): which kernel a call of these shapes runs.  launch() and
+// lvc_roi_align_fpn_backward_nhwc route through it, and the tests assert it for every row that names a route.
+//   forward:  0 = roi_align_fwd_kernel (scalar), 1 = roi_align_fwd_nhwc4_kernel, 2 = roi_align_fwd_nhwc_wave_kernel<7>
+//   backward: 0 = roi_align_bwd_kernel (scatter), 1 = roi_align_bwd_rows_kernel<7, 7>
+// largest_level_elems = max over the levels of H * W * C: the wave form keeps tap offsets inside one image of a level as 32-bit
+// element counts.
+extern "C" int lvc_roi_align_route(int backward, int nhwc, int C, int pooled_h, int pooled_w, int has_num_valid,
+                                   long long largest_level_elems) {
+  if (backward) return nhwc && pooled_h == 7 && pooled_w == 7 ? 1 : 0;
+  if (!nhwc || (C & 3) != 0 || has_num_valid) return 0;
+  if (pooled_h <= 8 && pooled_w == 7 && largest_level_elems < (1ll << 31)) return 2;
+  return 1;
+}
+
 static int launch(RoiAlignArgs& a, void* stream) {
   if (a.K == 0) return LVC_OK;
-  bool small = true;     // the staged kernel keeps tap offsets inside one image of a level as 32-bit element counts
+  long long largest = 0;
   for (int l = 0; l < LVC_MAX_LEVELS; ++l)
-    if (a.feat[l] && (long long)a.H[l] * a.W[l] * a.C >= (1ll << 31)) small = false;
-  if (a.nhwc && (a.C & 3) == 0 && a.ph <= 8 && a.pw == 7 && a.num_valid == nullptr && a.so_c == 1 && small) {
+    if (a.feat[l] && (long long)a.H[l] * a.W[l] * a.C > largest) largest = (long long)a.H[l] * a.W[l] * a.C;
+  const int route = lvc_roi_align_route(0, a.nhwc && a.so_c == 1, a.C, a.ph, a.pw, a.num_valid != nullptr, largest);
+  if (route == 2) {
     hipLaunchKernelGGL(roi_align_fwd_nhwc_wave_kernel<7>, dim3(a.K, lvc_cdiv(a.C, 256)), dim3(64 * a.ph), 0, (hipStream_t)stream, a);
     LVC_CHECK_LAUNCH();
     return LVC_OK;
   }
-  if (a.nhwc && (a.C & 3) == 0 && a.num_valid == nullptr && a.so_c == 1) {
+  if (route == 1) {
     dim3 grid4(a.K * a.ph * a.pw, lvc_cdiv(a.C, 256)), block4(64);
     hipLaunchKernelGGL(roi_align_fwd_nhwc4_kernel, grid4, block4, 0, (hipStream_t)stream, a);
     LVC_CHECK_LAUNCH();
@@ -686,7 +701,7 @@ extern "C" int lvc_roi_align_fpn_backward_nhwc(const float* grad, float* const* 
   LVC_CHECK_ARG(L >= 1 && L <= LVC_MAX_LEVELS, "1..8 levels");
   LVC_CHECK_ARG(grad_feats && Hs && Ws && scales && (K == 0 || (grad && rois)), "null pointer");
   LVC_CHECK_ARG(B > 0 && C > 0 && pooled_h > 0 && pooled_w > 0 && K >= 0, "bad shape");
-  LVC_CHECK_ARG(L == 1 || levels, "levels required when L > 1");
+  LVC_CHECK_ARG(L == 1 || K == 0 || levels, "levels required when L > 1");
   RoiAlignArgs a;
   memset(&a, 0, sizeof a);
   for (int l = 0; l < L; ++l) {
@@ -705,7 +720,7 @@ extern "C" int lvc_roi_align_fpn_backward_nhwc(const float* grad, float* const* 
   a.so_k = (long long)C * pooled_h * pooled_w; a.so_c = 1;
   a.so_h = (long long)pooled_w * C; a.so_w = C;
   a.status = d_status;
-  if (pooled_h == 7 && pooled_w == 7)      // the separable form: one atomic per footprint pixel
+  if (lvc_roi_align_route(1, 1, C, pooled_h, pooled_w, d_num_valid != nullptr, 0) == 1)      // the separable form: one atomic per footprint pixel
     hipLaunchKernelGGL((roi_align_bwd_rows_kernel<7, 7>), dim3(K, lvc_cdiv(C, 256)), dim3(256), 0, (hipStream_t)stream, a);
   else
     hipLaunchKernelGGL(roi_align_bwd_kernel, dim3(K, lvc_cdiv(C, 256)), dim3(256), 0, (hipStream_t)stream, a);
@@ -857,7 +872,7 @@ static int roi_align_fpn_nhwc_impl(const float* const* feats, const int* Hs, con
   LVC_CHECK_ARG(L >= 1 && L <= LVC_MAX_LEVELS, "1..8 levels");
   LVC_CHECK_ARG(K == 0 || (feats && Hs && Ws && scales && rois && output), "null pointer");
   LVC_CHECK_ARG(B > 0 && C > 0 && pooled_h > 0 && pooled_w > 0 && K >= 0, "bad shape");
-  LVC_CHECK_ARG(L == 1 || levels, "levels required when L > 1");
+  LVC_CHECK_ARG(L == 1 || K == 0 || levels, "levels required when L > 1");
   RoiAlignArgs a;
   memset(&a, 0, sizeof a);
   for (int l = 0; l < L; ++l) {

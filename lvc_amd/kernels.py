@@ -1314,19 +1314,33 @@ def roi_align_forward(input, rois, spatial_scale, pooled_h, pooled_w, sampling_r
     return out
 
 
+ROI_FWD_ROUTES = ("scalar", "nhwc4", "wave")      # lvc_roi_align_route, forward: its answers by name
+ROI_BWD_ROUTES = ("scatter", "rows")              # ... and backward
+
+
+def roi_align_route(backward, nhwc, C, pooled_h, pooled_w, has_num_valid=False, largest_level_elems=0):
+    """The kernel a ROIAlign call of these shapes runs, by name, from the library's own dispatch (host only, nothing is launched);
+    largest_level_elems: max over the levels of H * W * C."""
+    r = _lib.lib().lvc_roi_align_route(1 if backward else 0, 1 if nhwc else 0, C, pooled_h, pooled_w, 1 if has_num_valid else 0,
+                                       largest_level_elems)
+    return (ROI_BWD_ROUTES if backward else ROI_FWD_ROUTES)[r]
+
+
 ROI_ORDER_MIN = 1024     # RoIs per launch from which a work order is computed (lvc_roi_work_order: one small launch)
 
 
 def roi_align_fpn_nhwc(feats, scales, rois, levels, pooled_h, pooled_w, sampling_ratio, aligned,
-                       num_valid=None, status=None, order=None):
+                       num_valid=None, status=None, order=None, out=None):
     """feats: list of NHWC level tensors [B,H_l,W_l,C]; rois [K,5]; levels [K] int32 (or None when one
-    level).  Returns [K, ph, pw, C]."""
+    level).  Returns [K, ph, pw, C] (written into `out` when one is given)."""
     _req_cuda(rois, *feats)
     L = len(feats)
     B, _, _, C = feats[0].shape
     K = rois.shape[0]
     rois = rois.contiguous().float()
-    out = torch.empty(K, pooled_h, pooled_w, C, device=rois.device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty(K, pooled_h, pooled_w, C, device=rois.device, dtype=torch.float32)
+    assert out.shape == (K, pooled_h, pooled_w, C) and out.is_contiguous() and out.dtype == torch.float32
     FP = c_void_p * L
     IP = c_int * L
     FL = c_float * L
@@ -1376,16 +1390,20 @@ def roi_align_backward(grad, rois, spatial_scale, pooled_h, pooled_w, batch_size
 
 
 def roi_align_fpn_backward_nhwc(grad, shapes, scales, rois, levels, sampling_ratio, aligned, num_valid=None,
-                                status=None):
+                                status=None, outs=None):
     """Gradient of roi_align_fpn_nhwc.  grad [K,ph,pw,C]; shapes: list of (B,H_l,W_l,C).  Returns the list of
-    NHWC level gradients."""
+    NHWC level gradients (zeroed and written into `outs` when they are given)."""
     _req_cuda(grad, rois)
     grad = grad.contiguous().float()
     rois = rois.contiguous().float()
     K, ph, pw, C = grad.shape
     L = len(shapes)
     B = shapes[0][0]
-    outs = [torch.empty(*sh, device=grad.device, dtype=torch.float32) for sh in shapes]
+    if outs is None:
+        outs = [torch.empty(*sh, device=grad.device, dtype=torch.float32) for sh in shapes]
+    assert len(outs) == L
+    for o, sh in zip(outs, shapes):
+        assert o.shape == tuple(sh) and o.is_contiguous() and o.dtype == torch.float32 and sh[0] == B and sh[3] == C
     FP = c_void_p * L
     IP = c_int * L
     FL = c_float * L

@@ -531,7 +531,8 @@ def test_roi_align_fpn_backward_nhwc_matches_oracle():
 def test_roi_align_fpn_backward_edge_rois(sr):
     """The separable backward (weight tables per axis, one atomic per footprint pixel) on the RoIs that stress its
     bookkeeping: boxes hanging over every edge of the map (dropped samples, clamped rows), degenerate and one-pixel boxes,
-    boxes covering the whole map on the coarsest level, and RoIs too large for the tables (scatter path)."""
+    and boxes covering the whole map on the coarsest level.  Every RoI here fits the kernel's tables (at most 63 samples and an
+    85-pixel footprint per axis); the scatter loop at the kernel's end is run by tests/test_gpu_roi_align_routes.py."""
     from lvc_amd import kernels as k
     from oracle import ops as oops
 
