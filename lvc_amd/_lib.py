@@ -1,4 +1,5 @@
-"""ctypes loader of the C-ABI kernel library `liblvc_amd.so` (declared in include/lvc_amd.h).
+"""ctypes loader of the C-ABI kernel library `liblvc_amd.so` (declared in include/lvc_amd.h; the semantic / panoptic entries, prefix
+`lvcseg_`, in include/lvc_amd_seg.h).
 
 The product path has NO CPU fallback: if the library is missing or a call fails, this raises.
 Errors follow the reference's behaviour for its native ops (C++ exception -> Python RuntimeError,
@@ -13,8 +14,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # LVC_AMD_LIB: another build of the same library (A/B measurements of one kernel against its predecessor in alternating processes)
 _SO = os.environ.get("LVC_AMD_LIB") or os.path.join(_HERE, "liblvc_amd.so")
 _HEADER = os.path.join(os.path.dirname(_HERE), "include", "lvc_amd.h")
+_HEADER_SEG = os.path.join(os.path.dirname(_HERE), "include", "lvc_amd_seg.h")
 _lib = None
 _signatures = None
+_signatures_seg = None
 
 c_void_p = ctypes.c_void_p
 c_int = ctypes.c_int
@@ -28,8 +31,9 @@ class LvcNativeError(RuntimeError):
     pass
 
 
-def parse_header(text):
-    """{entry point: (restype, [argtypes])} from the text of include/lvc_amd.h, the one statement of the ABI.  The header is plain
+def parse_header(text, prefix="lvc_"):
+    """{entry point: (restype, [argtypes])} from the text of a header of the ABI (include/lvc_amd.h; with prefix "lvcseg_",
+    include/lvc_amd_seg.h): every declaration names a function that starts with `prefix`.  The header is plain
     C99 without typedefs, structs or function pointers, so a declaration is `ret name(type name, ...);`.  Every pointer parameter is
     a c_void_p, whatever it points to (it takes `ptr(t)`, None, a ctypes host array and `byref`); a type that is not listed here is
     an error that names the declaration, never a default.  The variadic lvc_set_error is not bound."""
@@ -37,9 +41,9 @@ def parse_header(text):
     text = re.sub(r"//[^\n]*|^[ \t]*#[^\n]*|extern\s+\"C\"\s*\{|^\s*\}\s*$", " ", text, flags=re.M)
     table = {}
     for decl in filter(None, (" ".join(d.split()) for d in text.split(";"))):
-        m = re.fullmatch(r"(.+?)\b(lvc_\w+) ?\((.*)\)", decl)
+        m = re.fullmatch(r"(.+?)\b(" + re.escape(prefix) + r"\w+) ?\((.*)\)", decl)
         if m is None:
-            raise ValueError("lvc_amd.h: cannot read the declaration `{}`".format(decl))
+            raise ValueError("lvc_amd.h: cannot read the declaration `{}` (a function named {}*)".format(decl, prefix))
         ret, name, params = m.group(1).strip(), m.group(2), m.group(3).strip()
         if "..." in params:
             continue
@@ -76,6 +80,17 @@ def signatures():
     return _signatures
 
 
+def signatures_seg():
+    """The parsed include/lvc_amd_seg.h (the lvcseg_ entries), read once per process; `signatures()` stays the table of lvc_amd.h."""
+    global _signatures_seg
+    if _signatures_seg is None:
+        if not os.path.exists(_HEADER_SEG):
+            raise ImportError("lvc_amd: the C ABI header {} not found; the native calls are bound from it".format(_HEADER_SEG))
+        with open(_HEADER_SEG) as f:
+            _signatures_seg = parse_header(f.read(), prefix="lvcseg_")
+    return _signatures_seg
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -85,7 +100,8 @@ def lib():
                 "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C lvc_amd/csrc` "
                 "(there is no CPU fallback)".format(_SO)
             )
-        sigs = signatures()
+        sigs = dict(signatures())
+        sigs.update(signatures_seg())
         L = ctypes.CDLL(_SO)
         # every call is checked by ctypes against the header from here on: the number of arguments (too few), an int for an int, a
         # pointer for a pointer, and a `long long` travels whole

@@ -28,6 +28,9 @@ def _limits(model):
 
 
 def _refuse_masks(model, what):
+    if getattr(model, "sem_seg_head", None) is not None:
+        raise NotImplementedError("MODEL.META_ARCHITECTURE = {} (MODEL.SEM_SEG_HEAD): {} carries the box branch only; run a semantic or "
+                                  "panoptic model through its own forward()".format(type(model).__name__, what))
     if getattr(getattr(model, "roi_heads", None), "mask_on", False):
         raise NotImplementedError("MODEL.MASK_ON: {} carries the box branch only; run a mask model through its own forward()".format(what))
     if getattr(getattr(model, "roi_heads", None), "keypoint_on", False):

@@ -3853,3 +3853,146 @@ def keypoint_deconv_wgrad(x, dlow, num_keypoints, num_valid=None):
     check(lib.lvc_keypoint_deconv_wgrad(ptr(x), ptr(dlow), ptr(num_valid), ptr(dw), ptr(db), M, S, cin, k,
                                         ptr(ws), ws.numel() * 8, _stream(x)), "lvc_keypoint_deconv_wgrad")
     return unpack_keypoint_deconv_dx(dw, k), db
+
+
+# --------------------------------------------------------------------------- semantic head and panoptic combine (csrc/sem_seg.hip)
+# The entries of include/lvc_amd_seg.h.
+SEG_POST_FIELDS = 9          # int64 words per job of lvcseg_sem_seg_postprocess
+SEG_COMBINE_FIELDS = 9       # int64 words per image of lvcseg_panoptic_combine
+SEG_SEGMENT_FIELDS = 8       # int32 words per row of its segment table
+SEG_MAX_INSTANCES = 1024
+SEG_MAX_LABELS = 4096
+
+
+def _upload_table(table, device):
+    """A host int64 table as a device tensor: pinned and asynchronous, the host does not wait for the device."""
+    return torch.from_numpy(table).pin_memory().to(device, non_blocking=True)
+
+
+def upsample2_bilinear_nhwc(x, acc=None, out=None):
+    """nn.Upsample(scale_factor=2, mode="bilinear", align_corners=False) on NHWC fp32 in one launch: up2(x), or acc + up2(x) with
+    the accumulator added last (`out` may be `acc`).  x [N,H,W,C], C % 4 == 0 -> [N,2H,2W,C]."""
+    _req_cuda(x, acc, out)
+    assert x.dim() == 4 and x.dtype == torch.float32 and x.is_contiguous()
+    N, H, W, C = x.shape
+    if out is None:
+        out = torch.empty(N, 2 * H, 2 * W, C, device=x.device, dtype=torch.float32)
+    for t in (acc, out):
+        assert t is None or (t.shape == (N, 2 * H, 2 * W, C) and t.dtype == torch.float32 and t.is_contiguous())
+    check(_lib.lib().lvcseg_upsample2_bilinear_nhwc(ptr(x), ptr(acc), ptr(out), N, H, W, C, _stream(x)),
+          "lvcseg_upsample2_bilinear_nhwc")
+    return out
+
+
+def sem_seg_jobs(low_sizes, image_sizes, out_sizes, num_classes, ld, low_offsets=None):
+    """The host job table of `sem_seg_postprocess`, one row per image: low_sizes [(h, w)] of the low-resolution logits, image_sizes
+    [(h, w)] the crop of the upsampled map, out_sizes [(h, w)].  The images' logits follow each other in one buffer (low_offsets: their
+    offsets in floats, default packed [h, w, ld] blocks), their soft planes [K, out_h, out_w] and label maps [out_h, out_w] are packed
+    in this order.  -> (int64 numpy [n, SEG_POST_FIELDS], soft_numel, labels_numel)."""
+    import numpy as np
+
+    n = len(low_sizes)
+    jobs = np.zeros((n, SEG_POST_FIELDS), dtype=np.int64)
+    low = soft = lab = 0
+    for i in range(n):
+        (h, w), (ih, iw), (oh, ow) = low_sizes[i], image_sizes[i], out_sizes[i]
+        jobs[i] = [low if low_offsets is None else low_offsets[i], h, w, ih, iw, oh, ow, soft, lab]
+        low += h * w * ld
+        soft += num_classes * oh * ow
+        lab += oh * ow
+    return jobs, soft, lab
+
+
+def sem_seg_postprocess(logits, jobs, num_classes, scale, soft_numel, labels_numel, want_soft=True, want_labels=True, soft=None,
+                        labels=None, ld=None):
+    """F.interpolate(scale_factor=scale) -> crop -> F.interpolate(size=output) -> argmax for a batch in one launch, without the
+    intermediate maps.  logits: fp32, `ld` floats per pixel (default: its last dimension), only the first num_classes are read; jobs:
+    `sem_seg_jobs`' table.  -> (soft fp32 [soft_numel] or None, labels uint8 (int32 above 256 classes) [labels_numel] or None);
+    elements outside the jobs' planes are not written."""
+    import numpy as np
+
+    _req_cuda(logits, soft, labels)
+    assert logits.dtype == torch.float32 and logits.is_contiguous()
+    assert want_soft or want_labels
+    K, ld = int(num_classes), int(logits.shape[-1] if ld is None else ld)
+    jobs = np.ascontiguousarray(jobs, dtype=np.int64).reshape(-1, SEG_POST_FIELDS)
+    label_dtype = torch.uint8 if K <= 256 else torch.int32
+    if want_soft and soft is None:
+        soft = torch.empty(int(soft_numel), device=logits.device, dtype=torch.float32)
+    if want_labels and labels is None:
+        labels = torch.empty(int(labels_numel), device=logits.device, dtype=label_dtype)
+    assert soft is None or (soft.dtype == torch.float32 and soft.is_contiguous())
+    assert labels is None or (labels.dtype in (torch.uint8, torch.int32) and labels.is_contiguous())
+    if jobs.shape[0] == 0:
+        return soft, labels
+    d_jobs = _upload_table(jobs, logits.device)
+    check(_lib.lib().lvcseg_sem_seg_postprocess(ptr(logits), logits.numel(), c_void_p(jobs.ctypes.data), ptr(d_jobs), jobs.shape[0],
+                                                K, ld, int(scale), ptr(soft), 0 if soft is None else soft.numel(), ptr(labels),
+                                                0 if labels is None else labels.numel(),
+                                                4 if labels is not None and labels.dtype == torch.int32 else 1, _stream(logits)),
+          "lvcseg_sem_seg_postprocess")
+    return soft, labels
+
+
+def panoptic_combine(planes, plane_jobs, counts, sizes, scores, classes, score_offsets, labels, label_offsets, num_labels,
+                     overlap_thresh, stuff_area_limit, instances_thresh, use_boxes=True):
+    """combine_semantic_and_instance_outputs for a batch in one launch (one workgroup per image), nothing read back.
+    planes: uint8 buffer of 0 / 1 planes [h, w]; plane_jobs: their `paste_jobs` table (image after image; counts [B] instances per
+    image); sizes [(h, w)]; scores fp32 / classes int32 device tensors, score_offsets [B] the index of each image's first instance in
+    them; labels uint8 / int32 buffer with each image's [h, w] map at label_offsets [B]; use_boxes: scan a plane inside its job's box
+    only (planes of `paste_masks` with a positive threshold are zero outside it).
+    -> (panoptic int32 [sum h*w], image after image; segments int32 [rows, SEG_SEGMENT_FIELDS]; seg_counts int32 [B]; pan_offsets,
+    seg_offsets: host lists)."""
+    import numpy as np
+
+    _req_cuda(planes, scores, classes, labels)
+    B = len(sizes)
+    plane_jobs = np.ascontiguousarray(plane_jobs, dtype=np.int64).reshape(-1, PASTE_FIELDS)
+    assert labels.dtype in (torch.uint8, torch.int32) and labels.is_contiguous()
+    assert scores.dtype == torch.float32 and classes.dtype == torch.int32 and scores.is_contiguous() and classes.is_contiguous()
+    assert planes is None or (planes.dtype == torch.uint8 and planes.is_contiguous())
+    images = np.zeros((B, SEG_COMBINE_FIELDS), dtype=np.int64)
+    first = pan = rows = 0
+    pan_offsets, seg_offsets = [], []
+    for i, (h, w) in enumerate(sizes):
+        n = int(counts[i])
+        if n > SEG_MAX_INSTANCES:
+            raise NotImplementedError("panoptic_combine: {} instances in one image, the kernel takes {} "
+                                      "(TEST.DETECTIONS_PER_IMAGE)".format(n, SEG_MAX_INSTANCES))
+        assert int(score_offsets[i]) + n <= scores.numel()
+        images[i] = [first, n, h, w, label_offsets[i], pan, rows, n + num_labels, score_offsets[i]]
+        pan_offsets.append(pan)
+        seg_offsets.append(rows)
+        first += n
+        pan += h * w
+        rows += n + num_labels
+    dev = labels.device
+    panoptic = torch.empty(pan, device=dev, dtype=torch.int32)
+    segments = torch.empty(max(rows, 1), SEG_SEGMENT_FIELDS, device=dev, dtype=torch.int32)
+    seg_counts = torch.empty(max(B, 1), device=dev, dtype=torch.int32)
+    if B == 0:
+        return panoptic, segments, seg_counts, pan_offsets, seg_offsets
+    d_images = _upload_table(images, dev)
+    d_planes = _upload_table(plane_jobs, dev) if plane_jobs.shape[0] else None
+    check(_lib.lib().lvcseg_panoptic_combine(ptr(planes), 0 if planes is None else planes.numel(), c_void_p(plane_jobs.ctypes.data),
+                                             ptr(d_planes), plane_jobs.shape[0], 1 if use_boxes else 0, ptr(scores), ptr(classes),
+                                             ptr(labels), labels.numel(), 4 if labels.dtype == torch.int32 else 1, int(num_labels),
+                                             c_void_p(images.ctypes.data), ptr(d_images), B, float(overlap_thresh),
+                                             float(stuff_area_limit), float(instances_thresh), ptr(panoptic), panoptic.numel(),
+                                             ptr(segments), rows, ptr(seg_counts), _stream(labels)),
+          "lvcseg_panoptic_combine")
+    return panoptic, segments, seg_counts, pan_offsets, seg_offsets
+
+
+def segments_info(rows):
+    """The reference's `segments_info` of one image from the rows of its segment table (host int32 numpy [count, SEG_SEGMENT_FIELDS])."""
+    import numpy as np
+
+    out = []
+    for r in np.asarray(rows, dtype=np.int32):
+        if r[1]:
+            out.append({"id": int(r[0]), "isthing": True, "score": float(r[4:5].view(np.float32)[0]), "category_id": int(r[2]),
+                        "instance_id": int(r[3])})
+        else:
+            out.append({"id": int(r[0]), "isthing": False, "category_id": int(r[2]), "area": int(r[5])})
+    return out

@@ -3,7 +3,8 @@ from .anchor_generator import ANCHOR_GENERATOR_REGISTRY, DefaultAnchorGenerator,
 from .backbone import (BACKBONE_REGISTRY, FPN, Backbone, LastLevelP6P7, ResNet, build_backbone, build_resnet_backbone, build_resnet_fpn_backbone,
                        build_retinanet_resnet_fpn_backbone)
 from .box_regression import Box2BoxTransform
-from .meta_arch import META_ARCH_REGISTRY, GeneralizedRCNN, GeneralizedRCNNRegOnly, ProposalNetwork, RetinaNet, RetinaNetHead, build_model
+from .meta_arch import (META_ARCH_REGISTRY, SEM_SEG_HEADS_REGISTRY, GeneralizedRCNN, GeneralizedRCNNRegOnly, PanopticFPN, ProposalNetwork, RetinaNet,
+                        RetinaNetHead, SemanticSegmentor, SemSegFPNHead, build_model, build_sem_seg_head)
 from .poolers import ROIPooler
 from .postprocessing import detector_postprocess
 from .proposal_generator import PROPOSAL_GENERATOR_REGISTRY, RPN, RPN_HEAD_REGISTRY, StandardRPNHead, build_proposal_generator

@@ -387,6 +387,7 @@ class GeneralizedRCNN(_RCNNBase):
         heads = self.roi_heads
         ob, osc, ocl, _orow, cnt = heads.forward_batched(feats, pboxes, pcount, sizes_dev, post=None, status=status)
         out, rows = branch(heads, feats, ob, ocl, cnt, status)
+        self._on_features(feats, batched_inputs, sizes, do_postprocess)
         out_sizes, post = [tuple(s) for s in sizes], None
         if do_postprocess:
             post_rows, out_sizes = self.post_rows(batched_inputs, sizes)
@@ -398,6 +399,10 @@ class GeneralizedRCNN(_RCNNBase):
             post = self._dev_const(post_rows, torch.float32)
             ob, osc, ocl, rows, cnt = K.gather_detections(ob, osc, ocl, rows, keep, cnt, T, post=post)
         return ob, osc, ocl, rows, cnt, out, status, out_sizes, post
+
+    def _on_features(self, feats, batched_inputs, sizes, do_postprocess):
+        """What a model with a further consumer of the trunk's features (PanopticFPN's semantic head) enqueues behind the branch,
+        in front of the pass's read.  Nothing here."""
 
     def _masks_device(self, batched_inputs, do_postprocess):
         """The device part of a mask model's forward (`_branch_device` with the mask branch): in `rows` the row of `prob` each survivor
@@ -411,6 +416,12 @@ class GeneralizedRCNN(_RCNNBase):
         a torch.bool [n, out_h, out_w] view of that launch's uint8 buffer (without do_postprocess: the soft [n, 1, 2S, 2S] masks).  The buffer is ONE fresh allocation per
         call (sum of n * out_h * out_w bytes over the batch) and every image's `pred_masks` aliases it: a caller that keeps one image's
         masks keeps the whole batch's bytes alive; `.clone()` what is to outlive the batch."""
+        out, _ = self._masks_and_planes(batched_inputs, do_postprocess)
+        return [{"instances": r} for r in out] if do_postprocess else out
+
+    def _masks_and_planes(self, batched_inputs, do_postprocess):
+        """`_inference_masks` -> (per image Instances, planes): planes (with do_postprocess, else None) is what the paste launch read and
+        wrote -- its job table, its uint8 buffer, the instances per image, the batch's scores / classes [B, T] and the output sizes."""
         import numpy as np
 
         ob, osc, ocl, rows, cnt, prob, status, out_sizes = self._masks_device(batched_inputs, do_postprocess)
@@ -424,7 +435,7 @@ class GeneralizedRCNN(_RCNNBase):
             K.check_conv_error_word(self.device)
         rows_h = meta[B + 2: B + 2 + B * T].reshape(B, T)
         boxes_h = np.ascontiguousarray(meta[B + 2 + B * T:]).view(np.float32).reshape(B, T, 4)
-        buf, bases = None, []
+        buf, bases, planes = None, [], None
         if do_postprocess:
             jr, jb, js, jo, total = [], [], [], [], 0
             for i, (oh, ow) in enumerate(out_sizes):
@@ -437,6 +448,7 @@ class GeneralizedRCNN(_RCNNBase):
                 total += n * oh * ow
             jobs = K.paste_jobs(np.concatenate(jr), np.concatenate(jb), js, jo)
             buf = K.paste_masks(prob, jobs, total, threshold=self.mask_threshold)
+            planes = {"jobs": jobs, "buffer": buf, "counts": counts, "scores": osc, "classes": ocl, "out_sizes": out_sizes}
         out = []
         for i, size in enumerate(out_sizes):
             n = counts[i]
@@ -451,7 +463,7 @@ class GeneralizedRCNN(_RCNNBase):
                 r0 = int(rows_h[i, 0]) if n else 0      # an image's real rows are consecutive in prob
                 inst.pred_masks = prob[r0: r0 + n][:, None]
             out.append(inst)
-        return [{"instances": r} for r in out] if do_postprocess else out
+        return out, planes
 
     def _keypoints_device(self, batched_inputs, do_postprocess):
         """The device part of a keypoint model's forward, nothing read back: trunk -> proposals -> box branch with post=None (raw

@@ -12,6 +12,9 @@ from . import test_time_augmentation as _tta
 class GeneralizedRCNNWithTTA(_tta.GeneralizedRCNNWithTTA):
     def __init__(self, cfg, model, tta_mapper=None, batch_size=3):
         inner = model.module if isinstance(model, DistributedDataParallel) else model
+        if getattr(inner, "sem_seg_head", None) is not None:
+            raise NotImplementedError("MODEL.META_ARCHITECTURE = {} (MODEL.SEM_SEG_HEAD): semantic and panoptic outputs under test-time "
+                                      "augmentation are not built".format(type(inner).__name__))
         if cfg.MODEL.MASK_ON or getattr(getattr(inner, "roi_heads", None), "mask_on", False):
             raise NotImplementedError("MODEL.MASK_ON: masks under test-time augmentation are not built (the box branch only)")
         super().__init__(cfg, model, tta_mapper=tta_mapper, batch_size=batch_size)
