@@ -1,5 +1,5 @@
 """ctypes loader of the C-ABI kernel library `liblvc_amd.so` (declared in include/lvc_amd.h; the semantic / panoptic entries, prefix
-`lvcseg_`, in include/lvc_amd_seg.h).
+`lvcseg_`, in include/lvc_amd_seg.h; the entries that train the semantic branch, prefix `lvcst_`, in include/lvc_amd_segtrain.h).
 
 The product path has NO CPU fallback: if the library is missing or a call fails, this raises.
 Errors follow the reference's behaviour for its native ops (C++ exception -> Python RuntimeError,
@@ -15,9 +15,11 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.environ.get("LVC_AMD_LIB") or os.path.join(_HERE, "liblvc_amd.so")
 _HEADER = os.path.join(os.path.dirname(_HERE), "include", "lvc_amd.h")
 _HEADER_SEG = os.path.join(os.path.dirname(_HERE), "include", "lvc_amd_seg.h")
+_HEADER_SEGTRAIN = os.path.join(os.path.dirname(_HERE), "include", "lvc_amd_segtrain.h")
 _lib = None
 _signatures = None
 _signatures_seg = None
+_signatures_segtrain = None
 
 c_void_p = ctypes.c_void_p
 c_int = ctypes.c_int
@@ -33,7 +35,7 @@ class LvcNativeError(RuntimeError):
 
 def parse_header(text, prefix="lvc_"):
     """{entry point: (restype, [argtypes])} from the text of a header of the ABI (include/lvc_amd.h; with prefix "lvcseg_",
-    include/lvc_amd_seg.h): every declaration names a function that starts with `prefix`.  The header is plain
+    include/lvc_amd_seg.h; with "lvcst_", include/lvc_amd_segtrain.h): every declaration names a function that starts with `prefix`.  The header is plain
     C99 without typedefs, structs or function pointers, so a declaration is `ret name(type name, ...);`.  Every pointer parameter is
     a c_void_p, whatever it points to (it takes `ptr(t)`, None, a ctypes host array and `byref`); a type that is not listed here is
     an error that names the declaration, never a default.  The variadic lvc_set_error is not bound."""
@@ -91,6 +93,17 @@ def signatures_seg():
     return _signatures_seg
 
 
+def signatures_segtrain():
+    """The parsed include/lvc_amd_segtrain.h (the lvcst_ entries), read once per process; the other two tables stay as they are."""
+    global _signatures_segtrain
+    if _signatures_segtrain is None:
+        if not os.path.exists(_HEADER_SEGTRAIN):
+            raise ImportError("lvc_amd: the C ABI header {} not found; the native calls are bound from it".format(_HEADER_SEGTRAIN))
+        with open(_HEADER_SEGTRAIN) as f:
+            _signatures_segtrain = parse_header(f.read(), prefix="lvcst_")
+    return _signatures_segtrain
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -102,6 +115,7 @@ def lib():
             )
         sigs = dict(signatures())
         sigs.update(signatures_seg())
+        sigs.update(signatures_segtrain())
         L = ctypes.CDLL(_SO)
         # every call is checked by ctypes against the header from here on: the number of arguments (too few), an int for an int, a
         # pointer for a pointer, and a `long long` travels whole

@@ -56,7 +56,8 @@ def mask_rcnn_fpn(depth=50, num_classes=80, device="cuda"):
 def panoptic_fpn(depth=50, num_classes=80, num_stuff_classes=54, device="cuda"):
     """Panoptic FPN on the ResNet-FPN trunk: `mask_rcnn_fpn` with detectron2's `COCO-PanopticSegmentation/Base-Panoptic-FPN.yaml` on
     top (`META_ARCHITECTURE: PanopticFPN`, the semantic head's class count; the head keeps the defaults' GN, 128 channels, p2 .. p5
-    and common stride 4; `MODEL.PANOPTIC_FPN.COMBINE.*` keep their defaults).  Inference only."""
+    and common stride 4; `MODEL.PANOPTIC_FPN.COMBINE.*` keep their defaults).  Training is opt-in:
+    `build_model(cfg).enable_mask_training().enable_sem_seg_training()`; every item then carries "sem_seg" beside its "instances"."""
     cfg = mask_rcnn_fpn(depth=depth, num_classes=num_classes, device=device)
     cfg.merge_from_list(["MODEL.META_ARCHITECTURE", "PanopticFPN", "MODEL.SEM_SEG_HEAD.NUM_CLASSES", num_stuff_classes])
     return cfg

@@ -9,6 +9,7 @@
 // header is a compile error (conflicting types for an extern "C" function), and no file restates another file's prototype.
 #include "../../include/lvc_amd.h"
 #include "../../include/lvc_amd_seg.h"      // the lvcseg_ entry points (csrc/sem_seg.hip)
+#include "../../include/lvc_amd_segtrain.h" // the lvcst_ entry points (csrc/sem_seg_train.hip)
 
 // LVC_OK 0, LVC_ERR_INVALID 1 (bad argument: shape / alignment / null) and LVC_ERR_HIP 2 (a HIP runtime call failed, see
 // lvc_last_error) are the header's

@@ -10,28 +10,7 @@
 #include <stdint.h>
 
 #include "common.h"
-
-struct SegTap {
-  int i0, i1;
-  float w0, w1;
-};
-
-// area_pixel_compute_source_index (cubic = false) and the two taps of upsample_bilinear2d
-__host__ __device__ __forceinline__ SegTap seg_tap(float scale, int d, int size) {
-  float s = scale * ((float)d + 0.5f) - 0.5f;
-  s = s < 0.f ? 0.f : s;
-  SegTap t;
-  t.i0 = (int)s;
-  if (t.i0 > size - 1) t.i0 = size - 1;      // (never for an output inside scale * size; keeps every index in bounds)
-  t.i1 = t.i0 + (t.i0 < size - 1 ? 1 : 0);
-  t.w1 = s - (float)t.i0;
-  t.w0 = 1.f - t.w1;
-  return t;
-}
-
-__device__ __forceinline__ float seg_bilerp(float l0, float l1, float m0, float m1, float a, float b, float c, float d) {
-  return l0 * (m0 * a + m1 * b) + l1 * (m0 * c + m1 * d);
-}
+#include "seg_bilinear.h"      // SegTap, seg_tap, seg_bilerp: shared with sem_seg_train.hip
 
 // ------------------------------------------------------------------------------------------------ x2 upsample (+ accumulator)
 // A thread owns four channels of one output pixel: four 16-byte loads (L2 serves the re-reads of the 2x2 neighbourhood), one 16-byte

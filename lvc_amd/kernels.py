@@ -3996,3 +3996,106 @@ def segments_info(rows):
         else:
             out.append({"id": int(r[0]), "isthing": False, "category_id": int(r[2]), "area": int(r[5])})
     return out
+
+
+# --------------------------------------------------------------------------- training the semantic branch (csrc/sem_seg_train.hip)
+# The entries of include/lvc_amd_segtrain.h.
+SEGTRAIN_LOSS_FIELDS = 3               # int64 words per image of the loss entries' job table
+SEGTRAIN_STATUS_LABEL_RANGE = 1        # bit of the loss's status word: a label neither ignored nor in [0, K)
+
+
+def upsample2_bilinear_bwd_nhwc(dy, out=None):
+    """The adjoint of `upsample2_bilinear_nhwc` without accumulator: dy [N,2H,2W,C] -> dx [N,H,W,C], one gather launch, no atomics
+    (two runs give the same bits)."""
+    _req_cuda(dy, out)
+    assert dy.dim() == 4 and dy.dtype == torch.float32 and dy.is_contiguous()
+    N, H2, W2, C = dy.shape
+    assert H2 % 2 == 0 and W2 % 2 == 0, dy.shape
+    if out is None:
+        out = torch.empty(N, H2 // 2, W2 // 2, C, device=dy.device, dtype=torch.float32)
+    assert out.shape == (N, H2 // 2, W2 // 2, C) and out.dtype == torch.float32 and out.is_contiguous()
+    check(_lib.lib().lvcst_upsample2_bilinear_bwd_nhwc(ptr(dy), ptr(out), N, H2 // 2, W2 // 2, C, _stream(dy)),
+          "lvcst_upsample2_bilinear_bwd_nhwc")
+    return out
+
+
+def sem_seg_loss_jobs(label_sizes, offsets=None):
+    """The host job table of the semantic loss, one row per image: label_sizes [(h, w)] of each image's own label map; the maps follow
+    each other in one buffer (offsets: in elements, default packed).  -> (int64 numpy [n, SEGTRAIN_LOSS_FIELDS], labels_numel)."""
+    import numpy as np
+
+    jobs = np.zeros((len(label_sizes), SEGTRAIN_LOSS_FIELDS), dtype=np.int64)
+    at = 0
+    for i, (h, w) in enumerate(label_sizes):
+        jobs[i] = [at if offsets is None else offsets[i], h, w]
+        at += h * w
+    return jobs, at
+
+
+def _loss_labels_checked(labels, ignore_value):
+    assert labels.dtype in (torch.uint8, torch.int64) and labels.is_contiguous(), "labels: a contiguous uint8 or int64 buffer"
+    if labels.dtype == torch.uint8 and not 0 <= int(ignore_value) <= 255:
+        raise ValueError("MODEL.SEM_SEG_HEAD.IGNORE_VALUE = {}: outside what uint8 labels hold".format(ignore_value))
+    return 1 if labels.dtype == torch.uint8 else 8
+
+
+def sem_seg_loss_fwd(logits, labels, jobs, num_classes, scale, ignore_value, status, ld=None, lse=None, d_jobs=None, maps=None):
+    """F.cross_entropy(F.interpolate(logits, scale_factor=scale, bilinear), labels, "mean", ignore_index) without the interpolated
+    tensor.  logits [N,h,w,ld] fp32 (the first num_classes channels are read); labels: one uint8 / int64 buffer that holds every image's
+    own map where `jobs` (`sem_seg_loss_jobs`) says; status: an int32 [1] word the kernel ORs SEGTRAIN_STATUS_LABEL_RANGE into; lse: an
+    fp32 [N,scale*h,scale*w] buffer for the per-pixel log-sum-exp, or None (the backward takes its two parts, `maps`).
+    -> (loss fp32 [1], maps = (max, log-sum) fp32 [N,scale*h,scale*w] each, sum fp64 [1], count int64 [1], d_jobs); nothing is read back."""
+    import numpy as np
+
+    _req_cuda(logits, labels, status, lse)
+    assert logits.dim() == 4 and logits.dtype == torch.float32 and logits.is_contiguous()
+    N, h, w, last = logits.shape
+    Kc, ld, scale = int(num_classes), int(last if ld is None else ld), int(scale)
+    assert ld == last, "logits rows of ld floats"
+    label_bytes = _loss_labels_checked(labels, ignore_value)
+    jobs = np.ascontiguousarray(jobs, dtype=np.int64).reshape(-1, SEGTRAIN_LOSS_FIELDS)
+    assert jobs.shape[0] == N and status.dtype == torch.int32 and status.numel() >= 1
+    dev = logits.device
+    if maps is None:
+        maps = (torch.empty(N, scale * h, scale * w, device=dev, dtype=torch.float32),
+                torch.empty(N, scale * h, scale * w, device=dev, dtype=torch.float32))
+    for t in tuple(maps) + (lse,):
+        assert t is None or (t.shape == (N, scale * h, scale * w) and t.dtype == torch.float32 and t.is_contiguous())
+    nbytes = _lib.lib().lvcst_sem_seg_loss_workspace_bytes(N, h, w, Kc, scale)      # (_lib.size_query names entries of lvc_amd.h)
+    if nbytes < 0:
+        raise LvcNativeError("lvcst_sem_seg_loss_workspace_bytes answered {}: arguments outside the kernel's range".format(nbytes))
+    ws = torch.empty(max(nbytes // 8, 1), device=dev, dtype=torch.float64)
+    loss = torch.empty(1, device=dev, dtype=torch.float32)
+    total = torch.empty(1, device=dev, dtype=torch.float64)
+    count = torch.empty(1, device=dev, dtype=torch.int64)
+    if d_jobs is None:
+        d_jobs = _upload_table(jobs, dev) if N else None
+    check(_lib.lib().lvcst_sem_seg_loss_fwd(ptr(logits), N, h, w, Kc, ld, scale, ptr(labels), labels.numel(), label_bytes,
+                                            int(ignore_value), c_void_p(jobs.ctypes.data), ptr(d_jobs), ptr(maps[0]), ptr(maps[1]), ptr(lse),
+                                            ptr(ws), ws.numel() * 8, ptr(loss), ptr(total), ptr(count), ptr(status), _stream(logits)),
+          "lvcst_sem_seg_loss_fwd")
+    return loss, tuple(maps), total, count, d_jobs
+
+
+def sem_seg_loss_bwd(logits, labels, jobs, d_jobs, num_classes, scale, ignore_value, maps, g, count, out=None):
+    """The gradient of `sem_seg_loss_fwd`'s loss times the device scalar g with respect to the logits: [N,h,w,ld], channels past
+    num_classes zero.  maps, count: the forward's.  No atomics: two runs give the same bits."""
+    import numpy as np
+
+    mmax, lsum = maps
+    _req_cuda(logits, labels, mmax, lsum, g, count, out)
+    N, h, w, ld = logits.shape
+    label_bytes = _loss_labels_checked(labels, ignore_value)
+    jobs = np.ascontiguousarray(jobs, dtype=np.int64).reshape(-1, SEGTRAIN_LOSS_FIELDS)
+    assert logits.dtype == torch.float32 and logits.is_contiguous() and jobs.shape[0] == N
+    for t in (mmax, lsum):
+        assert t.shape == (N, int(scale) * h, int(scale) * w) and t.dtype == torch.float32 and t.is_contiguous()
+    assert g.dtype == torch.float32 and g.numel() == 1 and count.dtype == torch.int64 and count.numel() == 1
+    if out is None:
+        out = torch.empty_like(logits)
+    assert out.shape == logits.shape and out.dtype == torch.float32 and out.is_contiguous()
+    check(_lib.lib().lvcst_sem_seg_loss_bwd(ptr(logits), N, h, w, int(num_classes), ld, int(scale), ptr(labels), labels.numel(),
+                                            label_bytes, int(ignore_value), c_void_p(jobs.ctypes.data), ptr(d_jobs), ptr(mmax), ptr(lsum),
+                                            ptr(g), ptr(count), ptr(out), _stream(logits)),
+          "lvcst_sem_seg_loss_bwd")
+    return out

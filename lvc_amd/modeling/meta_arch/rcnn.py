@@ -201,6 +201,7 @@ class GeneralizedRCNN(_RCNNBase):
         # frozen trunk (the fine-tune yamls): no graph; otherwise the fused Conv2d autograd records res3.. / FPN
         with torch.set_grad_enabled(torch.is_grad_enabled() and any(p.requires_grad for p in self.backbone.parameters())):
             features = self.backbone(images.tensor)
+        self._on_train_features(features, batched_inputs, images)
         from ..proposal_generator.rbg import RBG
 
         if isinstance(self.proposal_generator, RBG):  # reference rcnn.py:150-155: loaded proposals -> jittered GT boxes
@@ -226,12 +227,26 @@ class GeneralizedRCNN(_RCNNBase):
             proposals = [x["proposals"].to(self.device) for x in batched_inputs]
             proposal_losses = {}
         _, detector_losses = self.roi_heads(images, features, proposals, gt_instances)
+        return self._train_losses(detector_losses, proposal_losses)
+
+    deferred_reads = True      # class switch for A/B runs and tests (False: RPN.forward / ROIHeads.forward with their own reads)
+
+    # Hooks of the training step, empty here as `_on_features` is for inference (PanopticFPN: the semantic loss on the same features).
+    def _on_train_features(self, features, batched_inputs, images):
+        """Called once per step with the trunk's features, in front of the proposal generator."""
+
+    def _train_extra_words(self):
+        """int64 device tensors that ride on the deferred-read step's one device->host read (none here)."""
+        return []
+
+    def _on_train_extra_words(self, words):
+        """The host copy of `_train_extra_words`' tensors, flattened."""
+
+    def _train_losses(self, detector_losses, proposal_losses):
         losses = {}
         losses.update(detector_losses)
         losses.update(proposal_losses)
         return losses
-
-    deferred_reads = True      # class switch for A/B runs and tests (False: RPN.forward / ROIHeads.forward with their own reads)
 
     def _forward_train_deferred(self, images, features, gt_instances):
         """RPN + StandardROIHeads training (reference rcnn.py:127-175) as ONE stream of launches with ONE device->host read at the end:
@@ -245,11 +260,17 @@ class GeneralizedRCNN(_RCNNBase):
         boxes, logits, count, proposal_losses, rpn_counts, gt, gt_off = rpn.forward_train_batched(images, features, gt_instances)
         detector_losses, cnt, (stats, layout) = heads.forward_train_batched(features, boxes, logits, count, gt, gt_off, gt_instances)
         B, bs = boxes.shape[0], heads.batch_size_per_image
-        meta = torch.cat([count.long(), rpn_counts.view(-1).long(), cnt.view(-1).long(), stats.long(), K.range_summary(self.device).long()]).tolist()
-        pc, rc, cc, st, flagged = meta[:B], meta[B:3 * B], meta[3 * B:5 * B], meta[5 * B:-1], meta[-1]      # (st: the heads' counts, named by `layout`)
+        extra = self._train_extra_words()
+        ne = sum(t.numel() for t in extra)
+        meta = torch.cat([count.long(), rpn_counts.view(-1).long(), cnt.view(-1).long(), stats.long(), *extra,
+                          K.range_summary(self.device).long()]).tolist()
+        end = len(meta) - 1 - ne
+        pc, rc, cc, st, flagged = meta[:B], meta[B:3 * B], meta[3 * B:5 * B], meta[5 * B:end], meta[-1]      # (st: the heads' counts, named by `layout`)
         if flagged:
             K.check_conv_error_word(self.device)      # re-routes the layers concerned and raises: `run_with_fallbacks` repeats the pass
         self.__dict__["_range_checked"] = True
+        if ne:
+            self._on_train_extra_words(meta[end:-1])
         storage = get_event_storage()
         storage.put_scalar("rpn/num_pos_anchors", sum(rc[0::2]) / B)
         storage.put_scalar("rpn/num_neg_anchors", sum(rc[1::2]) / B)
@@ -265,10 +286,7 @@ class GeneralizedRCNN(_RCNNBase):
                 proposals.append(inst)
             _, detector_losses = heads(images, features, proposals, gt_instances)
             K.check_conv_error_word(self.device)      # this second heads pass raised its own range words: judged in THIS step
-        losses = {}
-        losses.update(detector_losses)
-        losses.update(proposal_losses)
-        return losses
+        return self._train_losses(detector_losses, proposal_losses)
 
     # ------------------------------------------------------------------ device-side fast path
     def inference_batched(self, batched_inputs, do_postprocess=True, status=None):

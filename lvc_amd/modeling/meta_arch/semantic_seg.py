@@ -1,4 +1,4 @@
-"""SemSegFPNHead / SemanticSegmentor (reference detectron2/modeling/meta_arch/semantic_seg.py), inference only.
+"""SemSegFPNHead / SemanticSegmentor (reference detectron2/modeling/meta_arch/semantic_seg.py).
 
 The head's state_dict is the reference's (`p2.0.weight`, `p2.0.norm.weight`, `p4.2.*`, `predictor.*`: the `Sequential` slots of the
 upsamples stay empty of parameters, so a reference checkpoint loads with strict=True).  Each block is the project's Conv2d with a
@@ -12,7 +12,13 @@ GroupNorm norm (conv -> GN -> ReLU on the existing routes); the bilinear x2 upsa
   * the full-resolution [K, H, W] map of the reference's `forward` is never formed: `postprocess` goes from the stride-`COMMON_STRIDE`
     logits to the output-size soft logits and / or label map in one launch per batch.
 
-Training (`loss_sem_seg`) is not built and refuses before anything touches a device.
+Training is opt-in (`enable_sem_seg_training()`; without it a model in training mode refuses before anything touches a device).  The
+head then runs on the same NHWC features under autograd: the scale heads through `Conv2d.forward_nhwc` (conv -> GN -> ReLU), the x2
+upsamples through `_Upsample2Fn` (backward: csrc/sem_seg_train.hip's gather kernel; the accumulator's gradient is dy itself), the
+predictor in its packed, zero-padded form (`_PackedPredictorFn`: the training logits are `forward_nhwc`'s bits; the padded rows of
+dW / db are dropped), and `loss_sem_seg` as ONE autograd.Function from the stride-`COMMON_STRIDE` logits and the label maps where
+they lie -- forward `lvcst_sem_seg_loss_fwd`, backward `lvcst_sem_seg_loss_bwd` -- so the training path never forms the
+full-resolution map either.
 """
 import numpy as np
 import torch
@@ -37,10 +43,118 @@ def build_sem_seg_head(cfg, input_shape):
     return SEM_SEG_HEADS_REGISTRY.get(cfg.MODEL.SEM_SEG_HEAD.NAME)(cfg, input_shape)
 
 
+class _Upsample2Fn(torch.autograd.Function):
+    """y = up2(x), or y = acc + up2(x) (a new tensor: the accumulator is another node's output).  Backward: dx by the gather kernel of
+    csrc/sem_seg_train.hip, and d acc = dy itself, passed through."""
+
+    @staticmethod
+    def forward(ctx, x, acc):
+        ctx.has_acc = acc is not None
+        return K.upsample2_bilinear_nhwc(x, acc=acc)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        dy = dy.contiguous()
+        dx = K.upsample2_bilinear_bwd_nhwc(dy) if ctx.needs_input_grad[0] else None
+        return dx, dy if ctx.has_acc and ctx.needs_input_grad[1] else None
+
+
+def upsample2_bilinear(x, acc=None):
+    """`K.upsample2_bilinear_nhwc` under autograd: up2(x), or acc + up2(x) with the accumulator added last."""
+    return _Upsample2Fn.apply(x, acc)
+
+
+class _PackedPredictorFn(torch.autograd.Function):
+    """The 1x1 predictor in its packed form (output channels zero-padded to `logits_ld`): the launch of `forward_nhwc`, so the training
+    logits are its bits.  Backward from the [N,h,w,ld] gradient: dW and db of the ld rows, of which the first NUM_CLASSES are the
+    parameters' (the padded rows are dropped), and dx on the predictor's own data-gradient operand, whose contraction is padded with
+    zero rows to the same width."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, head):
+        ctx.save_for_backward(x)
+        ctx.head = head
+        return K.conv2d_nhwc(x, head.packed_predictor(), relu=False)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, = ctx.saved_tensors
+        head, dy = ctx.head, dy.contiguous()
+        kc = head.num_classes
+        dx = dw = db = None
+        if ctx.needs_input_grad[1]:
+            dw = K.conv_wgrad(x, dy, None, 1, 1, 1, 0)[:kc].permute(0, 3, 1, 2).contiguous()      # [ld,1,1,C] -> the parameter's OIHW
+        if ctx.needs_input_grad[2]:
+            db = K.colsum_rows(dy.view(-1, dy.shape[-1]))[:kc]
+        if ctx.needs_input_grad[0]:
+            dx = K.conv_dgrad(dy, head.predictor.packed_dgrad(), x.shape, 1)
+        return dx, dw, db, None
+
+
+class _SemSegLossFn(torch.autograd.Function):
+    """mean cross entropy of the x`scale` bilinear interpolation of the logits against the label maps (ignore_index), from the
+    stride-`scale` logits: forward lvcst_sem_seg_loss_fwd (keeps the per-pixel max and log-sum maps, the two parts of the log-sum-exp),
+    backward lvcst_sem_seg_loss_bwd (reads the upstream scalar and the valid-pixel count on the device)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, jobs, num_classes, scale, ignore_value, status):
+        loss, (mmax, lsum), _total, count, d_jobs = K.sem_seg_loss_fwd(logits, labels, jobs, num_classes, scale, ignore_value, status)
+        ctx.save_for_backward(logits, labels, mmax, lsum, count, d_jobs)
+        ctx.args = (jobs, num_classes, scale, ignore_value)
+        return loss.view(())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        logits, labels, mmax, lsum, count, d_jobs = ctx.saved_tensors
+        jobs, num_classes, scale, ignore_value = ctx.args
+        dlow = K.sem_seg_loss_bwd(logits, labels, jobs, d_jobs, num_classes, scale, ignore_value, (mmax, lsum), g.contiguous().view(1), count)
+        return dlow, None, None, None, None, None, None
+
+
+def sem_seg_loss(logits, labels, jobs, num_classes, scale, ignore_value, status):
+    """-> the scalar mean loss (fp32, on the device) of logits [N,h,w,ld] against the label maps in `labels` (`K.sem_seg_loss_jobs`)."""
+    return _SemSegLossFn.apply(logits, labels, jobs, int(num_classes), int(scale), int(ignore_value), status)
+
+
+def check_sem_seg_items(batched_inputs, ignore_value, sizes=None):
+    """The host's refusals, before anything touches a device: every item carries "sem_seg", an integer tensor of its image's size
+    (sizes: per item (h, w); default the item's "image"), and IGNORE_VALUE is a value the maps' type holds.  -> the maps."""
+    maps = []
+    for i, inp in enumerate(batched_inputs):
+        if "sem_seg" not in inp:
+            raise ValueError('item {}: no "sem_seg" (the ground-truth label map [H, W] of the image) to train the semantic branch on'.format(i))
+        m = inp["sem_seg"]
+        if not torch.is_tensor(m) or m.is_floating_point() or m.dtype == torch.bool or m.is_complex():
+            raise ValueError('item {}: "sem_seg" must be an integer tensor, got {}'.format(i, getattr(m, "dtype", type(m).__name__)))
+        size = sizes[i] if sizes is not None else (tuple(inp["image"].shape[-2:]) if "image" in inp else None)
+        if size is not None and tuple(m.shape) != (int(size[0]), int(size[1])):
+            raise ValueError('item {}: "sem_seg" is {} but the image is {}'.format(i, tuple(m.shape), (int(size[0]), int(size[1]))))
+        maps.append(m)
+    if maps and all(m.dtype == torch.uint8 for m in maps) and not 0 <= int(ignore_value) <= 255:
+        raise ValueError('MODEL.SEM_SEG_HEAD.IGNORE_VALUE = {}: outside what the uint8 "sem_seg" maps hold'.format(ignore_value))
+    return maps
+
+
+def sem_seg_targets(batched_inputs, sizes, device, ignore_value):
+    """The items' "sem_seg" label maps as ONE device buffer and its job table.  Each map is an integer tensor of its item's image size
+    (`sizes`: what the network saw); the padding to the batch size is the loss kernel's (a pixel outside a map counts as IGNORE_VALUE).
+    -> (labels uint8 / int64 [sum h*w], jobs)."""
+    maps = check_sem_seg_items(batched_inputs, ignore_value, sizes)
+    dtype = torch.uint8 if all(m.dtype == torch.uint8 for m in maps) else torch.int64
+    jobs, _ = K.sem_seg_loss_jobs([tuple(m.shape) for m in maps])
+    on_dev = [m.to(device, non_blocking=True).to(dtype).reshape(-1) for m in maps]
+    return (on_dev[0] if len(on_dev) == 1 else torch.cat(on_dev)).contiguous(), jobs
+
+
 class Upsample2(nn.Module):
     """The parameter-free slot of nn.Upsample(scale_factor=2, mode="bilinear", align_corners=False) in a scale head."""
 
     def forward_nhwc(self, x, acc=None):
+        if torch.is_grad_enabled() and (x.requires_grad or (acc is not None and acc.requires_grad)):
+            return upsample2_bilinear(x, acc)
         return K.upsample2_bilinear_nhwc(x, acc=acc, out=acc)
 
     def extra_repr(self):
@@ -111,27 +225,56 @@ class SemSegFPNHead(nn.Module):
         pc.state = conv._range_state
         return pc
 
+    def _level_sum(self, features):
+        x = None
+        for f, head in zip(self.in_features, self.scale_heads):
+            y, ops = features[f], list(head)
+            for k, op in enumerate(ops):
+                if isinstance(op, Upsample2):
+                    last = k == len(ops) - 1
+                    if last and x is not None:
+                        x = op.forward_nhwc(y, acc=x)
+                        y = None
+                    else:
+                        y = op.forward_nhwc(y)
+                else:
+                    y = op.forward_nhwc(y)
+            if y is not None:
+                assert x is None
+                x = y
+        return x
+
     def forward_nhwc(self, features):
         """features {name: [N,H_l,W_l,C]} -> the stride-COMMON_STRIDE logits [N,h,w,logits_ld] (channels past NUM_CLASSES: the packed
         operand's zero padding).  Gradient-free."""
         with torch.no_grad():
-            x = None
-            for f, head in zip(self.in_features, self.scale_heads):
-                y, ops = features[f], list(head)
-                for k, op in enumerate(ops):
-                    if isinstance(op, Upsample2):
-                        last = k == len(ops) - 1
-                        if last and x is not None:
-                            x = op.forward_nhwc(y, acc=x)
-                            y = None
-                        else:
-                            y = op.forward_nhwc(y)
-                    else:
-                        y = op.forward_nhwc(y)
-                if y is not None:
-                    assert x is None
-                    x = y
-            return K.conv2d_nhwc(x, self.packed_predictor(), relu=False)
+            return K.conv2d_nhwc(self._level_sum(features), self.packed_predictor(), relu=False)
+
+    def forward_train_nhwc(self, features):
+        """`forward_nhwc` under autograd: the same launches in the same order (an accumulating upsample writes a new tensor, not the
+        running sum), so the logits are the same bits; every step has its backward on the device."""
+        x = self._level_sum(features)
+        p = self.predictor
+        if torch.is_grad_enabled() and (x.requires_grad or p.weight.requires_grad or p.bias.requires_grad):
+            return _PackedPredictorFn.apply(x, p.weight, p.bias, self)
+        return K.conv2d_nhwc(x, self.packed_predictor(), relu=False)
+
+    def losses(self, predictions, targets, status=None):
+        """reference semantic_seg.py:179-187 with the stride-COMMON_STRIDE logits [N,h,w,logits_ld] in place of the full-size map, which
+        is never formed.  targets: (labels buffer, job table) of `sem_seg_targets`.  status: the int32 word the loss kernel ORs an
+        out-of-range label into (a new one when None; `check_loss_status` reads it).  -> {"loss_sem_seg": loss * LOSS_WEIGHT}."""
+        labels, jobs = targets
+        if status is None:
+            status = torch.zeros(1, device=predictions.device, dtype=torch.int32)
+        self.__dict__["_loss_status"] = status
+        loss = sem_seg_loss(predictions, labels, jobs, self.num_classes, self.common_stride, self.ignore_value, status)
+        return {"loss_sem_seg": loss * self.loss_weight}
+
+    def check_loss_status(self, word):
+        """Raise for the host copy of the loss's status word, as torch's CPU cross entropy raises for such a target."""
+        if int(word) & K.SEGTRAIN_STATUS_LABEL_RANGE:
+            raise IndexError('"sem_seg": a label is neither MODEL.SEM_SEG_HEAD.IGNORE_VALUE ({}) nor in [0, NUM_CLASSES = {}): target out of '
+                             "bounds".format(self.ignore_value, self.num_classes))
 
     def postprocess(self, logits, image_sizes, out_sizes, want_soft=True, want_labels=True):
         """F.interpolate(x COMMON_STRIDE) + sem_seg_postprocess (+ argmax) of a batch in one launch.  logits: `forward_nhwc`'s.
@@ -151,9 +294,10 @@ class SemSegFPNHead(nn.Module):
 
     def forward(self, features, targets=None):
         """The reference's interface on NCHW maps: eval -> ([N, K, H, W] logits at the input resolution, {}).  The models go through
-        `forward_nhwc` + `postprocess` instead and never form this tensor."""
+        `forward_nhwc` + `postprocess` (training: `forward_train_nhwc` + `losses`) instead and never form this tensor."""
         if self.training:
-            raise NotImplementedError(TRAIN_REFUSAL)
+            raise NotImplementedError(TRAIN_REFUSAL + " through SemSegFPNHead.forward: the models call forward_train_nhwc and losses "
+                                      "(enable_sem_seg_training)")
         from ...layers.layout import to_nhwc
 
         logits = self.forward_nhwc({f: to_nhwc(features[f]) for f in self.in_features})
@@ -186,12 +330,42 @@ class SemanticSegmentor(_RCNNBase):
         self.sem_seg_head = build_sem_seg_head(cfg, self.backbone.output_shape())
         self.to(self.device)
 
+    def enable_sem_seg_training(self, on=True):
+        """Switch the training forward on (or off again); returns self.  Without the call the model in training mode refuses, as
+        before.  Every item then carries "sem_seg": an integer label map of the image's size."""
+        self.__dict__["_sem_seg_train_enabled"] = bool(on)
+        return self
+
     def forward(self, batched_inputs):
-        if self.training:
-            raise NotImplementedError(TRAIN_REFUSAL)
         from ..roi_heads.roi_heads import run_with_fallbacks
 
+        if self.training:
+            if not self.__dict__.get("_sem_seg_train_enabled", False):
+                raise NotImplementedError(TRAIN_REFUSAL)
+            check_sem_seg_items(batched_inputs, self.sem_seg_head.ignore_value)
+            return run_with_fallbacks(self, lambda: self._forward_train(batched_inputs))
         return run_with_fallbacks(self, lambda: self._inference(batched_inputs))
+
+    def _losses_device(self, batched_inputs):
+        """The step up to its one read: preprocess -> trunk (a graph only if something in it trains) -> head -> loss.
+        -> (losses, the words that read brings back: the loss's status word, then the conv kernels' range summary)."""
+        self._prepack_trainable()
+        x4, sizes = self.preprocess_nhwc(batched_inputs)
+        targets = sem_seg_targets(batched_inputs, sizes, self.device, self.sem_seg_head.ignore_value)
+        with torch.set_grad_enabled(torch.is_grad_enabled() and any(p.requires_grad for p in self.backbone.parameters())):
+            feats = self.backbone.forward_nhwc(x4)
+        logits = self.sem_seg_head.forward_train_nhwc(feats)
+        status = torch.zeros(1, device=self.device, dtype=torch.int32)
+        losses = self.sem_seg_head.losses(logits, targets, status)
+        return losses, torch.cat([status.long(), K.range_summary(self.device).long()])
+
+    def _forward_train(self, batched_inputs):
+        losses, words = self._losses_device(batched_inputs)
+        word, flagged = words.tolist()      # the step's one read
+        if flagged:
+            K.check_conv_error_word(self.device)      # re-routes the layers concerned and raises: `run_with_fallbacks` repeats the pass
+        self.sem_seg_head.check_loss_status(word)
+        return losses
 
     def _inference(self, batched_inputs):
         x4, sizes = self.preprocess_nhwc(batched_inputs)
