@@ -1,5 +1,8 @@
-"""ctypes loader of the C-ABI kernel library `liblvc_amd.so` (declared in include/lvc_amd.h; the semantic / panoptic entries, prefix
-`lvcseg_`, in include/lvc_amd_seg.h; the entries that train the semantic branch, prefix `lvcst_`, in include/lvc_amd_segtrain.h).
+"""ctypes loader of the C-ABI kernel library `liblvc_amd.so`.  The ABI is declared in the headers under include/ that `HEADERS`
+lists, each with the prefix of its entries: lvc_amd.h (`lvc_`), lvc_amd_seg.h (the semantic / panoptic entries, `lvcseg_`) and
+lvc_amd_segtrain.h (the entries that train the semantic branch, `lvcst_`).  `signatures()` is the one loader of all of them and
+`lib()` binds every entry from it.  A new entry is declared in lvc_amd.h under `lvc_`, and the count in tests/test_host_abi.py moves
+with it in the same commit; a new header is one row in `HEADERS`, with no loader and no test file of its own.
 
 The product path has NO CPU fallback: if the library is missing or a call fails, this raises.
 Errors follow the reference's behaviour for its native ops (C++ exception -> Python RuntimeError,
@@ -13,13 +16,11 @@ import re
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # LVC_AMD_LIB: another build of the same library (A/B measurements of one kernel against its predecessor in alternating processes)
 _SO = os.environ.get("LVC_AMD_LIB") or os.path.join(_HERE, "liblvc_amd.so")
-_HEADER = os.path.join(os.path.dirname(_HERE), "include", "lvc_amd.h")
-_HEADER_SEG = os.path.join(os.path.dirname(_HERE), "include", "lvc_amd_seg.h")
-_HEADER_SEGTRAIN = os.path.join(os.path.dirname(_HERE), "include", "lvc_amd_segtrain.h")
+_INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
+# The headers of the ABI and the prefix every declaration of each carries: the one list of them.  A new header is one row here.
+HEADERS = (("lvc_amd.h", "lvc_"), ("lvc_amd_seg.h", "lvcseg_"), ("lvc_amd_segtrain.h", "lvcst_"))
 _lib = None
-_signatures = None
-_signatures_seg = None
-_signatures_segtrain = None
+_tables = {}      # header file name -> its parsed table; None -> the union
 
 c_void_p = ctypes.c_void_p
 c_int = ctypes.c_int
@@ -33,9 +34,9 @@ class LvcNativeError(RuntimeError):
     pass
 
 
-def parse_header(text, prefix="lvc_"):
-    """{entry point: (restype, [argtypes])} from the text of a header of the ABI (include/lvc_amd.h; with prefix "lvcseg_",
-    include/lvc_amd_seg.h; with "lvcst_", include/lvc_amd_segtrain.h): every declaration names a function that starts with `prefix`.  The header is plain
+def parse_header(text, prefix="lvc_", where="lvc_amd.h"):
+    """{entry point: (restype, [argtypes])} from the text of a header of the ABI (a row of `HEADERS`): every declaration names a
+    function that starts with `prefix`, and an error names the header as `where`.  The header is plain
     C99 without typedefs, structs or function pointers, so a declaration is `ret name(type name, ...);`.  Every pointer parameter is
     a c_void_p, whatever it points to (it takes `ptr(t)`, None, a ctypes host array and `byref`); a type that is not listed here is
     an error that names the declaration, never a default.  The variadic lvc_set_error is not bound."""
@@ -45,7 +46,7 @@ def parse_header(text, prefix="lvc_"):
     for decl in filter(None, (" ".join(d.split()) for d in text.split(";"))):
         m = re.fullmatch(r"(.+?)\b(" + re.escape(prefix) + r"\w+) ?\((.*)\)", decl)
         if m is None:
-            raise ValueError("lvc_amd.h: cannot read the declaration `{}` (a function named {}*)".format(decl, prefix))
+            raise ValueError("{}: cannot read the declaration `{}` (a function named {}*)".format(where, decl, prefix))
         ret, name, params = m.group(1).strip(), m.group(2), m.group(3).strip()
         if "..." in params:
             continue
@@ -56,7 +57,7 @@ def parse_header(text, prefix="lvc_"):
         elif ret in _SCALARS:
             restype = _SCALARS[ret]
         else:
-            raise ValueError("lvc_amd.h: unknown return type `{}` in `{}`".format(ret, decl))
+            raise ValueError("{}: unknown return type `{}` in `{}`".format(where, ret, decl))
         argtypes = []
         for param in ([] if params == "void" else params.split(",")):
             if "*" in param:
@@ -64,44 +65,32 @@ def parse_header(text, prefix="lvc_"):
                 continue
             ctype = " ".join(t for t in param.split()[:-1] if t != "const")      # the last word is the parameter's name
             if ctype not in _SCALARS:
-                raise ValueError("lvc_amd.h: unknown parameter type in `{}` of `{}`".format(param.strip(), decl))
+                raise ValueError("{}: unknown parameter type in `{}` of `{}`".format(where, param.strip(), decl))
             argtypes.append(_SCALARS[ctype])
         table[name] = (restype, argtypes)
     return table
 
 
-def signatures():
-    """The parsed header, read once per process.  Needs no liblvc_amd.so (scripts/conv_dispatch_trace.py records without one)."""
-    global _signatures
-    if _signatures is None:
-        if not os.path.exists(_HEADER):
-            raise ImportError("lvc_amd: the C ABI header {} not found; the native calls are bound from it "
-                              "(there is no hand-written table to fall back on)".format(_HEADER))
-        with open(_HEADER) as f:
-            _signatures = parse_header(f.read())
-    return _signatures
-
-
-def signatures_seg():
-    """The parsed include/lvc_amd_seg.h (the lvcseg_ entries), read once per process; `signatures()` stays the table of lvc_amd.h."""
-    global _signatures_seg
-    if _signatures_seg is None:
-        if not os.path.exists(_HEADER_SEG):
-            raise ImportError("lvc_amd: the C ABI header {} not found; the native calls are bound from it".format(_HEADER_SEG))
-        with open(_HEADER_SEG) as f:
-            _signatures_seg = parse_header(f.read(), prefix="lvcseg_")
-    return _signatures_seg
-
-
-def signatures_segtrain():
-    """The parsed include/lvc_amd_segtrain.h (the lvcst_ entries), read once per process; the other two tables stay as they are."""
-    global _signatures_segtrain
-    if _signatures_segtrain is None:
-        if not os.path.exists(_HEADER_SEGTRAIN):
-            raise ImportError("lvc_amd: the C ABI header {} not found; the native calls are bound from it".format(_HEADER_SEGTRAIN))
-        with open(_HEADER_SEGTRAIN) as f:
-            _signatures_segtrain = parse_header(f.read(), prefix="lvcst_")
-    return _signatures_segtrain
+def signatures(header=None):
+    """The parsed table of one header of `HEADERS` (by file name), or with None the whole ABI: the union of the tables, where a name
+    declared in two headers is an error.  Read once per process.  Needs no liblvc_amd.so (scripts/conv_dispatch_trace.py records
+    without one)."""
+    if not _tables:
+        tables, union = {}, {}
+        for name, prefix in HEADERS:
+            path = os.path.join(_INCLUDE, name)
+            if not os.path.exists(path):
+                raise ImportError("lvc_amd: the C ABI header {} not found; the native calls are bound from it "
+                                  "(there is no hand-written table to fall back on)".format(path))
+            with open(path) as f:
+                tables[name] = parse_header(f.read(), prefix, where=name)
+            twice = sorted(set(union) & set(tables[name]))
+            if twice:
+                raise ValueError("{}: {} declared in an earlier header too".format(name, ", ".join(twice)))
+            union.update(tables[name])
+        tables[None] = union
+        _tables.update(tables)
+    return _tables[header]
 
 
 def lib():
@@ -113,13 +102,10 @@ def lib():
                 "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C lvc_amd/csrc` "
                 "(there is no CPU fallback)".format(_SO)
             )
-        sigs = dict(signatures())
-        sigs.update(signatures_seg())
-        sigs.update(signatures_segtrain())
         L = ctypes.CDLL(_SO)
         # every call is checked by ctypes against the header from here on: the number of arguments (too few), an int for an int, a
         # pointer for a pointer, and a `long long` travels whole
-        for name, (restype, argtypes) in sigs.items():
+        for name, (restype, argtypes) in signatures().items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes
         if os.environ.get("LVC_WINO_STREAMK", "0") != "0":

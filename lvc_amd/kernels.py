@@ -1575,7 +1575,7 @@ def fast_rcnn_inference(cls_logits, deltas, proposals, prop_count, image_sizes, 
 
 
 RETINANET_MAX_SURVIVORS = 1 << 16     # default capacity of the per-(image, level) list of entries above the score threshold
-RETINANET_OVERFLOW = 4                # the status bit lvc_retinanet_select raises when such a list overflows
+RETINANET_OVERFLOW = RETINA_OVERFLOW  # the status bit lvc_retinanet_select raises when such a list overflows
 
 
 def retinanet_select(logits, deltas, cell_anchors, strides, anchor_offset, num_classes, topk, score_thresh,
@@ -3429,6 +3429,12 @@ def pack_mask_deconv(weight):
     return weight.detach().permute(2, 3, 1, 0).reshape(4 * cmid, cin).contiguous().float()
 
 
+def _upload_table(table, device):
+    """A host int64 table as a device tensor: pinned and asynchronous, the upload is ordered on the stream and the host does not
+    wait for the device."""
+    return torch.from_numpy(table).pin_memory().to(device, non_blocking=True)
+
+
 def _check_num_valid(num_valid):
     """The `num_valid` operand of the mask and keypoint kernels: None or ONE device int32."""
     if num_valid is not None:
@@ -3452,19 +3458,23 @@ def _mask_tail_args(x, w_deconv, b_deconv, w_pred, b_pred, classes, num_valid):
     return M, S, cin, cmid, Kc, w_pred
 
 
-def mask_deconv_predict(x, w_deconv, b_deconv, w_pred, b_pred, classes=None, num_valid=None, status=None, out=None):
-    """Deconv 2x2 s2 + bias + ReLU + 1x1 predictor of one class per row + bias + sigmoid (csrc/mask_deconv.hip).
-    x [M,S,S,Cin] NHWC; w_deconv [4*Cmid,Cin] (`pack_mask_deconv`); w_pred [K,Cmid]; classes [M] int32 or None (class 0);
-    num_valid: device int32, rows past it are neither read nor written.  Returns prob [M,2S,2S] (`out` when given)."""
+def _mask_deconv(entry, x, w_deconv, b_deconv, w_pred, b_pred, classes, num_valid, status, out):
+    """The body of `mask_deconv_predict` and `mask_deconv_logits`: `entry` names the one of the two kernels, which share a signature."""
     _req_cuda(x, w_deconv, b_deconv, w_pred, b_pred, classes, num_valid, status)
     M, S, cin, cmid, Kc, w_pred = _mask_tail_args(x, w_deconv, b_deconv, w_pred, b_pred, classes, num_valid)
     if out is None:
         out = torch.empty(M, 2 * S, 2 * S, device=x.device, dtype=torch.float32)
     assert out.shape == (M, 2 * S, 2 * S) and out.is_contiguous() and out.dtype == torch.float32
-    check(_lib.lib().lvc_mask_deconv_predict(ptr(x), ptr(w_deconv), ptr(b_deconv), ptr(w_pred), ptr(b_pred), ptr(classes), ptr(num_valid),
-                                             ptr(out), M, S, cin, cmid, Kc, ptr(status), _stream(x)),
-          "lvc_mask_deconv_predict")
+    check(getattr(_lib.lib(), entry)(ptr(x), ptr(w_deconv), ptr(b_deconv), ptr(w_pred), ptr(b_pred), ptr(classes), ptr(num_valid),
+                                     ptr(out), M, S, cin, cmid, Kc, ptr(status), _stream(x)), entry)
     return out
+
+
+def mask_deconv_predict(x, w_deconv, b_deconv, w_pred, b_pred, classes=None, num_valid=None, status=None, out=None):
+    """Deconv 2x2 s2 + bias + ReLU + 1x1 predictor of one class per row + bias + sigmoid (csrc/mask_deconv.hip).
+    x [M,S,S,Cin] NHWC; w_deconv [4*Cmid,Cin] (`pack_mask_deconv`); w_pred [K,Cmid]; classes [M] int32 or None (class 0);
+    num_valid: device int32, rows past it are neither read nor written.  Returns prob [M,2S,2S] (`out` when given)."""
+    return _mask_deconv("lvc_mask_deconv_predict", x, w_deconv, b_deconv, w_pred, b_pred, classes, num_valid, status, out)
 
 
 def paste_jobs(rows, boxes, sizes, offsets):
@@ -3501,8 +3511,7 @@ def paste_masks(prob, jobs, out_bytes, threshold=0.5, out=None):
     n = jobs.shape[0]
     if n == 0:
         return out
-    # pinned and asynchronous: the upload is ordered on the stream, the host does not wait for the device
-    d_jobs = torch.from_numpy(jobs).pin_memory().to(prob.device, non_blocking=True)
+    d_jobs = _upload_table(jobs, prob.device)
     check(_lib.lib().lvc_paste_masks(ptr(prob), prob.shape[0], prob.shape[1], c_void_p(jobs.ctypes.data), ptr(d_jobs),
                                      n, ptr(out), padded, threshold, _stream(prob)),
           "lvc_paste_masks")
@@ -3611,8 +3620,7 @@ def mask_targets(boxes, matched, count, planes, mask_size, out=None):
     assert out.dtype == torch.uint8 and out.is_contiguous() and out.shape == (B * R, T, T)
     if B == 0 or R == 0:
         return out
-    # pinned and asynchronous: the upload is ordered on the stream, the host does not wait for the device
-    d_table = torch.from_numpy(table).pin_memory().to(boxes.device, non_blocking=True)
+    d_table = _upload_table(table, boxes.device)
     check(_lib.lib().lvc_mask_targets(ptr(boxes), ptr(matched), ptr(count), count.stride(0), c_void_p(table.ctypes.data), ptr(d_table),
                                       B, R, T, ptr(out), _stream(boxes)), "lvc_mask_targets")
     return out
@@ -3620,15 +3628,7 @@ def mask_targets(boxes, matched, count, planes, mask_size, out=None):
 
 def mask_deconv_logits(x, w_deconv, b_deconv, w_pred, b_pred, classes=None, num_valid=None, status=None, out=None):
     """`mask_deconv_predict` without the sigmoid: the logits [M,2S,2S] of each row's class (training: the ground-truth class)."""
-    _req_cuda(x, w_deconv, b_deconv, w_pred, b_pred, classes, num_valid, status)
-    M, S, cin, cmid, Kc, w_pred = _mask_tail_args(x, w_deconv, b_deconv, w_pred, b_pred, classes, num_valid)
-    if out is None:
-        out = torch.empty(M, 2 * S, 2 * S, device=x.device, dtype=torch.float32)
-    assert out.shape == (M, 2 * S, 2 * S) and out.is_contiguous() and out.dtype == torch.float32
-    check(_lib.lib().lvc_mask_deconv_logits(ptr(x), ptr(w_deconv), ptr(b_deconv), ptr(w_pred), ptr(b_pred), ptr(classes), ptr(num_valid),
-                                            ptr(out), M, S, cin, cmid, Kc, ptr(status), _stream(x)),
-          "lvc_mask_deconv_logits")
-    return out
+    return _mask_deconv("lvc_mask_deconv_logits", x, w_deconv, b_deconv, w_pred, b_pred, classes, num_valid, status, out)
 
 
 def mask_loss(logits, targets, num_valid=None):
@@ -3725,8 +3725,7 @@ def keypoint_targets(boxes, matched, count, keypoints, size, apply_selection=Tru
     sel_count = torch.zeros(B, dtype=torch.int32, device=dev)
     if B == 0:
         return target, valid, selected, sel_count
-    # pinned and asynchronous: the upload is ordered on the stream, the host does not wait for the device
-    d_table = torch.from_numpy(table).pin_memory().to(dev, non_blocking=True)
+    d_table = _upload_table(table, dev)
     check(_lib.lib().lvc_keypoint_targets(ptr(boxes), ptr(matched), ptr(count), count.stride(0), c_void_p(table.ctypes.data),
                                           ptr(d_table), B, R, k, int(size), 1 if apply_selection else 0,
                                           ptr(target), ptr(valid), ptr(selected), ptr(sel_count), _stream(boxes)), "lvc_keypoint_targets")
@@ -3862,11 +3861,6 @@ SEG_COMBINE_FIELDS = 9       # int64 words per image of lvcseg_panoptic_combine
 SEG_SEGMENT_FIELDS = 8       # int32 words per row of its segment table
 SEG_MAX_INSTANCES = 1024
 SEG_MAX_LABELS = 4096
-
-
-def _upload_table(table, device):
-    """A host int64 table as a device tensor: pinned and asynchronous, the host does not wait for the device."""
-    return torch.from_numpy(table).pin_memory().to(device, non_blocking=True)
 
 
 def upsample2_bilinear_nhwc(x, acc=None, out=None):
@@ -4061,9 +4055,7 @@ def sem_seg_loss_fwd(logits, labels, jobs, num_classes, scale, ignore_value, sta
                 torch.empty(N, scale * h, scale * w, device=dev, dtype=torch.float32))
     for t in tuple(maps) + (lse,):
         assert t is None or (t.shape == (N, scale * h, scale * w) and t.dtype == torch.float32 and t.is_contiguous())
-    nbytes = _lib.lib().lvcst_sem_seg_loss_workspace_bytes(N, h, w, Kc, scale)      # (_lib.size_query names entries of lvc_amd.h)
-    if nbytes < 0:
-        raise LvcNativeError("lvcst_sem_seg_loss_workspace_bytes answered {}: arguments outside the kernel's range".format(nbytes))
+    nbytes = _lib.size_query("lvcst_sem_seg_loss_workspace_bytes", N, h, w, Kc, scale)
     ws = torch.empty(max(nbytes // 8, 1), device=dev, dtype=torch.float64)
     loss = torch.empty(1, device=dev, dtype=torch.float32)
     total = torch.empty(1, device=dev, dtype=torch.float64)

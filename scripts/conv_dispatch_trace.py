@@ -55,7 +55,7 @@ class _Fn:
 
     def __init__(self, rec, name, real):
         self._rec, self._name, self._real = rec, name, real
-        self._argtypes = _lib.signatures()[name][1]      # KeyError: not an entry point of include/lvc_amd.h
+        self._argtypes = _lib.signatures()[name][1]      # KeyError: not an entry point of any header of the ABI
 
     def __call__(self, *args):
         rec = self._rec

@@ -1,11 +1,16 @@
 """Training Panoptic FPN on the host: tests/seg_train_ref.py -- the plain restatement of the loss and both gradients -- agrees with torch's
 float64 autograd of F.interpolate + F.cross_entropy; the opt-in switches; the refusals of the label maps; the reference's loss dict with
 its two scalings.  No kernel is launched."""
+import ctypes
+
+import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
 import seg_train_ref
+
+from lvc_amd import _lib
 
 IGNORE = 255
 
@@ -147,3 +152,53 @@ def test_the_loss_dict_scales_the_detector_losses_and_leaves_the_rpn_losses():
     base = GeneralizedRCNN._train_losses(stub, det, rpn)
     assert {k: float(v) for k, v in base.items()} == {k: float(v) for k, v in {**det, **rpn}.items()}
     assert GeneralizedRCNN._train_extra_words(stub) == [] and GeneralizedRCNN._on_train_features(stub, None, None, None) is None
+
+
+# ------------------------------------------------------------------------------------------------ the host checks of csrc/sem_seg_train.hip
+def _jobs(rows):
+    t = np.ascontiguousarray(rows, dtype=np.int64)
+    return t, ctypes.c_void_p(t.ctypes.data)
+
+
+def test_argument_validation_returns_an_error_without_a_device():
+    """Every refusal below is decided on the host, in front of any launch: a status and a text, with pointers that are never followed."""
+    lib = _lib.lib()
+    fake = ctypes.c_void_p(4096)      # (non-null, 16-byte aligned, never dereferenced: each call fails its check first)
+
+    def err():
+        return lib.lvc_last_error().decode()
+
+    assert lib.lvcst_upsample2_bilinear_bwd_nhwc(fake, fake, 1, 1, 1, 6, None) == 1 and "multiple of 4" in err()
+    assert lib.lvcst_upsample2_bilinear_bwd_nhwc(None, None, 1, 1, 1, 4, None) == 1 and "null pointer" in err()
+    assert lib.lvcst_upsample2_bilinear_bwd_nhwc(ctypes.c_void_p(4100), fake, 1, 1, 1, 4, None) == 1 and "16-byte" in err()
+    assert lib.lvcst_upsample2_bilinear_bwd_nhwc(None, None, 0, 1, 1, 4, None) == 0      # an empty batch launches nothing
+
+    keep, jobs = _jobs([[0, 8, 12]])
+    # (`lse` below: the max map, the first of the two maps the backward takes)
+    fwd = lambda logits, K, ld, scale, numel, bytes_, j, lse: lib.lvcst_sem_seg_loss_fwd(      # noqa: E731
+        logits, 1, 2, 3, K, ld, scale, fake, numel, bytes_, 255, j, fake, lse, fake, None, fake, 1 << 20, fake, fake, fake, fake, None)
+    bwd = lambda logits, K, ld, scale, numel, bytes_, j, lse: lib.lvcst_sem_seg_loss_bwd(      # noqa: E731
+        logits, 1, 2, 3, K, ld, scale, fake, numel, bytes_, 255, j, fake, lse, fake, fake, fake, fake, None)
+    for call, name in ((fwd, "lvcst_sem_seg_loss_fwd"), (bwd, "lvcst_sem_seg_loss_bwd")):
+        assert call(fake, 5, 4, 4, 96, 1, jobs, fake) == 1 and "ld >= K" in err() and name in err()
+        assert call(fake, 5, 8, 0, 96, 1, jobs, fake) == 1 and "scale" in err()
+        assert call(fake, 5, 8, 65, 96, 1, jobs, fake) == 1 and "scale" in err()
+        assert call(fake, 4097, 4100, 4, 96, 1, jobs, fake) == 1 and "K <= 4096" in err()
+        assert call(fake, 5, 8, 4, 96, 4, jobs, fake) == 1 and "label_bytes" in err()
+        assert call(fake, 5, 8, 4, 95, 1, jobs, fake) == 1 and "a job's label map lies outside the buffer" in err()
+        assert call(fake, 5, 8, 4, 96, 1, None, fake) == 1 and "null pointer" in err()
+        assert call(None, 5, 8, 4, 96, 1, jobs, fake) == 1 and "null pointer" in err()
+        assert call(fake, 5, 8, 4, 96, 1, jobs, None) == 1 and "null pointer" in err()
+        keep2, big = _jobs([[0, 9, 12]])      # taller than scale x h = 8
+        assert call(fake, 5, 8, 4, 200, 1, big, fake) == 1 and "exceeds scale x the logits" in err()
+        keep3, neg = _jobs([[-1, 8, 12]])
+        assert call(fake, 5, 8, 4, 200, 1, neg, fake) == 1 and "outside the buffer" in err()
+    # the forward's workspace: the query's answer is what the call asks for
+    need = lib.lvcst_sem_seg_loss_workspace_bytes(1, 2, 3, 5, 4)
+    assert need == 16      # one workgroup: an fp64 sum and an int64 count
+    assert lib.lvcst_sem_seg_loss_fwd(fake, 1, 2, 3, 5, 8, 4, fake, 96, 1, 255, jobs, fake, fake, fake, None, fake, need - 1, fake, fake, fake,
+                                      fake, None) == 1 and "workspace too small" in err()
+    assert lib.lvcst_sem_seg_loss_workspace_bytes(8, 200, 336, 54, 4) == 8 * 50 * 21 * 16      # 16 x 64 tiles of 800 x 1344
+    assert lib.lvcst_sem_seg_loss_workspace_bytes(1, 2, 3, 5, 65) == -1 and lib.lvcst_sem_seg_loss_workspace_bytes(1, 0, 3, 5, 4) == -1
+    assert lib.lvcst_sem_seg_loss_workspace_bytes(1, 2, 3, 4096, 4) == -1      # one pixel's 2 x 2 footprint of 4097 floats: past the LDS
+    del keep, keep2, keep3
